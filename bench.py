@@ -11,10 +11,16 @@ deterministic synthetic tensors of the reference architecture (the real checkpoi
 offline).  N > 1: every rank runs this workload on its own sequence (independent 32 Mb windows, the reference's
 structural-variant-screen pattern, BASELINE config 5): weak scaling, no data-path collective.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Also measured in the same run, OUTSIDE the timed region, and reported in the same JSON line:
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the fields derived from them.
+`--dump-outputs DIR` writes what the last timed step returned on rank 0 - the six strand-merged maps, levels 32, 16, 8, 4, 2, 1 Mb
+in that order, as DIR/pred_0.npy .. pred_5.npy (float32 [250,250], the fixture G8's `pred_<j>`); the inputs are seeded, so two
+builds run with the same arguments can be compared map for map.
+
+`--full` also times the conv kernels of the timed steps with HIP events (`roofline`, `roofline_hbm_bound_kernel`) and measures, in
+the same run, OUTSIDE the timed region, and reports in the same JSON line:
   * `sharded_256mb` (every N, BASELINE config 4 / north star): H1esc_256M-shaped model on one random 256 Mb sequence,
     both strands - the Encoder's 64 000 bins sharded over the N ranks (each rank holds only its bins' bases +- the 112 kb halo),
     ONE RCCL all-gather per strand (through the C ABI's orca_allgather; torch.distributed if that cannot be set up), then
@@ -642,7 +648,12 @@ def main():
     ap.add_argument("--sharded-timeout", type=float, default=420.0, help="N > 1: seconds the 256 Mb sharded section (and the final barrier) may take before the line is printed without it")
     ap.add_argument("--sharded-steps", type=int, default=3)
     ap.add_argument("--torch-collective", action="store_true", help="256 Mb section: torch.distributed all-gather instead of the C ABI's RCCL communicator")
+    ap.add_argument("--full", action="store_true", help="also run every section beside the headline figure (module docstring); the --no-* and "
+                                                        "--sharded-* options above select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the six maps of the last timed step (rank 0) as DIR/pred_<j>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.cpu_full_strand:
         print(json.dumps({"cpu_baseline_full_strand": cpu_baseline(0, L_BP)}))
@@ -699,7 +710,7 @@ def main():
     for _ in range(args.warmup):
         step()
     sync()
-    ctx.set_timing(True)
+    ctx.set_timing(args.full)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         outs = step()
@@ -711,6 +722,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for j, o in enumerate(outs):
+            np.save(os.path.join(args.dump_outputs, f"pred_{j}.npy"), o.float().cpu().numpy())
 
     # ---- dominant kernel: per-instantiation HIP-event timings collected in the timed region
     inst = inst_rooflines(recs)
@@ -771,7 +786,7 @@ def main():
                  "1x1 heads, pools, upsampling, merges: fp32",
         "data": "synthetic",
         "config": {"workload": f"H1-ESC 32Mb model forward, single random {args.seq_mb}Mb sequence, fp32-class ({enc_prec} split operands on the 16-bit matrix "
-                               "cores, see dtype; parity vs the reference's fp32 in `parity`), both strands (genomepredict-equivalent, 1 model): "
+                               "cores, see dtype; parity vs the reference's fp32 in `parity` with --full), both strands (genomepredict-equivalent, 1 model): "
                                "Encoder+Encoder2+6 Decoder+Decoder_1m per strand",
                    "sequence_bp": Lbp, "strands": 2, "levels": 6, "weights": "synthetic seed 0",
                    "input": "float32 [1,4,L] strands in HBM" if args.float_input else "1 byte/base packed sequence in HBM, both strands read from it",
@@ -779,9 +794,15 @@ def main():
         "contact_map_pixels_per_s": round(world * 2 * 6 * 62500 * args.steps / elapsed, 1),
         "step_tflop_algorithmic": round(step_flops() * Lbp / L_BP, 3) if Lbp == L_BP else None,
         "whole_step_tflops": round(world * step_flops() * args.steps / elapsed, 2) if Lbp == L_BP else None,
-        "roofline": roofline,
-        "roofline_hbm_bound_kernel": roofline_hbm,
     }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    res["roofline"], res["roofline_hbm_bound_kernel"] = roofline, roofline_hbm
 
     # ---- parity of THIS run's maps against the reference's own output for the same sequence / weights / position (G8)
     g8 = os.path.join(ROOT, "tests", "golden", "G8_full32m.npz")

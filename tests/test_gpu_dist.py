@@ -182,7 +182,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo(cuda):
     max-over-ranks clock, the 256 Mb section with bin-sharded Encoders, the all-gathers, one strand's tail per rank parity and the map
     gather - runs on a 1-GPU box.  The sharded maps must be the single-rank ones (checksum of the four merged maps)."""
     env = dict(os.environ, ORCA_BENCH_ONE_DEVICE="1", ORCA_BENCH_BACKEND="gloo")
-    base = [os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--sharded-steps", "1", "--no-cpu-baseline"]
+    base = [os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--sharded-steps", "1", "--no-cpu-baseline"]
     p1 = subprocess.run([sys.executable] + base + ["--gpus", "1"], env=env, capture_output=True, text=True, timeout=900)
     assert p1.returncode == 0, p1.stderr[-2000:]
     one = json.loads([l for l in p1.stdout.splitlines() if l.startswith("{")][-1])
@@ -253,7 +253,7 @@ def test_bench_four_ranks_on_one_gpu_over_gloo(cuda):
     reproduce the reference's fixtures (G20 at 256 Mb, G8 at 32 Mb) exactly as at N = 1."""
     env = dict(os.environ, ORCA_BENCH_ONE_DEVICE="1", ORCA_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4", "--master-addr", "127.0.0.1",
-           "--master-port", str(29700 + os.getpid() % 200), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "1",
+           "--master-port", str(29700 + os.getpid() % 200), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--steps", "1", "--warmup", "1",
            "--sharded-steps", "1", "--no-cpu-baseline"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-1500:]
@@ -281,7 +281,7 @@ def test_bench_eight_ranks_on_one_gpu_over_gloo(cuda):
     maps of the N = 8 job are NOT bit-equal to N = 1 where a shard's stage 7 changed kernels (another fp32 summation order, ~1e-6) - the
     checksum relation asserted here is the one that is true: relative 1e-6."""
     env = dict(os.environ, ORCA_BENCH_ONE_DEVICE="1", ORCA_BENCH_BACKEND="gloo")
-    base = [os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--sharded-steps", "1", "--no-cpu-baseline", "--no-configs", "--sharded-timeout", "1500"]
+    base = [os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--sharded-steps", "1", "--no-cpu-baseline", "--no-configs", "--sharded-timeout", "1500"]
     p1 = subprocess.run([sys.executable] + base + ["--gpus", "1"], env=env, capture_output=True, text=True, timeout=900)
     assert p1.returncode == 0, p1.stderr[-2000:]
     one = json.loads([l for l in p1.stdout.splitlines() if l.startswith("{")][-1])
