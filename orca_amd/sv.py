@@ -587,13 +587,25 @@ def s3_encode(net0, caches, pcs, codes_w, reverse, out_row):
     `Stage4Cache`s (all of ``caches`` one kind): the same with rows, the front + stage 4, and stages 5-7."""
     if next(iter(caches.values())).level == 4:
         return _s4_encode(net0, caches, pcs, codes_w, reverse, out_row)
+    s4, front_bases = s3_assemble(net0, caches, pcs, codes_w, reverse)
+    net0.back(s4, int(codes_w.numel()) // (S3_GRID * S3_POOL), out_row)
+    return front_bases
+
+
+def _plan(caches, pcs, L, **kw):
+    if None in caches:
+        return s3_plan(pcs, caches[None].C, L, regions=caches[None].region, **kw)
+    return s3_plan(pcs, {c: k.C for c, k in caches.items()}, L, regions={c: k.region for c, k in caches.items()}, **kw)
+
+
+def s3_assemble(net0, caches, pcs, codes_w, reverse, s4=None):
+    """The stage-4 input of a window strand (`s3_encode` without stages 4-7): P16 planes [32, p16_plane_units(n4), 4] of n4 = L / 80 positions,
+    written into ``s4`` if given (positions [0, n4) only), and the number of bases that went through the Encoder's front."""
     L = int(codes_w.numel())
     n4 = L // (S3_GRID * S3_POOL)
-    if None in caches:
-        takes, snippets = s3_plan(pcs, caches[None].C, L, regions=caches[None].region)
-    else:
-        takes, snippets = s3_plan(pcs, {c: k.C for c, k in caches.items()}, L, regions={c: k.region for c, k in caches.items()})
-    s4 = torch.empty((32, engine.p16_plane_units(n4), 4), dtype=torch.float32, device=codes_w.device)
+    takes, snippets = _plan(caches, pcs, L)
+    if s4 is None:
+        s4 = torch.empty((32, engine.p16_plane_units(n4), 4), dtype=torch.float32, device=codes_w.device)
     ctx = engine.get_context(codes_w.device)
     for m_lo, m_hi, chrom, strand, phase, c in takes:
         src = caches[chrom].get(strand, phase)
@@ -602,19 +614,23 @@ def s3_encode(net0, caches, pcs, codes_w, reverse, out_row):
         engine.p16_pool5_into(ctx, src, (c - caches[chrom]._origin(strand, phase)) // S3_GRID, s4, m_lo, m_hi - m_lo)
     for ga, gb, b0, nb, skip in snippets:
         net0.front_snippet(codes_w, reverse, b0, nb, skip, gb - ga, s4, ga)
-    net0.back(s4, n4, out_row)
-    return sum(sn[3] for sn in snippets)
+    return s4, sum(sn[3] for sn in snippets)
 
 
 def _s4_encode(net0, caches, pcs, codes_w, reverse, out_row):
+    s5, front_bases = s4_assemble(net0, caches, pcs, codes_w, reverse)
+    net0.back5(s5, out_row)
+    return front_bases
+
+
+def s4_assemble(net0, caches, pcs, codes_w, reverse, s5=None):
+    """The stage-5 input of a window strand from `Stage4Cache`s (`_s4_encode` without stages 5-7): fp32 rows [n5, 128], n5 = L / 400, written
+    into ``s5`` if given, and the number of bases that went through the Encoder's front (+ stage 4)."""
     L = int(codes_w.numel())
     n5 = L // (S4_GRID * S3_POOL)
-    kw = dict(margin=S4_MARGIN_BP, grid=S4_GRID, pad=S4_PAD_BP, min_snippet=S4_MIN_SNIPPET_BP)
-    if None in caches:
-        takes, snippets = s3_plan(pcs, caches[None].C, L, regions=caches[None].region, **kw)
-    else:
-        takes, snippets = s3_plan(pcs, {c: k.C for c, k in caches.items()}, L, regions={c: k.region for c, k in caches.items()}, **kw)
-    s5 = torch.empty((n5, 128), dtype=torch.float32, device=codes_w.device)
+    takes, snippets = _plan(caches, pcs, L, margin=S4_MARGIN_BP, grid=S4_GRID, pad=S4_PAD_BP, min_snippet=S4_MIN_SNIPPET_BP)
+    if s5 is None:
+        s5 = torch.empty((n5, 128), dtype=torch.float32, device=codes_w.device)
     ctx = engine.get_context(codes_w.device)
     for m_lo, m_hi, chrom, strand, phase, c in takes:
         src = caches[chrom].get(strand, phase)
@@ -635,8 +651,7 @@ def _s4_encode(net0, caches, pcs, codes_w, reverse, out_row):
     else:
         for ga, gb, b0, nb, skip in snippets:
             net0.front4_snippet(codes_w, reverse, b0, nb, skip, gb - ga, s5, ga)
-    net0.back5(s5, out_row)
-    return sum(sn[3] for sn in snippets)
+    return s5, sum(sn[3] for sn in snippets)
 
 
 POOL_MAX_BINS = 500     # longer runs (whole windows: phases that are not held) are not spread over the pool's contexts - they fill the chip on their own
