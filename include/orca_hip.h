@@ -252,6 +252,24 @@ int orca_encoder_front4_ranges(orca_ctx* ctx, orca_net* net, const uint8_t* code
                                float* dst, int64_t dst_rows);
 int orca_encoder_back5(orca_ctx* ctx, orca_net* net, const float* rows, int64_t n5, float* out, int64_t so_c);
 
+/* The 1 Mb in-silico mutagenesis screen (orca_amd/screen.py): length-preserving edits of one window, each re-encoded through the front + stage 4
+ * on a few kb around it and stages 5-7 on its own copy of the window's stage-5 rows, then Decoder_1m.  One launch per step for a whole batch.
+ *   orca_screen_edit_codes    edited snippets of the L-base window `window` (device codes 0..4) packed back to back into out[total]: `table` (DEVICE,
+ *                             n_snippets x 8 int64, in out_off order) = [out_off, b0, nb, kind, pos, len, pay_off, 0] per snippet: bases [b0, b0 + nb)
+ *                             of the window with the span [pos, pos + len) substituted by payload[pay_off ..] (kind 0), set to N = 4 (kind 1) or
+ *                             reverse-complemented in place (kind 2, N stays N).  Reads outside the window / payload give N.
+ *   orca_screen_splice_rows   B stage-5 row images out[B][n5][128]: ref[n5][128] broadcast, rows [row_lo, row_lo + row_cnt) of image b replaced by rows
+ *                             [src_row, ..) of fresh[n_fresh][128]; `table` (DEVICE, B x 3 int64) = [row_lo, row_cnt, src_row] per image
+ *   orca_encoder_back5_batch  orca_encoder_back5 of B windows at once: rows [B][n5][128] (n5 % 10 == 0) -> out[b * so_b + c * so_c + bin]; each window
+ *                             zero padded on its own; a window's result does not depend on B or on its place in the batch
+ *   orca_screen_scores        B maps alt[b * map_bs + i * n + j] against ref[n][n]: profile[b][i] = mean_j |alt - ref|, mean[b] = mean over the map,
+ *                             amax[b] = max |alt - ref| (sums in fp64; a NaN difference gives NaN) */
+int orca_screen_edit_codes(orca_ctx* ctx, const uint8_t* window, int64_t L, const int64_t* table, int n_snippets, const uint8_t* payload, int64_t n_payload,
+                           uint8_t* out, int64_t total);
+int orca_screen_splice_rows(orca_ctx* ctx, const float* ref, int64_t n5, const float* fresh, int64_t n_fresh, const int64_t* table, int B, float* out);
+int orca_encoder_back5_batch(orca_ctx* ctx, orca_net* net, const float* rows, int B, int64_t n5, float* out, int64_t so_b, int64_t so_c);
+int orca_screen_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, float* profile, float* mean, float* amax);
+
 /* Number of 4 kb bins Encoder emits for an L-bp input (floor through the
  * 4,4,5,5,5,2 pooling chain). */
 int64_t orca_encoder_num_bins(int64_t L);

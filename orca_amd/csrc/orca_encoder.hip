@@ -13,6 +13,7 @@
 #include "conv_small.h"
 #include "misc_kernels.h"
 #include "p16_planes.h"
+#include "screen.h"
 
 // ---------------------------------------------------------------------------
 // kernel launch helpers
@@ -104,14 +105,15 @@ static void launch_b16_t(hipStream_t s, ConvB16Args a, int B) {
 }
 
 template <int NS, int DT>
-static int launch_conv1d_b16_ns(orca_ctx* ctx, const ConvLayer& L, const ConvB16Args& a, int B) {
+static int launch_conv1d_b16_ns(orca_ctx* ctx, const ConvLayer& L, const ConvB16Args& a, int B, int fixed_tile = 0) {
   hipStream_t s = ctx->stream;
   if (L.cout == 64) launch_b16_t<64, 2, 2, 4, 1, NS, DT>(s, a, B);
   else if (L.cout == 96) launch_b16_t<96, 1, 3, 8, 1, NS, DT>(s, a, B);
   else if (L.cout == 128) {
     // stages 6-7 of the Encoder (16 000 / 8 000 positions) make 63 / 32 tiles of 256 positions for 256 CUs: 64-position tiles there
+    // (fixed_tile: the 256-position tiles whatever the batch - a batch of edits is many rows)
     if constexpr (NS <= 2) {
-      if (((a.n + 255) / 256) * B < 200) { launch_b16_t<128, 1, 2, 2, 2, NS, DT>(s, a, B); return ORCA_OK; }
+      if (!fixed_tile && ((a.n + 255) / 256) * B < 200) { launch_b16_t<128, 1, 2, 2, 2, NS, DT>(s, a, B); return ORCA_OK; }
     }
     launch_b16_t<128, 2, 2, 4, 2, NS, DT>(s, a, B);
   }
@@ -121,7 +123,7 @@ static int launch_conv1d_b16_ns(orca_ctx* ctx, const ConvLayer& L, const ConvB16
 
 // x [B][n][cin], y/r1 [B][n][cout] channel-last.  precision: ORCA_PRECISION_BF16 / _BF16X2 / _BF16X3
 int launch_conv1d_b16(orca_ctx* ctx, const ConvLayer& L, int precision, const float* x, long x_bs, float* y, long y_bs,
-                             const float* r1, int B, long n, int relu, int pool4, const float* r2) {
+                             const float* r1, int B, long n, int relu, int pool4, const float* r2, int fixed_tile) {
   if (!L.d_wb16) return fail(ORCA_EINVAL, "layer has no bf16 split pack (cin %d)", L.cin);
   if (n <= 0 || B <= 0) return ORCA_OK;
   ConvB16Args a;
@@ -157,7 +159,7 @@ int launch_conv1d_b16(orca_ctx* ctx, const ConvLayer& L, int precision, const fl
   }
   if (precision == ORCA_PRECISION_BF16X3) rc = launch_conv1d_b16_ns<3, 0>(ctx, L, a, B);
   else if (precision == ORCA_PRECISION_BF16X2) rc = launch_conv1d_b16_ns<2, 0>(ctx, L, a, B);
-  else if (precision == ORCA_PRECISION_F16X2) rc = launch_conv1d_b16_ns<2, 1>(ctx, L, a, B);
+  else if (precision == ORCA_PRECISION_F16X2) rc = launch_conv1d_b16_ns<2, 1>(ctx, L, a, B, fixed_tile);
   else rc = launch_conv1d_b16_ns<1, 0>(ctx, L, a, B);
   if (rc != ORCA_OK) return rc;
   LAUNCHCHECK("conv1d_k9_bf16s_kernel");
@@ -1069,6 +1071,83 @@ extern "C" int orca_encoder_back5(orca_ctx* ctx, orca_net* net, const float* row
   ORCA_TRY(encoder_chunk(ctx, net, src, n5, buf, ru4(n5), &res, &rld, &rn, ENC_BACK5));
   if (rld >= 0 || rn != n5 / 10) return fail(ORCA_EINVAL, "internal: stages 5-7 produced %ld bins for %ld positions", rn, (long)n5);
   return launch_copy2d(ctx, res, 1, 128, out, so_c, 128, rn);
+}
+
+// ---- the 1 Mb mutagenesis screen (orca_amd/screen.py; kernels in screen.h) ----------------------------------------------------------------
+extern "C" int orca_screen_edit_codes(orca_ctx* ctx, const uint8_t* window, int64_t L, const int64_t* table, int n_snippets, const uint8_t* payload,
+                                      int64_t n_payload, uint8_t* out, int64_t total) {
+  if (!ctx || !window || !table || !out || n_snippets <= 0) return fail(ORCA_EINVAL, "orca_screen_edit_codes: NULL / empty argument");
+  if (n_payload > 0 && !payload) return fail(ORCA_EINVAL, "orca_screen_edit_codes: NULL payload");
+  if (total <= 0) return ORCA_OK;
+  HIPCHECK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(screen_edit_codes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, window, (long)L,
+                     reinterpret_cast<const long long*>(table), n_snippets, payload, (long)n_payload, out, (long)total);
+  LAUNCHCHECK("screen_edit_codes_kernel");
+  return ORCA_OK;
+}
+
+extern "C" int orca_screen_splice_rows(orca_ctx* ctx, const float* ref, int64_t n5, const float* fresh, int64_t n_fresh, const int64_t* table, int B, float* out) {
+  if (!ctx || !ref || !table || !out || (n_fresh > 0 && !fresh)) return fail(ORCA_EINVAL, "orca_screen_splice_rows: NULL argument");
+  if (B <= 0 || n5 <= 0) return ORCA_OK;
+  if (!al16(ref) || !al16(out) || (fresh && !al16(fresh))) return fail(ORCA_EINVAL, "orca_screen_splice_rows: rows must be 16-byte aligned");
+  HIPCHECK(hipSetDevice(ctx->device));
+  const long units = (long)B * n5 * 32;
+  hipLaunchKernelGGL(screen_splice_rows_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, ctx->stream, reinterpret_cast<const f32x4*>(ref), (long)n5,
+                     reinterpret_cast<const f32x4*>(fresh), (long)n_fresh, reinterpret_cast<const long long*>(table), B, reinterpret_cast<f32x4*>(out));
+  LAUNCHCHECK("screen_splice_rows_kernel");
+  return ORCA_OK;
+}
+
+// stages 5-7 of B windows at once: rows [B][n5][128] -> out[b * so_b + c * so_c + bin].  Every conv is ONE launch for the batch with a batch stride, so
+// each window keeps its own zero padding (stacking the windows end to end would leak activations across the seams from the first conv on).  The
+// rows are read in place (stage 5's first conv reads them; nothing writes them).
+extern "C" int orca_encoder_back5_batch(orca_ctx* ctx, orca_net* net, const float* rows, int B, int64_t n5, float* out, int64_t so_b, int64_t so_c) {
+  if (!ctx || !net || !rows || !out) return fail(ORCA_EINVAL, "orca_encoder_back5_batch: NULL argument");
+  if (net->kind != ORCA_NET_ENCODER || net->precision != ORCA_PRECISION_F16X2) return fail(ORCA_EINVAL, "orca_encoder_back5_batch: an Encoder net in the f16x2 arithmetic");
+  if (n5 <= 0 || n5 % 10) return fail(ORCA_EINVAL, "orca_encoder_back5_batch: %ld stage-5 positions (a multiple of 10)", (long)n5);
+  if (B <= 0) return ORCA_OK;
+  HIPCHECK(hipSetDevice(ctx->device));
+  const size_t per = (size_t)B * n5 * 128;
+  ORCA_TRY(ws_ensure(ctx, 3 * ru256(per * sizeof(float))));
+  float* w[3];
+  for (int i = 0; i < 3; ++i) w[i] = ws_take(ctx, per);
+  const int prec = ORCA_PRECISION_F16X2;
+  long n = n5;
+  const float* x = rows;
+  float* res = nullptr;
+  // stage 5 (st 4): rows -> w[2] (T = w[0], LO = w[1]); stage 6: pool5 w[2] -> w[0], out -> w[0] (T = w[1], LO = w[2]);
+  // stage 7: pool2 w[0] -> w[1], out -> w[1] (T = w[2], LO = w[0]; no residual)
+  for (int st = 4; st < 7; ++st) {
+    const ConvLayer* Ls = &net->convs[4 * st];
+    float *P, *T, *LO;
+    if (st == 4) { T = w[0]; LO = w[1]; P = w[2]; }
+    else {
+      const int q = st == 5 ? 0 : 1;
+      const long n2 = n / kEncPools[st];
+      ORCA_TRY(launch_pool_nlc(ctx, res, w[q], (long)B * n2, Ls[0].cin, kEncPools[st]));
+      n = n2; x = w[q]; P = w[q]; T = w[(q + 1) % 3]; LO = w[(q + 2) % 3];
+    }
+    const long bs = n * 128;
+    ORCA_TRY(launch_conv1d_b16(ctx, Ls[0], prec, x, bs, T, bs, nullptr, B, n, 0, 0, nullptr, 1));
+    ORCA_TRY(launch_conv1d_b16(ctx, Ls[1], prec, T, bs, LO, bs, nullptr, B, n, 0, 0, nullptr, 1));
+    ORCA_TRY(launch_conv1d_b16(ctx, Ls[2], prec, LO, bs, T, bs, nullptr, B, n, 1, 0, nullptr, 1));
+    ORCA_TRY(launch_conv1d_b16(ctx, Ls[3], prec, T, bs, P, bs, st < 6 ? LO : nullptr, B, n, 1, 0, nullptr, 1));
+    res = P;
+  }
+  if (n != n5 / 10) return fail(ORCA_EINVAL, "internal: stages 5-7 produced %ld bins for %ld positions", n, (long)n5);
+  const long total = (long)B * n * 128;
+  hipLaunchKernelGGL(screen_rows_to_bins_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, res, n, B, out, (long)so_b, (long)so_c);
+  LAUNCHCHECK("screen_rows_to_bins_kernel");
+  return ORCA_OK;
+}
+
+extern "C" int orca_screen_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, float* profile, float* mean, float* amax) {
+  if (!ctx || !alt || !ref || !profile || !mean || !amax) return fail(ORCA_EINVAL, "orca_screen_scores: NULL argument");
+  if (B <= 0 || n <= 0) return ORCA_OK;
+  HIPCHECK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(screen_scores_kernel, dim3((unsigned)B), dim3(512), 0, ctx->stream, alt, (long)map_bs, ref, n, profile, mean, amax);
+  LAUNCHCHECK("screen_scores_kernel");
+  return ORCA_OK;
 }
 
 extern "C" int orca_pack_sequence(orca_ctx* ctx, const float* x, int64_t sx_c, int64_t sx_l, int64_t L, uint8_t* codes, int* packable) {

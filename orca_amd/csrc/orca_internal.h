@@ -126,8 +126,9 @@ struct FusedFirst;
 // orca_encoder.hip
 int launch_conv1d(orca_ctx* ctx, const ConvLayer& L, const float* x, long x_bs, long ldx, float* y, long y_bs, long ldy, const float* r1, const float* r2,
                   int B, long n, int relu, int tile, int y_nlc = 0);
+// fixed_tile: the tile shape of a long 128-cout layer depends on n alone, not on B (orca_encoder_back5_batch: a row's result never depends on its batch)
 int launch_conv1d_b16(orca_ctx* ctx, const ConvLayer& L, int precision, const float* x, long x_bs, float* y, long y_bs, const float* r1, int B, long n, int relu,
-                      int pool4 = 0, const float* r2 = nullptr);
+                      int pool4 = 0, const float* r2 = nullptr, int fixed_tile = 0);
 int launch_conv1d_p16(orca_ctx* ctx, const ConvLayer& L, const float* x, void* y, const float* r1, long n, int relu, int out_mode, const FusedFirst* f1 = nullptr,
                       int fmt = 0);
 int launch_p16_zero_pads(orca_ctx* ctx, float* base, int C, long n_valid, int fmt = 0);

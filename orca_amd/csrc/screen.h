@@ -1,0 +1,118 @@
+// screen.h - the small kernels of the 1 Mb in-silico mutagenesis screen (orca_amd/screen.py): edited snippets straight from the window's
+// codes, the per-edit stage-5 row images, the [B][n][128] -> [B][128][n] hand-over of batched stages 5-7, and the map scores.
+// All of them are HBM-bound and tiny next to the Decoder_1m they feed; each is ONE launch for a whole batch of edits.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+// ---- edit table (int64 per snippet, SCREEN_EDIT_FIELDS fields; include/orca_hip.h: orca_screen_edit_codes) ---------------------------------------------
+//   [0] out_off  first output base of this snippet in the packed output
+//   [1] b0       first window base of the snippet
+//   [2] nb       bases in the snippet
+//   [3] kind     0 substitution (payload), 1 N-mask, 2 in-place reverse complement
+//   [4] pos      first window base of the edited span
+//   [5] len      bases in the edited span
+//   [6] pay_off  first payload code of a substitution
+//   [7] (unused)
+// Snippets are packed back to back in table order (out_off ascending, no gaps).
+#define SCREEN_EDIT_FIELDS 8
+
+// one thread per output base: binary search of its snippet, then the window base with the edit applied.  Every read is bounds-checked
+// against L / npay (an out-of-range index reads as N), so a malformed table cannot make the kernel leave its buffers.
+static __global__ void screen_edit_codes_kernel(const unsigned char* __restrict__ win, long L, const long long* __restrict__ tab, int ns,
+                                                const unsigned char* __restrict__ pay, long npay, unsigned char* __restrict__ out, long total) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  int lo = 0, hi = ns - 1;
+  while (lo < hi) {                                  // last snippet with out_off <= t
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[(long)mid * SCREEN_EDIT_FIELDS] <= t) lo = mid; else hi = mid - 1;
+  }
+  const long long* e = tab + (long)lo * SCREEN_EDIT_FIELDS;
+  const long w = (long)e[1] + (t - (long)e[0]);
+  unsigned c = (w >= 0 && w < L) ? win[w] : 4u;
+  const long pos = (long)e[4], len = (long)e[5];
+  if (w >= pos && w < pos + len) {
+    const long k = w - pos;
+    if (e[3] == 0) {
+      const long p = (long)e[6] + k;
+      c = (p >= 0 && p < npay) ? pay[p] : 4u;
+    } else if (e[3] == 1) {
+      c = 4u;
+    } else {
+      const long src = pos + len - 1 - k;
+      const unsigned s = (src >= 0 && src < L) ? win[src] : 4u;
+      c = s < 4u ? 3u - s : 4u;                        // A<->T, C<->G; N stays N
+    }
+  }
+  out[t] = (unsigned char)(c > 4u ? 4u : c);
+}
+
+// splice table (int64 per edit, 3 fields): [row_lo, row_cnt, src_row] - rows [row_lo, row_lo + row_cnt) of edit b's image come from rows
+// [src_row, ..) of `fresh`, every other row from `ref`.  One thread per 16-byte unit of the output [B][n5][128].
+static __global__ void screen_splice_rows_kernel(const f32x4* __restrict__ ref, long n5, const f32x4* __restrict__ fresh, long nfresh,
+                                                 const long long* __restrict__ tab, int B, f32x4* __restrict__ out) {
+  const long u = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long per = n5 * 32;
+  if (u >= (long)B * per) return;
+  const int b = (int)(u / per);
+  const long r = (u - (long)b * per) >> 5, q = u & 31;
+  const long r0 = (long)tab[3 * b], cnt = (long)tab[3 * b + 1], s0 = (long)tab[3 * b + 2];
+  const long s = s0 + (r - r0);
+  out[u] = (r >= r0 && r < r0 + cnt && s >= 0 && s < nfresh) ? fresh[s * 32 + q] : ref[r * 32 + q];
+}
+
+// channel-last rows [B][n][128] -> out[b * so_b + c * so_c + j]
+static __global__ void screen_rows_to_bins_kernel(const float* __restrict__ src, long n, int B, float* __restrict__ out, long so_b, long so_c) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * n * 128) return;
+  const long c = i % 128, j = (i / 128) % n, b = i / (128 * n);
+  out[b * so_b + c * so_c + j] = src[i];
+}
+
+// scores of B alt maps [B][n][n] (batch stride map_bs) against ref [n][n]: profile[b][i] = mean_j |alt - ref|, mean[b] = mean of the
+// profile (= mean over the map), amax[b] = max |alt - ref|.  One workgroup per map, one wave per row at a time; every map element is
+// read once.  A NaN difference propagates into all three (as numpy's mean / max do).
+static __global__ void __launch_bounds__(512) screen_scores_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, int n,
+                                                                   float* __restrict__ profile, float* __restrict__ mean, float* __restrict__ amax) {
+  __shared__ double s_sum[8];
+  __shared__ float s_max[8];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float* a = alt + (long)b * map_bs;
+  double wsum = 0.0;            // sums in fp64: the scores match a host fp64 restatement to ~1e-12 relative, whatever the order
+  float wmax = 0.f;
+  bool wnan = false;
+  for (int i = wv; i < n; i += 8) {
+    double rs = 0.0;
+    for (int j = lane; j < n; j += 64) {
+      const float d = fabsf(a[(long)i * n + j] - ref[(long)i * n + j]);
+      rs += (double)d;
+      wnan |= d != d;
+      wmax = fmaxf(wmax, d);
+    }
+    for (int o = 32; o > 0; o >>= 1) rs += __shfl_xor(rs, o, 64);
+    if (lane == 0) profile[(long)b * n + i] = (float)(rs / (double)n);
+    wsum += rs;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    wmax = fmaxf(wmax, __shfl_xor(wmax, o, 64));
+    wnan |= __shfl_xor((int)wnan, o, 64) != 0;
+  }
+  if (lane == 0) {
+    s_sum[wv] = wsum;
+    s_max[wv] = wnan ? __int_as_float(0x7fc00000) : wmax;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    float m = 0.f;
+    bool nan = false;
+    for (int k = 0; k < 8; ++k) {
+      t += s_sum[k];
+      nan |= s_max[k] != s_max[k];
+      m = fmaxf(m, s_max[k]);
+    }
+    mean[b] = nan ? __int_as_float(0x7fc00000) : (float)(t / ((double)n * (double)n));
+    amax[b] = nan ? __int_as_float(0x7fc00000) : m;
+  }
+}

@@ -568,6 +568,82 @@ def encoder_back5(net, rows, out):
     return out
 
 
+# ---- the 1 Mb mutagenesis screen (include/orca_hip.h: orca_screen_*; orca_amd/screen.py is the user) ------------------------------------------
+SCREEN_EDIT_FIELDS = 8          # int64 per snippet of an edit table: out_off, b0, nb, kind, pos, len, pay_off, 0
+SCREEN_KINDS = {"sub": 0, "mask": 1, "inv": 2}
+
+
+def _i64_cuda(t, name, cols):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == cols):
+        raise ValueError(f"{name}: a contiguous [k,{cols}] int64 ROCm tensor")
+    return t
+
+
+def screen_edit_codes(ctx, window, table_host, table, payload, out):
+    """Edited snippets of ``window`` [L] uint8 into ``out`` [total] (orca_screen_edit_codes).  ``table_host``: the same [k, 8] int64 table as numpy,
+    checked here (the kernel also clamps every read); ``table``: its device copy."""
+    window, out = _codes1d(window), _codes1d(out)
+    _i64_cuda(table, "table", SCREEN_EDIT_FIELDS)
+    t = np.asarray(table_host, dtype=np.int64)
+    L, npay = window.numel(), (0 if payload is None else payload.numel())
+    if t.shape != tuple(table.shape) or t.shape[0] == 0:
+        raise ValueError("edit table: host and device copies differ or are empty")
+    off, b0, nb, kind, pos, ln, po = (t[:, k] for k in range(7))
+    if (off[0] != 0 or np.any(off[1:] != (off + nb)[:-1]) or int((off + nb)[-1]) != out.numel() or np.any(nb <= 0) or np.any(b0 < 0)
+            or np.any(b0 + nb > L) or np.any(pos < 0) or np.any(ln <= 0) or np.any(pos + ln > L) or np.any((kind < 0) | (kind > 2))
+            or np.any((kind == 0) & ((po < 0) | (po + ln > npay)))):
+        raise ValueError("edit table: snippets must be packed back to back inside the window, edits inside it, payloads inside the payload buffer")
+    if payload is not None:
+        payload = _codes1d(payload)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_edit_codes(ctx.handle, _p(window), L, _p(table), t.shape[0], ctypes.c_void_p(0) if payload is None else _p(payload), npay,
+                                             _p(out), out.numel()), "orca_screen_edit_codes")
+    return out
+
+
+def screen_splice_rows(ctx, ref, fresh, table, out):
+    """B stage-5 row images ``out`` [B, n5, 128]: ``ref`` [n5, 128] with rows [row_lo, row_lo + row_cnt) of image b taken from rows [src_row, ..) of
+    ``fresh`` [R, 128]; ``table`` [B, 3] int64 on the device."""
+    _rows(ref, "ref")
+    _rows(fresh, "fresh")
+    _i64_cuda(table, "table", 3)
+    n5 = ref.shape[0]
+    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3 and tuple(out.shape[1:]) == (n5, 128)
+            and out.shape[0] == table.shape[0]):
+        raise ValueError(f"out: a contiguous [B,{n5},128] float32 ROCm tensor, B = the table's rows")
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_splice_rows(ctx.handle, _p(ref), n5, _p(fresh), fresh.shape[0], _p(table), out.shape[0], _p(out)), "orca_screen_splice_rows")
+    return out
+
+
+def encoder_back5_batch(net, rows, out=None):
+    """Stages 5-7 of B windows from their stage-5 rows ``rows`` [B, n5, 128] into ``out`` [B, 128, n5 / 10] (unit stride along the bins)."""
+    if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dtype == torch.float32 and rows.is_contiguous() and rows.dim() == 3 and rows.shape[2] == 128):
+        raise ValueError("rows: a contiguous [B,n5,128] float32 ROCm tensor")
+    B, n5 = rows.shape[0], rows.shape[1]
+    if out is None:
+        out = torch.empty((B, 128, n5 // 10), dtype=torch.float32, device=rows.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, 128, n5 // 10) and out.stride(2) == 1):
+        raise ValueError(f"out must be a [{B},128,{n5 // 10}] float32 view with unit stride along the bins")
+    net.ctx.sync_stream()
+    check(_lib.load().orca_encoder_back5_batch(net.ctx.handle, net.handle, _p(rows), B, n5, _p(out), out.stride(0), out.stride(1)), "orca_encoder_back5_batch")
+    return out
+
+
+def screen_scores(ctx, alt, ref):
+    """alt [B, n, n] (any batch stride, rows contiguous) against ref [n, n]: (profile [B, n], mean [B], max [B]) of |alt - ref|."""
+    alt, ref = _f32_cuda(alt, "alt"), _f32_cuda(ref, "ref").contiguous()
+    B, n = alt.shape[0], ref.shape[0]
+    if alt.dim() != 3 or tuple(alt.shape[1:]) != (n, n) or alt.stride(2) != 1 or alt.stride(1) != n or tuple(ref.shape) != (n, n):
+        raise ValueError(f"alt [B,{n},{n}] with contiguous maps, ref [{n},{n}]")
+    profile = torch.empty((B, n), dtype=torch.float32, device=alt.device)
+    mean = torch.empty((B,), dtype=torch.float32, device=alt.device)
+    amax = torch.empty((B,), dtype=torch.float32, device=alt.device)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_scores(ctx.handle, _p(alt), alt.stride(0), _p(ref), B, n, _p(profile), _p(mean), _p(amax)), "orca_screen_scores")
+    return profile, mean, amax
+
+
 def encoder_forward_2bit(net, two, nmask, start, L, reverse=False, bin_lo=0, bin_hi=0, chunk_bp=0, out=None):
     """Encoder on bases [start, start + L) of a chromosome stored as 2 bits per base + N mask in HBM (genome.TwoBitGenome planes): no
     unpacked window is made (orca_encoder_forward_2bit).  Returns [1,128,bins]."""

@@ -249,6 +249,10 @@ class Encoder(_HipModule):
     def back5(self, rows, out):
         return engine.encoder_back5(self._parts_net(rows.device), rows, out)
 
+    def back5_batch(self, rows, out=None):
+        """Stages 5-7 of B windows from their stage-5 rows [B, n5, 128] -> [B, 128, n5 / 10] (screen.screen_1m)."""
+        return engine.encoder_back5_batch(self._parts_net(rows.device), rows, out)
+
     def forward_2bit(self, genome, chrom, start, end, reverse=False, bin_lo=0, bin_hi=0, out=None):
         """Encoder on `chrom`[start:end) of a genome.TwoBitGenome resident on the MI355X, read in place: 2 bits per base + N mask straight
         into the first-layer kernels (one-hot expansion in LDS) - no unpacked 1 byte/base window, no float window (selene_utils2.py:216-222)."""

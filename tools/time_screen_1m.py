@@ -1,0 +1,104 @@
+"""Edits per second of the 1 Mb mutagenesis screen (orca_amd/screen.py) against the naive route, in one process, alternated.
+
+Workload: synthetic H1esc_1M on one 1 Mb window (random bases with N runs); the 3 000 saturation SNVs of 1 kb in its middle plus the 250 4 kb
+mask tiles of the whole window (3 250 edits).
+  screen  screen.screen_1m(model, window, edits, batch=B)
+  naive   per batch of B edits: the edited windows (one orca_screen_edit_codes launch), Net's Encoder on them (forward_codes, whole 1 Mb each),
+          Decoder_1m + the 1-D head on the batch, the same scores - what a user without the screen would run
+Both routes' maps are compared on the first 64 edits (2e-5).  JSON on stdout and in profiles/screen_1m.json.
+
+    python tools/time_screen_1m.py                          # B = 16 and 64, 2 alternated repetitions
+    python tools/time_screen_1m.py --screen-only --batches 64 --reps 1 --out ''     # what a profiler run wraps
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from orca_amd import engine
+from orca_amd import orca_models as M
+from orca_amd import screen as S
+
+L = 1_000_000
+
+
+def window(seed=5):
+    rs = np.random.RandomState(seed)
+    c = rs.randint(0, 4, L).astype(np.uint8)
+    for a in rs.randint(0, L - 2000, 12):
+        c[a: a + rs.randint(50, 2000)] = 4
+    return c
+
+
+def naive(model, win, edits, batch, keep_maps=False):
+    net = model.net
+    sc = S._Screen(net, win, {})
+    ref_map, _ = sc.whole([])
+    ref_map = ref_map[0].contiguous()
+    out, maps_all = [], []
+    with torch.no_grad():
+        for i0 in range(0, len(edits), batch):
+            maps, h = sc.whole(edits[i0: i0 + batch])
+            out.append(engine.screen_scores(sc.ctx, maps, ref_map)[1])
+            if keep_maps:
+                maps_all.append(maps.clone())
+    return torch.cat(out), (torch.cat(maps_all) if keep_maps else None)
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="16,64")
+    ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--screen-only", action="store_true")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "screen_1m.json"))
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    model = M.H1esc_1M(synthetic_seed=0).to(dev)
+    c = window()
+    win = torch.from_numpy(c).to(dev)
+    edits = S.saturation_edits(c, 499_500, 500_500) + S.tile_edits("mask", 4000, 4000, 0, L)
+    rep = {"workload": f"H1esc_1M synthetic, 1 Mb window, {len(edits)} edits (saturation SNVs of 1 kb + 250 4 kb mask tiles)", "edits": len(edits)}
+    # warm-up (library load, nets, workspaces) and the cross-check of both routes' maps
+    st = {}
+    rs = S.screen_1m(model, win, edits[:64], batch=64, keep_maps=True, stats=st)
+    rep["route"] = st["route"]
+    if not a.screen_only:
+        _, mn = naive(model, win, edits[:64], 64, keep_maps=True)
+        rep["maps_maxabs_screen_vs_naive"] = float((rs.maps - mn).abs().max())
+        assert rep["maps_maxabs_screen_vs_naive"] < 2e-5, rep
+    for B in [int(b) for b in a.batches.split(",")]:
+        ts, tn = [], []
+        for _ in range(a.reps):
+            t, _ = timed(lambda: S.screen_1m(model, win, edits, batch=B))
+            ts.append(t)
+            if not a.screen_only:
+                t, _ = timed(lambda: naive(model, win, edits, B))
+                tn.append(t)
+        row = {"screen_s": [round(t, 3) for t in ts], "screen_edits_per_s": round(len(edits) / min(ts), 1)}
+        if tn:
+            row.update({"naive_s": [round(t, 3) for t in tn], "naive_edits_per_s": round(len(edits) / min(tn), 1),
+                        "speedup": round(min(tn) / min(ts), 2)})
+        rep[f"B{B}"] = row
+        print(json.dumps({f"B{B}": row}), flush=True)
+    print(json.dumps(rep))
+    if a.out:
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rep, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
