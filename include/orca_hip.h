@@ -328,6 +328,19 @@ int orca_decoder1m_forward_rows(orca_ctx* ctx, orca_net* net, const float* const
 int orca_decoder1m_forward(orca_ctx* ctx, orca_net* net, const float* x, int64_t sx_b, int64_t sx_c,
                            int64_t sx_l, int B, int n, float* out, int accumulate);
 
+/* For tests: a Decoder / Decoder_1m forward (arguments of orca_decoder_forward_mt; a Decoder_1m takes distenc = y = NULL) that stops behind
+ * the launches that complete `stage` and writes that feature map, decoded from its 16-bit planes, to map_out [B,channels,n,n] (contiguous).
+ * It is the forward's own launch sequence with an early return.  Stages:
+ *   0      IN: the Decoder's distenc chunk (T channels, then zeros; 16) / the Decoder_1m's x_i + x_j (128)
+ *   1      after lcombinerD's first conv (Decoder; 64)
+ *   2      A (Decoder): combinerD(.) + . in channels 0..63; with y 80 channels - the up-sampled y in 64..64+T-1, zeros to 79
+ *   3 + i  the residual stream after block i (64): i < 28 (Decoder; block 0 = lcombiner / combiner with y) or i < 19 (Decoder_1m)
+ * ORCA_EINVAL: a stage the net kind does not have, `channels` other than the stage's, an ORCA_PRECISION_F32 net (no 16-bit planes). */
+int orca_decoder_probe(orca_ctx* ctx, orca_net* net, const float* x, int64_t sx_b, int64_t sx_c, int64_t sx_l,
+                       const float* distenc, int64_t sd_b, int64_t sd_c, int64_t sd_h, int64_t sd_w, const float* y,
+                       int64_t sy_b, int64_t sy_c, int64_t sy_h, int64_t sy_w, int B, int n, int stage, int channels,
+                       float* map_out);
+
 /* Replaces: the strand merge `0.5*fwd + 0.5*rev[::-1, ::-1]`
  * (orca_predict.py:514-523) for contiguous [n,n] maps. */
 int orca_strand_merge(orca_ctx* ctx, const float* fwd, const float* rev, float* out, int n);
@@ -415,6 +428,12 @@ int orca_conv2d_forward(orca_ctx* ctx, const orca_conv_desc* conv, const float* 
  * (two fp16 planes, or one bf16 / fp16 plane). */
 int orca_conv2d_m16_forward(orca_ctx* ctx, const orca_conv_desc* conv, int precision, const float* x, float* y,
                             const float* r, int B, int n, int relu);
+/* One whole residual block of the Decoders at dilation 16 / 32 / 64 (conv2d_dblock.h: cur += lm(cur); cur += m(cur), four 3x3 convs
+ * 64 -> 32 -> 64 -> 32 -> 64 in one launch, in place), wrapped for tests: convs[4] = lm.a, lm.b, m.a, m.b (BN folded, ONE dilation of
+ * 16, 32, 64), x and y contiguous [B,64,n,n], 1 <= n <= 256 (odd sizes included), precision ORCA_PRECISION_F16X2 / _BF16 / _F16; the map
+ * makes a round trip through the M16 storage and the launch has the grid of the Decoder forward.  ORCA_EINVAL, before any launch, on
+ * anything else. */
+int orca_conv2d_dblock_forward(orca_ctx* ctx, const orca_conv_desc* convs, int precision, const float* x, float* y, int B, int n);
 /* y[c][m] = max_{j<k} x[c][k*m+j]  (nn.MaxPool1d(k,k)); x: [rows][ldx], y: [rows][ldy]. */
 int orca_maxpool1d_forward(orca_ctx* ctx, const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows,
                            int64_t n_out, int k);

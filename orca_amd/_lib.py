@@ -83,6 +83,8 @@ SIGNATURES = {
     "orca_decoder1m_forward_rows": (c_int, [c_void_p, c_void_p, POINTER(c_void_p), c_int64, c_int64, c_int, c_int, c_void_p, c_int]),
     "orca_net_num_targets": (c_int, [c_void_p, POINTER(c_int)]),
     "orca_decoder1m_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int]),
+    "orca_decoder_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                   c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
     "orca_strand_merge": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "orca_block_mean_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int]),
     "orca_adaptive_coarsegrain": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, ctypes.c_float, c_int, c_int, c_void_p, c_int64]),
@@ -98,6 +100,7 @@ SIGNATURES = {
     "orca_conv1d_b16_forward": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int]),
     "orca_conv2d_forward": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]),
     "orca_conv2d_m16_forward": (c_int, [c_void_p, POINTER(ConvDesc), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]),
+    "orca_conv2d_dblock_forward": (c_int, [c_void_p, POINTER(ConvDesc), c_int, c_void_p, c_void_p, c_int, c_int]),
     "orca_maxpool1d_forward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int]),
     "orca_pointwise1d_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64,
                                           c_int64, c_int, c_int64, c_int]),

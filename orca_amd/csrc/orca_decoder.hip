@@ -116,11 +116,18 @@ static int launch_final(orca_ctx* ctx, orca_net* net, const float* cur, long cur
   return ORCA_OK;
 }
 
+// orca_decoder_probe: the forward stops behind the launches that complete `stage` and hands out that map as fp32 [B][channels][n][n].
+// Stages (oracle/orca_oracle.py `decoder_stages`): 0 = IN, 1 = after lcombinerD.a (Decoder), 2 = A (Decoder), 3 + i = the residual stream after block i.
+struct DecoderProbe {
+  int stage, channels;
+  float* out;
+};
+
 // Decoder / Decoder_1m on the 16-bit matrix cores, feature maps in M16 (conv2d_m16.h)
 template <int NS, int DT>
 static int decoder_m16(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx_c, long sx_l, const RowSrc& de,
                        long sd_c, long sd_h, long sd_w, const RowSrc& y, long sy_c, long sy_h, long sy_w, int B, int n,
-                       float* out, int accumulate) {
+                       float* out, int accumulate, const DecoderProbe* probe = nullptr) {
   const int nt2 = net->num_2d;
   const bool is1m = net->kind == ORCA_NET_DECODER_1M, bf16 = DT == 0;
   const int mode = DT == 0 ? 1 : (NS == 1 ? 2 : 0);
@@ -150,6 +157,16 @@ static int decoder_m16(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx_c,
     f32x4* T = T0 + b0 * sz32;
     hipStream_t s = ctx->stream;
     float* TAB = is1m ? nullptr : TAB0 + b0 * tabsz;
+    // probe: map `buf` (batch stride bs units) is what stage k leaves - convert it and stop
+    auto emit = [&](const f32x4* buf, size_t bs) -> int {
+      for (int b = 0; b < nb; ++b)
+        hipLaunchKernelGGL((m16_to_nchw_kernel<NS, DT>), dim3((unsigned)n), dim3(ORCA_LDW), 0, s, buf + b * bs, probe->channels, n,
+                           probe->out + (size_t)(b0 + b) * probe->channels * n * n);
+      LAUNCHCHECK("m16_to_nchw_kernel");
+      return ORCA_OK;
+    };
+#define PROBE(k, buf, bs) \
+  if (probe && probe->stage == (k)) return emit(buf, bs)
     // everything computed from the inputs alone - IN (outer sum / distenc chunk), the separable tables, the upsampled coarse prediction - in one
     // launch per 8 maps (decoder_head_m16_kernel)
     for (int c0 = 0; c0 < nb; c0 += 8) {
@@ -166,6 +183,7 @@ static int decoder_m16(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx_c,
       hipLaunchKernelGGL((decoder_head_m16_kernel<NS, DT>), dim3((unsigned)n, roles, (unsigned)nc), dim3(256), 0, s, ha);
       LAUNCHCHECK("decoder_head_m16_kernel");
     }
+    PROBE(0, IN, szIN);
     const ConvLayer* L = net->convs.data();
     const ConvLayer* pairs;
     int npairs;
@@ -174,9 +192,11 @@ static int decoder_m16(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx_c,
     if (!is1m) {
       // lcombinerD.a = (MFMA conv over the distenc chunk) + (separable outer-sum part from the tables, added in the epilogue)
       ORCA_TRY(launch_conv2d_m16(ctx, L[0], IN, szIN, oIN, Bf, sz64, 8, nullptr, 0, nb, n, 0, mode, 8, 1, TAB, (long)tabsz));
+      PROBE(1, Bf, sz64);
       C2(L[1], Bf, sz64, 8, Cf, sz64, 8, nullptr, 0, 0);
       C2(L[2], Cf, sz64, 8, Bf, sz64, 8, nullptr, 0, 1);
       C2(L[3], Bf, sz64, 8, A, szA, oA, Cf, sz64, 1);           // A[octets 0..7] = combinerD(.) + .
+      PROBE(2, A, szA);
       pairs = L + 8; npairs = 28;
       if (y) {
         // (octets 8, 9 of A - the upsampled coarse prediction - were written by the head launch)
@@ -200,6 +220,7 @@ static int decoder_m16(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx_c,
     f32x4* cur = Df;
     f32x4* oth = Cf;
     for (int i = 1; i < npairs; ++i) {
+      PROBE(3 + i - 1, cur, sz64);
       const ConvLayer* p = pairs + 4 * i;
       const int dil = p[0].dil;
       if (dil >= 16) {
@@ -223,6 +244,8 @@ static int decoder_m16(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx_c,
       C2(p[3], T, sz32, 4, cur, sz64, 8, oth, sz64, 1);
     }
 #undef C2
+    PROBE(3 + npairs - 1, cur, sz64);
+#undef PROBE
     const ConvLayer& fa = net->convs[net->convs.size() - 2];
     const ConvLayer& fb = net->convs[net->convs.size() - 1];
     FinalArgs fa_;
@@ -239,17 +262,18 @@ static int decoder_m16(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx_c,
 
 static int decoder_common(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx_c, long sx_l, const RowSrc& de,
                           long sd_c, long sd_h, long sd_w, const RowSrc& y, long sy_c, long sy_h, long sy_w,
-                          int B, int n, float* out, int accumulate) {
+                          int B, int n, float* out, int accumulate, const DecoderProbe* probe = nullptr) {
   const int nt2 = net->num_2d;
   if (n <= 0 || n > ORCA_LDW || (n & 1)) return fail(ORCA_EINVAL, "map size %d unsupported (even, <=256)", n);
   if (B <= 0) return ORCA_OK;
   HIPCHECK(hipSetDevice(ctx->device));
   if (net->precision == ORCA_PRECISION_F16X2)
-    return decoder_m16<2, 1>(ctx, net, x, sx_c, sx_l, de, sd_c, sd_h, sd_w, y, sy_c, sy_h, sy_w, B, n, out, accumulate);
+    return decoder_m16<2, 1>(ctx, net, x, sx_c, sx_l, de, sd_c, sd_h, sd_w, y, sy_c, sy_h, sy_w, B, n, out, accumulate, probe);
   if (net->precision == ORCA_PRECISION_BF16)
-    return decoder_m16<1, 0>(ctx, net, x, sx_c, sx_l, de, sd_c, sd_h, sd_w, y, sy_c, sy_h, sy_w, B, n, out, accumulate);
+    return decoder_m16<1, 0>(ctx, net, x, sx_c, sx_l, de, sd_c, sd_h, sd_w, y, sy_c, sy_h, sy_w, B, n, out, accumulate, probe);
   if (net->precision == ORCA_PRECISION_F16)
-    return decoder_m16<1, 1>(ctx, net, x, sx_c, sx_l, de, sd_c, sd_h, sd_w, y, sy_c, sy_h, sy_w, B, n, out, accumulate);
+    return decoder_m16<1, 1>(ctx, net, x, sx_c, sx_l, de, sd_c, sd_h, sd_w, y, sy_c, sy_h, sy_w, B, n, out, accumulate, probe);
+  if (probe) return fail(ORCA_EINVAL, "orca_decoder_probe: an f32 net has no M16 stages (its convs are conv2d_3x3_kernel)");
   const bool is1m = net->kind == ORCA_NET_DECODER_1M;
   const size_t plane = (size_t)n * ORCA_LDW;
   const int cin0 = is1m ? 128 : 136;
@@ -365,6 +389,24 @@ extern "C" int orca_decoder1m_forward(orca_ctx* ctx, orca_net* net, const float*
   RowSrc xs, none;
   xs.base = x; xs.bs = sx_b;
   return decoder_common(ctx, net, xs, sx_c, sx_l, none, 0, 0, 0, none, 0, 0, 0, B, n, out, accumulate);
+}
+
+extern "C" int orca_decoder_probe(orca_ctx* ctx, orca_net* net, const float* x, int64_t sx_b, int64_t sx_c, int64_t sx_l, const float* distenc,
+                                  int64_t sd_b, int64_t sd_c, int64_t sd_h, int64_t sd_w, const float* y, int64_t sy_b, int64_t sy_c, int64_t sy_h,
+                                  int64_t sy_w, int B, int n, int stage, int channels, float* map_out) {
+  if (!ctx || !net || !x || !map_out) return fail(ORCA_EINVAL, "orca_decoder_probe: NULL argument");
+  const bool is1m = net->kind == ORCA_NET_DECODER_1M;
+  if (!is1m && net->kind != ORCA_NET_DECODER) return fail(ORCA_EINVAL, "orca_decoder_probe: net is neither a Decoder nor a Decoder_1m");
+  if (is1m ? (distenc || y) : !distenc) return fail(ORCA_EINVAL, "orca_decoder_probe: a Decoder needs distenc, a Decoder_1m takes neither distenc nor y");
+  const int last = 3 + (is1m ? 19 : 28) - 1;
+  if (stage < 0 || stage > last || (is1m && (stage == 1 || stage == 2)))
+    return fail(ORCA_EINVAL, "orca_decoder_probe: this net has no stage %d", stage);
+  const int want = stage == 0 ? (is1m ? 128 : 16) : (stage == 2 && y ? 80 : 64);
+  if (channels != want) return fail(ORCA_EINVAL, "orca_decoder_probe: stage %d has %d channels, got %d", stage, want, channels);
+  const DecoderProbe probe{stage, channels, map_out};
+  RowSrc xs, ds, ys;
+  xs.base = x; xs.bs = sx_b; ds.base = distenc; ds.bs = sd_b; ys.base = y; ys.bs = sy_b;
+  return decoder_common(ctx, net, xs, sx_c, sx_l, ds, sd_c, sd_h, sd_w, ys, sy_c, sy_h, sy_w, B, n, nullptr, 0, &probe);
 }
 
 extern "C" int orca_strand_merge(orca_ctx* ctx, const float* fwd, const float* rev, float* out, int n) {

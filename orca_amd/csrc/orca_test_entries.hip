@@ -4,6 +4,7 @@
 
 #include "conv_p16.h"        // nlc <-> P16 / B16 conversions
 #include "conv2d_m16.h"      // nchw <-> M16 conversions
+#include "conv2d_dblock.h"
 #include "misc_kernels.h"
 
 // ---------------------------------------------------------------------------
@@ -123,7 +124,8 @@ extern "C" int orca_conv2d_forward(orca_ctx* ctx, const orca_conv_desc* conv, co
   return rc;
 }
 
-// single dilated 3x3 layer on M16 maps (conv2d_m16.h; dilations 1-8) - or, for dilation 16 / 32 / 64, a whole residual block
+// single dilated 3x3 layer on M16 maps (conv2d_m16.h; dilations 1-8: launch_conv2d_m16 refuses larger ones, which only run as whole residual
+// blocks - conv2d_dblock_test below)
 template <int NS, int DT>
 static int conv2d_m16_test(orca_ctx* ctx, const ConvLayer& L, int mode, const float* x, float* y, const float* r, int B, int n, int relu) {
   const int xo = 2 * ((L.cin + 15) / 16), yo = L.cout / 8;
@@ -158,6 +160,57 @@ extern "C" int orca_conv2d_m16_forward(orca_ctx* ctx, const orca_conv_desc* conv
   else rc = fail(ORCA_EINVAL, "orca_conv2d_m16_forward: precision %d has no M16 kernel", precision);
   (void)hipStreamSynchronize(ctx->stream);
   free_layer(L);
+  return rc;
+}
+
+// one whole residual block of dilation 16 / 32 / 64 (conv2d_dblock.h) on caller-owned maps: the launch of decoder_m16, grid included
+template <int NS, int DT>
+static int conv2d_dblock_test(orca_ctx* ctx, const ConvLayer* L, const float* x, float* y, int B, int n) {
+  const size_t sz64 = (size_t)NS * n * ORCA_LDW * 8;
+  ORCA_TRY(ws_ensure(ctx, ru256(B * sz64 * 16)));
+  f32x4* cur = reinterpret_cast<f32x4*>(ws_take(ctx, B * sz64 * 4));
+  hipStream_t s = ctx->stream;
+  for (int b = 0; b < B; ++b)
+    hipLaunchKernelGGL((nchw_to_m16_kernel<NS, DT>), dim3((unsigned)n), dim3(ORCA_LDW), 0, s, x + (size_t)b * 64 * n * n, 64, n, cur + b * sz64, 8);
+  DBlockArgs da;
+  da.cur = cur; da.bs = (long)sz64; da.H = n; da.W = n; da.dil = L[0].dil; da.flag = ctx->d_flag;
+  for (int k = 0; k < 4; ++k) {
+    da.w[k] = DT == 0 ? L[k].d_wb16p : L[k].d_wf16;
+    da.bias[k] = L[k].d_bias;
+  }
+  hipLaunchKernelGGL((conv2d_dblock_kernel<NS, DT>), dim3(256, (unsigned)B), dim3(512), 0, s, da);
+  for (int b = 0; b < B; ++b)
+    hipLaunchKernelGGL((m16_to_nchw_kernel<NS, DT>), dim3((unsigned)n), dim3(ORCA_LDW), 0, s, cur + b * sz64, 64, n, y + (size_t)b * 64 * n * n);
+  LAUNCHCHECK("conv2d_dblock test path");
+  return ORCA_OK;
+}
+
+extern "C" int orca_conv2d_dblock_forward(orca_ctx* ctx, const orca_conv_desc* convs, int precision, const float* x, float* y, int B, int n) {
+  if (!ctx || !convs || !x || !y) return fail(ORCA_EINVAL, "orca_conv2d_dblock_forward: NULL argument");
+  if (n <= 0 || n > ORCA_LDW || B <= 0 || B > 65535) return fail(ORCA_EINVAL, "orca_conv2d_dblock_forward: map size %d / batch %d unsupported", n, B);
+  if (precision != ORCA_PRECISION_F16X2 && precision != ORCA_PRECISION_BF16 && precision != ORCA_PRECISION_F16)
+    return fail(ORCA_EINVAL, "orca_conv2d_dblock_forward: precision %d has no block kernel", precision);
+  const int d = convs[0].dilation;
+  if (!(d == 16 || d == 32 || d == 64)) return fail(ORCA_EINVAL, "orca_conv2d_dblock_forward: dilation %d (16, 32 or 64)", d);
+  for (int k = 0; k < 4; ++k) {
+    const int cin = k & 1 ? 32 : 64, cout = k & 1 ? 64 : 32;
+    if (convs[k].ksize != 3 || convs[k].cin != cin || convs[k].cout != cout || convs[k].dilation != d)
+      return fail(ORCA_EINVAL, "orca_conv2d_dblock_forward: conv %d must be 3x3, %d -> %d, dilation %d", k, cin, cout, d);
+  }
+  HIPCHECK(hipSetDevice(ctx->device));
+  ConvLayer L[4];
+  int rc = ORCA_OK;
+  for (int k = 0; k < 4 && rc == ORCA_OK; ++k) {
+    rc = make_layer(convs[k], &L[k]);
+    if (rc == ORCA_OK && precision != ORCA_PRECISION_BF16 && !L[k].f16_ok) rc = fail(ORCA_EINVAL, "layer weights exceed the fp16 range");
+  }
+  if (rc == ORCA_OK) {
+    if (precision == ORCA_PRECISION_F16X2) rc = conv2d_dblock_test<2, 1>(ctx, L, x, y, B, n);
+    else if (precision == ORCA_PRECISION_BF16) rc = conv2d_dblock_test<1, 0>(ctx, L, x, y, B, n);
+    else rc = conv2d_dblock_test<1, 1>(ctx, L, x, y, B, n);
+  }
+  (void)hipStreamSynchronize(ctx->stream);
+  for (int k = 0; k < 4; ++k) free_layer(L[k]);
   return rc;
 }
 

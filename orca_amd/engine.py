@@ -781,6 +781,35 @@ def decoder1m_forward(net, x, out=None, accumulate=False):
     return out
 
 
+def decoder_probe(net, x, distenc, y, stage):
+    """Test entry (orca_decoder_probe): the Decoder / Decoder_1m forward of ``net`` stopped behind the launches that complete ``stage``;
+    returns that feature map as fp32 [B,C,n,n].  Stages: 0 = IN (16 channels; Decoder_1m 128), 1 = after lcombinerD's first conv, 2 = A
+    (80 channels with y, else 64), 3 + i = the residual stream after block i.  A Decoder_1m takes distenc = y = None."""
+    x = _f32_cuda(x, "x")
+    B, C, n = x.shape
+    if C != 128:
+        raise ValueError(f"Decoder input must be [B,128,n], got {tuple(x.shape)}")
+    is1m = net.kind == _lib.ORCA_NET_DECODER_1M
+    T = net.num_targets()
+    dp, sd, yp, sy = ctypes.c_void_p(0), (0, 0, 0, 0), ctypes.c_void_p(0), (0, 0, 0, 0)
+    if distenc is not None:
+        distenc = _f32_cuda(distenc, "distenc")
+        if distenc.dim() != 4 or tuple(distenc.shape[1:]) != (T, n, n) or distenc.shape[0] not in (1, B):
+            raise ValueError(f"distenc must be [B or 1,{T},{n},{n}], got {tuple(distenc.shape)}")
+        dp, sd = _p(distenc), (distenc.stride(0) if distenc.shape[0] == B else 0, distenc.stride(1), distenc.stride(2), distenc.stride(3))
+    if y is not None:
+        y = _f32_cuda(y, "y")
+        if tuple(y.shape) != (B, T, n // 2, n // 2):
+            raise ValueError(f"coarse prediction must be [{B},{T},{n // 2},{n // 2}], got {tuple(y.shape)}")
+        yp, sy = _p(y), (y.stride(0), y.stride(1), y.stride(2), y.stride(3))
+    channels = (128 if is1m else 16) if stage == 0 else (80 if stage == 2 and y is not None else 64)
+    out = torch.empty((B, channels, n, n), dtype=torch.float32, device=x.device)
+    net.ctx.sync_stream()
+    check(_lib.load().orca_decoder_probe(net.ctx.handle, net.handle, _p(x), x.stride(0), x.stride(1), x.stride(2), dp, *sd, yp, *sy, B, n,
+                                         int(stage), channels, _p(out)), "orca_decoder_probe")
+    return out
+
+
 def strand_merge(fwd, rev):
     """0.5*fwd + 0.5*rev[::-1, ::-1] for contiguous [n,n] maps (orca_predict.py:514-523)."""
     fwd, rev = _f32_cuda(fwd, "fwd").contiguous(), _f32_cuda(rev, "rev").contiguous()
@@ -890,6 +919,25 @@ def conv2d_m16(x, w, b, dilation=1, relu=False, r=None, precision="f16x2"):
     r = r.contiguous() if r is not None else None
     check(_lib.load().orca_conv2d_m16_forward(ctx.handle, d, _lib.PRECISIONS[precision], _p(x), _p(y), _p(r) if r is not None else None, B, n,
                                               1 if relu else 0), "orca_conv2d_m16_forward")
+    return y
+
+
+def conv2d_dblock(x, convs, dilation, precision="f16x2"):
+    """One whole residual block of the Decoders at dilation 16 / 32 / 64 in one launch (conv2d_dblock.h; test wrapper): x [B,64,n,n],
+    convs = [(w, b)] * 4 for lm.a (64 -> 32), lm.b (32 -> 64), m.a, m.b -> lm(x) + x =: o, m(o) + o, [B,64,n,n]; 1 <= n <= 256."""
+    x = _f32_cuda(x, "x").contiguous()
+    B, _, n, _ = x.shape
+    layers = []
+    for w, b in convs:
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        layers.append({"w": w, "b": np.ascontiguousarray(b, dtype=np.float32), "cout": w.shape[0], "cin": w.shape[1], "k": w.shape[2],
+                       "dil": int(dilation)})
+    if len(layers) != 4:
+        raise ValueError("conv2d_dblock: four convs (lm.a, lm.b, m.a, m.b)")
+    d = make_descs(layers)
+    y = torch.empty_like(x)
+    ctx = get_context(x.device)
+    check(_lib.load().orca_conv2d_dblock_forward(ctx.handle, d, _lib.PRECISIONS[precision], _p(x), _p(y), B, n), "orca_conv2d_dblock_forward")
     return y
 
 
