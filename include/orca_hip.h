@@ -270,6 +270,27 @@ int orca_screen_splice_rows(orca_ctx* ctx, const float* ref, int64_t n5, const f
 int orca_encoder_back5_batch(orca_ctx* ctx, orca_net* net, const float* rows, int B, int64_t n5, float* out, int64_t so_b, int64_t so_c);
 int orca_screen_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, float* profile, float* mean, float* amax);
 
+/* Compound edits (screen.EditSet: several disjoint spans applied together) and region scores.  Each small table is passed twice, the DEVICE copy the
+ * kernel reads and a HOST copy with the same content that is checked here before anything is launched; a bad argument returns ORCA_EINVAL with the
+ * cause in orca_last_error().  The kernels clip every table-derived index as well.
+ *   orca_screen_edit_codes_multi   as orca_screen_edit_codes with any number of spans per snippet: `table` (n_snippets x 8 int64, out_off ascending from 0
+ *                                  without gaps, ending at `total`) = [out_off, b0, nb, span_lo, span_cnt, 0, 0, 0]; `spans` (n_spans x 4 int64) =
+ *                                  [kind, pos, len, pay_off]; spans [span_lo, span_lo + span_cnt) of a snippet are sorted by pos and pairwise disjoint,
+ *                                  in window coordinates; a span may stick out of the snippet; an inversion reads the unedited window
+ *   orca_screen_splice_rows_multi  as orca_screen_splice_rows with any number of row ranges per image: `segments` (n_segments x 3 int64) =
+ *                                  [row_lo, row_cnt, src_row]; image b owns segments [seg_off[b], seg_off[b + 1]) (seg_off: B + 1 int64, monotone, from 0
+ *                                  to n_segments), sorted by row_lo and disjoint
+ *   orca_screen_region_scores      K rectangles (1..64) `rects` (K x 4 int32) = [i0, i1, j0, j1], half open, 0 <= i0 < i1 <= n and the same for j:
+ *                                  mean_signed[b][k] = mean of alt - ref over rows [i0, i1) x columns [j0, j1) of map b, mean_abs[b][k] = mean of
+ *                                  |alt - ref| (differences and sums in fp64; a NaN difference gives NaN in both) */
+int orca_screen_edit_codes_multi(orca_ctx* ctx, const uint8_t* window, int64_t L, const int64_t* table, const int64_t* table_host, int n_snippets,
+                                 const int64_t* spans, const int64_t* spans_host, int64_t n_spans, const uint8_t* payload, int64_t n_payload, uint8_t* out,
+                                 int64_t total);
+int orca_screen_splice_rows_multi(orca_ctx* ctx, const float* ref, int64_t n5, const float* fresh, int64_t n_fresh, const int64_t* segments,
+                                  const int64_t* segments_host, int64_t n_segments, const int64_t* seg_off, const int64_t* seg_off_host, int B, float* out);
+int orca_screen_region_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* rects,
+                              const int32_t* rects_host, int K, float* mean_signed, float* mean_abs);
+
 /* Number of 4 kb bins Encoder emits for an L-bp input (floor through the
  * 4,4,5,5,5,2 pooling chain). */
 int64_t orca_encoder_num_bins(int64_t L);

@@ -116,3 +116,115 @@ static __global__ void __launch_bounds__(512) screen_scores_kernel(const float* 
     amax[b] = nan ? __int_as_float(0x7fc00000) : m;
   }
 }
+
+// ---- compound edits (screen.EditSet): several disjoint spans applied to one snippet, several (snippet, row range) segments per image -------------------
+// snippet table (int64 per snippet, SCREEN_EDIT_FIELDS fields; include/orca_hip.h: orca_screen_edit_codes_multi)
+//   [0] out_off  [1] b0  [2] nb  as above     [3] span_lo  first span of this snippet in the span table     [4] span_cnt  spans of this snippet
+// span table (int64 per span, SCREEN_SPAN_FIELDS fields): [0] kind  [1] pos  [2] len  [3] pay_off - a snippet's spans are sorted by pos and
+// pairwise disjoint, so a binary search finds the one span that can hold a base.  An inversion reads its source from the unedited window.
+#define SCREEN_SPAN_FIELDS 4
+
+// one thread per output base: binary search of its snippet, binary search of the snippet's spans, then the window base with that span's
+// edit applied.  The span range is clipped to the table and every read is bounds-checked against L / npay (an out-of-range index reads as N).
+static __global__ void screen_edit_codes_multi_kernel(const unsigned char* __restrict__ win, long L, const long long* __restrict__ tab, int ns,
+                                                      const long long* __restrict__ spans, long nspans, const unsigned char* __restrict__ pay, long npay,
+                                                      unsigned char* __restrict__ out, long total) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  int lo = 0, hi = ns - 1;
+  while (lo < hi) {                                  // last snippet with out_off <= t
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[(long)mid * SCREEN_EDIT_FIELDS] <= t) lo = mid; else hi = mid - 1;
+  }
+  const long long* e = tab + (long)lo * SCREEN_EDIT_FIELDS;
+  const long w = (long)e[1] + (t - (long)e[0]);
+  unsigned c = (w >= 0 && w < L) ? win[w] : 4u;
+  long s0 = (long)e[3], s1 = (long)e[3] + (long)e[4];
+  s0 = s0 < 0 ? 0 : s0;
+  s1 = s1 > nspans ? nspans : s1;
+  if (s0 < s1) {
+    long a = s0, b = s1 - 1;
+    while (a < b) {                                  // last span with pos <= w (the first one when none is)
+      const long mid = (a + b + 1) >> 1;
+      if ((long)spans[mid * SCREEN_SPAN_FIELDS + 1] <= w) a = mid; else b = mid - 1;
+    }
+    const long long* sp = spans + a * SCREEN_SPAN_FIELDS;
+    const long pos = (long)sp[1], len = (long)sp[2];
+    if (w >= pos && w - pos < len) {
+      const long k = w - pos;
+      if (sp[0] == 0) {
+        const long p = (long)sp[3] + k;
+        c = (p >= 0 && p < npay) ? pay[p] : 4u;
+      } else if (sp[0] == 1) {
+        c = 4u;
+      } else {
+        const long src = pos + len - 1 - k;
+        const unsigned s = (src >= 0 && src < L) ? win[src] : 4u;
+        c = s < 4u ? 3u - s : 4u;                        // A<->T, C<->G; N stays N
+      }
+    }
+  }
+  out[t] = (unsigned char)(c > 4u ? 4u : c);
+}
+
+// segment table (int64 per segment, 3 fields): [row_lo, row_cnt, src_row] as the splice table above; image b owns segments
+// [seg_off[b], seg_off[b + 1]), sorted by row_lo and disjoint.  One thread per 16-byte unit of the output [B][n5][128]: binary search of the
+// image's segments for the last one with row_lo <= r.  The segment range is clipped to the table, the source row to `fresh`.
+static __global__ void screen_splice_rows_multi_kernel(const f32x4* __restrict__ ref, long n5, const f32x4* __restrict__ fresh, long nfresh,
+                                                       const long long* __restrict__ seg, long nseg, const long long* __restrict__ seg_off, int B,
+                                                       f32x4* __restrict__ out) {
+  const long u = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long per = n5 * 32;
+  if (u >= (long)B * per) return;
+  const int b = (int)(u / per);
+  const long r = (u - (long)b * per) >> 5, q = u & 31;
+  long s0 = (long)seg_off[b], s1 = (long)seg_off[b + 1];
+  s0 = s0 < 0 ? 0 : s0;
+  s1 = s1 > nseg ? nseg : s1;
+  f32x4 v = ref[r * 32 + q];
+  if (s0 < s1) {
+    long a = s0, z = s1 - 1;
+    while (a < z) {
+      const long mid = (a + z + 1) >> 1;
+      if ((long)seg[3 * mid] <= r) a = mid; else z = mid - 1;
+    }
+    const long r0 = (long)seg[3 * a], cnt = (long)seg[3 * a + 1], s = (long)seg[3 * a + 2] + (r - r0);
+    if (r >= r0 && r - r0 < cnt && s >= 0 && s < nfresh) v = fresh[s * 32 + q];
+  }
+  out[u] = v;
+}
+
+// region scores of B alt maps [B][n][n] (batch stride map_bs) against ref [n][n]: for rectangle k = (i0, i1, j0, j1) (int32, half open, inside
+// [0, n) - the host entry point checks it; clipped here all the same) signed[b][k] = mean of alt - ref, absm[b][k] = mean of |alt - ref|.
+// One workgroup per (map, rectangle).  The differences and both sums are fp64 (an fp32 difference is exact in fp64, so the signed mean keeps
+// its accuracy under cancellation); a NaN difference propagates through both sums.
+static __global__ void __launch_bounds__(256) screen_region_scores_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, int n,
+                                                                          const int* __restrict__ rects, int K, float* __restrict__ signed_out,
+                                                                          float* __restrict__ abs_out) {
+  __shared__ double s_sum[4], s_abs[4];
+  const int b = blockIdx.x, k = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int i0 = rects[4 * k], i1 = rects[4 * k + 1], j0 = rects[4 * k + 2], j1 = rects[4 * k + 3];
+  i0 = i0 < 0 ? 0 : i0; j0 = j0 < 0 ? 0 : j0;
+  i1 = i1 > n ? n : i1; j1 = j1 > n ? n : j1;
+  const int h = i1 > i0 ? i1 - i0 : 0, w = j1 > j0 ? j1 - j0 : 0;
+  const float* a = alt + (long)b * map_bs;
+  double sum = 0.0, asum = 0.0;
+  for (int e = threadIdx.x; e < h * w; e += 256) {
+    const long at = (long)(i0 + e / w) * n + (j0 + e % w);
+    const double d = (double)a[at] - (double)ref[at];
+    sum += d;
+    asum += fabs(d);
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    sum += __shfl_xor(sum, o, 64);
+    asum += __shfl_xor(asum, o, 64);
+  }
+  if (lane == 0) { s_sum[wv] = sum; s_abs[wv] = asum; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double cnt = (double)h * (double)w;
+    const double t = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]), ta = (s_abs[0] + s_abs[1]) + (s_abs[2] + s_abs[3]);
+    signed_out[(long)b * K + k] = (float)(t / cnt);
+    abs_out[(long)b * K + k] = (float)(ta / cnt);
+  }
+}

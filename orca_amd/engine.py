@@ -644,6 +644,92 @@ def screen_scores(ctx, alt, ref):
     return profile, mean, amax
 
 
+# compound edits and region scores (orca_screen_*_multi, orca_screen_region_scores).  The small tables are numpy on the host; the wrappers upload the
+# device copies, and the library checks the host copies before it launches anything (a malformed table is an OrcaHipError, never a launch)
+SCREEN_SPAN_FIELDS = 4          # int64 per span: kind, pos, len, pay_off
+
+
+def _on_device(t, name, dtype):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise OrcaHipError(f"{name} is on '{t.device}': orca_amd has no CPU path (move it to the MI355X with .cuda())")
+    if t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f"{name}: a contiguous {dtype} ROCm tensor")
+    return t
+
+
+def _host_table(a, dtype, cols, name):
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if a.ndim != 2 or a.shape[1] != cols:
+        raise ValueError(f"{name}: a [k,{cols}] table")
+    return a
+
+
+def _np_p(a):
+    return ctypes.c_void_p(a.ctypes.data if a.size else 0)
+
+
+def _dev_p(t):
+    return ctypes.c_void_p(t.data_ptr() if t.numel() else 0)
+
+
+def screen_edit_codes_multi(ctx, window, table_host, spans_host, payload, out):
+    """Edited snippets of ``window`` [L] uint8 into ``out`` [total] with any number of spans per snippet (orca_screen_edit_codes_multi).
+    ``table_host`` [k, 8] int64 numpy = [out_off, b0, nb, span_lo, span_cnt, 0, 0, 0]; ``spans_host`` [s, 4] int64 numpy = [kind, pos, len, pay_off]."""
+    window, out = _on_device(window, "window", torch.uint8), _on_device(out, "out", torch.uint8)
+    if window.dim() != 1 or out.dim() != 1:
+        raise ValueError("window, out: [L] and [total] uint8")
+    if payload is not None:
+        payload = _on_device(payload, "payload", torch.uint8)
+    t, s = _host_table(table_host, np.int64, SCREEN_EDIT_FIELDS, "snippet table"), _host_table(spans_host, np.int64, SCREEN_SPAN_FIELDS, "span table")
+    td, sd = torch.from_numpy(t).to(window.device), torch.from_numpy(s).to(window.device)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_edit_codes_multi(ctx.handle, _p(window), window.numel(), _dev_p(td), _np_p(t), t.shape[0], _dev_p(sd), _np_p(s), s.shape[0],
+                                                   ctypes.c_void_p(0) if payload is None else _dev_p(payload), 0 if payload is None else payload.numel(),
+                                                   _dev_p(out), out.numel()), "orca_screen_edit_codes_multi")
+    return out
+
+
+def screen_splice_rows_multi(ctx, ref, fresh, segments_host, seg_off_host, out):
+    """B stage-5 row images ``out`` [B, n5, 128]: ``ref`` [n5, 128] with, for every segment [row_lo, row_cnt, src_row] of image b (``segments_host``
+    [s, 3] int64 numpy, image b's at [seg_off_host[b], seg_off_host[b + 1])), rows [row_lo, row_lo + row_cnt) from rows [src_row, ..) of ``fresh``."""
+    ref, fresh, out = _on_device(ref, "ref", torch.float32), _on_device(fresh, "fresh", torch.float32), _on_device(out, "out", torch.float32)
+    if ref.dim() != 2 or ref.shape[1] != 128 or fresh.dim() != 2 or fresh.shape[1] != 128:
+        raise ValueError("ref, fresh: [n,128] float32")
+    n5 = ref.shape[0]
+    g = _host_table(segments_host, np.int64, 3, "segment table")
+    o = np.ascontiguousarray(seg_off_host, dtype=np.int64)
+    if o.ndim != 1 or o.size < 1:
+        raise ValueError("segment offsets: [B + 1] int64")
+    B = o.size - 1
+    if out.dim() != 3 or tuple(out.shape) != (B, n5, 128):
+        raise ValueError(f"out: a contiguous [{B},{n5},128] float32 ROCm tensor, B + 1 = the number of segment offsets")
+    gd, od = torch.from_numpy(g).to(ref.device), torch.from_numpy(o).to(ref.device)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_splice_rows_multi(ctx.handle, _dev_p(ref), n5, _dev_p(fresh), fresh.shape[0], _dev_p(gd), _np_p(g), g.shape[0], _dev_p(od), _np_p(o),
+                                                    B, _dev_p(out)), "orca_screen_splice_rows_multi")
+    return out
+
+
+def screen_region_scores(ctx, alt, ref, rects_host):
+    """alt [B, n, n] (any batch stride, rows contiguous) against ref [n, n] over the K rectangles ``rects_host`` [K, 4] = (i0, i1, j0, j1), half open:
+    (mean of alt - ref [B, K], mean of |alt - ref| [B, K]) (orca_screen_region_scores)."""
+    alt, ref = _f32_cuda(alt, "alt"), _f32_cuda(ref, "ref").contiguous()
+    n = ref.shape[0]
+    if alt.dim() != 3 or ref.dim() != 2 or tuple(alt.shape[1:]) != (n, n) or alt.stride(2) != 1 or alt.stride(1) != n or tuple(ref.shape) != (n, n):
+        raise ValueError(f"alt [B,{n},{n}] with contiguous maps, ref [{n},{n}]")
+    r = _host_table(rects_host, np.int32, 4, "rectangles")
+    B, K = alt.shape[0], r.shape[0]
+    rd = torch.from_numpy(r).to(alt.device)
+    sg = torch.empty((B, K), dtype=torch.float32, device=alt.device)
+    ab = torch.empty((B, K), dtype=torch.float32, device=alt.device)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_region_scores(ctx.handle, _dev_p(alt), alt.stride(0), _p(ref), B, n, _dev_p(rd), _np_p(r), K, _dev_p(sg), _dev_p(ab)),
+          "orca_screen_region_scores")
+    return sg, ab
+
+
 def encoder_forward_2bit(net, two, nmask, start, L, reverse=False, bin_lo=0, bin_hi=0, chunk_bp=0, out=None):
     """Encoder on bases [start, start + L) of a chromosome stored as 2 bits per base + N mask in HBM (genome.TwoBitGenome planes): no
     unpacked window is made (orca_encoder_forward_2bit).  Returns [1,128,bins]."""

@@ -15,6 +15,12 @@ orca_encoder_back5_batch).  The route needs the Encoder's two-part form (default
 precision or Encoder form, `engine.force_safe_precision()` - every batch goes through the whole-window route (the edited windows through
 `Net`'s own Encoder and Decoder_1m), with the same API and results.  The fp16-range check is deferred to the end of the reference and of each
 batch; when it fires, that batch (or, for the reference, the whole screen) is redone on the whole-window route in the range-safe arithmetic.
+
+An `EditSet` is a compound edit: several pairwise disjoint `Edit`s of the same window applied together (a haplotype's SNVs, two sites knocked
+out at once, `pair_edits` for epistasis).  It is still length-preserving, so the same argument holds: the rows inside some member's cone
+change, and no others.  The rows of the members are merged into clusters, each cluster is one snippet, and the item's row image takes one
+row range per cluster (orca_screen_edit_codes_multi, orca_screen_splice_rows_multi).  ``regions`` adds the signed and the absolute mean of
+alt - ref over chosen bin rectangles (orca_screen_region_scores).
 """
 from dataclasses import dataclass, field
 from typing import Optional
@@ -89,18 +95,80 @@ class Edit:
         return f"Edit({self.kind!r}, {self.pos}, {self.length}{s})"
 
 
+class EditSet:
+    """A compound edit: ``EditSet(edits, name=None)``, a non-empty immutable sequence of pairwise disjoint `Edit`s of one window that are applied
+    together.  All positions are in the unedited window's coordinates (an ``inv`` member reads its source from the unedited window - the members
+    are disjoint, so nothing else could be meant).  The members are kept sorted by ``pos``: the order they are given in changes nothing."""
+
+    __slots__ = ("edits", "name")
+
+    def __init__(self, edits, name=None):
+        edits = list(edits)
+        if not edits:
+            raise ValueError("an EditSet needs at least one Edit")
+        for e in edits:
+            if not isinstance(e, Edit):
+                raise TypeError(f"an EditSet's members are screen.Edit, got {e!r}")
+        edits.sort(key=lambda e: e.pos)
+        for a, b in zip(edits, edits[1:]):
+            if b.pos < a.end:
+                raise ValueError(f"an EditSet's members must be disjoint: {a!r} and {b!r} overlap")
+        object.__setattr__(self, "edits", tuple(edits))
+        object.__setattr__(self, "name", name)
+
+    def __setattr__(self, key, value):
+        raise AttributeError("an EditSet is immutable")
+
+    def __len__(self):
+        return len(self.edits)
+
+    def __getitem__(self, i):
+        return self.edits[i]
+
+    def __iter__(self):
+        return iter(self.edits)
+
+    @property
+    def pos(self):
+        return self.edits[0].pos
+
+    @property
+    def end(self):
+        return self.edits[-1].end
+
+    def check(self, L):
+        for e in self.edits:
+            e.check(L)
+
+    def __repr__(self):
+        head = ", ".join(repr(e) for e in self.edits[:3]) + (f", ... {len(self.edits)} members" if len(self.edits) > 3 else "")
+        return f"EditSet([{head}]" + ("" if self.name is None else f", name={self.name!r}") + ")"
+
+
+def members_of(item):
+    """The `Edit`s of a screen item (an `Edit` or an `EditSet`), sorted by ``pos``."""
+    if isinstance(item, Edit):
+        return (item,)
+    if isinstance(item, EditSet):
+        return item.edits
+    raise TypeError(f"a screen item is a screen.Edit or a screen.EditSet, got {item!r}")
+
+
 def apply_edit(codes, edit):
-    """The edited window as numpy uint8 (host restatement of the device kernel; ``codes``: [L] codes 0..4)."""
-    c = np.array(codes, dtype=np.uint8, copy=True)
+    """The edited window as numpy uint8 (host restatement of the device kernels; ``codes``: [L] codes 0..4; ``edit``: an `Edit` or an `EditSet`,
+    whose members all read the unedited window)."""
+    src = np.asarray(codes, dtype=np.uint8)
+    c = np.array(src, dtype=np.uint8, copy=True)
     edit.check(c.size)
-    s = slice(edit.pos, edit.end)
-    if edit.kind == "sub":
-        c[s] = edit.seq
-    elif edit.kind == "mask":
-        c[s] = N_CODE
-    else:
-        r = c[s][::-1]
-        c[s] = np.where(r < 4, 3 - r, r)
+    for e in members_of(edit):
+        s = slice(e.pos, e.end)
+        if e.kind == "sub":
+            c[s] = e.seq
+        elif e.kind == "mask":
+            c[s] = N_CODE
+        else:
+            r = src[s][::-1]
+            c[s] = np.where(r < 4, 3 - r, r)
     return c
 
 
@@ -122,13 +190,52 @@ def tile_edits(kind, width, step, start, end):
     return [Edit(kind, p, width) for p in range(start, end - width + 1, step)]
 
 
+def pair_edits(a, b):
+    """Every pair from two edit lists applied together (epistasis screens): ``(sets, index)`` - one `EditSet` per (x, y) in a x b whose spans are
+    disjoint, and ``index[k] = (i, j)``: sets[k] = {a[i], b[j]}, to line the rows up with those of the single edits."""
+    sets, index = [], []
+    for i, x in enumerate(a):
+        for j, y in enumerate(b):
+            if x.end <= y.pos or y.end <= x.pos:
+                sets.append(EditSet([x, y]))
+                index.append((i, j))
+    return sets, index
+
+
+def snv_set(codes, variants, name=None):
+    """One `EditSet` of 1-base substitutions from ``variants`` = [(pos, ref, alt)] (bases as ACGTN letters or codes 0..4), e.g. a haplotype
+    inside one window.  A ``ref`` that is not the window's base at ``pos``, or two variants at one position, is a ValueError."""
+    c = np.asarray(codes.cpu() if isinstance(codes, torch.Tensor) else codes)
+    seen, edits = set(), []
+    for pos, ref, alt in variants:
+        pos = int(pos)
+        if not 0 <= pos < c.size:
+            raise ValueError(f"variant at {pos} outside the window of {c.size} bases")
+        if pos in seen:
+            raise ValueError(f"two variants at position {pos}")
+        seen.add(pos)
+        r, a = _codes_of(ref if isinstance(ref, str) else [ref]), _codes_of(alt if isinstance(alt, str) else [alt])
+        if r.size != 1 or a.size != 1:
+            raise ValueError(f"variant at {pos}: ref and alt are single bases")
+        if int(r[0]) != int(c[pos]):
+            raise ValueError(f"variant at {pos}: ref {'ACGTN'[int(r[0])]} but the window has {'ACGTN'[int(c[pos])]}")
+        edits.append(Edit("sub", pos, 1, a))
+    return EditSet(edits, name)
+
+
 # ---- planning (pure; tests/test_screen_cpu.py checks it against the fp64 oracle) -----------------------------------------------------------
 @dataclass
 class BatchPlan:
-    """The two-part route's work for one batch of edits on an L-base window.  Per edit i: snippet[i] = (b0, nb) window bases through the front,
-    rows[i] = (r0, r1) the stage-5 rows it replaces (pooled rows (r0 - b0 / 400) .. of its run); ``order``: the edits' snippets in the packed
-    codes buffer; ``runs``: (first base in the buffer, bases, [(skip, count, fresh_row0)]) - one front run each; ``fresh[i]``: edit i's first
-    row in the recomputed rows [R, 128]; ``edit_table`` / ``splice_table``: the device tables of orca_screen_edit_codes / _splice_rows."""
+    """The two-part route's work for one batch of items (`Edit` / `EditSet`) on an L-base window.  A bare `Edit` is one snippet; an `EditSet` is
+    one snippet per CLUSTER of its members' rows (row intervals that overlap or touch are merged).  For a list of bare `Edit`s snippet k is
+    edit k.  Per snippet k: ``item_of[k]`` its item, snippet[k] = (b0, nb) window bases through the front, rows[k] = (r0, r1) the stage-5
+    rows it replaces (pooled rows (r0 - b0 / 400) .. of its run); ``order``: the snippets in the packed codes buffer; ``runs``: (first base in
+    the buffer, bases, [(skip, count, fresh_row0)]) - one front run each; ``fresh[k]``: snippet k's first row in the recomputed rows [R, 128].
+    Device tables: ``edit_table`` / ``splice_table`` of orca_screen_edit_codes / _splice_rows (None when an item has more than one member);
+    ``snippet_table`` [S, 8] = [out_off, b0, nb, span_lo, span_cnt, 0, 0, 0] in ``order``, ``span_table`` [n, 4] = [kind, pos, len, pay_off]
+    (item by item, sorted by pos within an item; a snippet applies every span of its item that meets it, whichever cluster the span
+    belongs to), ``segments`` [S, 3] = [row_lo, row_cnt, src_row] item by item, sorted by row_lo, item i's at
+    [seg_off[i], seg_off[i + 1]) - the tables of orca_screen_edit_codes_multi / _splice_rows_multi."""
     L: int
     snippet: np.ndarray
     rows: np.ndarray
@@ -136,9 +243,14 @@ class BatchPlan:
     runs: list
     fresh: np.ndarray
     n_fresh: int
-    edit_table: np.ndarray
-    splice_table: np.ndarray
+    edit_table: Optional[np.ndarray]
+    splice_table: Optional[np.ndarray]
     payload: np.ndarray
+    item_of: np.ndarray = None
+    snippet_table: np.ndarray = None
+    span_table: np.ndarray = None
+    segments: np.ndarray = None
+    seg_off: np.ndarray = None
 
 
 def edit_rows(edit, L, margin=MARGIN_BP):
@@ -188,20 +300,63 @@ def _runs(snips, L, run_max):
     return runs + [[i] for i in alone]
 
 
+def set_clusters(item, L, margin=MARGIN_BP):
+    """The row clusters of an item: `edit_rows` of every member, intervals that overlap or touch merged - [(r0, r1)] ascending.  Rows between
+    two clusters are outside every member's cone, so they keep the reference's values."""
+    out = []
+    for e in members_of(item):                       # sorted by pos: r0 ascends
+        r0, r1 = edit_rows(e, L, margin)
+        if out and r0 <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], r1)
+        else:
+            out.append([r0, r1])
+    return [(a, b) for a, b in out]
+
+
+def _span_table(items):
+    """(span table [n, 4] int64, first span of every item [E + 1], payload): every item's members, item by item."""
+    n = sum(len(members_of(it)) for it in items)
+    spans = np.zeros((n, engine.SCREEN_SPAN_FIELDS), dtype=np.int64)
+    base = np.zeros(len(items) + 1, dtype=np.int64)
+    payload, npay, k = [], 0, 0
+    for i, it in enumerate(items):
+        for e in members_of(it):
+            po = 0
+            if e.kind == "sub":
+                po = npay
+                payload.append(e.seq)
+                npay += e.length
+            spans[k] = (engine.SCREEN_KINDS[e.kind], e.pos, e.length, po)
+            k += 1
+        base[i + 1] = k
+    return spans, base, (np.concatenate(payload) if payload else np.zeros(0, dtype=np.uint8))
+
+
+def _spans_meeting(spans, lo, hi, b0, b1):
+    """Of spans [lo, hi) (sorted by pos, disjoint) those that meet bases [b0, b1): (first, count)."""
+    pos, end = spans[lo:hi, 1], spans[lo:hi, 1] + spans[lo:hi, 2]
+    a, b = int(np.searchsorted(end, b0, side="right")), int(np.searchsorted(pos, b1, side="left"))
+    return lo + a, max(0, b - a)
+
+
 def plan_batch(edits, L, pad=PAD_BP, margin=MARGIN_BP, min_snippet=MIN_SNIPPET_BP, run_max=RUN_MAX_BP):
-    """The `BatchPlan` of ``edits`` on an L-base window (L a multiple of 400)."""
+    """The `BatchPlan` of ``edits`` (`Edit`s and `EditSet`s) on an L-base window (L a multiple of 400)."""
     if L % ROW_BP:
         raise ValueError(f"window length must be a multiple of {ROW_BP}")
     if pad < margin or pad % ROW_BP:
         raise ValueError("pad must cover the margin and be a multiple of 400")
     E = len(edits)
-    rows = np.zeros((E, 2), dtype=np.int64)
-    snips = []
+    rows_l, snips, item_of = [], [], []
+    seg_off = np.zeros(E + 1, dtype=np.int64)
     for i, e in enumerate(edits):
         e.check(L)
-        r0, r1 = edit_rows(e, L, margin)
-        rows[i] = r0, r1
-        snips.append(edit_snippet(r0, r1, L, pad, min_snippet))
+        for r0, r1 in set_clusters(e, L, margin):
+            rows_l.append((r0, r1))
+            snips.append(edit_snippet(r0, r1, L, pad, min_snippet))
+            item_of.append(i)
+        seg_off[i + 1] = len(snips)
+    S = len(snips)
+    rows = np.array(rows_l, dtype=np.int64).reshape(S, 2)
     runs_idx = _runs(snips, L, run_max)
     order = [i for r in runs_idx for i in r]
     out_off = {}
@@ -209,7 +364,7 @@ def plan_batch(edits, L, pad=PAD_BP, margin=MARGIN_BP, min_snippet=MIN_SNIPPET_B
     for i in order:
         out_off[i] = off
         off += snips[i][1] - snips[i][0]
-    fresh = np.zeros(E, dtype=np.int64)
+    fresh = np.zeros(S, dtype=np.int64)
     n_fresh = 0
     for i in order:
         fresh[i] = n_fresh
@@ -220,20 +375,21 @@ def plan_batch(edits, L, pad=PAD_BP, margin=MARGIN_BP, min_snippet=MIN_SNIPPET_B
         nb = sum(snips[i][1] - snips[i][0] for i in r)
         ranges = [(int(out_off[i] - o0 + rows[i, 0] * ROW_BP - snips[i][0]) // ROW_BP, int(rows[i, 1] - rows[i, 0]), int(fresh[i])) for i in r]
         runs.append((o0, nb, ranges))
-    payload, pay_off = [], {}
-    npay = 0
-    for i, e in enumerate(edits):
-        if e.kind == "sub":
-            pay_off[i] = npay
-            payload.append(e.seq)
-            npay += e.length
-    table = np.zeros((E, engine.SCREEN_EDIT_FIELDS), dtype=np.int64)
+    spans, span_base, payload = _span_table(edits)
+    snippet_table = np.zeros((S, engine.SCREEN_EDIT_FIELDS), dtype=np.int64)
     for k, i in enumerate(order):
-        e = edits[i]
-        table[k, :7] = (out_off[i], snips[i][0], snips[i][1] - snips[i][0], engine.SCREEN_KINDS[e.kind], e.pos, e.length, pay_off.get(i, 0))
-    splice = np.stack([rows[:, 0], rows[:, 1] - rows[:, 0], fresh], axis=1).astype(np.int64)
-    return BatchPlan(L, np.array([(b0, b1 - b0) for b0, b1 in snips], dtype=np.int64).reshape(E, 2), rows, order, runs, fresh, n_fresh, table, splice,
-                     np.concatenate(payload) if payload else np.zeros(0, dtype=np.uint8))
+        it = item_of[i]
+        lo, cnt = _spans_meeting(spans, int(span_base[it]), int(span_base[it + 1]), snips[i][0], snips[i][1])
+        snippet_table[k, :5] = (out_off[i], snips[i][0], snips[i][1] - snips[i][0], lo, cnt)
+    segments = np.stack([rows[:, 0], rows[:, 1] - rows[:, 0], fresh], axis=1).astype(np.int64).reshape(S, 3)
+    table = splice = None
+    if len(spans) == E:                              # one member per item: the tables of the single-span kernels
+        table = np.zeros((E, engine.SCREEN_EDIT_FIELDS), dtype=np.int64)
+        for k, i in enumerate(order):
+            table[k, :7] = (out_off[i], snips[i][0], snips[i][1] - snips[i][0], *spans[i])
+        splice = segments.copy()
+    return BatchPlan(L, np.array([(b0, b1 - b0) for b0, b1 in snips], dtype=np.int64).reshape(S, 2), rows, order, runs, fresh, n_fresh, table, splice,
+                     payload, np.array(item_of, dtype=np.int64), snippet_table, spans, segments, seg_off)
 
 
 def whole_window_table(edits, L):
@@ -250,12 +406,50 @@ def whole_window_table(edits, L):
     return table, (np.concatenate(payload) if payload else np.zeros(0, dtype=np.uint8))
 
 
+def whole_window_set_tables(items, L):
+    """`whole_window_table` for `Edit`s and `EditSet`s: (snippet table, span table, payload) of orca_screen_edit_codes_multi - item i's complete
+    edited window at bases [i L, (i + 1) L) of the output, carrying all of the item's spans."""
+    for it in items:
+        it.check(L)
+    spans, base, payload = _span_table(items)
+    table = np.zeros((len(items), engine.SCREEN_EDIT_FIELDS), dtype=np.int64)
+    for i in range(len(items)):
+        table[i, :5] = (i * L, 0, L, base[i], base[i + 1] - base[i])
+    return table, spans, payload
+
+
 # ---- scores ---------------------------------------------------------------------------------------------------------------------------------
 def scores_host(maps, ref_map):
     """The scores of `ScreenResult` from alt maps [E, n, n] and the reference map [n, n] (fp64 host restatement of orca_screen_scores):
     d = |alt - ref|; delta_profile[e, i] = mean_j d[e, i, j]; delta_abs_mean[e] = mean_ij d[e, i, j]; delta_abs_max[e] = max_ij d[e, i, j]."""
     d = np.abs(np.asarray(maps, dtype=np.float64) - np.asarray(ref_map, dtype=np.float64)[None])
     return d.mean(axis=2), d.mean(axis=(1, 2)), d.max(axis=(1, 2))
+
+
+def check_regions(regions, n):
+    """``regions`` as a [K, 4] int32 array of half-open bin rectangles (i0, i1, j0, j1), 0 <= i0 < i1 <= n and the same for j, 1 <= K <= 64."""
+    try:
+        r = np.array([[int(v) for v in rect] for rect in regions], dtype=np.int64)
+    except (TypeError, ValueError):
+        raise ValueError("regions: a list of (i0, i1, j0, j1) bin rectangles") from None
+    if r.ndim != 2 or r.shape[1] != 4 or not 1 <= r.shape[0] <= 64:
+        raise ValueError("regions: 1 to 64 rectangles (i0, i1, j0, j1)")
+    for k, (i0, i1, j0, j1) in enumerate(r):
+        if not (0 <= i0 < i1 <= n and 0 <= j0 < j1 <= n):
+            raise ValueError(f"region {k} = rows [{i0}, {i1}) x columns [{j0}, {j1}): half open, non-empty, inside the map's {n} bins")
+    return r.astype(np.int32)
+
+
+def region_scores_host(maps, ref_map, regions):
+    """The region scores of `ScreenResult` from alt maps [E, n, n] and the reference map [n, n] (fp64 host restatement of
+    orca_screen_region_scores): with d = alt - ref, (delta_region [E, K], delta_region_abs [E, K]) = the means of d and of |d| over rows
+    [i0, i1) x columns [j0, j1) of every rectangle (i0, i1, j0, j1)."""
+    ref = np.asarray(ref_map, dtype=np.float64)
+    d = np.asarray(maps, dtype=np.float64) - ref[None]
+    r = check_regions(regions, ref.shape[0])
+    sg = np.stack([d[:, i0:i1, j0:j1].mean(axis=(1, 2)) for i0, i1, j0, j1 in r], axis=1)
+    ab = np.stack([np.abs(d[:, i0:i1, j0:j1]).mean(axis=(1, 2)) for i0, i1, j0, j1 in r], axis=1)
+    return sg, ab
 
 
 @dataclass
@@ -268,7 +462,9 @@ class ScreenResult:
       delta_abs_max    [E]            delta_abs_max[e] = max_ij d[e, i, j]
       delta_1d         [E, num_1d, n] alt 1-D head - ref_1d (signed; None without a 1-D head)
       maps             [E, n, n]      the alt maps (``keep_maps=True`` only)
-    `scores_host` computes the three map scores from maps on the host."""
+      delta_region     [E, K]         mean of alt - ref (signed) over rectangle k of ``regions`` (None without regions)
+      delta_region_abs [E, K]         mean of |alt - ref| over rectangle k (None without regions)
+    `scores_host` computes the three map scores from maps on the host, `region_scores_host` the two region scores."""
     ref_map: torch.Tensor
     ref_1d: Optional[torch.Tensor]
     delta_profile: torch.Tensor
@@ -277,6 +473,8 @@ class ScreenResult:
     delta_1d: Optional[torch.Tensor] = None
     maps: Optional[torch.Tensor] = None
     edits: list = field(default_factory=list)
+    delta_region: Optional[torch.Tensor] = None
+    delta_region_abs: Optional[torch.Tensor] = None
 
 
 # ---- the screen -----------------------------------------------------------------------------------------------------------------------------
@@ -334,10 +532,15 @@ class _Screen:
         """Maps of the edited windows through Net's own Encoder and Decoder_1m (the module guards apply as in Net.forward)."""
         if not edits:
             return self._decode(self.net._enc.forward_codes(self.window[None]))
-        table, payload = whole_window_table(edits, self.L)
         codes = torch.empty(len(edits) * self.L, dtype=torch.uint8, device=self.dev)
-        pay = self._upload(payload, torch.uint8) if payload.size else None
-        engine.screen_edit_codes(self.ctx, self.window, table, self._upload(table, torch.int64), pay, codes)
+        if all(isinstance(e, Edit) for e in edits):
+            table, payload = whole_window_table(edits, self.L)
+            pay = self._upload(payload, torch.uint8) if payload.size else None
+            engine.screen_edit_codes(self.ctx, self.window, table, self._upload(table, torch.int64), pay, codes)
+        else:
+            table, spans, payload = whole_window_set_tables(edits, self.L)
+            pay = self._upload(payload, torch.uint8) if payload.size else None
+            engine.screen_edit_codes_multi(self.ctx, self.window, table, spans, pay, codes)
         return self._decode(self.net._enc.forward_codes(codes.view(len(edits), self.L)))
 
     def reference_rows(self):
@@ -352,20 +555,28 @@ class _Screen:
         total = int(p.snippet[:, 1].sum())
         codes = torch.empty(total, dtype=torch.uint8, device=self.dev)
         pay = self._upload(p.payload, torch.uint8) if p.payload.size else None
-        engine.screen_edit_codes(self.ctx, self.window, p.edit_table, self._upload(p.edit_table, torch.int64), pay, codes)
+        single = all(isinstance(e, Edit) for e in edits)             # bare edits: the single-span kernels, as ever
+        if single:
+            engine.screen_edit_codes(self.ctx, self.window, p.edit_table, self._upload(p.edit_table, torch.int64), pay, codes)
+        else:
+            engine.screen_edit_codes_multi(self.ctx, self.window, p.snippet_table, p.span_table, pay, codes)
         fresh = torch.empty((p.n_fresh, 128), dtype=torch.float32, device=self.dev)
         for o0, nb, ranges in p.runs:
             enc.front4_ranges(codes[o0: o0 + nb], False, ranges, fresh)
         rows = torch.empty((len(edits), self.n5, 128), dtype=torch.float32, device=self.dev)
-        engine.screen_splice_rows(self.ctx, s5_ref, fresh, self._upload(p.splice_table, torch.int64), rows)
+        if single:
+            engine.screen_splice_rows(self.ctx, s5_ref, fresh, self._upload(p.splice_table, torch.int64), rows)
+        else:
+            engine.screen_splice_rows_multi(self.ctx, s5_ref, fresh, p.segments, p.seg_off, rows)
         out = enc.back5_batch(rows)
+        self.stats["segments"] += len(p.segments)
         self.stats["front_runs"] += len(p.runs)
         self.stats["front_bases"] += total
         return self._decode(out)
 
 
-def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None):
-    """Score ``edits`` (a list of `Edit`) of one window with the 1 Mb model: a `ScreenResult`.
+def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regions=None):
+    """Score ``edits`` (a list of `Edit` and `EditSet`, one row of every result tensor each) of one window with the 1 Mb model: a `ScreenResult`.
 
     ``model``: an ``H1esc_1M`` / ``Hff_1M`` container or a bare ``orca_modules.Net``.  ``window``: the window's base codes, a [L] uint8 tensor on
     the MI355X, or ``(genome, chrom, start)`` / ``(genome, chrom, start, L)`` for a `genome.PackedGenome` / `TwoBitGenome` resident there
@@ -373,18 +584,21 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None):
     reference's ``pred_1m``).  ``batch``: edits per batch.  ``keep_maps``: also return every alt map.  ``stats``: a dict that receives
     counters - ``route`` ("two_part" / "whole_window"), ``two_part_batches``, ``whole_window_batches``, ``range_fallback_batches`` (batches
     redone on the whole-window route in the range-safe arithmetic after the fp16-range check fired), ``range_fallback_reference`` (the
-    reference itself tripped: every batch went that way), ``front_runs``, ``front_bases``, ``edits``."""
+    reference itself tripped: every batch went that way), ``front_runs``, ``front_bases``, ``edits``, ``set_items`` (items that are an
+    `EditSet`), ``segments`` ((snippet, row range) segments planned on the two-part route: one per bare edit, one per cluster of a set).
+    ``regions``: up to 64 half-open bin rectangles (i0, i1, j0, j1) for `ScreenResult.delta_region` / ``delta_region_abs``."""
     net = _net_of(model)
     win = _window_codes(window)
     edits = list(edits)
     for e in edits:
-        if not isinstance(e, Edit):
-            raise TypeError("edits: a list of screen.Edit")
+        if not isinstance(e, (Edit, EditSet)):
+            raise TypeError("edits: a list of screen.Edit and screen.EditSet")
         e.check(win.numel())
     if batch <= 0:
         raise ValueError("batch must be positive")
+    rects = None if regions is None else check_regions(regions, win.numel() // 4000)
     st = {"route": None, "two_part_batches": 0, "whole_window_batches": 0, "range_fallback_batches": 0, "range_fallback_reference": False,
-          "front_runs": 0, "front_bases": 0, "edits": len(edits)}
+          "front_runs": 0, "front_bases": 0, "edits": len(edits), "set_items": sum(isinstance(e, EditSet) for e in edits), "segments": 0}
     sc = _Screen(net, win, st)
     E, n, dev = len(edits), sc.n, sc.dev
     two_part = net._enc.two_part_ok()
@@ -411,6 +625,9 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None):
                            torch.zeros(E, dtype=torch.float32, device=dev),
                            torch.zeros((E, sc.num_1d, n), dtype=torch.float32, device=dev) if sc.num_1d else None,
                            torch.zeros((E, n, n), dtype=torch.float32, device=dev) if keep_maps else None, edits)
+        if rects is not None:
+            res.delta_region = torch.zeros((E, len(rects)), dtype=torch.float32, device=dev)
+            res.delta_region_abs = torch.zeros((E, len(rects)), dtype=torch.float32, device=dev)
         for i0 in range(0, E, batch):
             chunk = edits[i0: i0 + batch]
             if two_part:
@@ -434,6 +651,8 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None):
             res.delta_profile[i0:i1] = prof
             res.delta_abs_mean[i0:i1] = mean
             res.delta_abs_max[i0:i1] = amax
+            if rects is not None:
+                res.delta_region[i0:i1], res.delta_region_abs[i0:i1] = engine.screen_region_scores(sc.ctx, maps, ref_map, rects)
             if h is not None:
                 torch.sub(h, ref_1d[None], out=res.delta_1d[i0:i1])
             if keep_maps:

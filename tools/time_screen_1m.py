@@ -9,6 +9,11 @@ Both routes' maps are compared on the first 64 edits (2e-5).  JSON on stdout and
 
     python tools/time_screen_1m.py                          # B = 16 and 64, 2 alternated repetitions
     python tools/time_screen_1m.py --screen-only --batches 64 --reps 1 --out ''     # what a profiler run wraps
+    python tools/time_screen_1m.py --pairs 50 --haplotype 400 --batches 64          # compound edits, into profiles/screen_1m_sets.json
+
+Compound edits (screen.EditSet), items per second against the same edited windows through model.net:
+  --pairs N      every pair of N 4 kb mask tiles of bases [100 000, ..) with N of bases [600 000, ..): N x N sets of two members
+  --haplotype M  --haplotypes H sets (64 by default) of M SNVs each, drawn uniformly from --haplotype-span bases in the window's middle
 """
 import argparse
 import json
@@ -58,17 +63,74 @@ def timed(fn):
     return time.perf_counter() - t0, r
 
 
+def time_sets(a, model, win, c, dev):
+    """The --pairs / --haplotype workloads: items/s of the screen and of the naive route, alternated, per batch size."""
+    rep = {"device": torch.cuda.get_device_name(dev)}
+    work = {}
+    if a.pairs:
+        ta = S.tile_edits("mask", 4000, 4000, 100_000, 100_000 + 4000 * a.pairs)
+        tb = S.tile_edits("mask", 4000, 4000, 600_000, 600_000 + 4000 * a.pairs)
+        work[f"pairs_{a.pairs}x{a.pairs}_mask_4kb"] = S.pair_edits(ta, tb)[0]
+    if a.haplotype:
+        rs = np.random.RandomState(17)
+        lo = (L - a.haplotype_span) // 2
+        sets = []
+        for _ in range(a.haplotypes):
+            pos = lo + np.sort(rs.choice(a.haplotype_span, a.haplotype, replace=False))
+            sets.append(S.snv_set(c, [(int(p), int(c[p]), (int(c[p]) + 1 + int(p) % 3) % 4 if c[p] < 4 else int(p) % 4) for p in pos]))
+        work[f"haplotype_{a.haplotype}_snvs_in_{a.haplotype_span}_bp"] = sets
+    for name, items in work.items():
+        st = {}
+        rs_ = S.screen_1m(model, win, items[:64], batch=64, keep_maps=True, stats=st)            # warm-up and cross-check
+        row = {"items": len(items), "route": st["route"], "segments_per_item": round(st["segments"] / max(1, len(items[:64])), 2),
+               "front_bases_per_item": round(st["front_bases"] / max(1, len(items[:64])))}
+        if not a.screen_only:
+            _, mn = naive(model, win, items[:64], 64, keep_maps=True)
+            row["maps_maxabs_screen_vs_naive"] = float((rs_.maps - mn).abs().max())
+            assert row["maps_maxabs_screen_vs_naive"] < 2e-5, row
+        del rs_
+        for B in [int(b) for b in a.batches.split(",")]:
+            ts, tn = [], []
+            for _ in range(a.reps):
+                ts.append(timed(lambda: S.screen_1m(model, win, items, batch=B))[0])
+                if not a.screen_only:
+                    tn.append(timed(lambda: naive(model, win, items, B))[0])
+            r = {"screen_s": [round(t, 3) for t in ts], "screen_items_per_s": round(len(items) / min(ts), 1)}
+            if tn:
+                r.update({"naive_s": [round(t, 3) for t in tn], "naive_items_per_s": round(len(items) / min(tn), 1), "speedup": round(min(tn) / min(ts), 2)})
+            row[f"B{B}"] = r
+        rep[name] = row
+        print(json.dumps({name: row}), flush=True)
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="16,64")
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--screen-only", action="store_true")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "screen_1m.json"))
+    ap.add_argument("--pairs", type=int, default=0, help="N: time the N x N pairs of two lists of N 4 kb mask tiles")
+    ap.add_argument("--haplotype", type=int, default=0, help="M: time sets of M SNVs")
+    ap.add_argument("--haplotypes", type=int, default=64)
+    ap.add_argument("--haplotype-span", type=int, default=L)
+    ap.add_argument("--commit", default="", help="recorded in the report")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     model = M.H1esc_1M(synthetic_seed=0).to(dev)
     c = window()
     win = torch.from_numpy(c).to(dev)
+    if a.pairs or a.haplotype:
+        rep = {"workload": "H1esc_1M synthetic, 1 Mb window, compound edits (screen.EditSet); naive = the same edited windows through model.net",
+               "commit": a.commit}
+        rep.update(time_sets(a, model, win, c, dev))
+        print(json.dumps(rep))
+        out = a.out if a.out != ap.get_default("out") else os.path.join(os.path.dirname(a.out), "screen_1m_sets.json")
+        if out:
+            os.makedirs(os.path.dirname(out), exist_ok=True)
+            with open(out, "w") as f:
+                json.dump(rep, f, indent=1)
+        return
     edits = S.saturation_edits(c, 499_500, 500_500) + S.tile_edits("mask", 4000, 4000, 0, L)
     rep = {"workload": f"H1esc_1M synthetic, 1 Mb window, {len(edits)} edits (saturation SNVs of 1 kb + 250 4 kb mask tiles)", "edits": len(edits)}
     # warm-up (library load, nets, workspaces) and the cross-check of both routes' maps
