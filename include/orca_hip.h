@@ -291,6 +291,26 @@ int orca_screen_splice_rows_multi(orca_ctx* ctx, const float* ref, int64_t n5, c
 int orca_screen_region_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* rects,
                               const int32_t* rects_host, int K, float* mean_signed, float* mean_abs);
 
+/* Insertions and deletions (screen.Edit "del" / "ins").  The alt window of an item is a list of pieces in ALT coordinates over the CONTEXT, the window
+ * followed by its right flank (C bases).  Tables come twice as above (device copy for the kernel, host copy checked here before any launch).
+ *   orca_screen_assemble_codes  `table` (n_snippets x 8 int64, out_off ascending from 0 without gaps, ending at `total`) = [out_off, a0, nb, piece_lo,
+ *                               piece_cnt, 0, 0, 0], a0 the snippet's first alt base; `pieces` (n_pieces x 4 int64) = [dst, kind, src, len], pieces
+ *                               [piece_lo, piece_lo + piece_cnt) of a snippet sorted by dst and pairwise disjoint.  kind 0: context [src, src + len)
+ *                               forward; 1: its reverse complement (N stays N); 2: payload [src, src + len); 3: N.  An alt base no piece covers and a
+ *                               read past the context give N; a piece past the payload is refused.  One [0, L) snippet per item assembles whole windows
+ *   orca_screen_gather_rows     B row images out[B][n5][128].  `segments` (n_segments x 4 int64) = [row_lo, row_cnt, source, src_row]; image b owns
+ *                               segments [seg_off[b], seg_off[b + 1]), sorted by row_lo and disjoint.  source -1: rows [src_row, ..) of `fresh`; -2: rows
+ *                               [src_row, ..) of `ref`; 0 <= p < P: row row_lo + t = MaxPool1d(5) of rows src_row + 5 t .. + 4 of phase entry p.
+ *                               `entries`: DEVICE array of P pointers to [entry_rows[p]][128] float rows (16-byte aligned), `entry_rows` the counts
+ *                               (device, and the host copy that is checked).  Rows in no segment are `ref` at their own index.  Pooled rows are bit for
+ *                               bit orca_rows_pool5_into's */
+int orca_screen_assemble_codes(orca_ctx* ctx, const uint8_t* context, int64_t C, const int64_t* table, const int64_t* table_host, int n_snippets,
+                               const int64_t* pieces, const int64_t* pieces_host, int64_t n_pieces, const uint8_t* payload, int64_t n_payload, uint8_t* out,
+                               int64_t total);
+int orca_screen_gather_rows(orca_ctx* ctx, const float* ref, int64_t n5, const float* fresh, int64_t n_fresh, const float* const* entries,
+                            const int64_t* entry_rows, const int64_t* entry_rows_host, int P, const int64_t* segments, const int64_t* segments_host,
+                            int64_t n_segments, const int64_t* seg_off, const int64_t* seg_off_host, int B, float* out);
+
 /* Number of 4 kb bins Encoder emits for an L-bp input (floor through the
  * 4,4,5,5,5,2 pooling chain). */
 int64_t orca_encoder_num_bins(int64_t L);

@@ -228,3 +228,112 @@ static __global__ void __launch_bounds__(256) screen_region_scores_kernel(const 
     abs_out[(long)b * K + k] = (float)(ta / cnt);
   }
 }
+
+// ---- insertions and deletions (screen.Edit "del" / "ins"): the edited bases from a piece list, the row images from several sources ---------------------
+// The alt window of an item is a list of PIECES in alt coordinates; the context is the window followed by its right flank.
+// snippet table (int64 per snippet, SCREEN_EDIT_FIELDS fields; include/orca_hip.h: orca_screen_assemble_codes)
+//   [0] out_off  [1] a0  first ALT base of the snippet  [2] nb  [3] piece_lo  first piece of this snippet in the piece table  [4] piece_cnt
+// piece table (int64 per piece, SCREEN_PIECE_FIELDS fields): [0] dst  first alt base  [1] kind  [2] src  [3] len - a snippet's pieces are sorted by
+// dst and pairwise disjoint.  kind 0: context bases [src, src + len) forward; 1: their reverse complement (alt base dst + t is the complement of
+// context[src + len - 1 - t], N stays N); 2: payload codes [src, src + len); 3: N.
+#define SCREEN_PIECE_FIELDS 4
+
+// one thread per output base: binary search of its snippet, binary search of the snippet's pieces.  The piece range is clipped to the table; a base no
+// piece covers and a read outside the context / the payload give N.
+static __global__ void screen_assemble_codes_kernel(const unsigned char* __restrict__ cx, long C, const long long* __restrict__ tab, int ns,
+                                                    const long long* __restrict__ pieces, long npieces, const unsigned char* __restrict__ pay, long npay,
+                                                    unsigned char* __restrict__ out, long total) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  int lo = 0, hi = ns - 1;
+  while (lo < hi) {                                  // last snippet with out_off <= t
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[(long)mid * SCREEN_EDIT_FIELDS] <= t) lo = mid; else hi = mid - 1;
+  }
+  const long long* e = tab + (long)lo * SCREEN_EDIT_FIELDS;
+  const long w = (long)e[1] + (t - (long)e[0]);
+  unsigned c = 4u;
+  long s0 = (long)e[3], s1 = (long)e[3] + (long)e[4];
+  s0 = s0 < 0 ? 0 : s0;
+  s1 = s1 > npieces ? npieces : s1;
+  if (s0 < s1) {
+    long a = s0, b = s1 - 1;
+    while (a < b) {                                  // last piece with dst <= w (the first one when none is)
+      const long mid = (a + b + 1) >> 1;
+      if ((long)pieces[mid * SCREEN_PIECE_FIELDS] <= w) a = mid; else b = mid - 1;
+    }
+    const long long* pc = pieces + a * SCREEN_PIECE_FIELDS;
+    const long dst = (long)pc[0], src = (long)pc[2], len = (long)pc[3];
+    if (w >= dst && w - dst < len) {
+      const long k = w - dst;
+      if (pc[1] == 0) {
+        const long p = src + k;
+        c = (p >= 0 && p < C) ? cx[p] : 4u;
+      } else if (pc[1] == 1) {
+        const long p = src + len - 1 - k;
+        const unsigned s = (p >= 0 && p < C) ? cx[p] : 4u;
+        c = s < 4u ? 3u - s : 4u;                        // A<->T, C<->G; N stays N
+      } else if (pc[1] == 2) {
+        const long p = src + k;
+        c = (p >= 0 && p < npay) ? pay[p] : 4u;
+      }
+    }
+  }
+  out[t] = (unsigned char)(c > 4u ? 4u : c);
+}
+
+// segment table (int64 per segment, SCREEN_GATHER_FIELDS fields): [row_lo, row_cnt, source, src_row]; image b owns segments [seg_off[b], seg_off[b + 1]),
+// sorted by row_lo and disjoint.  source -1: rows [src_row, ..) of `fresh`; -2: rows [src_row, ..) of `ref`; p >= 0: row row_lo + t is the MaxPool1d(5) of
+// rows src_row + 5 t .. + 4 of phase entry p (`entries[p]`, `entry_rows[p]` rows of 128 floats).  A row in no segment is `ref` at its own index.
+// One thread per 16-byte unit of the output [B][n5][128].  The segment range is clipped to the table, every source row to its buffer (a row that
+// would leave it is `ref` at its own index).  The pooling expression is rows_pool5_into_kernel's (p16_planes.h): the same bits.
+#define SCREEN_GATHER_FIELDS 4
+
+static __global__ void screen_gather_rows_kernel(const f32x4* __restrict__ ref, long n5, const f32x4* __restrict__ fresh, long nfresh,
+                                                 const f32x4* const* __restrict__ entries, const long long* __restrict__ entry_rows, int P,
+                                                 const long long* __restrict__ seg, long nseg, const long long* __restrict__ seg_off, int B,
+                                                 f32x4* __restrict__ out) {
+  const long u = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long per = n5 * 32;
+  if (u >= (long)B * per) return;
+  const int b = (int)(u / per);
+  const long r = (u - (long)b * per) >> 5, q = u & 31;
+  long s0 = (long)seg_off[b], s1 = (long)seg_off[b + 1];
+  s0 = s0 < 0 ? 0 : s0;
+  s1 = s1 > nseg ? nseg : s1;
+  const f32x4* from = ref + r * 32 + q;
+  bool pool = false;
+  if (s0 < s1) {
+    long a = s0, z = s1 - 1;
+    while (a < z) {
+      const long mid = (a + z + 1) >> 1;
+      if ((long)seg[SCREEN_GATHER_FIELDS * mid] <= r) a = mid; else z = mid - 1;
+    }
+    const long long* g = seg + SCREEN_GATHER_FIELDS * a;
+    const long r0 = (long)g[0], cnt = (long)g[1], source = (long)g[2], k = r - r0;
+    if (r >= r0 && k < cnt) {
+      if (source == -1) {
+        const long s = (long)g[3] + k;
+        if (s >= 0 && s < nfresh) from = fresh + s * 32 + q;
+      } else if (source == -2) {
+        const long s = (long)g[3] + k;
+        if (s >= 0 && s < n5) from = ref + s * 32 + q;
+      } else if (source >= 0 && source < P) {
+        const long s = (long)g[3] + 5 * k;
+        if (s >= 0 && s + 5 <= (long)entry_rows[source]) {
+          from = entries[source] + s * 32 + q;
+          pool = true;
+        }
+      }
+    }
+  }
+  f32x4 v = from[0];
+  if (pool) {
+#pragma unroll
+    for (int j = 1; j < 5; ++j) {
+      const f32x4 x = from[j * 32];
+      v.x = fmaxf(v.x, x.x); v.y = fmaxf(v.y, x.y); v.z = fmaxf(v.z, x.z); v.w = fmaxf(v.w, x.w);
+    }
+  }
+  out[u] = v;
+}

@@ -712,6 +712,59 @@ def screen_splice_rows_multi(ctx, ref, fresh, segments_host, seg_off_host, out):
     return out
 
 
+# insertions and deletions (orca_screen_assemble_codes, orca_screen_gather_rows)
+SCREEN_PIECE_FIELDS = 4         # int64 per piece: dst (alt base), kind, src, len
+SCREEN_PIECE_KINDS = {"fwd": 0, "rc": 1, "payload": 2, "n": 3}
+SCREEN_GATHER_FIELDS = 4        # int64 per segment: row_lo, row_cnt, source, src_row
+SCREEN_SRC_FRESH, SCREEN_SRC_REF = -1, -2
+
+
+def screen_assemble_codes(ctx, context, table_host, pieces_host, payload, out):
+    """Alt bases from piece lists over ``context`` [C] uint8 (the window followed by its right flank) into ``out`` [total]
+    (orca_screen_assemble_codes).  ``table_host`` [k, 8] int64 numpy = [out_off, a0, nb, piece_lo, piece_cnt, 0, 0, 0] (a0 in alt coordinates);
+    ``pieces_host`` [n, 4] int64 numpy = [dst, kind, src, len], kind 0 context forward, 1 its reverse complement, 2 payload, 3 N."""
+    context, out = _on_device(context, "context", torch.uint8), _on_device(out, "out", torch.uint8)
+    if context.dim() != 1 or out.dim() != 1:
+        raise ValueError("context, out: [C] and [total] uint8")
+    if payload is not None:
+        payload = _on_device(payload, "payload", torch.uint8)
+    t, s = _host_table(table_host, np.int64, SCREEN_EDIT_FIELDS, "snippet table"), _host_table(pieces_host, np.int64, SCREEN_PIECE_FIELDS, "piece table")
+    td, sd = torch.from_numpy(t).to(context.device), torch.from_numpy(s).to(context.device)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_assemble_codes(ctx.handle, _dev_p(context), context.numel(), _dev_p(td), _np_p(t), t.shape[0], _dev_p(sd), _np_p(s), s.shape[0],
+                                                 ctypes.c_void_p(0) if payload is None else _dev_p(payload), 0 if payload is None else payload.numel(),
+                                                 _dev_p(out), out.numel()), "orca_screen_assemble_codes")
+    return out
+
+
+def screen_gather_rows(ctx, ref, fresh, entries, segments_host, seg_off_host, out):
+    """B stage-5 row images ``out`` [B, n5, 128] (orca_screen_gather_rows): for every segment [row_lo, row_cnt, source, src_row] of image b
+    (``segments_host`` [s, 4] int64 numpy, image b's at [seg_off_host[b], seg_off_host[b + 1])) rows [row_lo, row_lo + row_cnt) come from rows
+    [src_row, ..) of ``fresh`` [R, 128] (source -1) or of ``ref`` [n5, 128] (-2), or are the MaxPool1d(5) of rows src_row + 5 t .. + 4 of
+    ``entries[source]`` (a list of [n, 128] float32 tensors: stage-4 phase entries); every other row is ``ref`` at its own index."""
+    ref, fresh, out = _on_device(ref, "ref", torch.float32), _on_device(fresh, "fresh", torch.float32), _on_device(out, "out", torch.float32)
+    if ref.dim() != 2 or ref.shape[1] != 128 or fresh.dim() != 2 or fresh.shape[1] != 128:
+        raise ValueError("ref, fresh: [n,128] float32")
+    entries = [_on_device(e, "a phase entry", torch.float32) for e in entries]
+    if any(e.dim() != 2 or e.shape[1] != 128 or e.data_ptr() % 16 for e in entries):
+        raise ValueError("phase entries: [n,128] float32, 16-byte aligned")
+    n5 = ref.shape[0]
+    g = _host_table(segments_host, np.int64, SCREEN_GATHER_FIELDS, "segment table")
+    o = np.ascontiguousarray(seg_off_host, dtype=np.int64)
+    if o.ndim != 1 or o.size < 1:
+        raise ValueError("segment offsets: [B + 1] int64")
+    B = o.size - 1
+    if out.dim() != 3 or tuple(out.shape) != (B, n5, 128):
+        raise ValueError(f"out: a contiguous [{B},{n5},128] float32 ROCm tensor, B + 1 = the number of segment offsets")
+    ptrs = np.array([e.data_ptr() for e in entries], dtype=np.int64)
+    cnts = np.array([e.shape[0] for e in entries], dtype=np.int64)
+    gd, od, pd, cd = (torch.from_numpy(a).to(ref.device) for a in (g, o, ptrs, cnts))
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_gather_rows(ctx.handle, _dev_p(ref), n5, _dev_p(fresh), fresh.shape[0], _dev_p(pd), _dev_p(cd), _np_p(cnts), len(entries),
+                                              _dev_p(gd), _np_p(g), g.shape[0], _dev_p(od), _np_p(o), B, _dev_p(out)), "orca_screen_gather_rows")
+    return out
+
+
 def screen_region_scores(ctx, alt, ref, rects_host):
     """alt [B, n, n] (any batch stride, rows contiguous) against ref [n, n] over the K rectangles ``rects_host`` [K, 4] = (i0, i1, j0, j1), half open:
     (mean of alt - ref [B, K], mean of |alt - ref| [B, K]) (orca_screen_region_scores)."""

@@ -21,6 +21,14 @@ out at once, `pair_edits` for epistasis).  It is still length-preserving, so the
 change, and no others.  The rows of the members are merged into clusters, each cluster is one snippet, and the item's row image takes one
 row range per cluster (orca_screen_edit_codes_multi, orca_screen_splice_rows_multi).  ``regions`` adds the signed and the absolute mean of
 alt - ref over chosen bin rectangles (orca_screen_region_scores).
+
+``Edit("del", ...)`` and ``Edit("ins", ...)`` change the length.  The alt window is still L bases and starts where the window starts: it is the
+first L bases of (edited window ++ right flank ++ N ...), so a net deletion is refilled from the flank and a net insertion pushes the tail
+out.  Behind a length change the same bases sit at another offset s (context position - alt position).  Stage 4 is translation-covariant on
+the 80-base grid, so their rows are the MaxPool1d(5) of stage 4's output on the CONTEXT (window ++ flank) at phase s mod 80
+(`sv.Stage4Cache`), or plainly the reference's rows s / 400 further on when 400 divides s; only the junctions and the alt window's right
+end go through the front again.  A batch that holds such an item takes its bases from piece lists (orca_screen_assemble_codes) and its rows
+from a table of sources (orca_screen_gather_rows); `plan_batch` states the rule.
 """
 from dataclasses import dataclass, field
 from typing import Optional
@@ -40,7 +48,9 @@ MIN_SNIPPET_BP = sv.S4_MIN_SNIPPET_BP
 # runs alone
 RUN_MAX_BP = 256_000
 N_CODE = 4
-KINDS = ("sub", "mask", "inv")
+KINDS = ("sub", "mask", "inv", "del", "ins")
+LEN_KINDS = ("del", "ins")                # the kinds that change the length
+FLANK_BP = 8_000                          # bases read behind a (genome, chrom, start) window for the refill after deletions
 _ACGTN = {c: i for i, c in enumerate("ACGTN")}
 
 
@@ -57,17 +67,35 @@ def _codes_of(seq):
 
 
 class Edit:
-    """A length-preserving edit of a window, ``pos`` relative to the window's first base:
+    """An edit of a window, ``pos`` relative to the window's first base:
       ``Edit("sub", pos, length, seq)``  bases [pos, pos + length) replaced by ``seq`` (an ACGTN string or codes 0..4 = A, C, G, T, N)
       ``Edit("mask", pos, length)``      the span set to N (code 4: the reference's 0.25 row)
-      ``Edit("inv", pos, length)``       the span reverse-complemented in place (N stays N)"""
+      ``Edit("inv", pos, length)``       the span reverse-complemented in place (N stays N)
+      ``Edit("del", pos, length)``       bases [pos, pos + length) removed, pos >= 1: the alt window keeps the window's first base (it is anchored
+                                         there, and refilled from the right flank)
+      ``Edit("ins", pos, seq)``          ``seq`` inserted in front of base ``pos`` (0 <= pos <= L); it consumes no base: ``length`` is 0
+    The first three keep the length; ``removed`` / ``inserted`` are the bases a ``del`` / ``ins`` takes out / puts in."""
 
     __slots__ = ("kind", "pos", "length", "seq")
 
     def __init__(self, kind, pos, length, seq=None):
         if kind not in KINDS:
             raise ValueError(f"edit kind must be one of {KINDS}, got {kind!r}")
+        if kind == "ins":
+            if seq is None:
+                seq, length = length, 0                                   # Edit("ins", pos, seq)
+            seq = _codes_of(seq)
+            if seq.size == 0:
+                raise ValueError("an insertion needs a non-empty seq")
+            if int(length) not in (0, seq.size):
+                raise ValueError(f"insertion of {seq.size} bases with a length of {length}")
+            if int(pos) < 0:
+                raise ValueError(f"edit position must be >= 0, got {pos}")
+            self.kind, self.pos, self.length, self.seq = kind, int(pos), 0, seq
+            return
         pos, length = int(pos), int(length)
+        if kind == "del" and pos == 0 and length > 0:
+            raise ValueError("a deletion starts at base 1 or later: the alt window keeps the window's first base")
         if length <= 0:
             raise ValueError(f"edit length must be positive, got {length}")
         if pos < 0:
@@ -86,19 +114,31 @@ class Edit:
     def end(self):
         return self.pos + self.length
 
+    @property
+    def removed(self):
+        return self.length if self.kind == "del" else 0
+
+    @property
+    def inserted(self):
+        return int(self.seq.size) if self.kind == "ins" else 0
+
     def check(self, L):
         if self.end > L:
             raise ValueError(f"edit [{self.pos}, {self.end}) leaves the window of {L} bases")
 
     def __repr__(self):
-        s = "" if self.seq is None else ", " + "".join("ACGTN"[c] for c in self.seq[:16]) + ("..." if self.length > 16 else "")
+        s = "" if self.seq is None else ", " + "".join("ACGTN"[c] for c in self.seq[:16]) + ("..." if self.seq.size > 16 else "")
+        if self.kind == "ins":
+            return f"Edit('ins', {self.pos}{s})"
         return f"Edit({self.kind!r}, {self.pos}, {self.length}{s})"
 
 
 class EditSet:
     """A compound edit: ``EditSet(edits, name=None)``, a non-empty immutable sequence of pairwise disjoint `Edit`s of one window that are applied
     together.  All positions are in the unedited window's coordinates (an ``inv`` member reads its source from the unedited window - the members
-    are disjoint, so nothing else could be meant).  The members are kept sorted by ``pos``: the order they are given in changes nothing."""
+    are disjoint, so nothing else could be meant).  The members are kept sorted by ``pos``, an ``ins`` before a span that starts at its ``pos``:
+    the order they are given in changes nothing.  An ``ins`` may sit at a span's first base or right behind its last one, not strictly inside
+    it, and no two ``ins`` share a ``pos``."""
 
     __slots__ = ("edits", "name")
 
@@ -109,10 +149,12 @@ class EditSet:
         for e in edits:
             if not isinstance(e, Edit):
                 raise TypeError(f"an EditSet's members are screen.Edit, got {e!r}")
-        edits.sort(key=lambda e: e.pos)
+        edits.sort(key=lambda e: (e.pos, e.kind != "ins"))
         for a, b in zip(edits, edits[1:]):
             if b.pos < a.end:
                 raise ValueError(f"an EditSet's members must be disjoint: {a!r} and {b!r} overlap")
+            if a.kind == "ins" and b.kind == "ins" and a.pos == b.pos:
+                raise ValueError(f"an EditSet takes one insertion per position: {a!r} and {b!r}")
         object.__setattr__(self, "edits", tuple(edits))
         object.__setattr__(self, "name", name)
 
@@ -134,7 +176,7 @@ class EditSet:
 
     @property
     def end(self):
-        return self.edits[-1].end
+        return max(e.end for e in self.edits)
 
     def check(self, L):
         for e in self.edits:
@@ -154,12 +196,48 @@ def members_of(item):
     raise TypeError(f"a screen item is a screen.Edit or a screen.EditSet, got {item!r}")
 
 
-def apply_edit(codes, edit):
-    """The edited window as numpy uint8 (host restatement of the device kernels; ``codes``: [L] codes 0..4; ``edit``: an `Edit` or an `EditSet`,
-    whose members all read the unedited window)."""
+def changes_length(item):
+    """True if a member of the item is a ``del`` or an ``ins`` (a balanced set included)."""
+    return any(e.kind in LEN_KINDS for e in members_of(item))
+
+
+def shift_of(item):
+    """Bases removed minus bases inserted: what lies behind the item's last member is displaced by that much towards the window's start."""
+    return sum(e.removed - e.inserted for e in members_of(item))
+
+
+def _flank_host(flank, L):
+    """``flank`` (None, numpy or a tensor) as numpy uint8 codes [F], 0 <= F <= L."""
+    if flank is None:
+        return np.zeros(0, dtype=np.uint8)
+    f = np.asarray(flank.cpu() if isinstance(flank, torch.Tensor) else flank)
+    if f.ndim != 1 or not np.issubdtype(f.dtype, np.integer) or f.size > L or (f.size and (f.min() < 0 or f.max() > 4)):
+        raise ValueError(f"flank: [F] codes 0..4 with 0 <= F <= {L}, the bases that follow the window")
+    return f.astype(np.uint8)
+
+
+def apply_edit(codes, edit, flank=None):
+    """The alt window as numpy uint8, always L bases (host restatement of the device kernels; ``codes``: [L] codes 0..4; ``edit``: an `Edit` or
+    an `EditSet`, whose members all read the unedited window).  With a ``del`` / ``ins`` member it is the first L bases of (edited window ++
+    ``flank`` ++ N ...); ``flank`` ([F] codes, the bases that follow the window) changes nothing otherwise."""
     src = np.asarray(codes, dtype=np.uint8)
     c = np.array(src, dtype=np.uint8, copy=True)
     edit.check(c.size)
+    fl = _flank_host(flank, c.size)
+    if changes_length(edit):
+        cx, parts, p = np.concatenate([src, fl]), [], 0
+        for e in members_of(edit):
+            parts.append(cx[p: e.pos])
+            if e.kind in ("sub", "ins"):
+                parts.append(e.seq)
+            elif e.kind == "mask":
+                parts.append(np.full(e.length, N_CODE, dtype=np.uint8))
+            elif e.kind == "inv":
+                r = src[e.pos: e.end][::-1]
+                parts.append(np.where(r < 4, 3 - r, r).astype(np.uint8))
+            p = e.end
+        parts += [cx[p:], np.full(c.size, N_CODE, dtype=np.uint8)]
+        return np.concatenate(parts)[: c.size].astype(np.uint8)
     for e in members_of(edit):
         s = slice(e.pos, e.end)
         if e.kind == "sub":
@@ -223,6 +301,38 @@ def snv_set(codes, variants, name=None):
     return EditSet(edits, name)
 
 
+def indel(codes, pos, ref, alt, name=None):
+    """The minimal item of a VCF-style variant: at window base ``pos`` the bases ``ref`` (checked against ``codes``) become ``alt`` (ACGTN strings or
+    codes, either may be empty).  The common prefix, then the common suffix, are trimmed; what is left is an `Edit` ``sub`` (equal lengths),
+    ``del`` or ``ins`` (one side empty), or an `EditSet` of a ``sub`` of the shorter side's length followed by the ``del`` / ``ins`` of the rest.
+    A deletion that is left starting at window base 0 (a VCF line without an anchor base there) is refused like any ``Edit("del", 0, ...)``:
+    the alt window keeps the window's first base.  An insertion anchored at the window's last base gives ``Edit("ins", L, ...)``, which leaves
+    the L-base alt window as it is."""
+    c = np.asarray(codes.cpu() if isinstance(codes, torch.Tensor) else codes)
+    pos = int(pos)
+    r, a = _codes_of(ref), _codes_of(alt)
+    if not 0 <= pos <= pos + r.size <= c.size:
+        raise ValueError(f"variant [{pos}, {pos + r.size}) outside the window of {c.size} bases")
+    if not np.array_equal(c[pos: pos + r.size], r):
+        raise ValueError(f"variant at {pos}: ref {''.join('ACGTN'[k] for k in r[:16])} but the window has {''.join('ACGTN'[int(k)] for k in c[pos: pos + min(r.size, 16)])}")
+    m = min(r.size, a.size)
+    pre = 0
+    while pre < m and r[pre] == a[pre]:
+        pre += 1
+    suf = 0
+    while suf < m - pre and r[r.size - 1 - suf] == a[a.size - 1 - suf]:
+        suf += 1
+    r, a, pos = r[pre: r.size - suf], a[pre: a.size - suf], pos + pre
+    if r.size == 0 and a.size == 0:
+        raise ValueError(f"variant at {pos}: ref and alt are the same")
+    m = min(r.size, a.size)
+    rest = None if r.size == a.size else Edit("del", pos + m, r.size - m) if r.size > a.size else Edit("ins", pos + m, a[m:])
+    if m == 0:
+        return rest
+    sub = Edit("sub", pos, m, a[:m])
+    return sub if rest is None else EditSet([sub, rest], name)
+
+
 # ---- planning (pure; tests/test_screen_cpu.py checks it against the fp64 oracle) -----------------------------------------------------------
 @dataclass
 class BatchPlan:
@@ -235,7 +345,15 @@ class BatchPlan:
     ``snippet_table`` [S, 8] = [out_off, b0, nb, span_lo, span_cnt, 0, 0, 0] in ``order``, ``span_table`` [n, 4] = [kind, pos, len, pay_off]
     (item by item, sorted by pos within an item; a snippet applies every span of its item that meets it, whichever cluster the span
     belongs to), ``segments`` [S, 3] = [row_lo, row_cnt, src_row] item by item, sorted by row_lo, item i's at
-    [seg_off[i], seg_off[i + 1]) - the tables of orca_screen_edit_codes_multi / _splice_rows_multi."""
+    [seg_off[i], seg_off[i + 1]) - the tables of orca_screen_edit_codes_multi / _splice_rows_multi.
+
+    A batch with a length-changing item (``indel`` True; `plan_batch` states the row-source rule): snippets are in ALT coordinates,
+    ``snippet_table`` [S, 8] = [out_off, a0, nb, piece_lo, piece_cnt, 0, 0, 0] and ``piece_table`` [n, 4] = [dst, kind, src, len] (item by item,
+    item i's at [piece_off[i], piece_off[i + 1]), sorted by dst; kind 0 context forward, 1 context reverse complement, 2 payload, 3 N) are the
+    tables of orca_screen_assemble_codes; ``gather_segments`` [G, 4] = [row_lo, row_cnt, source, src_row] with offsets ``gather_off`` [E + 1]
+    those of orca_screen_gather_rows (source -1 fresh, -2 ref, p >= 0 entry ``phases[p]`` of the stage-4 cache, which must hold
+    ``entry_rows[p]`` rows); ``segments`` keeps the fresh ones; ``take_rows`` counts the pooled rows, ``shift[i]`` = bases removed - inserted.
+    The single-span and span tables are None."""
     L: int
     snippet: np.ndarray
     rows: np.ndarray
@@ -251,6 +369,16 @@ class BatchPlan:
     span_table: np.ndarray = None
     segments: np.ndarray = None
     seg_off: np.ndarray = None
+    indel: bool = False
+    flank: int = 0
+    piece_table: np.ndarray = None
+    piece_off: np.ndarray = None
+    gather_segments: np.ndarray = None
+    gather_off: np.ndarray = None
+    phases: list = None
+    entry_rows: list = None
+    take_rows: int = 0
+    shift: np.ndarray = None
 
 
 def edit_rows(edit, L, margin=MARGIN_BP):
@@ -339,12 +467,195 @@ def _spans_meeting(spans, lo, hi, b0, b1):
     return lo + a, max(0, b - a)
 
 
-def plan_batch(edits, L, pad=PAD_BP, margin=MARGIN_BP, min_snippet=MIN_SNIPPET_BP, run_max=RUN_MAX_BP):
-    """The `BatchPlan` of ``edits`` (`Edit`s and `EditSet`s) on an L-base window (L a multiple of 400)."""
+# ---- insertions and deletions: piece lists and row sources -----------------------------------------------------------------------------------
+def entry_rows(C, phase):
+    """Rows of entry ``phase`` (0..79) of `sv.Stage4Cache` over a context of C bases: stage 4's output on context bases [phase, phase + 80 rows)
+    (the entry's run).  The five entries of a phase mod 16 share stage-3 planes that end at a multiple of 80 from that phase."""
+    p16, k = phase % sv.S3_GRID, phase // sv.S3_GRID
+    return max(0, min((C - phase) // sv.S4_GRID, ((C - p16) // sv.S4_GRID * sv.S3_POOL - k) // sv.S3_POOL))
+
+
+def item_pieces(item, L, F, pay_off=0):
+    """The alt window of ``item`` as pieces over the context (window ++ flank, C = L + F): ([(dst, kind, src, len)], payload codes).  The pieces
+    tile alt bases [0, L) in order.  kind 0: context [src, src + len) forward; 1: its reverse complement; 2: payload codes [src, src + len)
+    (``pay_off`` = the first code's place in the batch's payload); 3: N."""
+    C, out, pay, d, p = L + F, [], [], 0, 0
+
+    def put(kind, src, ln, back=False):
+        nonlocal d
+        n = min(ln, L - d)
+        if n > 0:
+            out.append((d, kind, src + (ln - n if back else 0), n))         # a reverse complement cut at L keeps its FIRST alt bases: the span's last
+            d += n
+    npay = pay_off
+    for e in members_of(item):
+        put(0, p, e.pos - p)
+        if e.kind in ("sub", "ins"):
+            put(2, npay, int(e.seq.size))
+            pay.append(e.seq)
+            npay += int(e.seq.size)
+        elif e.kind == "mask":
+            put(3, 0, e.length)
+        elif e.kind == "inv":
+            put(1, e.pos, e.length, back=True)
+        p = e.end
+    put(0, p, C - p)
+    put(3, 0, L - d)
+    return out, (np.concatenate(pay) if pay else np.zeros(0, dtype=np.uint8))
+
+
+def item_sources(pieces, L, F, margin=MARGIN_BP):
+    """Where the stage-5 rows of an alt window come from: (segments, fresh) with segments = [(row_lo, row_cnt, source, src_row)] for source -2
+    (reference rows [src_row, ..)) and source = a phase 0..79 (pooled from that cache entry's stage-4 row src_row on), and fresh = [(r0, r1)]
+    the maximal runs of rows that go through the front.  Rows in neither keep the reference's row of their own index.  The rule, with the
+    cone of row r = alt bases [400 r - margin, 400 r + 400 + margin) and s = context position - alt position of a context-forward piece:
+      * a row is served without the front only if its cone lies inside ONE context-forward piece (the alt window's start counts as inside for
+        a piece with s = 0 that starts there, its end for a piece with s = 0 that ends there: these ends are the window's own);
+      * s = 0: the reference's row r.  400 | s: the reference's row r + s / 400 if that row's cone lies inside the window [0, L) (the
+        reference rows saw zero padding there).  Otherwise entry s mod 80, stage-4 rows (400 r + s - phase) / 80 .. + 4, if the cone in
+        context coordinates lies inside the entry's run (the cache saw zero padding at its ends);
+      * everything else is fresh: junctions, payload, inversions, N fill, and the alt window's right end whenever s != 0 there."""
+    n5, C = L // ROW_BP, L + F
+    segs, served = [], np.zeros(n5, dtype=bool)
+    for d0, kind, src, ln in pieces:
+        if kind != 0:
+            continue
+        d1, s = d0 + ln, src - d0
+        lo = 0 if (d0 == 0 and s == 0) else -(-(d0 + margin) // ROW_BP)
+        hi = n5 if (d1 == L and s == 0) else (d1 - margin) // ROW_BP
+        lo, hi = max(lo, 0), min(hi, n5)
+        if hi <= lo:
+            continue
+        if s == 0:
+            served[lo:hi] = True
+            continue
+        cuts = [(lo, hi)]
+        if s % ROW_BP == 0:
+            q = s // ROW_BP
+            a, b = max(lo, -(-margin // ROW_BP) - q), min(hi, (L - margin) // ROW_BP - q)
+            if b > a:
+                segs.append((a, b - a, engine.SCREEN_SRC_REF, a + q))
+                served[a:b] = True
+                cuts = [(lo, a), (b, hi)]
+        ph = s % sv.S4_GRID
+        run1 = ph + sv.S4_GRID * entry_rows(C, ph)
+        for x, y in cuts:
+            a, b = max(x, -(-(ph + margin - s) // ROW_BP)), min(y, (run1 - margin - s) // ROW_BP)
+            if b > a:
+                segs.append((a, b - a, ph, (ROW_BP * a + s - ph) // sv.S4_GRID))
+                served[a:b] = True
+    edge = np.flatnonzero(np.diff(np.concatenate([[False], ~served, [False]]).astype(np.int8)))
+    return sorted(segs), [(int(a), int(b)) for a, b in zip(edge[0::2], edge[1::2])]
+
+
+def needed_phases(items, L, F, margin=MARGIN_BP):
+    """The stage-4 cache entries (phases 0..79, ascending) the two-part route of ``items`` pools rows from."""
+    ph = set()
+    for it in items:
+        if changes_length(it):
+            ph.update(g[2] for g in item_sources(item_pieces(it, L, F)[0], L, F, margin)[0] if g[2] >= 0)
+    return sorted(ph)
+
+
+def _pieces_meeting(pieces, lo, hi, a0, a1):
+    """Of pieces [lo, hi) (sorted by dst, disjoint) those that meet alt bases [a0, a1): (first, count)."""
+    dst, end = pieces[lo:hi, 0], pieces[lo:hi, 0] + pieces[lo:hi, 3]
+    a, b = int(np.searchsorted(end, a0, side="right")), int(np.searchsorted(dst, a1, side="left"))
+    return lo + a, max(0, b - a)
+
+
+def _piece_table(items, L, F):
+    """(piece table [n, 4] int64, first piece of every item [E + 1], payload, per-item piece lists): every item's pieces, item by item."""
+    rows, lists, pay, npay = [], [], [], 0
+    base = np.zeros(len(items) + 1, dtype=np.int64)
+    for i, it in enumerate(items):
+        pcs, py = item_pieces(it, L, F, npay)
+        lists.append(pcs)
+        rows += pcs
+        pay.append(py)
+        npay += py.size
+        base[i + 1] = len(rows)
+    return (np.array(rows, dtype=np.int64).reshape(-1, engine.SCREEN_PIECE_FIELDS), base,
+            (np.concatenate(pay) if pay else np.zeros(0, dtype=np.uint8)), lists)
+
+
+def _pack(snips, rows, L, run_max):
+    """Snippets into front runs (`_runs`): (runs_idx, order, out_off {snippet: first base in the buffer}, fresh [S], n_fresh, runs)."""
+    runs_idx = _runs(snips, L, run_max)
+    order = [i for r in runs_idx for i in r]
+    out_off, off = {}, 0
+    for i in order:
+        out_off[i] = off
+        off += snips[i][1] - snips[i][0]
+    fresh = np.zeros(len(snips), dtype=np.int64)
+    n_fresh = 0
+    for i in order:
+        fresh[i] = n_fresh
+        n_fresh += int(rows[i, 1] - rows[i, 0])
+    runs = []
+    for r in runs_idx:
+        o0 = out_off[r[0]]
+        nb = sum(snips[i][1] - snips[i][0] for i in r)
+        ranges = [(int(out_off[i] - o0 + rows[i, 0] * ROW_BP - snips[i][0]) // ROW_BP, int(rows[i, 1] - rows[i, 0]), int(fresh[i])) for i in r]
+        runs.append((o0, nb, ranges))
+    return order, out_off, fresh, n_fresh, runs
+
+
+def _plan_indels(edits, L, F, pad, margin, min_snippet, run_max):
+    """`plan_batch` for a batch that holds a length-changing item: every item, the length-preserving ones too, as pieces and row sources.  A
+    length-preserving item gets the clusters, snippets and fresh rows it gets alone (its pieces all have s = 0, so the rows outside every
+    member's cone are served and the others are not: `set_clusters`' rule), and the front runs give a snippet's rows bit for bit in
+    whichever run it lands."""
+    E = len(edits)
+    pieces, piece_off, payload, lists = _piece_table(edits, L, F)
+    rows_l, snips, item_of, served = [], [], [], []
+    seg_off = np.zeros(E + 1, dtype=np.int64)
+    for i, e in enumerate(edits):
+        segs, fresh_runs = item_sources(lists[i], L, F, margin)
+        served.append(segs)
+        for r0, r1 in fresh_runs:
+            rows_l.append((r0, r1))
+            snips.append(edit_snippet(r0, r1, L, pad, min_snippet))
+            item_of.append(i)
+        seg_off[i + 1] = len(snips)
+    S = len(snips)
+    rows = np.array(rows_l, dtype=np.int64).reshape(S, 2)
+    order, out_off, fresh, n_fresh, runs = _pack(snips, rows, L, run_max)
+    snippet_table = np.zeros((S, engine.SCREEN_EDIT_FIELDS), dtype=np.int64)
+    for k, i in enumerate(order):
+        it = item_of[i]
+        lo, cnt = _pieces_meeting(pieces, int(piece_off[it]), int(piece_off[it + 1]), snips[i][0], snips[i][1])
+        snippet_table[k, :5] = (out_off[i], snips[i][0], snips[i][1] - snips[i][0], lo, cnt)
+    segments = np.stack([rows[:, 0], rows[:, 1] - rows[:, 0], fresh], axis=1).astype(np.int64).reshape(S, 3)
+    phases = sorted({g[2] for segs in served for g in segs if g[2] >= 0})
+    index = {ph: k for k, ph in enumerate(phases)}
+    gather, gather_off, take_rows = [], np.zeros(E + 1, dtype=np.int64), 0
+    for i in range(E):
+        mine = [(int(r0), int(cnt), engine.SCREEN_SRC_FRESH, int(src)) for r0, cnt, src in segments[seg_off[i]: seg_off[i + 1]]]
+        for r0, cnt, source, src in served[i]:
+            mine.append((r0, cnt, index[source] if source >= 0 else source, src))
+            take_rows += cnt if source >= 0 else 0
+        gather += sorted(mine)
+        gather_off[i + 1] = len(gather)
+    return BatchPlan(L, np.array([(b0, b1 - b0) for b0, b1 in snips], dtype=np.int64).reshape(S, 2), rows, order, runs, fresh, n_fresh, None, None,
+                     payload, np.array(item_of, dtype=np.int64), snippet_table, None, segments, seg_off, True, F, pieces, piece_off,
+                     np.array(gather, dtype=np.int64).reshape(-1, engine.SCREEN_GATHER_FIELDS), gather_off, phases,
+                     [entry_rows(L + F, ph) for ph in phases], take_rows, np.array([shift_of(e) for e in edits], dtype=np.int64))
+
+
+def plan_batch(edits, L, pad=PAD_BP, margin=MARGIN_BP, min_snippet=MIN_SNIPPET_BP, run_max=RUN_MAX_BP, flank=0):
+    """The `BatchPlan` of ``edits`` (`Edit`s and `EditSet`s) on an L-base window (L a multiple of 400) followed by ``flank`` bases of right flank
+    (only a batch with a ``del`` / ``ins`` member looks at it; such a batch is planned by the row-source rule of `item_sources`)."""
     if L % ROW_BP:
         raise ValueError(f"window length must be a multiple of {ROW_BP}")
     if pad < margin or pad % ROW_BP:
         raise ValueError("pad must cover the margin and be a multiple of 400")
+    if not 0 <= int(flank) <= L:
+        raise ValueError(f"flank of {flank} bases: 0 .. {L}")
+    if any(changes_length(e) for e in edits):
+        for e in edits:
+            e.check(L)
+        return _plan_indels(edits, L, int(flank), pad, margin, min_snippet, run_max)
     E = len(edits)
     rows_l, snips, item_of = [], [], []
     seg_off = np.zeros(E + 1, dtype=np.int64)
@@ -406,6 +717,18 @@ def whole_window_table(edits, L):
     return table, (np.concatenate(payload) if payload else np.zeros(0, dtype=np.uint8))
 
 
+def whole_window_piece_tables(items, L, F):
+    """`whole_window_set_tables` for a batch with a length-changing item: (snippet table, piece table, payload) of orca_screen_assemble_codes -
+    item i's complete alt window at bases [i L, (i + 1) L) of the output, one [0, L) snippet with all of the item's pieces."""
+    for it in items:
+        it.check(L)
+    pieces, base, payload, _ = _piece_table(items, L, F)
+    table = np.zeros((len(items), engine.SCREEN_EDIT_FIELDS), dtype=np.int64)
+    for i in range(len(items)):
+        table[i, :5] = (i * L, 0, L, base[i], base[i + 1] - base[i])
+    return table, pieces, payload
+
+
 def whole_window_set_tables(items, L):
     """`whole_window_table` for `Edit`s and `EditSet`s: (snippet table, span table, payload) of orca_screen_edit_codes_multi - item i's complete
     edited window at bases [i L, (i + 1) L) of the output, carrying all of the item's spans."""
@@ -464,6 +787,10 @@ class ScreenResult:
       maps             [E, n, n]      the alt maps (``keep_maps=True`` only)
       delta_region     [E, K]         mean of alt - ref (signed) over rectangle k of ``regions`` (None without regions)
       delta_region_abs [E, K]         mean of |alt - ref| over rectangle k (None without regions)
+      shift            [E] int64      bases removed minus bases inserted by the item (0 without ``del`` / ``ins``).  The alt window is anchored at
+                                      the window's first base, so what lies behind the item's last member sits ``shift`` bases (shift / 4000
+                                      bins) earlier in the alt map than in ``ref_map``: the scores compare bin with bin all the same, and behind
+                                      an unbalanced indel they therefore also hold that displacement
     `scores_host` computes the three map scores from maps on the host, `region_scores_host` the two region scores."""
     ref_map: torch.Tensor
     ref_1d: Optional[torch.Tensor]
@@ -475,6 +802,7 @@ class ScreenResult:
     edits: list = field(default_factory=list)
     delta_region: Optional[torch.Tensor] = None
     delta_region_abs: Optional[torch.Tensor] = None
+    shift: Optional[torch.Tensor] = None
 
 
 # ---- the screen -----------------------------------------------------------------------------------------------------------------------------
@@ -507,9 +835,31 @@ def _net_of(model):
     return net
 
 
+def _flank_codes(window, flank, win):
+    """The right flank of the window as a [F] uint8 tensor on the window's device (0 <= F <= L): ``flank`` as given, else read from the genome
+    of a ``(genome, chrom, start[, L])`` window (`FLANK_BP` bases, fewer at the chromosome's end), else empty."""
+    L = win.numel()
+    if flank is None:
+        if not isinstance(window, tuple):
+            return win[:0]
+        genome, chrom, start = window[:3]
+        n = dict(genome.get_chr_lens())[chrom]
+        flank = genome.get_codes_from_coords(chrom, int(start) + L, min(int(start) + L + min(FLANK_BP, L), n))
+    if not isinstance(flank, torch.Tensor):
+        raise TypeError("flank: a [F] uint8 codes tensor on the MI355X")
+    if not flank.is_cuda:
+        raise OrcaHipError(f"screen_1m: the flank is on '{flank.device}': orca_amd runs on MI355X only, there is no CPU path")
+    if flank.dtype != torch.uint8 or flank.dim() != 1 or flank.numel() > L or flank.device != win.device:
+        raise ValueError(f"flank: a [F] uint8 codes tensor beside the window, 0 <= F <= {L}")
+    return flank.contiguous()
+
+
 class _Screen:
-    def __init__(self, net, window, stats):
+    def __init__(self, net, window, stats, flank=None):
         self.net, self.window, self.stats = net, window, stats
+        self.F = 0 if flank is None else flank.numel()
+        self.context = window if not self.F else torch.cat([window, flank])       # what the pieces of an indel batch read
+        self.cache = None
         self.dev = window.device
         self.L = window.numel()
         self.n5, self.n = self.L // ROW_BP, self.L // 4000
@@ -533,7 +883,11 @@ class _Screen:
         if not edits:
             return self._decode(self.net._enc.forward_codes(self.window[None]))
         codes = torch.empty(len(edits) * self.L, dtype=torch.uint8, device=self.dev)
-        if all(isinstance(e, Edit) for e in edits):
+        if any(changes_length(e) for e in edits):
+            table, pieces, payload = whole_window_piece_tables(edits, self.L, self.F)
+            pay = self._upload(payload, torch.uint8) if payload.size else None
+            engine.screen_assemble_codes(self.ctx, self.context, table, pieces, pay, codes)
+        elif all(isinstance(e, Edit) for e in edits):
             table, payload = whole_window_table(edits, self.L)
             pay = self._upload(payload, torch.uint8) if payload.size else None
             engine.screen_edit_codes(self.ctx, self.window, table, self._upload(table, torch.int64), pay, codes)
@@ -549,8 +903,46 @@ class _Screen:
         enc.front4_ranges(self.window, False, [(0, self.n5, 0)], s5)
         return s5
 
-    def two_part(self, edits, s5_ref):
+    def build_entries(self, phases):
+        """The stage-4 cache entries of ``phases`` over the context ('+' strand; `sv.Stage4Cache` builds a phase's group of five)."""
+        if self.cache is None:
+            self.cache = sv.Stage4Cache(self.net._enc, self.context)
+        out = []
+        for ph in phases:
+            e = self.cache.get("+", ph)
+            if e is None:
+                raise OrcaHipError(f"screen_1m: stage-4 cache entry {ph} unavailable (fp16 range)")
+            if e.shape[0] != entry_rows(self.L + self.F, ph):
+                raise OrcaHipError(f"screen_1m: stage-4 cache entry {ph} holds {e.shape[0]} rows, the plan expects {entry_rows(self.L + self.F, ph)}")
+            out.append(e)
+        self.stats["cache_phases"] = self.cache.builds
+        return out
+
+    def two_part_indels(self, edits, s5_ref, p):
+        """`two_part` for a batch with a length-changing item: the bases of every snippet from the items' pieces, the row images from the
+        reference rows, the recomputed rows and the cache entries."""
         enc = self.net._enc
+        total = int(p.snippet[:, 1].sum())
+        codes = torch.empty(total, dtype=torch.uint8, device=self.dev)
+        pay = self._upload(p.payload, torch.uint8) if p.payload.size else None
+        if total:                                        # no snippet at all: every row of every item is served (an ``ins`` behind the last base)
+            engine.screen_assemble_codes(self.ctx, self.context, p.snippet_table, p.piece_table, pay, codes)
+        fresh = torch.empty((p.n_fresh, 128), dtype=torch.float32, device=self.dev)
+        for o0, nb, ranges in p.runs:
+            enc.front4_ranges(codes[o0: o0 + nb], False, ranges, fresh)
+        rows = torch.empty((len(edits), self.n5, 128), dtype=torch.float32, device=self.dev)
+        engine.screen_gather_rows(self.ctx, s5_ref, fresh, self.build_entries(p.phases), p.gather_segments, p.gather_off, rows)
+        out = enc.back5_batch(rows)
+        self.stats["segments"] += len(p.segments)
+        self.stats["front_runs"] += len(p.runs)
+        self.stats["front_bases"] += total
+        self.stats["take_rows"] += p.take_rows
+        return self._decode(out)
+
+    def two_part(self, edits, s5_ref, plan=None):
+        enc = self.net._enc
+        if plan is not None:
+            return self.two_part_indels(edits, s5_ref, plan)
         p = plan_batch(edits, self.L)
         total = int(p.snippet[:, 1].sum())
         codes = torch.empty(total, dtype=torch.uint8, device=self.dev)
@@ -575,7 +967,7 @@ class _Screen:
         return self._decode(out)
 
 
-def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regions=None):
+def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regions=None, flank=None):
     """Score ``edits`` (a list of `Edit` and `EditSet`, one row of every result tensor each) of one window with the 1 Mb model: a `ScreenResult`.
 
     ``model``: an ``H1esc_1M`` / ``Hff_1M`` container or a bare ``orca_modules.Net``.  ``window``: the window's base codes, a [L] uint8 tensor on
@@ -586,7 +978,14 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
     redone on the whole-window route in the range-safe arithmetic after the fp16-range check fired), ``range_fallback_reference`` (the
     reference itself tripped: every batch went that way), ``front_runs``, ``front_bases``, ``edits``, ``set_items`` (items that are an
     `EditSet`), ``segments`` ((snippet, row range) segments planned on the two-part route: one per bare edit, one per cluster of a set).
-    ``regions``: up to 64 half-open bin rectangles (i0, i1, j0, j1) for `ScreenResult.delta_region` / ``delta_region_abs``."""
+    ``regions``: up to 64 half-open bin rectangles (i0, i1, j0, j1) for `ScreenResult.delta_region` / ``delta_region_abs``.
+
+    ``del`` / ``ins`` members: the alt window is the first L bases of (edited window ++ flank ++ N ...).  ``flank``: a [F] uint8 tensor on the
+    MI355X with the bases that follow the window, 0 <= F <= L; for a ``(genome, chrom, start[, L])`` window it is read from the genome
+    (`FLANK_BP` bases, fewer at the chromosome's end); bases beyond it are N.  It is validated and otherwise ignored when no item changes
+    length.  `ScreenResult.shift` says how far each item displaces what follows it.  More ``stats``: ``indel_items`` (items with a ``del`` /
+    ``ins`` member), ``take_rows`` (stage-5 rows pooled from stage-4 cache entries on the two-part route), ``cache_phases`` (entries built: 512
+    bytes per context base for all 80; they are built with the reference, inside its deferred range check)."""
     net = _net_of(model)
     win = _window_codes(window)
     edits = list(edits)
@@ -598,10 +997,13 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
         raise ValueError("batch must be positive")
     rects = None if regions is None else check_regions(regions, win.numel() // 4000)
     st = {"route": None, "two_part_batches": 0, "whole_window_batches": 0, "range_fallback_batches": 0, "range_fallback_reference": False,
-          "front_runs": 0, "front_bases": 0, "edits": len(edits), "set_items": sum(isinstance(e, EditSet) for e in edits), "segments": 0}
-    sc = _Screen(net, win, st)
+          "front_runs": 0, "front_bases": 0, "edits": len(edits), "set_items": sum(isinstance(e, EditSet) for e in edits), "segments": 0,
+          "indel_items": sum(changes_length(e) for e in edits), "take_rows": 0, "cache_phases": 0}
+    fl = _flank_codes(window, flank, win) if (flank is not None or st["indel_items"]) else None
+    sc = _Screen(net, win, st, fl if st["indel_items"] else None)
     E, n, dev = len(edits), sc.n, sc.dev
     two_part = net._enc.two_part_ok()
+    plans = {}
     with torch.no_grad():
         s5_ref = None
         if two_part:
@@ -610,6 +1012,11 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
                 enc_ref = torch.empty((1, 128, n), dtype=torch.float32, device=dev)
                 net._enc.back5(s5_ref, enc_ref[0])
                 ref_map, ref_1d = sc._decode(enc_ref)
+                if st["indel_items"]:                    # the cache entries the batches will pool from, under the reference's range check
+                    for i0 in range(0, E, batch):        # every indel batch is planned once, here; the phases built are the phases used
+                        if any(changes_length(e) for e in edits[i0: i0 + batch]):
+                            plans[i0] = plan_batch(edits[i0: i0 + batch], sc.L, flank=sc.F)
+                    sc.build_entries(sorted({ph for p in plans.values() for ph in p.phases}))
             if sc.ctx.take_overflow():
                 two_part = False
                 st["range_fallback_reference"] = True
@@ -625,6 +1032,7 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
                            torch.zeros(E, dtype=torch.float32, device=dev),
                            torch.zeros((E, sc.num_1d, n), dtype=torch.float32, device=dev) if sc.num_1d else None,
                            torch.zeros((E, n, n), dtype=torch.float32, device=dev) if keep_maps else None, edits)
+        res.shift = torch.tensor([shift_of(e) for e in edits], dtype=torch.int64, device=dev)
         if rects is not None:
             res.delta_region = torch.zeros((E, len(rects)), dtype=torch.float32, device=dev)
             res.delta_region_abs = torch.zeros((E, len(rects)), dtype=torch.float32, device=dev)
@@ -632,7 +1040,7 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
             chunk = edits[i0: i0 + batch]
             if two_part:
                 with engine.defer_overflow_guard():
-                    maps, h = sc.two_part(chunk, s5_ref)
+                    maps, h = sc.two_part(chunk, s5_ref, plans.get(i0))
                 if sc.ctx.take_overflow():
                     st["range_fallback_batches"] += 1
                     with engine.force_safe_precision():

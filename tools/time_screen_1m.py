@@ -14,6 +14,10 @@ Both routes' maps are compared on the first 64 edits (2e-5).  JSON on stdout and
 Compound edits (screen.EditSet), items per second against the same edited windows through model.net:
   --pairs N      every pair of N 4 kb mask tiles of bases [100 000, ..) with N of bases [600 000, ..): N x N sets of two members
   --haplotype M  --haplotypes H sets (64 by default) of M SNVs each, drawn uniformly from --haplotype-span bases in the window's middle
+
+Insertions and deletions, into profiles/screen_1m_indels.json:
+  --indels N     N random indels of 1-50 bases (half deletions, half insertions, anywhere in the window, 8 000 bases of right flank) at B = 64,
+                 against the same alt windows through model.net and against N SNVs at the same positions through the screen, in the same run
 """
 import argparse
 import json
@@ -40,9 +44,9 @@ def window(seed=5):
     return c
 
 
-def naive(model, win, edits, batch, keep_maps=False):
+def naive(model, win, edits, batch, keep_maps=False, flank=None):
     net = model.net
-    sc = S._Screen(net, win, {})
+    sc = S._Screen(net, win, {}, flank)
     ref_map, _ = sc.whole([])
     ref_map = ref_map[0].contiguous()
     out, maps_all = [], []
@@ -104,6 +108,38 @@ def time_sets(a, model, win, c, dev):
     return rep
 
 
+def time_indels(a, model, win, c, dev):
+    """The --indels workload: items/s of the screen on N random indels, of the naive route on the same alt windows and of the screen on N SNVs
+    at the same positions, alternated, at B = 64."""
+    rs = np.random.RandomState(23)
+    flank = torch.from_numpy(rs.randint(0, 4, S.FLANK_BP).astype(np.uint8)).to(dev)
+    pos = rs.randint(1, L - 50, a.indels)
+    size = rs.randint(1, 51, a.indels)
+    items = [S.Edit("del", int(p), int(n)) if k % 2 == 0 else S.Edit("ins", int(p), rs.randint(0, 4, int(n))) for k, (p, n) in enumerate(zip(pos, size))]
+    snvs = [S.Edit("sub", int(p), 1, [(int(c[p]) + 1) % 4]) for p in pos]
+    B = 64
+    st = {}
+    rs_ = S.screen_1m(model, win, items[:B], batch=B, keep_maps=True, stats=st, flank=flank)               # warm-up and cross-check
+    S.screen_1m(model, win, snvs[:B], batch=B)
+    row = {"items": len(items), "batch": B, "flank": S.FLANK_BP, "route": st["route"], "segments_per_item": round(st["segments"] / B, 2),
+           "front_bases_per_item": round(st["front_bases"] / B), "take_rows_per_item": round(st["take_rows"] / B), "cache_phases": st["cache_phases"]}
+    _, mn = naive(model, win, items[:B], B, keep_maps=True, flank=flank)
+    row["maps_maxabs_screen_vs_naive"] = float((rs_.maps - mn).abs().max())
+    del rs_, mn
+    ti, tn, tsub = [], [], []
+    for _ in range(a.reps):
+        st = {}
+        ti.append(timed(lambda: S.screen_1m(model, win, items, batch=B, stats=st, flank=flank))[0])
+        tn.append(timed(lambda: naive(model, win, items, B, flank=flank))[0])
+        tsub.append(timed(lambda: S.screen_1m(model, win, snvs, batch=B))[0])
+    row.update({"cache_phases_full_run": st["cache_phases"], "screen_s": [round(t, 3) for t in ti], "naive_s": [round(t, 3) for t in tn],
+                "snv_screen_s": [round(t, 3) for t in tsub], "screen_items_per_s": round(len(items) / min(ti), 1),
+                "naive_items_per_s": round(len(items) / min(tn), 1), "snv_screen_items_per_s": round(len(items) / min(tsub), 1),
+                "speedup_over_naive": round(min(tn) / min(ti), 2), "cost_over_snv_screen": round(min(ti) / min(tsub), 2)})
+    print(json.dumps({"indels": row}), flush=True)
+    return {"device": torch.cuda.get_device_name(dev), f"indels_{a.indels}_of_1_to_50_bp": row}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="16,64")
@@ -114,12 +150,25 @@ def main():
     ap.add_argument("--haplotype", type=int, default=0, help="M: time sets of M SNVs")
     ap.add_argument("--haplotypes", type=int, default=64)
     ap.add_argument("--haplotype-span", type=int, default=L)
+    ap.add_argument("--indels", type=int, default=0, help="N: time N random 1-50-base indels at B = 64")
     ap.add_argument("--commit", default="", help="recorded in the report")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     model = M.H1esc_1M(synthetic_seed=0).to(dev)
     c = window()
     win = torch.from_numpy(c).to(dev)
+    if a.indels:
+        rep = {"workload": "H1esc_1M synthetic, 1 Mb window, random insertions and deletions; naive = the same alt windows through model.net; "
+                           "snv_screen = SNVs at the same positions through the screen (every call includes its reference and, for indels, "
+                           "building the stage-4 cache entries)", "commit": a.commit}
+        rep.update(time_indels(a, model, win, c, dev))
+        print(json.dumps(rep))
+        out = a.out if a.out != ap.get_default("out") else os.path.join(os.path.dirname(a.out), "screen_1m_indels.json")
+        if out:
+            os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+            with open(out, "w") as f:
+                json.dump(rep, f, indent=1)
+        return
     if a.pairs or a.haplotype:
         rep = {"workload": "H1esc_1M synthetic, 1 Mb window, compound edits (screen.EditSet); naive = the same edited windows through model.net",
                "commit": a.commit}
