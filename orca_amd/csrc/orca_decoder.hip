@@ -54,7 +54,7 @@ int launch_conv2d_m16(orca_ctx* ctx, const ConvLayer& L, const f32x4* x, long x_
     // batches of more than one round (SV screen: 4 strands, config 3: 8): the grid is ONE round, a workgroup walks the maps b, b + grid.y, ...
     // of its tile and requests the next map's first piece under the last piece of the current one (needs an even chunk count: the heads'
     // 16- / 80- / 144-channel layers keep one workgroup per map and tile)
-    static int ncu = [] { int dev = 0, v = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v; }();
+    const int ncu = device_cus();
     const int gx = (aq.ngroups * 2 + 7) / 8 * 8;
     int gy = B;
     // (single-plane modes, 32 couts: 73.7 KB of LDS and 111 VGPRs - TWO workgroups fit a CU, one's transfers and epilogue under the other's

@@ -13,14 +13,11 @@
 #include "conv_small.h"
 #include "misc_kernels.h"
 #include "p16_planes.h"
-#include "screen.h"
+#include "screen.h"   // screen_rows_to_bins_kernel (orca_encoder_back5_batch)
 
 // ---------------------------------------------------------------------------
 // kernel launch helpers
 // ---------------------------------------------------------------------------
-// position tile used for long 128-channel convs: 128 (2 waves/SIMD, 4 accumulators/wave); 256 (1 wave/SIMD, 8 accumulators/wave) on request (`tile`)
-static const int g_big_tile128 = 128;
-
 template <int COUT, int MW, int NW, int WM, int WN, int KC>
 static void launch_conv1d_t(hipStream_t s, const Conv1dArgs& a, int B) {
   constexpr int MT = WM * MW * 32;
@@ -38,13 +35,8 @@ int launch_conv1d(orca_ctx* ctx, const ConvLayer& L, const float* x, long x_bs, 
   a.x_vec_ok = al16(x) && (ldx % 4 == 0) && (x_bs % 4 == 0);
   a.y_vec_ok = al16(y) && (ldy % 4 == 0) && (y_bs % 4 == 0) && (!r1 || al16(r1)) && (!r2 || al16(r2));
   hipStream_t s = ctx->stream;
-  const bool timed = ctx->timing && n >= 65536;
-  TimedLaunch tl;
-  if (timed) {
-    HIPCHECK(hipEventCreate(&tl.e0));
-    HIPCHECK(hipEventCreate(&tl.e1));
-    HIPCHECK(hipEventRecord(tl.e0, s));
-  }
+  LaunchTimer timer(ctx, n);
+  ORCA_TRY(timer.open());
   int used_tile = 256;
   if (L.cout == 64) {
     if (L.kc == 4) launch_conv1d_t<64, 2, 2, 4, 1, 4>(s, a, B);
@@ -52,7 +44,8 @@ int launch_conv1d(orca_ctx* ctx, const ConvLayer& L, const float* x, long x_bs, 
   } else if (L.cout == 96) {
     launch_conv1d_t<96, 2, 3, 4, 1, 8>(s, a, B);
   } else {
-    if (tile == 0) tile = (n >= 65536) ? g_big_tile128 : (n >= 8192 ? 64 : 32);
+    // position tile of the long 128-channel convs: 128 (2 waves/SIMD, 4 accumulators/wave); 256 (1 wave/SIMD, 8 accumulators/wave) on request (`tile`)
+    if (tile == 0) tile = (n >= 65536) ? 128 : (n >= 8192 ? 64 : 32);
     if (tile == 256) launch_conv1d_t<128, 4, 2, 2, 2, 8>(s, a, B);
     else if (tile == 128) launch_conv1d_t<128, 2, 2, 2, 2, 8>(s, a, B);
     else if (tile == 64) launch_conv1d_t<128, 1, 2, 2, 2, 8>(s, a, B);
@@ -61,12 +54,7 @@ int launch_conv1d(orca_ctx* ctx, const ConvLayer& L, const float* x, long x_bs, 
     used_tile = tile;
   }
   LAUNCHCHECK("conv1d_k9_kernel");
-  if (timed) {
-    HIPCHECK(hipEventRecord(tl.e1, s));
-    tl.rec.cout = L.cout; tl.rec.cin = L.cin; tl.rec.tile = used_tile; tl.rec.batch = B; tl.rec.n = n; tl.rec.ms = 0.f; tl.rec.ksize = 9;
-    ctx->timed.push_back(tl);
-  }
-  return ORCA_OK;
+  return timer.close(L.cout, L.cin, used_tile, B, n, 9);
 }
 
 int launch_pool(orca_ctx* ctx, const float* x, long ldx, float* y, long ldy, long rows, long n_out, int k) {
@@ -86,17 +74,7 @@ int launch_pool(orca_ctx* ctx, const float* x, long ldx, float* y, long ldy, lon
 template <int COUT, int MW, int NW, int WM, int WN, int NS, int DT>
 static void launch_b16_t(hipStream_t s, ConvB16Args a, int B) {
   constexpr int MT = WM * MW * 32;
-  // persistent grid: CUs x resident workgroups per CU (queried once per instantiation)
-  static int resident = [] {
-    int dev = 0, ncu = 256, per_cu = 1;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv1d_k9_bf16s_kernel<COUT, MW, NW, WM, WN, NS, DT>, WM * WN * 64, 0) != hipSuccess || per_cu < 1) {
-      (void)hipGetLastError();
-      per_cu = 1;
-    }
-    return ncu * per_cu;
-  }();
+  const int resident = resident_workgroups<conv1d_k9_bf16s_kernel<COUT, MW, NW, WM, WN, NS, DT>, WM * WN * 64>();
   a.tiles_per_row = (a.n + MT - 1) / MT;
   a.batch = B;
   const long ntiles = a.tiles_per_row * B;
@@ -135,13 +113,8 @@ int launch_conv1d_b16(orca_ctx* ctx, const ConvLayer& L, int precision, const fl
     if (!L.f16_ok) return fail(ORCA_EINVAL, "layer weights exceed the fp16 range: use ORCA_PRECISION_BF16X3");
     a.w = L.d_wf16;
   }
-  const bool timed = ctx->timing && n >= 65536;
-  TimedLaunch tl;
-  if (timed) {
-    HIPCHECK(hipEventCreate(&tl.e0));
-    HIPCHECK(hipEventCreate(&tl.e1));
-    HIPCHECK(hipEventRecord(tl.e0, ctx->stream));
-  }
+  LaunchTimer timer(ctx, n);
+  ORCA_TRY(timer.open());
   int rc;
   a.cout = L.cout;
   // short rows (the Encoder's stages 5-7 of a local re-encode, one- to three-bin inputs): the K-chunks of a tile side by side, one global
@@ -164,18 +137,35 @@ int launch_conv1d_b16(orca_ctx* ctx, const ConvLayer& L, int precision, const fl
   if (rc != ORCA_OK) return rc;
   LAUNCHCHECK("conv1d_k9_bf16s_kernel");
   ctx->counts[1]++;
-  if (timed) {
-    HIPCHECK(hipEventRecord(tl.e1, ctx->stream));
-    tl.rec.cout = L.cout; tl.rec.cin = L.cin; tl.rec.tile = -precision; tl.rec.batch = B; tl.rec.n = n; tl.rec.ms = 0.f; tl.rec.ksize = 9;
-    ctx->timed.push_back(tl);
-  }
-  return ORCA_OK;
+  return timer.close(L.cout, L.cin, -precision, B, n, 9);
+}
+
+// ---- where a chunk's input comes from, and the kernel argument structs that carry the bases ----------------------------
+struct SeqSource {            // a float [.,4] view or packed base codes
+  const float* x = nullptr;   // already offset to the chunk start
+  long sx_c = 0, sx_l = 0;
+  const unsigned char* codes = nullptr;   // whole sequence of this batch row: 1 byte per base, or (nmask set) a 2-bit genome plane + N mask, the
+  const unsigned char* nmask = nullptr;   // sequence starting at genome index `origin` (conv_p16.h: p16_base_at)
+  long origin = 0;
+  long codes_L = 0, codes_off = 0;
+  int reverse = 0;
+};
+
+static void set_bases(ConvP16Args& a, const SeqSource& s) {
+  a.f1_codes = s.codes; a.f1_nmask = s.nmask; a.f1_origin = s.origin; a.f1_codes_L = s.codes_L; a.f1_codes_off = s.codes_off; a.f1_reverse = s.reverse;
+}
+static void set_bases(FirstMfmaArgs& a, const SeqSource& s) {
+  a.codes = s.codes; a.nmask = s.nmask; a.origin = s.origin; a.codes_L = s.codes_L; a.codes_off = s.codes_off; a.reverse = s.reverse;
+}
+static EdgeFixArgs edge_source(const SeqSource& s) {   // in_mode 1 (bases) or 0 (float rows); also FirstF32Args::in
+  EdgeFixArgs a{};
+  if (s.codes) { a.in_mode = 1; a.codes = s.codes; a.nmask = s.nmask; a.origin = s.origin; a.codes_L = s.codes_L; a.codes_off = s.codes_off; a.reverse = s.reverse; }
+  else { a.in_mode = 0; a.x = s.x; a.sc = s.sx_c; a.sl = s.sx_l; }
+  return a;
 }
 
 // ---- P16 (planar split fp16) conv1d with LDS-DMA staging (conv_p16.h) -------------------------------------
-// plane length in 16-byte units: P16_GUARD = 8 guard units on the left, >= 24 on the right (a 17-tap conv's second tap
-// half reads 9 units past the last tile); the +1 keeps the zero stores of a pooled output's ragged last tile
-// (128 * ceil(4n'/512) positions) inside the plane for every n'
+// (plane lengths: p16_plen in orca_internal.h)
 int launch_p16_zero_pads(orca_ctx* ctx, float* base, int C, long n_valid, int fmt) {
   hipLaunchKernelGGL(p16_zero_pads_kernel, dim3((unsigned)(fmt == 1 ? C / 8 : C / 8 * 2)), dim3(256), 0, ctx->stream, reinterpret_cast<f32x4*>(base),
                      p16_plen(n_valid), n_valid);
@@ -183,88 +173,49 @@ int launch_p16_zero_pads(orca_ctx* ctx, float* base, int C, long n_valid, int fm
   return ORCA_OK;
 }
 
-template <int CT, int MW, int NW, int WM, int OM, bool R1, int FMT = 0>
-static void launch_p16_k(hipStream_t s, ConvP16Args a) {
-  constexpr int MT = WM * MW * 32;
-  static int resident = [] {
-    int dev = 0, ncu = 256, per_cu = 1;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv1d_k9_p16_kernel<CT, MW, NW, WM, OM, R1, 0, false, FMT>, WM * 64, 0) != hipSuccess || per_cu < 1) {
-      (void)hipGetLastError();
-      per_cu = 1;
-    }
-    return ncu * per_cu;
-  }();
+static dim3 cu_grid(long ntiles) { const int ncu = device_cus(); return dim3((unsigned)(ntiles < ncu ? ntiles : ncu)); }   // persistent, one workgroup per CU
+// one persistent launch of a planar conv kernel on MT-position tiles x cout blocks of CT: CUs x resident workgroups at most
+template <auto KERNEL, int MT, int THREADS, int CT>
+static void launch_p16_persistent(hipStream_t s, ConvP16Args a) {
+  const int resident = resident_workgroups<KERNEL, THREADS>();
   a.tiles_per_row = (a.n + MT - 1) / MT;
   const long ntiles = a.tiles_per_row * (a.cout / CT);
   dim3 grid((unsigned)(ntiles < resident ? ntiles : resident));
-  hipLaunchKernelGGL((conv1d_k9_p16_kernel<CT, MW, NW, WM, OM, R1, 0, false, FMT>), grid, dim3(WM * 64), 0, s, a);
+  hipLaunchKernelGGL(KERNEL, grid, dim3(THREADS), 0, s, a);
 }
 
+// out_mode and the residual are compile-time in the kernel (its epilogue is branch-free)
+template <int CT, int MW, int NW, int WM, int OM, bool R1, int FMT = 0>
+static void launch_p16_k(hipStream_t s, const ConvP16Args& a) {
+  launch_p16_persistent<conv1d_k9_p16_kernel<CT, MW, NW, WM, OM, R1, 0, false, FMT>, WM * MW * 32, WM * 64, CT>(s, a);
+}
 // the conv that follows the first layer, with the first layer fused into its input-tile producer (conv_p16.h, F1)
-static void launch_p16_fused_first(hipStream_t s, ConvP16Args a) {
-  constexpr int MT = 512;
-  static int resident = [] {
-    int dev = 0, ncu = 256, per_cu = 1;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv1d_k9_p16_kernel<64, 2, 2, 8, 0, false, 0, true>, 512, 0) != hipSuccess || per_cu < 1) {
-      (void)hipGetLastError();
-      per_cu = 1;
-    }
-    return ncu * per_cu;
-  }();
-  a.tiles_per_row = (a.n + MT - 1) / MT;
-  const long ntiles = a.tiles_per_row;
-  dim3 grid((unsigned)(ntiles < resident ? ntiles : resident));
-  hipLaunchKernelGGL((conv1d_k9_p16_kernel<64, 2, 2, 8, 0, false, 0, true>), grid, dim3(512), 0, s, a);
+static void launch_p16_fused_first(hipStream_t s, const ConvP16Args& a) {
+  launch_p16_persistent<conv1d_k9_p16_kernel<64, 2, 2, 8, 0, false, 0, true>, 512, 512, 64>(s, a);
 }
-
 // stage 1's pooled conv on P16 planes with the residual computed from the bases in its epilogue (conv_p16.h, RL)
-static void launch_p16_res_bases(hipStream_t s, ConvP16Args a) {
-  constexpr int FMT = 0;
-  constexpr int MT = 512;
-  static int resident = [] {
-    int dev = 0, ncu = 256, per_cu = 1;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv1d_k9_p16_kernel<64, 2, 2, 8, 1, false, 0, false, FMT, true>, 512, 0) != hipSuccess || per_cu < 1) {
-      (void)hipGetLastError();
-      per_cu = 1;
-    }
-    return ncu * per_cu;
-  }();
-  a.tiles_per_row = (a.n + MT - 1) / MT;
-  const long ntiles = a.tiles_per_row;
-  dim3 grid((unsigned)(ntiles < resident ? ntiles : resident));
-  hipLaunchKernelGGL((conv1d_k9_p16_kernel<64, 2, 2, 8, 1, false, 0, false, FMT, true>), grid, dim3(512), 0, s, a);
+static void launch_p16_res_bases(hipStream_t s, const ConvP16Args& a) {
+  launch_p16_persistent<conv1d_k9_p16_kernel<64, 2, 2, 8, 1, false, 0, false, 0, true>, 512, 512, 64>(s, a);
 }
 
 // the 96-cout layers of B16 planes on 512-position tiles with ONE half-by-half refilled weight buffer (conv_p16w1.h)
 template <int OM, bool R1>
 static void launch_p16w1_k(hipStream_t s, ConvP16Args a) {
-  static int ncu = [] { int dev = 0, v = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v; }();
   a.tiles_per_row = (a.n + 511) / 512;
-  dim3 grid((unsigned)(a.tiles_per_row < ncu ? a.tiles_per_row : ncu));
-  hipLaunchKernelGGL((conv1d_k9_p16w1_kernel<OM, R1, 1>), grid, dim3(512), 0, s, a);
+  hipLaunchKernelGGL((conv1d_k9_p16w1_kernel<OM, R1, 1>), cu_grid(a.tiles_per_row), dim3(512), 0, s, a);
 }
 // the same layers of P16 planes on the 16 x 16 x 32 matrix instruction (conv_p16x.h)
 template <int OM, bool R1, int CT>
 static void launch_p16x_k(hipStream_t s, ConvP16Args a) {
-  static int ncu = [] { int dev = 0, v = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v; }();
   a.tiles_per_row = (a.n + 511) / 512;
-  const long ntiles = a.tiles_per_row * (a.cout / CT);
-  dim3 grid((unsigned)(ntiles < ncu ? ntiles : ncu));
-  hipLaunchKernelGGL((conv1d_k9_p16x_kernel<OM, R1, CT / 32, CT>), grid, dim3(1024), 0, s, a);
+  hipLaunchKernelGGL((conv1d_k9_p16x_kernel<OM, R1, CT / 32, CT>), cu_grid(a.tiles_per_row * (a.cout / CT)), dim3(1024), 0, s, a);
 }
 static bool launch_p16x(hipStream_t s, const ConvP16Args& a) {      // false: this (cout, out_mode, residual) combination stays on the 32 x 32 x 16 kernels
   const bool r1 = a.r1 != nullptr;
-  if (a.cout == 96) {
-    if (a.out_mode == 0 && !r1) launch_p16x_k<0, false, 96>(s, a);
-    else if (a.out_mode == 1 && r1) launch_p16x_k<1, true, 96>(s, a);
-    else return false;
-  } else return false;
+  if (a.cout != 96) return false;
+  if (a.out_mode == 0 && !r1) launch_p16x_k<0, false, 96>(s, a);
+  else if (a.out_mode == 1 && r1) launch_p16x_k<1, true, 96>(s, a);
+  else return false;
   return true;
 }
 static bool launch_p16w1(hipStream_t s, const ConvP16Args& a) {     // false: this (out_mode, residual) pair stays on the 256-position kernel
@@ -278,19 +229,17 @@ static bool launch_p16w1(hipStream_t s, const ConvP16Args& a) {     // false: th
 // a 128-cout layer with ReLU, residual and MaxPool1d(5) fused (conv_p16p5.h): out_mode 3
 template <int FMT>
 static void launch_p16p5(hipStream_t s, ConvP16Args a) {
-  static int ncu = [] { int dev = 0, v = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v; }();
   a.tiles_per_row = (a.n + 319) / 320;
-  dim3 grid((unsigned)(a.tiles_per_row < ncu ? a.tiles_per_row : ncu));
+  const dim3 grid = cu_grid(a.tiles_per_row);
   if (a.r1) hipLaunchKernelGGL((conv1d_k9_p16p5_kernel<true, FMT>), grid, dim3(512), 0, s, a);
   else hipLaunchKernelGGL((conv1d_k9_p16p5_kernel<false, FMT>), grid, dim3(512), 0, s, a);
 }
-
 
 // W-stationary barrier-free form (conv_ws.h): persistent, one workgroup per CU; the grid is a multiple of the number
 // of cout blocks (of 8 x that where possible: the blocks of one position range then share an XCD)
 template <int FMT, int CIN, int CT, int MW, int NW, int OM, bool R1>
 static void launch_ws_k(hipStream_t s, const ConvP16Args& a) {
-  static int ncu = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
+  const int ncu = device_cus();
   const int ncb = a.cout / CT;
   int grid = (ncu / (8 * ncb)) * (8 * ncb);
   if (grid < ncu - 8) grid = (ncu / ncb) * ncb;
@@ -312,7 +261,6 @@ static void launch_ws_t(hipStream_t s, const ConvP16Args& a) {
   }
 }
 
-// out_mode and the residual are compile-time in the kernel (its epilogue is branch-free)
 template <int CT, int MW, int NW, int WM, int FMT = 0>
 static void launch_p16_t(hipStream_t s, const ConvP16Args& a) {
   const bool r1 = a.r1 != nullptr;
@@ -328,11 +276,7 @@ static void launch_p16_t(hipStream_t s, const ConvP16Args& a) {
 
 // x: P16 [cin] of n positions; y: P16 (out_mode 0: n positions, 1: n/4 pooled) or fp32 [n][cout] (2); r1: P16 [cout], n
 struct FusedFirst {   // packed bases + first-layer table: the conv's input is produced instead of read (x may be NULL)
-  const unsigned char* codes = nullptr;
-  const unsigned char* nmask = nullptr;   // 2-bit genome window (conv_p16.h: p16_base_at)
-  long origin = 0;
-  long codes_L = 0, codes_off = 0;
-  int reverse = 0;
+  const SeqSource* src = nullptr;
   const float* table = nullptr;
   const float* bias = nullptr;
   bool residual = false;   // RL form instead: x IS read; the bases + the 17-tap pack (in `table`) give the residual in the epilogue
@@ -351,28 +295,22 @@ int launch_conv1d_p16(orca_ctx* ctx, const ConvLayer& L, const float* x, void* y
   a.r1 = reinterpret_cast<const f32x4*>(r1); a.x_plen = p16_plen(n); a.y_plen = p16_plen(out_mode == 1 ? n / 4 : out_mode == 3 ? n / 5 : n); a.n = n;
   a.nchunks = (fmt == 0 ? L.cin / 16 : L.cin / 32) * (k17 ? 2 : 1); a.cout = L.cout; a.relu = relu; a.out_mode = out_mode; a.flag = ctx->d_flag;
   a.k17 = k17 ? 1 : 0;
-  const bool timed = ctx->timing && n >= 65536;
-  TimedLaunch tl;
-  if (timed) {
-    HIPCHECK(hipEventCreate(&tl.e0));
-    HIPCHECK(hipEventCreate(&tl.e1));
-    HIPCHECK(hipEventRecord(tl.e0, ctx->stream));
-  }
-  a.f1_codes = nullptr; a.f1_nmask = nullptr; a.f1_origin = 0; a.f1_codes_L = a.f1_codes_off = 0; a.f1_reverse = 0; a.f1_table = a.f1_bias = nullptr; a.stamps = nullptr; a.rl_w = nullptr;
-  const bool ws_ok = fmt == 1 && !k17;     // W-stationary barrier-free kernel (conv_ws.h; P16: measured 3 % slower than the tiled kernel - profiles/HISTORY.md)
+  LaunchTimer timer(ctx, n);
+  ORCA_TRY(timer.open());
+  set_bases(a, f1 ? *f1->src : SeqSource());
+  a.f1_table = a.f1_bias = nullptr; a.stamps = nullptr; a.rl_w = nullptr;
   int tile_tag = fmt == 1 ? -6 : -5;
   if (f1 && f1->residual) {
     if (L.cout != 64 || L.cin != 64 || out_mode != 1 || r1 || k17) return fail(ORCA_EINVAL, "residual from the bases: only stage 1's pooled 64 -> 64 planar conv");
-    a.f1_codes = f1->codes; a.f1_nmask = f1->nmask; a.f1_origin = f1->origin; a.f1_codes_L = f1->codes_L; a.f1_codes_off = f1->codes_off; a.f1_reverse = f1->reverse;
     a.rl_w = reinterpret_cast<const f32x4*>(f1->table); a.f1_bias = f1->bias;
     if (fmt == 1) return fail(ORCA_EINVAL, "residual from the bases on B16 planes: the stage runs as ONE kernel (conv_stage1.h)");
     launch_p16_res_bases(ctx->stream, a);
   } else if (f1) {
     if (L.cout != 64 || L.cin != 64 || out_mode != 0 || r1 || fmt != 0 || k17) return fail(ORCA_EINVAL, "fused first layer: only the 64 -> 64 P16 conv that follows it");
-    a.f1_codes = f1->codes; a.f1_nmask = f1->nmask; a.f1_origin = f1->origin; a.f1_codes_L = f1->codes_L; a.f1_codes_off = f1->codes_off; a.f1_reverse = f1->reverse;
     a.f1_table = f1->table; a.f1_bias = f1->bias;
     launch_p16_fused_first(ctx->stream, a);
-  } else if (ws_ok && fmt == 1 && L.cin == 64 && L.cout == 64) {
+  } else if (fmt == 1 && !k17 && L.cin == 64 && L.cout == 64) {
+    // W-stationary barrier-free kernel (conv_ws.h; P16: measured 3 % slower than the tiled kernel - profiles/HISTORY.md)
     launch_ws_t<1, 64, 64, 2, 2>(ctx->stream, a);
     tile_tag = -8;
   } else if (out_mode == 3) {
@@ -383,42 +321,85 @@ int launch_conv1d_p16(orca_ctx* ctx, const ConvLayer& L, const float* x, void* y
     tile_tag = -14;                      // stage 2 of the Encoder on P16 planes: 16 x 16 x 32 matrix instruction (conv_p16x.h)
   } else if (L.cout == 96 && n >= 65536 && fmt == 1 && launch_p16w1(ctx->stream, a)) {
     tile_tag = -10;                      // ... on B16 planes: 512-position tiles, one half-by-half refilled weight buffer (conv_p16w1.h)
-  } else if (fmt == 1) {
-    if (L.cout == 96) launch_p16_t<96, 1, 3, 8, 1>(ctx->stream, a);
-    else if (L.cout % 64 == 0) launch_p16_t<64, 2, 2, 8, 1>(ctx->stream, a);
-    else return fail(ORCA_EINVAL, "b16 conv1d cout %d unsupported", L.cout);
-  } else
-  if (L.cout == 96) launch_p16_t<96, 1, 3, 8>(ctx->stream, a);
-  else if (L.cout % 64 == 0) launch_p16_t<64, 2, 2, 8>(ctx->stream, a);
-  else return fail(ORCA_EINVAL, "p16 conv1d cout %d unsupported", L.cout);
-  LAUNCHCHECK("conv1d_k9_p16_kernel");
-  if (timed) {
-    HIPCHECK(hipEventRecord(tl.e1, ctx->stream));
-    tl.rec.cout = L.cout; tl.rec.cin = L.cin; tl.rec.tile = tile_tag; tl.rec.batch = 1; tl.rec.n = n; tl.rec.ms = 0.f; tl.rec.ksize = k17 ? 17 : 9;
-    ctx->timed.push_back(tl);
+  } else if (L.cout == 96) {
+    if (fmt == 1) launch_p16_t<96, 1, 3, 8, 1>(ctx->stream, a); else launch_p16_t<96, 1, 3, 8>(ctx->stream, a);
+  } else if (L.cout % 64 == 0) {
+    if (fmt == 1) launch_p16_t<64, 2, 2, 8, 1>(ctx->stream, a); else launch_p16_t<64, 2, 2, 8>(ctx->stream, a);
+  } else {
+    return fail(ORCA_EINVAL, "%s conv1d cout %d unsupported", fmt == 1 ? "b16" : "p16", L.cout);
   }
-  return ORCA_OK;
+  LAUNCHCHECK("conv1d_k9_p16_kernel");
+  return timer.close(L.cout, L.cin, tile_tag, 1, n, k17 ? 17 : 9);
 }
 
-// the end positions of a composed linear group, recomputed conv by conv (conv_p16.h: lconv_edge_layer_kernel).  layers[l] with
-// relu[l]; the last layer covers `half_last` positions per end, layer l four more per layer behind it; ys[l] (may be NULL) receives
-// the outermost stores[l] positions per end of layer l.  Scratch: one 40 x 128 float slab per layer in the context.
-static int launch_edge_chain(orca_ctx* ctx, const ConvLayer* const* layers, const int* relu, int nl, int half_last, EdgeFixArgs src, long n,
-                             float* const* ys, const int* stores, int fmt, long ld_f32 = 0) {
+// one first-layer GEMM launch from the bases / flat [n][4] float rows onto planes (fmt 0 P16, 1 B16): ntap 9 (lconv1.a alone), 17 (lconv1 composed),
+// 25 (conv1.a o lconv1, + ReLU)
+static int launch_first_mfma(orca_ctx* ctx, const SeqSource& src, const float* rows, long n, int ntap, const void* w16, const float* bias, int relu,
+                             float* out, int fmt) {
+  hipStream_t s = ctx->stream;
+  FirstMfmaArgs fm;
+  set_bases(fm, src);
+  fm.x = src.codes ? nullptr : rows; fm.n = n;
+  fm.w = reinterpret_cast<const f32x4*>(w16); fm.bias = bias; fm.relu = relu;
+  fm.y = reinterpret_cast<f32x4*>(out); fm.y_plen = p16_plen(n); fm.flag = ctx->d_flag;
+  const long nt = (n + 255) / 256;
+  const dim3 grid((unsigned)(nt < 2048 ? nt : 2048));
+  LaunchTimer timer(ctx, n, ntap > 9);
+  ORCA_TRY(timer.open());
+  switch (ntap * 2 + fmt) {
+    case 18: hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 0, 9>), grid, dim3(256), 0, s, fm); break;
+    case 19: hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 1, 9>), grid, dim3(256), 0, s, fm); break;
+    case 34: hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 0, 17>), grid, dim3(256), 0, s, fm); break;
+    case 35: hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 1, 17>), grid, dim3(256), 0, s, fm); break;
+    case 50: hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 0, 25>), grid, dim3(256), 0, s, fm); break;
+    default: hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 1, 25>), grid, dim3(256), 0, s, fm); break;
+  }
+  LAUNCHCHECK("conv1d_first_mfma_p16_kernel");
+  return timer.close(64, 4, fmt == 1 ? -6 : -5, 1, n, ntap);
+}
+
+// stage 1 of the throughput mode (B16 planes) as ONE kernel from the bases (conv_stage1.h): conv1.b's input tiles are produced in LDS by the matrix
+// cores, a1 is neither written nor re-read; `a1_edge` holds the edge-fixed a1 at its first / last 8 positions, y receives the pooled stage output
+static int launch_stage1_b16(orca_ctx* ctx, const orca_net* net, const ConvLayer& Lb, const SeqSource& src, const float* a1_edge, float* y, long n) {
+  Stage1Args sa;
+  ConvP16Args& a1 = sa.c;
+  a1.x = nullptr; a1.w = reinterpret_cast<const f32x4*>(Lb.d_wb16p); a1.bias = Lb.d_bias; a1.y = y; a1.r1 = nullptr;
+  a1.x_plen = p16_plen(n); a1.y_plen = p16_plen(n / 4); a1.n = n; a1.tiles_per_row = (n + 63) / 64; a1.nchunks = 2; a1.cout = 64;
+  a1.relu = 1; a1.out_mode = 1; a1.k17 = 0; a1.flag = ctx->d_flag; a1.stamps = nullptr;
+  set_bases(a1, src);
+  a1.rl_w = reinterpret_cast<const f32x4*>(net->d_l1_w16); a1.f1_table = nullptr; a1.f1_bias = net->d_l1_bias;
+  sa.w25 = reinterpret_cast<const f32x4*>(net->d_c1a_w16); sa.b25 = net->d_c1a_bias;
+  sa.a1_edge = reinterpret_cast<const f32x4*>(a1_edge); sa.a1_plen = p16_plen(n);
+  LaunchTimer timer(ctx, n);
+  ORCA_TRY(timer.open());
+  hipLaunchKernelGGL((conv1d_stage1_b16_kernel<1>), cu_grid(((n + 63) / 64 + 7) / 8), dim3(512), 0, ctx->stream, sa);
+  LAUNCHCHECK("conv1d_stage1_b16_kernel");
+  ctx->counts[2]++;
+  // (both 64 -> 64 convs of the stage in one launch: recorded as cin = 128 so that 2 * 9 * cin * cout is the pair's algorithmic work)
+  return timer.close(64, 128, -15, 1, n, 9);
+}
+
+// the end positions of a stage's composed linear group, recomputed conv by conv (conv_p16.h: lconv_edge_layer_kernel): its first `depth` (2-4) layers
+// Ls[0 ..], ReLU behind the third and the fourth.  The last layer covers `half_last` positions per end, layer l four more per layer behind it; the
+// outermost 4 per end of lout (layer 2) go to `lo`, the outermost 8 of layer 3 to `t`, where given.  fmt 0 / 1: planes, 2: fp32 channel-major with row
+// stride ld_f32, 3: fp32 channel-last.  Scratch: one 40 x 128 float slab per layer in the context.
+static int launch_edge_chain(orca_ctx* ctx, const ConvLayer* Ls, int depth, int half_last, EdgeFixArgs src, long n, float* lo, float* t, int fmt,
+                             long ld_f32 = 0) {
   src.n = n;
-  if (nl > 4 || 2 * (half_last + 4 * (nl - 1)) > 40) return fail(ORCA_EINVAL, "edge fix: chain too deep");
-  for (int l = 0; l < nl; ++l) {
-    const ConvLayer& L = *layers[l];
+  if (depth > 4 || 2 * (half_last + 4 * (depth - 1)) > 40) return fail(ORCA_EINVAL, "edge fix: chain too deep");
+  for (int l = 0; l < depth; ++l) {
+    const ConvLayer& L = Ls[l];
     if (!L.d_w) return fail(ORCA_EINVAL, "edge fix: layer without an fp32 pack");
     EdgeLayerArgs a{};
     a.in = src;
     if (l > 0) a.in.in_mode = -1;
-    a.half = half_last + 4 * (nl - 1 - l); a.half_in = a.half + 4;
-    a.relu = relu[l]; a.cin = L.cin; a.cout = L.cout; a.kc = L.kc; a.w = L.d_w; a.b = L.d_bias;
+    a.half = half_last + 4 * (depth - 1 - l); a.half_in = a.half + 4;
+    a.relu = l >= 2; a.cin = L.cin; a.cout = L.cout; a.kc = L.kc; a.w = L.d_w; a.b = L.d_bias;
     a.sin = l > 0 ? ctx->d_edge + (l - 1) * ORCA_EDGE_SLAB : nullptr;
     a.sout = ctx->d_edge + l * ORCA_EDGE_SLAB;
-    a.y = reinterpret_cast<f32x4*>(ys[l]); a.y_plen = fmt == 2 ? ld_f32 : p16_plen(n); a.out_fmt = fmt;      // fmt 2: fp32 channel-major, row stride ld_f32
-    a.store_half = stores[l];
+    float* const y = l == 1 ? lo : l == 2 ? t : nullptr;
+    a.y = reinterpret_cast<f32x4*>(y); a.y_plen = fmt == 2 ? ld_f32 : p16_plen(n); a.out_fmt = fmt;
+    a.store_half = !y ? 0 : l == 1 ? 4 : 8;
     hipLaunchKernelGGL(lconv_edge_layer_kernel, dim3((unsigned)(2 * a.half)), dim3(512), 0, ctx->stream, a);
   }
   LAUNCHCHECK("lconv_edge_layer_kernel");
@@ -461,307 +442,269 @@ extern "C" int64_t orca_encoder_num_bins(int64_t L) {
   return n;
 }
 
-// One chunk: x (strided [4][n1]) -> 128 x n7 in the returned buffer.
-struct SeqSource {            // where a chunk's input comes from: a float [.,4] view or packed base codes
-  const float* x = nullptr;   // already offset to the chunk start
-  long sx_c = 0, sx_l = 0;
-  const unsigned char* codes = nullptr;   // whole sequence of this batch row: 1 byte per base, or (nmask set) a 2-bit genome plane + N mask, the
-  const unsigned char* nmask = nullptr;   // sequence starting at genome index `origin` (conv_p16.h: p16_base_at)
-  long origin = 0;
-  long codes_L = 0, codes_off = 0;
-  int reverse = 0;
-};
-
 // `part` (P16 planes only, SV screens off the 4 kb grid - orca_encoder_stage3_planes and friends below): the FRONT of the Encoder is stages 1-3
 // (99 % of its FLOPs; translation-covariant on a 16-base grid with a reach of 351 bases), the BACK stages 4-7 from the MaxPool1d(5)'d stage-3 output
 // (stage 4 - 1.2 of the back's 2.0 ms per window - moves into the cache too: ENC_STAGE4 runs it alone on a stage-4 input and hands its fp32 rows over,
 // ENC_FRONT4 = the front + stage 4 for the snippets, ENC_BACK5 = stages 5-7 from the MaxPool1d(5)'d rows: covariant on an 80-base grid, reach 1 631 bases)
 enum { ENC_FULL = 0, ENC_FRONT_POOLED = 1, ENC_FRONT_UNPOOLED = 2, ENC_BACK = 3, ENC_STAGE4 = 4, ENC_FRONT4 = 5, ENC_BACK5 = 6 };
 
-static int encoder_chunk(orca_ctx* ctx, orca_net* net, const SeqSource& src, long n1, float* const buf[3],
-                         long ld1, float** out, long* out_ld, long* out_n, int part = ENC_FULL) {
+// The route of one chunk, decided once (enc_route): the pipeline of its arithmetic mode, the form of stage 1, and its part as data.
+//   PIPE_P16 (f16x2) / PIPE_B16 (bf16): stages 1-4 on planar 16-bit activations with LDS-DMA staging (conv_p16.h; 2-way split fp16, fp32-class / one
+//     bf16 plane, the throughput mode of BASELINE config 3), stages 5-7 channel-last;  PIPE_NLC (bf16x2 / bf16x3): every stage on the channel-last
+//     split-operand kernels (conv_bf16s.h);  PIPE_F32: the exact fp32 kernels on channel-major rows
+enum { PIPE_P16, PIPE_B16, PIPE_NLC, PIPE_F32 };
+enum { OUT_BINS, OUT_PLANES, OUT_PLANES_POOLED, OUT_ROWS };   // the last stage's output: bins [n][128] | planes, every position | planes, MaxPool1d(5)'d | fp32 rows [n][128] before the pool
+struct EncRoute {
+  int pipe = PIPE_F32;
+  int fmt = 0;                 // planar pipelines: 0 P16, 1 B16
+  int first = 0, last = 6;     // stages run (0-based); a first stage > 0 reads its already pooled input from buf[0]
+  int out = OUT_BINS;
+  // planar pipelines.  Composed linear pairs (default; ORCA_ENCODER_FORM_TWO_CONV = the reference's layer sequence - also what a group whose composed
+  // weights leave the fp16 range falls back to): lconv1 is ONE 17-tap first layer (K = 68 MFMA GEMM from the bases / float rows), lconv2 / lconv3 are
+  // 17-tap planar convs.  The end positions of each group are redone exactly by the edge-fix chain (lconv_edge_layer_kernel).
+  bool compose = false;
+  bool compose25 = false;      // conv1.a, linear up to its ReLU, joins the group (25 taps from the bases + ReLU, K = 112); _FORM_LCONV1_ONLY keeps it a 64 -> 64 launch
+  bool res_from_bases = false; // ... and with packed bases the residual lout1 is computed inside conv1.b's epilogue (conv_p16.h, RL) instead of being stored
+                               // by a 17-tap first-layer launch and re-read (float rows, _FORM_STORED_RESIDUAL: the stored form)
+  bool stage1_fused = false;   // ... and on B16 planes the whole stage is then ONE kernel from the bases (conv_stage1.h)
+  bool fuse1 = false;          // two-conv form from packed input: the first layer is fused into the input-tile producer of the conv that follows it (conv_p16.h, F1)
+  // channel-last pipeline: stage 1 composed - from PACKED bases only: the first-layer GEMM splits its X operand into fp16 parts, exact for
+  // 0 / 0.25 / 1, while these modes promise fp32 range for arbitrary float rows
+  bool compose_nlc = false;
+  bool compose32 = false;      // exact-fp32 mode: stage 1's linear groups composed as in the 16-bit modes (conv_p16.h: first_taps_f32_kernel reads the source directly)
+  bool planar() const { return pipe == PIPE_P16 || pipe == PIPE_B16; }
+};
+
+static int enc_route(const orca_net* net, const SeqSource& src, int part, EncRoute* route) {
+  static const struct { int first, last, out; } kParts[7] = {
+      {0, 6, OUT_BINS}, {0, 2, OUT_PLANES_POOLED}, {0, 2, OUT_PLANES}, {3, 6, OUT_BINS}, {3, 3, OUT_ROWS}, {0, 3, OUT_ROWS}, {4, 6, OUT_BINS}};
+  EncRoute r;
+  const int prec = net->precision, form = net->enc_form;
+  r.pipe = prec == ORCA_PRECISION_F16X2 ? PIPE_P16 : prec == ORCA_PRECISION_BF16 ? PIPE_B16 : prec == ORCA_PRECISION_F32 ? PIPE_F32 : PIPE_NLC;
+  if (part != ENC_FULL && r.pipe != PIPE_P16) return fail(ORCA_EINVAL, "the Encoder's front / back parts exist in the f16x2 arithmetic (P16 planes) only");
+  r.first = kParts[part].first; r.last = kParts[part].last; r.out = kParts[part].out;
+  if (r.planar()) {
+    r.fmt = r.pipe == PIPE_B16 ? 1 : 0;
+    r.compose = form < ORCA_ENCODER_FORM_TWO_CONV && net->d_l1_w16 != nullptr;
+    r.compose25 = r.compose && form < ORCA_ENCODER_FORM_LCONV1_ONLY && net->d_c1a_w16 != nullptr;
+    r.res_from_bases = r.compose25 && src.codes && form < ORCA_ENCODER_FORM_STORED_RESIDUAL;
+    r.stage1_fused = r.res_from_bases && r.fmt == 1;
+    r.fuse1 = src.codes && r.fmt == 0 && !r.compose;
+  }
+  r.compose_nlc = r.pipe == PIPE_NLC && net->d_c1a_w16 && form < ORCA_ENCODER_FORM_LCONV1_ONLY && src.codes;
+  r.compose32 = r.pipe == PIPE_F32 && net->d_l1_f32 && form < ORCA_ENCODER_FORM_LCONV1_ONLY;
+  *route = r;
+  return ORCA_OK;
+}
+
+// buffer roles of the planar stages: S holds a stage's (pooled) input and receives its output, T the current conv's input, LO the stage's lout.
+// (guards and tails of every planar tensor are zeroed by p16_zero_pads_kernel AFTER its producer: the conv kernels write the units of a ragged
+// last tile unmasked.)  The channel-last and fp32 stages rotate: the input in buf[P], T = P + 1, LO = P + 2 (mod 3), the output back in buf[P]
+enum { kS = 0, kT = 1, kLO = 2 };
+static const int kPlanarStages = 4;   // stages on the planar kernels (pools 4, 4, 5 fused into the conv in front of them)
+
+// stage 1 on planes, the first-layer launches: lout1 into buf[kLO] (composed; not with res_from_bases, which never stores it) and / or the input of
+// the stage's next conv into buf[kT] (the first layer's output, or conv1.a's from the 25-tap group; not with stage1_fused)
+static int enc_stage1_first_layers(orca_ctx* ctx, const orca_net* net, const SeqSource& src, const EncRoute& r, long n, float* const buf[3]) {
   hipStream_t s = ctx->stream;
-  int P = 0;
-  long n = n1, ld = ld1;
+  const ConvLayer* L = net->convs.data();
+  const bool flat = src.codes || (src.sx_c == 1 && src.sx_l == 4 && al16(src.x));
+  if (r.compose || flat || r.fmt == 1) {
+    const float* rows = src.x;     // flat [n][4] float rows for the MFMA first-layer kernels (unused with packed input)
+    if (!flat) {
+      // strided float rows: gather them into a flat [n][4] copy (buf[kS] is free until the stage's last conv), then the MFMA kernel
+      hipLaunchKernelGGL(seq_to_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src.x, src.sx_c, src.sx_l, n, buf[kS]);
+      LAUNCHCHECK("seq_to_rows_kernel");
+      rows = buf[kS];
+    }
+    if (r.res_from_bases) { /* no lout1 tensor */ }
+    else if (r.compose) ORCA_TRY(launch_first_mfma(ctx, src, rows, n, 17, net->d_l1_w16, net->d_l1_bias, 0, buf[kLO], r.fmt));
+    else ORCA_TRY(launch_first_mfma(ctx, src, rows, n, 9, net->d_first_w16, L[0].d_bias, 0, buf[kT], r.fmt));
+    if (r.compose25 && !r.stage1_fused) {
+      ORCA_TRY(launch_first_mfma(ctx, src, rows, n, 25, net->d_c1a_w16, net->d_c1a_bias, 1, buf[kT], r.fmt));
+      ORCA_TRY(launch_p16_zero_pads(ctx, buf[kT], 64, n, r.fmt));
+    }
+  } else {      // strided float rows, two-conv form on P16 planes: the fp32 first layer
+    FirstP16Args fa;
+    fa.x = src.x; fa.sc = src.sx_c; fa.sl = src.sx_l; fa.n = n; fa.w = net->d_first_w; fa.bias = L[0].d_bias; fa.y = reinterpret_cast<f32x4*>(buf[kT]);
+    fa.y_plen = p16_plen(n); fa.flag = ctx->d_flag;
+    hipLaunchKernelGGL(conv1d_first_p16_kernel, dim3((unsigned)((n + 255) / 256), 8), dim3(256), 0, s, fa);
+    LAUNCHCHECK("conv1d_first_p16_kernel");
+  }
+  if (!r.res_from_bases) ORCA_TRY(launch_p16_zero_pads(ctx, r.compose ? buf[kLO] : buf[kT], 64, n, r.fmt));
+  return ORCA_OK;
+}
+
+// stage 1's last conv with the residual from the bases: relu(conv1.b) + lout1 computed in the epilogue, MaxPool1d(4); the pooled windows at the
+// ends from the edge chain's exact conv1.b (slab 3) and lout1 (slab 1)
+static int enc_stage1_last_from_bases(orca_ctx* ctx, const orca_net* net, const SeqSource& src, const EncRoute& r, long n, float* const buf[3]) {
+  const ConvLayer& Lb = net->convs[3];
+  if (r.stage1_fused) {
+    ORCA_TRY(launch_stage1_b16(ctx, net, Lb, src, buf[kT], buf[kS], n));
+  } else {
+    FusedFirst rl;
+    rl.src = &src; rl.table = reinterpret_cast<const float*>(net->d_l1_w16); rl.bias = net->d_l1_bias; rl.residual = true;
+    ORCA_TRY(launch_conv1d_p16(ctx, Lb, buf[kT], buf[kS], nullptr, n, 1, 1, &rl, r.fmt));
+  }
+  ORCA_TRY(launch_p16_zero_pads(ctx, buf[kS], Lb.cout, n / 4, r.fmt));
+  EdgePoolArgs ep{};
+  ep.sc = ctx->d_edge + 3 * ORCA_EDGE_SLAB; ep.half_c = 8; ep.sl = ctx->d_edge + 1 * ORCA_EDGE_SLAB; ep.half_l = 16; ep.n = n; ep.cout = Lb.cout;
+  ep.y = reinterpret_cast<f32x4*>(buf[kS]); ep.y_plen = p16_plen(n / 4); ep.out_fmt = r.fmt;
+  if (n / 4 > 0) hipLaunchKernelGGL(lconv_edge_pool_kernel, dim3(3), dim3(128), 0, ctx->stream, ep);
+  LAUNCHCHECK("lconv_edge_pool_kernel");
+  return ORCA_OK;
+}
+
+// stage 1 on planes: the source -> its MaxPool1d(4)'d output in buf[kS] (*n positions in, *n / 4 out).  Five variants (EncRoute): two convs with the
+// first layer fused into the second (fuse1) or stored; lconv1 composed; conv1.a composed too, the residual stored; the residual from the bases, as
+// one kernel on B16 planes
+static int enc_stage1_planes(orca_ctx* ctx, const orca_net* net, const SeqSource& src, const EncRoute& r, float* const buf[3], long* n_io) {
+  const ConvLayer* L = net->convs.data();
+  const long n = *n_io;
+  const int fmt = r.fmt, C = L[3].cout;
+  if (!r.fuse1) ORCA_TRY(enc_stage1_first_layers(ctx, net, src, r, n, buf));    // (fuse1: the first layer's output is never materialised)
+  if (r.compose) {
+    const EdgeFixArgs ef = edge_source(src);
+    // (res_from_bases: lout1 is never stored; conv1.b's own end positions are needed for the pooled windows)
+    if (r.res_from_bases) ORCA_TRY(launch_edge_chain(ctx, L, 4, 8, ef, n, nullptr, buf[kT], fmt));
+    else if (r.compose25) ORCA_TRY(launch_edge_chain(ctx, L, 3, 8, ef, n, buf[kLO], buf[kT], fmt));
+    else ORCA_TRY(launch_edge_chain(ctx, L, 2, 4, ef, n, buf[kLO], nullptr, fmt));
+  } else {
+    FusedFirst f1;
+    f1.src = &src; f1.table = net->d_first_tab; f1.bias = L[0].d_bias;
+    ORCA_TRY(launch_conv1d_p16(ctx, L[1], buf[kT], buf[kLO], nullptr, n, 0, 0, r.fuse1 ? &f1 : nullptr, fmt));   // lout
+    ORCA_TRY(launch_p16_zero_pads(ctx, buf[kLO], C, n, fmt));
+  }
+  if (!r.compose25) {     // (composed: conv1.a's output is already in buf[kT], straight from the bases)
+    ORCA_TRY(launch_conv1d_p16(ctx, L[2], buf[kLO], buf[kT], nullptr, n, 1, 0, nullptr, fmt));
+    ORCA_TRY(launch_p16_zero_pads(ctx, buf[kT], C, n, fmt));
+  }
+  if (r.res_from_bases) {
+    ORCA_TRY(enc_stage1_last_from_bases(ctx, net, src, r, n, buf));
+  } else {
+    ORCA_TRY(launch_conv1d_p16(ctx, L[3], buf[kT], buf[kS], buf[kLO], n, 1, 1, nullptr, fmt));          // relu(.)+lout, MaxPool1d(4)
+    ORCA_TRY(launch_p16_zero_pads(ctx, buf[kS], C, n / 4, fmt));
+  }
+  *n_io = n / 4;
+  return ORCA_OK;
+}
+
+// the planar stages behind stage 1 (2 .. 4, from r.first, up to r.last): buf[kS] with *n positions -> buf[kS].  The pool behind a stage is fused into
+// its last conv (conv_p16.h: MaxPool1d(4), conv_p16p5.h: MaxPool1d(5)) unless the route hands the planes over unpooled; stage 4 hands over fp32 rows
+static int enc_planar_stages(orca_ctx* ctx, const orca_net* net, const EncRoute& r, float* const buf[3], long* n_io) {
+  const int fmt = r.fmt;
+  float *S = buf[kS], *T = buf[kT], *LO = buf[kLO];
+  long n = *n_io;
+  for (int st = r.first > 1 ? r.first : 1; st < kPlanarStages && st <= r.last; ++st) {
+    const ConvLayer* Ls = &net->convs[4 * st];
+    const int C = Ls[3].cout;
+    // the stage's linear pair: (pooled) previous output S -> lout in LO
+    if (r.compose && st <= 2 && net->comp[st].d_wf16) {
+      ORCA_TRY(launch_conv1d_p16(ctx, net->comp[st], S, LO, nullptr, n, 0, 0, nullptr, fmt));
+      ORCA_TRY(launch_p16_zero_pads(ctx, LO, C, n, fmt));
+      EdgeFixArgs ef{};
+      ef.in_mode = fmt == 1 ? 3 : 2; ef.xp = reinterpret_cast<const f32x4*>(S); ef.x_plen = p16_plen(n);
+      ORCA_TRY(launch_edge_chain(ctx, Ls, 2, 4, ef, n, LO, nullptr, fmt));
+    } else {
+      ORCA_TRY(launch_conv1d_p16(ctx, Ls[0], S, T, nullptr, n, 0, 0, nullptr, fmt));
+      ORCA_TRY(launch_p16_zero_pads(ctx, T, C, n, fmt));
+      ORCA_TRY(launch_conv1d_p16(ctx, Ls[1], T, LO, nullptr, n, 0, 0, nullptr, fmt));   // lout
+      ORCA_TRY(launch_p16_zero_pads(ctx, LO, C, n, fmt));
+    }
+    ORCA_TRY(launch_conv1d_p16(ctx, Ls[2], LO, T, nullptr, n, 1, 0, nullptr, fmt));
+    ORCA_TRY(launch_p16_zero_pads(ctx, T, C, n, fmt));
+    // the last conv: relu(.) + lout
+    if (st + 1 == kPlanarStages) {
+      ORCA_TRY(launch_conv1d_p16(ctx, Ls[3], T, S, LO, n, 1, 2, nullptr, fmt));          // fp32 channel-last hand-over
+      break;
+    }
+    const int pool = kEncPools[st + 1];
+    if (pool != 4 && (pool != 5 || C != 128)) return fail(ORCA_EINVAL, "internal: planar stage %d followed by an unexpected pool", st + 1);
+    if (st == r.last && r.out == OUT_PLANES) {   // stage 3's output as it is, every position: what a stage-3 cache keeps (the pool is the reader's)
+      ORCA_TRY(launch_conv1d_p16(ctx, Ls[3], T, S, LO, n, 1, 0, nullptr, fmt));
+      ORCA_TRY(launch_p16_zero_pads(ctx, S, C, n, fmt));
+      break;
+    }
+    ORCA_TRY(launch_conv1d_p16(ctx, Ls[3], T, S, LO, n, 1, pool == 4 ? 1 : 3, nullptr, fmt));   // MaxPool1d(4) / MaxPool1d(5) (conv_p16p5.h)
+    ORCA_TRY(launch_p16_zero_pads(ctx, S, C, n / pool, fmt));
+    n /= pool;
+  }
+  *n_io = n;
+  return ORCA_OK;
+}
+
+// the pipelines that start from float rows: the source as channel-major [4][ld1] in buf[0] (packed bases are expanded into buf[2] as [n][4] first)
+static int enc_rows_channel_major(orca_ctx* ctx, const SeqSource& src, long n1, float* const buf[3], long ld1) {
   const float* x = src.x;
   long sx_c = src.sx_c, sx_l = src.sx_l;
-  // planar 16-bit activation formats of conv_p16.h for stages 1-3 (96 % of the FLOPs):
-  //   f16x2 -> P16 (2-way split fp16, fp32-class);  bf16 -> B16 (one bf16 plane, throughput mode of BASELINE config 3)
-  const bool use_b16 = net->precision == ORCA_PRECISION_BF16;
-  const bool use_p16 = net->precision == ORCA_PRECISION_F16X2 || use_b16;
-  const int fmt = use_b16 ? 1 : 0;
-  if (part != ENC_FULL && !(use_p16 && fmt == 0)) return fail(ORCA_EINVAL, "the Encoder's front / back parts exist in the f16x2 arithmetic (P16 planes) only");
-  // the channel-last split-operand pipeline (bf16x3 / bf16x2): stage 1 composed - from PACKED bases only: the
-  // first-layer GEMM splits its X operand into fp16 parts, exact for 0 / 0.25 / 1, while these modes promise fp32 range for arbitrary float rows
-  const bool compose_nlc = !use_p16 && net->precision != ORCA_PRECISION_F32 && net->d_c1a_w16 && net->enc_form < ORCA_ENCODER_FORM_LCONV1_ONLY && src.codes;
-  // exact-fp32 mode: stage 1's linear groups composed as in the 16-bit modes (conv_p16.h: first_taps_f32_kernel reads the source directly)
-  const bool compose32 = net->precision == ORCA_PRECISION_F32 && net->d_l1_f32 && net->enc_form < ORCA_ENCODER_FORM_LCONV1_ONLY;
-  if (src.codes && !use_p16 && !compose32 && !compose_nlc) {
-    // the other arithmetic modes start from float rows: expand the packed bases into buf[2] as [n][4]
-    hipLaunchKernelGGL(expand_codes_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, src.codes, src.nmask, src.origin, src.codes_L, src.codes_off,
-                       src.reverse, n1, buf[2]);
+  if (src.codes) {
+    hipLaunchKernelGGL(expand_codes_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, ctx->stream, src.codes, src.nmask, src.origin, src.codes_L,
+                       src.codes_off, src.reverse, n1, buf[2]);
     LAUNCHCHECK("expand_codes_kernel");
     x = buf[2]; sx_c = 1; sx_l = 4;
   }
-  if (!use_p16 && !compose32 && !compose_nlc) {
-    hipLaunchKernelGGL(seq_to_channel_major_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, x, sx_c, sx_l, n1, buf[P], ld1);
-    LAUNCHCHECK("seq_to_channel_major_kernel");
-  }
-  if (net->precision != ORCA_PRECISION_F32) {
-    // channel-last pipeline on the bf16 matrix cores (conv_bf16s.h); the 4-channel first layer stays on
-    // the fp32 kernel (K = 36, 1 % of the FLOPs) and writes channel-last.
-    const int prec = net->precision;
-    int st0 = part == ENC_BACK5 ? 4 : 0;          // (ENC_BACK5: stage 5's input - n1 positions, fp32 channel-last - is in buf[0])
-    if (use_p16 && part != ENC_BACK5) {
-      // stages 1-3 on planar 16-bit activations with LDS-DMA staging (conv_p16.h)
-      const ConvLayer* L = net->convs.data();
-      FirstP16Args fa;
-      fa.x = x; fa.sc = sx_c; fa.sl = sx_l; fa.n = n1; fa.w = nullptr; fa.bias = L[0].d_bias; fa.y = reinterpret_cast<f32x4*>(buf[1]);
-      fa.y_plen = p16_plen(n1); fa.flag = ctx->d_flag;
-      fa.w = net->d_first_w;
-      // Composed linear pairs (default; orca_net_set_encoder_form(ORCA_ENCODER_FORM_TWO_CONV) = the reference's layer sequence - also what a group
-      // whose composed weights leave the fp16 range falls back to): lconv1 is ONE
-      // 17-tap first layer straight into buf[LO] (K = 68 MFMA GEMM from the bases / float rows), lconv2 / lconv3 are 17-tap planar
-      // convs; conv1.a, linear up to its ReLU, is composed with lconv1 as well (25 taps from the bases).  The end positions of each
-      // group are redone exactly by the edge-fix chain (lconv_edge_layer_kernel).
-      const bool compose = net->enc_form < ORCA_ENCODER_FORM_TWO_CONV && net->d_l1_w16 != nullptr;
-      // two-conv form from packed input: the first layer is fused into the input-tile producer of the conv that follows it (conv_p16.h, F1)
-      const bool fuse1 = src.codes && fmt == 0 && !compose;
-      FusedFirst f1;
-      f1.codes = src.codes; f1.nmask = src.nmask; f1.origin = src.origin; f1.codes_L = src.codes_L; f1.codes_off = src.codes_off; f1.reverse = src.reverse;
-      f1.table = net->d_first_tab; f1.bias = L[0].d_bias;
-      int T = 1, LO = 2, S = 0;   // buffer roles: T holds the current input
-      // (guards and tails of every planar tensor are zeroed by p16_zero_pads_kernel AFTER its producer: the conv kernels
-      // write the units of a ragged last tile unmasked)
-      const bool flat = src.codes || (sx_c == 1 && sx_l == 4 && al16(x));
-      // conv1.a joins the composed group (25 taps from the bases + ReLU, K = 112); _FORM_LCONV1_ONLY keeps it a 64 -> 64 launch
-      const bool compose25 = compose && net->enc_form < ORCA_ENCODER_FORM_LCONV1_ONLY && net->d_c1a_w16 != nullptr;
-      // ... and with packed bases the residual lout1 is computed inside conv1.b's epilogue (conv_p16.h, RL) instead of being stored by a
-      // 17-tap first-layer launch and re-read (float rows, _FORM_STORED_RESIDUAL: the stored form)
-      const bool res_from_bases = compose25 && src.codes && net->enc_form < ORCA_ENCODER_FORM_STORED_RESIDUAL;
-      // ... and in the throughput mode (B16 planes) the whole stage is then ONE kernel from the bases (conv_stage1.h): conv1.b's input tiles are
-      // produced in LDS by the matrix cores, a1 is neither written nor re-read
-      const bool stage1_fused = res_from_bases && fmt == 1;
-      float* first_out = compose ? buf[LO] : buf[T];
-      const float* rows = x;     // flat [n][4] float rows for the MFMA first-layer kernels (unused with packed input)
-      // one first-layer GEMM launch: ntap 9 (lconv1.a alone), 17 (lconv1 composed), 25 (conv1.a o lconv1, + ReLU)
-      auto launch_first = [&](int ntap, const void* w16, const float* bias, int relu, float* out) -> int {
-        FirstMfmaArgs fm;
-        fm.codes = src.codes; fm.nmask = src.nmask; fm.origin = src.origin; fm.codes_L = src.codes_L; fm.codes_off = src.codes_off; fm.reverse = src.reverse;
-        fm.x = src.codes ? nullptr : rows; fm.n = n1;
-        fm.w = reinterpret_cast<const f32x4*>(w16); fm.bias = bias; fm.relu = relu;
-        fm.y = reinterpret_cast<f32x4*>(out); fm.y_plen = p16_plen(n1); fm.flag = ctx->d_flag;
-        const long nt = (n1 + 255) / 256;
-        const dim3 grid((unsigned)(nt < 2048 ? nt : 2048));
-        const bool timed = ctx->timing && n1 >= 65536 && ntap > 9;
-        TimedLaunch tl;
-        if (timed) {
-          HIPCHECK(hipEventCreate(&tl.e0));
-          HIPCHECK(hipEventCreate(&tl.e1));
-          HIPCHECK(hipEventRecord(tl.e0, s));
-        }
-        switch (ntap * 2 + fmt) {
-          case 18: hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 0, 9>), grid, dim3(256), 0, s, fm); break;
-          case 19: hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 1, 9>), grid, dim3(256), 0, s, fm); break;
-          case 34: hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 0, 17>), grid, dim3(256), 0, s, fm); break;
-          case 35: hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 1, 17>), grid, dim3(256), 0, s, fm); break;
-          case 50: hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 0, 25>), grid, dim3(256), 0, s, fm); break;
-          default: hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 1, 25>), grid, dim3(256), 0, s, fm); break;
-        }
-        LAUNCHCHECK("conv1d_first_mfma_p16_kernel");
-        if (timed) {
-          HIPCHECK(hipEventRecord(tl.e1, s));
-          tl.rec.cout = 64; tl.rec.cin = 4; tl.rec.tile = fmt == 1 ? -6 : -5; tl.rec.batch = 1; tl.rec.n = n1; tl.rec.ms = 0.f; tl.rec.ksize = ntap;
-          ctx->timed.push_back(tl);
-        }
-        return ORCA_OK;
-      };
-      if (part == ENC_BACK || part == ENC_STAGE4) {
-        // stage 4's input (n1 positions, 128 channels) is in buf[S] already
-      } else {
-      if (fuse1) {
-        // nothing to launch: buf[1] is never materialised
-      } else if (compose || flat || fmt == 1) {
-        if (!flat) {
-          // strided float rows: gather them into a flat [n][4] copy (buf[S] is free until the stage's last conv), then the MFMA kernel
-          hipLaunchKernelGGL(seq_to_rows_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, x, sx_c, sx_l, n1, buf[S]);
-          LAUNCHCHECK("seq_to_rows_kernel");
-          rows = buf[S];
-        }
-        if (res_from_bases) { /* no lout1 tensor */ }
-        else if (compose) ORCA_TRY(launch_first(17, net->d_l1_w16, net->d_l1_bias, 0, buf[LO]));
-        else ORCA_TRY(launch_first(9, net->d_first_w16, L[0].d_bias, 0, buf[T]));
-        if (compose25 && !stage1_fused) {
-          ORCA_TRY(launch_first(25, net->d_c1a_w16, net->d_c1a_bias, 1, buf[T]));
-          ORCA_TRY(launch_p16_zero_pads(ctx, buf[T], 64, n1, fmt));
-        }
-      } else {
-        hipLaunchKernelGGL(conv1d_first_p16_kernel, dim3((unsigned)((n1 + 255) / 256), 8), dim3(256), 0, s, fa);
-        LAUNCHCHECK("conv1d_first_p16_kernel");
-      }
-      if (!fuse1 && !res_from_bases) ORCA_TRY(launch_p16_zero_pads(ctx, first_out, 64, n1, fmt));
-      if (compose) {
-        EdgeFixArgs ef{};
-        if (src.codes) { ef.in_mode = 1; ef.codes = src.codes; ef.nmask = src.nmask; ef.origin = src.origin; ef.codes_L = src.codes_L; ef.codes_off = src.codes_off; ef.reverse = src.reverse; }
-        else { ef.in_mode = 0; ef.x = x; ef.sc = sx_c; ef.sl = sx_l; }
-        const ConvLayer* chain[4] = {&L[0], &L[1], &L[2], &L[3]};
-        const int relus[4] = {0, 0, 1, 1};
-        if (res_from_bases) {        // lout1 is never stored; conv1.b's own end positions are needed for the pooled windows (after the conv, below)
-          float* ys[4] = {nullptr, nullptr, buf[T], nullptr};
-          const int st_[4] = {0, 0, 8, 0};
-          ORCA_TRY(launch_edge_chain(ctx, chain, relus, 4, 8, ef, n1, ys, st_, fmt));
-        } else if (compose25) {
-          float* ys[3] = {nullptr, buf[LO], buf[T]};
-          const int st_[3] = {0, 4, 8};
-          ORCA_TRY(launch_edge_chain(ctx, chain, relus, 3, 8, ef, n1, ys, st_, fmt));
-        } else {
-          float* ys[2] = {nullptr, buf[LO]};
-          const int st_[2] = {0, 4};
-          ORCA_TRY(launch_edge_chain(ctx, chain, relus, 2, 4, ef, n1, ys, st_, fmt));
-        }
-      }
-      }
-      n = n1;
-      const int nplanar = 4;                                                // stages on the planar kernels (pools 4, 4, 5 fused into the conv in front of them)
-      const bool from4 = part == ENC_BACK || part == ENC_STAGE4;
-      for (st0 = from4 ? 3 : 0; st0 < nplanar; ++st0) {
-        const ConvLayer* Ls = L + 4 * st0;
-        const int C = Ls[3].cout;
-        if (kEncPools[st0] == 5 && !from4) n /= 5;   // the previous stage's last conv already pooled (conv_p16p5.h): buf[S] holds n / 5 positions
-        // the stage's linear pair: (pooled) previous output buf[S] -> lout in buf[LO]
-        const bool comp_st = compose && (st0 == 0 || (st0 <= 2 && net->comp[st0].d_wf16));
-        if (comp_st && st0 > 0) {
-          ORCA_TRY(launch_conv1d_p16(ctx, net->comp[st0], buf[S], buf[LO], nullptr, n, 0, 0, nullptr, fmt));
-          ORCA_TRY(launch_p16_zero_pads(ctx, buf[LO], C, n, fmt));
-          EdgeFixArgs ef{};
-          ef.in_mode = fmt == 1 ? 3 : 2; ef.xp = reinterpret_cast<const f32x4*>(buf[S]); ef.x_plen = p16_plen(n);
-          const ConvLayer* chain[2] = {&Ls[0], &Ls[1]};
-          const int relus[2] = {0, 0};
-          float* ys[2] = {nullptr, buf[LO]};
-          const int st_[2] = {0, 4};
-          ORCA_TRY(launch_edge_chain(ctx, chain, relus, 2, 4, ef, n, ys, st_, fmt));
-        } else if (!comp_st) {
-          if (st0 > 0) {  // first conv of the stage: previous (pooled) output in buf[S] -> buf[T]
-            ORCA_TRY(launch_conv1d_p16(ctx, Ls[0], buf[S], buf[T], nullptr, n, 0, 0, nullptr, fmt));
-            ORCA_TRY(launch_p16_zero_pads(ctx, buf[T], C, n, fmt));
-          }
-          ORCA_TRY(launch_conv1d_p16(ctx, Ls[1], buf[T], buf[LO], nullptr, n, 0, 0, (st0 == 0 && fuse1) ? &f1 : nullptr, fmt));   // lout
-          ORCA_TRY(launch_p16_zero_pads(ctx, buf[LO], C, n, fmt));
-        }
-        if (!(st0 == 0 && compose25)) {     // (stage 1, composed: conv1.a's output is already in buf[T], straight from the bases)
-          ORCA_TRY(launch_conv1d_p16(ctx, Ls[2], buf[LO], buf[T], nullptr, n, 1, 0, nullptr, fmt));
-          ORCA_TRY(launch_p16_zero_pads(ctx, buf[T], C, n, fmt));
-        }
-        if (st0 == 0 && res_from_bases) {
-          FusedFirst rl;     // relu(.) + lout1 computed from the bases in the epilogue, MaxPool1d(4)
-          rl.codes = src.codes; rl.nmask = src.nmask; rl.origin = src.origin; rl.codes_L = src.codes_L; rl.codes_off = src.codes_off; rl.reverse = src.reverse;
-          rl.table = reinterpret_cast<const float*>(net->d_l1_w16); rl.bias = net->d_l1_bias; rl.residual = true;
-          if (stage1_fused) {
-            Stage1Args sa;
-            ConvP16Args& a1 = sa.c;
-            a1.x = nullptr; a1.w = reinterpret_cast<const f32x4*>(Ls[3].d_wb16p); a1.bias = Ls[3].d_bias; a1.y = buf[S]; a1.r1 = nullptr;
-            a1.x_plen = p16_plen(n); a1.y_plen = p16_plen(n / 4); a1.n = n; a1.tiles_per_row = (n + 63) / 64; a1.nchunks = 2; a1.cout = 64;
-            a1.relu = 1; a1.out_mode = 1; a1.k17 = 0; a1.flag = ctx->d_flag; a1.stamps = nullptr;
-            a1.f1_codes = rl.codes; a1.f1_nmask = rl.nmask; a1.f1_origin = rl.origin; a1.f1_codes_L = rl.codes_L; a1.f1_codes_off = rl.codes_off; a1.f1_reverse = rl.reverse;
-            a1.rl_w = reinterpret_cast<const f32x4*>(net->d_l1_w16); a1.f1_table = nullptr; a1.f1_bias = net->d_l1_bias;
-            sa.w25 = reinterpret_cast<const f32x4*>(net->d_c1a_w16); sa.b25 = net->d_c1a_bias;
-            sa.a1_edge = reinterpret_cast<const f32x4*>(buf[T]); sa.a1_plen = p16_plen(n);
-            static int ncu_ = [] { int dev = 0, v = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v; }();
-            const long ntw_ = (n + 63) / 64;
-            const long need_ = (ntw_ + 7) / 8;
-            const bool timed_ = ctx->timing && n >= 65536;
-            TimedLaunch tl_;
-            if (timed_) {
-              HIPCHECK(hipEventCreate(&tl_.e0));
-              HIPCHECK(hipEventCreate(&tl_.e1));
-              HIPCHECK(hipEventRecord(tl_.e0, s));
-            }
-            hipLaunchKernelGGL((conv1d_stage1_b16_kernel<1>), dim3((unsigned)(need_ < ncu_ ? need_ : ncu_)), dim3(512), 0, s, sa);
-            LAUNCHCHECK("conv1d_stage1_b16_kernel");
-            ctx->counts[2]++;
-            if (timed_) {
-              HIPCHECK(hipEventRecord(tl_.e1, s));
-              // (both 64 -> 64 convs of the stage in one launch: recorded as cin = 128 so that 2 * 9 * cin * cout is the pair's algorithmic work)
-              tl_.rec.cout = 64; tl_.rec.cin = 128; tl_.rec.tile = -15; tl_.rec.batch = 1; tl_.rec.n = n; tl_.rec.ms = 0.f; tl_.rec.ksize = 9;
-              ctx->timed.push_back(tl_);
-            }
-          } else {
-            ORCA_TRY(launch_conv1d_p16(ctx, Ls[3], buf[T], buf[S], nullptr, n, 1, 1, &rl, fmt));
-          }
-          ORCA_TRY(launch_p16_zero_pads(ctx, buf[S], C, n / 4, fmt));
-          EdgePoolArgs ep{};
-          ep.sc = ctx->d_edge + 3 * ORCA_EDGE_SLAB; ep.half_c = 8; ep.sl = ctx->d_edge + 1 * ORCA_EDGE_SLAB; ep.half_l = 16; ep.n = n; ep.cout = C;
-          ep.y = reinterpret_cast<f32x4*>(buf[S]); ep.y_plen = p16_plen(n / 4); ep.out_fmt = fmt;
-          if (n / 4 > 0) hipLaunchKernelGGL(lconv_edge_pool_kernel, dim3(3), dim3(128), 0, s, ep);
-          LAUNCHCHECK("lconv_edge_pool_kernel");
-          n /= 4;
-        } else if (st0 + 1 < nplanar && kEncPools[st0 + 1] == 4) {
-          ORCA_TRY(launch_conv1d_p16(ctx, Ls[3], buf[T], buf[S], buf[LO], n, 1, 1, nullptr, fmt));          // relu(.)+lout, MaxPool1d(4)
-          ORCA_TRY(launch_p16_zero_pads(ctx, buf[S], C, n / 4, fmt));
-          n /= 4;
-        } else if (st0 + 1 < nplanar) {      // (the pool in front of stage 4)
-          if (kEncPools[st0 + 1] != 5 || C != 128) return fail(ORCA_EINVAL, "internal: planar stage %d followed by an unexpected pool", st0 + 1);
-          if (part == ENC_FRONT_UNPOOLED) {   // stage 3's output as it is, every position: what a stage-3 cache keeps (the pool is the reader's)
-            ORCA_TRY(launch_conv1d_p16(ctx, Ls[3], buf[T], buf[S], buf[LO], n, 1, 0, nullptr, fmt));
-            ORCA_TRY(launch_p16_zero_pads(ctx, buf[S], C, n, fmt));
-            *out = buf[S]; *out_ld = 0; *out_n = n;
-            return ORCA_OK;
-          }
-          ORCA_TRY(launch_conv1d_p16(ctx, Ls[3], buf[T], buf[S], buf[LO], n, 1, 3, nullptr, fmt));          // relu(.)+lout, MaxPool1d(5) (conv_p16p5.h)
-          ORCA_TRY(launch_p16_zero_pads(ctx, buf[S], C, n / 5, fmt));
-          if (part == ENC_FRONT_POOLED) { *out = buf[S]; *out_ld = 0; *out_n = n / 5; return ORCA_OK; }
-        } else {
-          ORCA_TRY(launch_conv1d_p16(ctx, Ls[3], buf[T], buf[S], buf[LO], n, 1, 2, nullptr, fmt));          // fp32 channel-last hand-over
-        }
-      }
-      P = S;
-      if (part == ENC_STAGE4 || part == ENC_FRONT4) { *out = buf[P]; *out_ld = -128; *out_n = n; return ORCA_OK; }     // stage 4's output, fp32 [n][128], before MaxPool1d(5)
+  hipLaunchKernelGGL(seq_to_channel_major_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, ctx->stream, x, sx_c, sx_l, n1, buf[0], ld1);
+  LAUNCHCHECK("seq_to_channel_major_kernel");
+  return ORCA_OK;
+}
+
+// stage 1's linear groups of the channel-last pipeline composed (the fallback of the fp16-range guard runs this in bf16x3): lconv1 and
+// conv1.a o lconv1 as 17- / 25-tap first-layer GEMMs writing fp32 channel-last, exact ends by the edge chain
+static int enc_stage1_groups_nlc(orca_ctx* ctx, const orca_net* net, const SeqSource& src, long n, float* lo, float* t) {
+  hipStream_t s = ctx->stream;
+  FirstMfmaArgs fm;
+  set_bases(fm, src);
+  fm.x = src.codes ? nullptr : src.x; fm.n = n; fm.y_plen = 0; fm.flag = nullptr;
+  const long nt = (n + 255) / 256;
+  const dim3 grid((unsigned)(nt < 2048 ? nt : 2048));
+  fm.w = reinterpret_cast<const f32x4*>(net->d_l1_w16); fm.bias = net->d_l1_bias; fm.relu = 0; fm.y = reinterpret_cast<f32x4*>(lo);
+  hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 2, 17>), grid, dim3(256), 0, s, fm);
+  fm.w = reinterpret_cast<const f32x4*>(net->d_c1a_w16); fm.bias = net->d_c1a_bias; fm.relu = 1; fm.y = reinterpret_cast<f32x4*>(t);
+  hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 2, 25>), grid, dim3(256), 0, s, fm);
+  LAUNCHCHECK("conv1d_first_mfma_p16_kernel");
+  return launch_edge_chain(ctx, net->convs.data(), 3, 8, edge_source(src), n, lo, t, 3);
+}
+
+// stages `st_from` .. 7 on the channel-last kernels (conv_bf16s.h / conv_small.h): every stage of the channel-last pipeline, stages 5-7 of the planar
+// ones (buf[0] holds stage 4's fp32 rows, or - first stage 5 - the already pooled rows of the caller)
+static int enc_stages_nlc(orca_ctx* ctx, const orca_net* net, const SeqSource& src, const EncRoute& r, int st_from, long n, float* const buf[3], long ld1,
+                          float** out, long* out_ld, long* out_n) {
+  const int prec = net->precision;
+  int P = 0;
+  // stage 1 uncomposed: the 4-channel first layer stays on the fp32 kernel (K = 36, 1 % of the FLOPs) and writes channel-last
+  if (r.pipe == PIPE_NLC && !r.compose_nlc) ORCA_TRY(enc_rows_channel_major(ctx, src, n, buf, ld1));
+  for (int st = st_from; st < 7; ++st) {
+    const ConvLayer* L = &net->convs[4 * st];
+    if (kEncPools[st] == 4) {
+      n = n / 4;  // MaxPool1d(4) was fused into the epilogue of the previous stage's last conv
+    } else if (kEncPools[st] > 1 && st != r.first) {
+      const long n2 = n / kEncPools[st];
+      const int Q = (P + 1) % 3;
+      ORCA_TRY(launch_pool_nlc(ctx, buf[P], buf[Q], n2, L[0].cin, kEncPools[st]));
+      P = Q; n = n2;
     }
-    for (int st = st0; st < 7; ++st) {
-      const ConvLayer* L = &net->convs[4 * st];
-      if (kEncPools[st] == 4 && st0 == 0) {
-        n = n / 4;  // MaxPool1d(4) was fused into the epilogue of the previous stage's last conv
-      } else if (kEncPools[st] > 1 && !(part == ENC_BACK5 && st == 4)) {
-        const long n2 = n / kEncPools[st];
-        const int Q = (P + 1) % 3;
-        ORCA_TRY(launch_pool_nlc(ctx, buf[P], buf[Q], n2, L[0].cin, kEncPools[st]));
-        P = Q; n = n2;
-      }
-      const int T = (P + 1) % 3, LO = (P + 2) % 3;
-      if (st == 0 && compose_nlc) {
-        // stage 1's linear groups composed here too (the fallback of the fp16-range guard runs this branch in bf16x3): lconv1 and
-        // conv1.a o lconv1 as 17- / 25-tap first-layer GEMMs writing fp32 channel-last, exact ends by the edge chain
-        FirstMfmaArgs fm;
-        fm.codes = src.codes; fm.nmask = src.nmask; fm.origin = src.origin; fm.codes_L = src.codes_L; fm.codes_off = src.codes_off; fm.reverse = src.reverse;
-        fm.x = src.codes ? nullptr : src.x; fm.n = n; fm.y_plen = 0; fm.flag = nullptr;
-        const long nt = (n + 255) / 256;
-        const dim3 grid((unsigned)(nt < 2048 ? nt : 2048));
-        fm.w = reinterpret_cast<const f32x4*>(net->d_l1_w16); fm.bias = net->d_l1_bias; fm.relu = 0; fm.y = reinterpret_cast<f32x4*>(buf[LO]);
-        hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 2, 17>), grid, dim3(256), 0, s, fm);
-        fm.w = reinterpret_cast<const f32x4*>(net->d_c1a_w16); fm.bias = net->d_c1a_bias; fm.relu = 1; fm.y = reinterpret_cast<f32x4*>(buf[T]);
-        hipLaunchKernelGGL((conv1d_first_mfma_p16_kernel<0, 2, 25>), grid, dim3(256), 0, s, fm);
-        LAUNCHCHECK("conv1d_first_mfma_p16_kernel");
-        EdgeFixArgs ef{};
-        if (src.codes) { ef.in_mode = 1; ef.codes = src.codes; ef.nmask = src.nmask; ef.origin = src.origin; ef.codes_L = src.codes_L; ef.codes_off = src.codes_off; ef.reverse = src.reverse; }
-        else { ef.in_mode = 0; ef.x = src.x; ef.sc = src.sx_c; ef.sl = src.sx_l; }
-        const ConvLayer* chain[3] = {&L[0], &L[1], &L[2]};
-        const int relus[3] = {0, 0, 1};
-        float* ys[3] = {nullptr, buf[LO], buf[T]};
-        const int st_[3] = {0, 4, 8};
-        ORCA_TRY(launch_edge_chain(ctx, chain, relus, 3, 8, ef, n, ys, st_, 3));
-      } else {
+    const int T = (P + 1) % 3, LO = (P + 2) % 3;
+    if (st == 0 && r.compose_nlc) {
+      ORCA_TRY(enc_stage1_groups_nlc(ctx, net, src, n, buf[LO], buf[T]));
+    } else {
       if (st == 0) ORCA_TRY(launch_conv1d(ctx, L[0], buf[P], 0, ld1, buf[T], 0, 0, nullptr, nullptr, 1, n, 0, 0, 1));
       else ORCA_TRY(launch_conv1d_b16(ctx, L[0], prec, buf[P], 0, buf[T], 0, nullptr, 1, n, 0));
       ORCA_TRY(launch_conv1d_b16(ctx, L[1], prec, buf[T], 0, buf[LO], 0, nullptr, 1, n, 0));
       ORCA_TRY(launch_conv1d_b16(ctx, L[2], prec, buf[LO], 0, buf[T], 0, nullptr, 1, n, 1));
-      }
-      ORCA_TRY(launch_conv1d_b16(ctx, L[3], prec, buf[T], 0, buf[P], 0, st < 6 ? buf[LO] : nullptr, 1, n, 1,
-                                 (st < 6 && kEncPools[st + 1] == 4) ? 1 : 0));
     }
-    *out = buf[P]; *out_ld = -128; *out_n = n;   // negative ld: result is channel-last [n][128]
-    return ORCA_OK;
+    ORCA_TRY(launch_conv1d_b16(ctx, L[3], prec, buf[T], 0, buf[P], 0, st < 6 ? buf[LO] : nullptr, 1, n, 1,
+                               (st < 6 && kEncPools[st + 1] == 4) ? 1 : 0));
   }
-  int cprev = 4;
+  *out = buf[P]; *out_ld = -128; *out_n = n;   // negative ld: result is channel-last [n][128]
+  return ORCA_OK;
+}
+
+// the exact-fp32 pipeline: channel-major rows [C][ld], every pool a launch
+static int enc_stages_f32(orca_ctx* ctx, const orca_net* net, const SeqSource& src, const EncRoute& r, long n, float* const buf[3], long ld,
+                          float** out, long* out_ld, long* out_n) {
+  hipStream_t s = ctx->stream;
+  int P = 0, cprev = 4;
+  if (!r.compose32) ORCA_TRY(enc_rows_channel_major(ctx, src, n, buf, ld));
   for (int st = 0; st < 7; ++st) {
     const ConvLayer* L = &net->convs[4 * st];
     if (kEncPools[st] > 1) {
@@ -771,11 +714,10 @@ static int encoder_chunk(orca_ctx* ctx, orca_net* net, const SeqSource& src, lon
       P = Q; n = n2; ld = ld2;
     }
     const int T = (P + 1) % 3, LO = (P + 2) % 3;
-    if (st == 0 && compose32) {
+    if (st == 0 && r.compose32) {
       // lconv1 (17 taps) and conv1.a o lconv1 (25 taps + ReLU) straight from the source, fp32 FMAs; exact ends by the edge chain
       FirstF32Args fa{};
-      if (src.codes) { fa.in.in_mode = 1; fa.in.codes = src.codes; fa.in.nmask = src.nmask; fa.in.origin = src.origin; fa.in.codes_L = src.codes_L; fa.in.codes_off = src.codes_off; fa.in.reverse = src.reverse; }
-      else { fa.in.in_mode = 0; fa.in.x = src.x; fa.in.sc = src.sx_c; fa.in.sl = src.sx_l; }
+      fa.in = edge_source(src);
       fa.in.n = n; fa.ldy = ld;
       const long nt = (n + 127) / 128;
       const dim3 grid((unsigned)(nt < 4096 ? nt : 4096));
@@ -784,15 +726,11 @@ static int encoder_chunk(orca_ctx* ctx, orca_net* net, const SeqSource& src, lon
       fa.w = net->d_c1a_f32; fa.bias = net->d_c1a_bias32; fa.relu = 1; fa.y = buf[T];
       hipLaunchKernelGGL((first_taps_f32_kernel<25>), grid, dim3(256), 0, s, fa);
       LAUNCHCHECK("first_taps_f32_kernel");
-      const ConvLayer* chain[3] = {&L[0], &L[1], &L[2]};
-      const int relus[3] = {0, 0, 1};
-      float* ys[3] = {nullptr, buf[LO], buf[T]};
-      const int st_[3] = {0, 4, 8};
-      ORCA_TRY(launch_edge_chain(ctx, chain, relus, 3, 8, fa.in, n, ys, st_, 2, ld));
+      ORCA_TRY(launch_edge_chain(ctx, L, 3, 8, fa.in, n, buf[LO], buf[T], 2, ld));
     } else {
-    ORCA_TRY(launch_conv1d(ctx, L[0], buf[P], 0, ld, buf[T], 0, ld, nullptr, nullptr, 1, n, 0, 0));
-    ORCA_TRY(launch_conv1d(ctx, L[1], buf[T], 0, ld, buf[LO], 0, ld, nullptr, nullptr, 1, n, 0, 0));
-    ORCA_TRY(launch_conv1d(ctx, L[2], buf[LO], 0, ld, buf[T], 0, ld, nullptr, nullptr, 1, n, 1, 0));
+      ORCA_TRY(launch_conv1d(ctx, L[0], buf[P], 0, ld, buf[T], 0, ld, nullptr, nullptr, 1, n, 0, 0));
+      ORCA_TRY(launch_conv1d(ctx, L[1], buf[T], 0, ld, buf[LO], 0, ld, nullptr, nullptr, 1, n, 0, 0));
+      ORCA_TRY(launch_conv1d(ctx, L[2], buf[LO], 0, ld, buf[T], 0, ld, nullptr, nullptr, 1, n, 1, 0));
     }
     ORCA_TRY(launch_conv1d(ctx, L[3], buf[T], 0, ld, buf[P], 0, ld, st < 6 ? buf[LO] : nullptr, nullptr, 1, n, 1, 0));
     cprev = L[3].cout;
@@ -800,6 +738,25 @@ static int encoder_chunk(orca_ctx* ctx, orca_net* net, const SeqSource& src, lon
   *out = buf[P]; *out_ld = ld; *out_n = n;
   return ORCA_OK;
 }
+
+// One chunk: src (n1 positions; a part that starts behind stage 1: its input in buf[0]) -> the route's output in one of the three buffers.
+// *out_ld: row stride of a channel-major result [128][ld]; negative: fp32 channel-last [n][128]; 0: planes
+static int encoder_chunk(orca_ctx* ctx, orca_net* net, const SeqSource& src, long n1, float* const buf[3],
+                         long ld1, float** out, long* out_ld, long* out_n, int part = ENC_FULL) {
+  EncRoute r;
+  ORCA_TRY(enc_route(net, src, part, &r));
+  if (r.pipe == PIPE_F32) return enc_stages_f32(ctx, net, src, r, n1, buf, ld1, out, out_ld, out_n);
+  long n = n1;
+  int st = r.first;
+  if (r.planar() && st < kPlanarStages) {
+    if (st == 0) ORCA_TRY(enc_stage1_planes(ctx, net, src, r, buf, &n));
+    ORCA_TRY(enc_planar_stages(ctx, net, r, buf, &n));
+    if (r.last < kPlanarStages) { *out = buf[kS]; *out_ld = r.out == OUT_ROWS ? -128 : 0; *out_n = n; return ORCA_OK; }
+    st = kPlanarStages;
+  }
+  return enc_stages_nlc(ctx, net, src, r, st, n, buf, ld1, out, out_ld, out_n);
+}
+
 
 static int encoder_forward_impl(orca_ctx* ctx, orca_net* net, const float* x, int64_t sx_b, int64_t sx_c, int64_t sx_l,
                                 const unsigned char* codes, int64_t sc_b, int reverse,
@@ -836,6 +793,7 @@ static int encoder_forward_impl(orca_ctx* ctx, orca_net* net, const float* x, in
   }
   if (chunk_bp % kBinBp) return fail(ORCA_EINVAL, "chunk_bp must be a multiple of 4000");
   long chunk_bins = 0, ld1 = 0;
+  float* buf[3];
   for (;;) {
     chunk_bins = chunk_bp / kBinBp;
     long max_n1 = 0;
@@ -846,7 +804,7 @@ static int encoder_forward_impl(orca_ctx* ctx, orca_net* net, const float* x, in
       if (hi - lo > max_n1) max_n1 = hi - lo;
     }
     ld1 = ru4(max_n1) + 1024;   // slack: P16 planes are padded to 512 positions + guards
-    const int rc = ws_ensure(ctx, 3 * ru256((size_t)64 * ld1 * sizeof(float)));
+    const int rc = ws_three(ctx, (size_t)64 * ld1, buf);
     if (rc == ORCA_OK) break;
     // the deterministic choice above looks at TOTAL memory; if the device cannot give that much right now (another process, ranks
     // sharing it without $ORCA_RANKS_PER_DEVICE, torch's allocator holding most of it) fall back chunk size by chunk size - same result
@@ -854,8 +812,6 @@ static int encoder_forward_impl(orca_ctx* ctx, orca_net* net, const float* x, in
     (void)hipGetLastError();
     chunk_bp /= 2;
   }
-  float* buf[3];
-  for (int i = 0; i < 3; ++i) buf[i] = ws_take(ctx, (size_t)64 * ld1);
   for (int b = 0; b < B; ++b) {
     for (long cb0 = bin_lo; cb0 < bin_hi; cb0 += chunk_bins) {
       const long cb1 = cb0 + chunk_bins < bin_hi ? cb0 + chunk_bins : bin_hi;
@@ -931,9 +887,8 @@ static int front_run(orca_ctx* ctx, orca_net* net, const uint8_t* codes, int64_t
   if (nbases <= 0 || nbases % 80 || base0 < 0 || base0 + nbases > L) return fail(ORCA_EINVAL, "encoder front: bases [%ld,+%ld) of %ld: a positive multiple of 80 inside the sequence", (long)base0, (long)nbases, (long)L);
   HIPCHECK(hipSetDevice(ctx->device));
   const long ld1 = ru4(nbases) + 1024;
-  ORCA_TRY(ws_ensure(ctx, 3 * ru256((size_t)64 * ld1 * sizeof(float))));
   float* buf[3];
-  for (int i = 0; i < 3; ++i) buf[i] = ws_take(ctx, (size_t)64 * ld1);
+  ORCA_TRY(ws_three(ctx, (size_t)64 * ld1, buf));
   SeqSource src;
   src.codes = codes; src.codes_L = L; src.codes_off = base0; src.reverse = reverse;
   long rld;
@@ -974,20 +929,23 @@ extern "C" int orca_encoder_front_snippet(orca_ctx* ctx, orca_net* net, const ui
   return ORCA_OK;
 }
 
+// stage 4 onwards (ENC_BACK / ENC_STAGE4) from a copy of the caller's stage-4 input planes
+static int back_run(orca_ctx* ctx, orca_net* net, const float* s4, int64_t s4_units, int64_t n4, int part, float** res, long* rld, long* rn) {
+  HIPCHECK(hipSetDevice(ctx->device));
+  const long ld = ru4(n4) + 1024;                         // per buffer: 128 channels x ld floats (P16 planes of 128 channels; fp32 [n][128] behind stage 4)
+  float* buf[3];
+  ORCA_TRY(ws_three(ctx, (size_t)128 * ld, buf));
+  HIPCHECK(hipMemcpyAsync(buf[0], s4, (size_t)32 * s4_units * 16, hipMemcpyDeviceToDevice, ctx->stream));
+  ORCA_TRY(launch_p16_zero_pads(ctx, buf[0], 128, n4, 0));
+  return encoder_chunk(ctx, net, SeqSource(), n4, buf, ru4(n4), res, rld, rn, part);
+}
+
 extern "C" int orca_encoder_back(orca_ctx* ctx, orca_net* net, const float* s4, int64_t s4_units, int64_t n4, float* out, int64_t so_c) {
   if (!ctx || !net || !s4 || !out) return fail(ORCA_EINVAL, "orca_encoder_back: NULL argument");
   if (net->kind != ORCA_NET_ENCODER || net->precision != ORCA_PRECISION_F16X2) return fail(ORCA_EINVAL, "orca_encoder_back: an Encoder net in the f16x2 arithmetic");
   if (n4 <= 0 || n4 % 50 || s4_units != p16_plen(n4)) return fail(ORCA_EINVAL, "orca_encoder_back: %ld stage-4 positions (a multiple of 50) in planes of %ld units (need %ld)", (long)n4, (long)s4_units, p16_plen(n4));
-  HIPCHECK(hipSetDevice(ctx->device));
-  const long ld = ru4(n4) + 1024;                         // per buffer: 128 channels x ld floats (P16 planes of 128 channels; fp32 [n][128] behind stage 4)
-  ORCA_TRY(ws_ensure(ctx, 3 * ru256((size_t)128 * ld * sizeof(float))));
-  float* buf[3];
-  for (int i = 0; i < 3; ++i) buf[i] = ws_take(ctx, (size_t)128 * ld);
-  HIPCHECK(hipMemcpyAsync(buf[0], s4, (size_t)32 * s4_units * 16, hipMemcpyDeviceToDevice, ctx->stream));
-  ORCA_TRY(launch_p16_zero_pads(ctx, buf[0], 128, n4, 0));
-  SeqSource src;
   float* res; long rld, rn;
-  ORCA_TRY(encoder_chunk(ctx, net, src, n4, buf, ru4(n4), &res, &rld, &rn, ENC_BACK));
+  ORCA_TRY(back_run(ctx, net, s4, s4_units, n4, ENC_BACK, &res, &rld, &rn));
   if (rld >= 0 || rn != n4 / 50) return fail(ORCA_EINVAL, "internal: the Encoder's back part produced %ld bins for %ld positions", rn, (long)n4);
   return launch_copy2d(ctx, res, 1, 128, out, so_c, 128, rn);
 }
@@ -997,16 +955,8 @@ extern "C" int orca_encoder_stage4_rows(orca_ctx* ctx, orca_net* net, const floa
   if (!ctx || !net || !s4 || !rows) return fail(ORCA_EINVAL, "orca_encoder_stage4_rows: NULL argument");
   if (net->kind != ORCA_NET_ENCODER || net->precision != ORCA_PRECISION_F16X2) return fail(ORCA_EINVAL, "orca_encoder_stage4_rows: an Encoder net in the f16x2 arithmetic");
   if (n4 <= 0 || s4_units != p16_plen(n4)) return fail(ORCA_EINVAL, "orca_encoder_stage4_rows: %ld positions in planes of %ld units (need %ld)", (long)n4, (long)s4_units, p16_plen(n4));
-  HIPCHECK(hipSetDevice(ctx->device));
-  const long ld = ru4(n4) + 1024;
-  ORCA_TRY(ws_ensure(ctx, 3 * ru256((size_t)128 * ld * sizeof(float))));
-  float* buf[3];
-  for (int i = 0; i < 3; ++i) buf[i] = ws_take(ctx, (size_t)128 * ld);
-  HIPCHECK(hipMemcpyAsync(buf[0], s4, (size_t)32 * s4_units * 16, hipMemcpyDeviceToDevice, ctx->stream));
-  ORCA_TRY(launch_p16_zero_pads(ctx, buf[0], 128, n4, 0));
-  SeqSource src;
   float* res; long rld, rn;
-  ORCA_TRY(encoder_chunk(ctx, net, src, n4, buf, ru4(n4), &res, &rld, &rn, ENC_STAGE4));
+  ORCA_TRY(back_run(ctx, net, s4, s4_units, n4, ENC_STAGE4, &res, &rld, &rn));
   if (rld >= 0 || rn != n4) return fail(ORCA_EINVAL, "internal: stage 4 produced %ld rows for %ld positions", rn, (long)n4);
   HIPCHECK(hipMemcpyAsync(rows, res, (size_t)n4 * 128 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
   return ORCA_OK;
@@ -1062,9 +1012,8 @@ extern "C" int orca_encoder_back5(orca_ctx* ctx, orca_net* net, const float* row
   if (n5 <= 0 || n5 % 10) return fail(ORCA_EINVAL, "orca_encoder_back5: %ld stage-5 positions (a multiple of 10)", (long)n5);
   HIPCHECK(hipSetDevice(ctx->device));
   const long ld = ru4(n5) + 1024;
-  ORCA_TRY(ws_ensure(ctx, 3 * ru256((size_t)128 * ld * sizeof(float))));
   float* buf[3];
-  for (int i = 0; i < 3; ++i) buf[i] = ws_take(ctx, (size_t)128 * ld);
+  ORCA_TRY(ws_three(ctx, (size_t)128 * ld, buf));
   HIPCHECK(hipMemcpyAsync(buf[0], rows, (size_t)n5 * 128 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
   SeqSource src;
   float* res; long rld, rn;
@@ -1073,30 +1022,6 @@ extern "C" int orca_encoder_back5(orca_ctx* ctx, orca_net* net, const float* row
   return launch_copy2d(ctx, res, 1, 128, out, so_c, 128, rn);
 }
 
-// ---- the 1 Mb mutagenesis screen (orca_amd/screen.py; kernels in screen.h) ----------------------------------------------------------------
-extern "C" int orca_screen_edit_codes(orca_ctx* ctx, const uint8_t* window, int64_t L, const int64_t* table, int n_snippets, const uint8_t* payload,
-                                      int64_t n_payload, uint8_t* out, int64_t total) {
-  if (!ctx || !window || !table || !out || n_snippets <= 0) return fail(ORCA_EINVAL, "orca_screen_edit_codes: NULL / empty argument");
-  if (n_payload > 0 && !payload) return fail(ORCA_EINVAL, "orca_screen_edit_codes: NULL payload");
-  if (total <= 0) return ORCA_OK;
-  HIPCHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(screen_edit_codes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, window, (long)L,
-                     reinterpret_cast<const long long*>(table), n_snippets, payload, (long)n_payload, out, (long)total);
-  LAUNCHCHECK("screen_edit_codes_kernel");
-  return ORCA_OK;
-}
-
-extern "C" int orca_screen_splice_rows(orca_ctx* ctx, const float* ref, int64_t n5, const float* fresh, int64_t n_fresh, const int64_t* table, int B, float* out) {
-  if (!ctx || !ref || !table || !out || (n_fresh > 0 && !fresh)) return fail(ORCA_EINVAL, "orca_screen_splice_rows: NULL argument");
-  if (B <= 0 || n5 <= 0) return ORCA_OK;
-  if (!al16(ref) || !al16(out) || (fresh && !al16(fresh))) return fail(ORCA_EINVAL, "orca_screen_splice_rows: rows must be 16-byte aligned");
-  HIPCHECK(hipSetDevice(ctx->device));
-  const long units = (long)B * n5 * 32;
-  hipLaunchKernelGGL(screen_splice_rows_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, ctx->stream, reinterpret_cast<const f32x4*>(ref), (long)n5,
-                     reinterpret_cast<const f32x4*>(fresh), (long)n_fresh, reinterpret_cast<const long long*>(table), B, reinterpret_cast<f32x4*>(out));
-  LAUNCHCHECK("screen_splice_rows_kernel");
-  return ORCA_OK;
-}
 
 // stages 5-7 of B windows at once: rows [B][n5][128] -> out[b * so_b + c * so_c + bin].  Every conv is ONE launch for the batch with a batch stride, so
 // each window keeps its own zero padding (stacking the windows end to end would leak activations across the seams from the first conv on).  The
@@ -1108,9 +1033,8 @@ extern "C" int orca_encoder_back5_batch(orca_ctx* ctx, orca_net* net, const floa
   if (B <= 0) return ORCA_OK;
   HIPCHECK(hipSetDevice(ctx->device));
   const size_t per = (size_t)B * n5 * 128;
-  ORCA_TRY(ws_ensure(ctx, 3 * ru256(per * sizeof(float))));
   float* w[3];
-  for (int i = 0; i < 3; ++i) w[i] = ws_take(ctx, per);
+  ORCA_TRY(ws_three(ctx, per, w));
   const int prec = ORCA_PRECISION_F16X2;
   long n = n5;
   const float* x = rows;
@@ -1141,174 +1065,6 @@ extern "C" int orca_encoder_back5_batch(orca_ctx* ctx, orca_net* net, const floa
   return ORCA_OK;
 }
 
-extern "C" int orca_screen_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, float* profile, float* mean, float* amax) {
-  if (!ctx || !alt || !ref || !profile || !mean || !amax) return fail(ORCA_EINVAL, "orca_screen_scores: NULL argument");
-  if (B <= 0 || n <= 0) return ORCA_OK;
-  HIPCHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(screen_scores_kernel, dim3((unsigned)B), dim3(512), 0, ctx->stream, alt, (long)map_bs, ref, n, profile, mean, amax);
-  LAUNCHCHECK("screen_scores_kernel");
-  return ORCA_OK;
-}
-
-// compound edits: the small tables come twice, on the device for the kernels and on the host for the checks made here before any launch (the
-// kernels clip every table-derived index all the same, so the two copies differing cannot make them leave their buffers)
-extern "C" int orca_screen_edit_codes_multi(orca_ctx* ctx, const uint8_t* window, int64_t L, const int64_t* table, const int64_t* table_host, int n_snippets,
-                                            const int64_t* spans, const int64_t* spans_host, int64_t n_spans, const uint8_t* payload, int64_t n_payload,
-                                            uint8_t* out, int64_t total) {
-  if (!ctx || !window || !table || !table_host || !out) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: NULL argument");
-  if (n_snippets <= 0 || n_spans < 0 || n_payload < 0 || total < 0 || L <= 0)
-    return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: %d snippets, %ld spans, %ld payload codes, %ld output bases, window of %ld", n_snippets, (long)n_spans,
-                (long)n_payload, (long)total, (long)L);
-  if (n_spans > 0 && (!spans || !spans_host)) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: NULL span table");
-  if (n_payload > 0 && !payload) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: NULL payload");
-  int64_t off = 0;
-  for (int k = 0; k < n_snippets; ++k) {
-    const int64_t* e = table_host + (size_t)k * SCREEN_EDIT_FIELDS;
-    if (e[0] != off || e[2] <= 0) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: snippet %d starts at output base %ld with %ld bases, expected %ld (out_off ascending, no gaps)",
-                                               k, (long)e[0], (long)e[2], (long)off);
-    if (e[1] < 0 || e[2] > L - e[1]) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: snippet %d = window bases [%ld, +%ld) outside the window of %ld", k, (long)e[1], (long)e[2], (long)L);
-    if (e[3] < 0 || e[4] < 0 || e[4] > n_spans - e[3]) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: snippet %d has spans [%ld, +%ld) of %ld", k, (long)e[3], (long)e[4], (long)n_spans);
-    for (int64_t s = e[3]; s < e[3] + e[4]; ++s) {
-      const int64_t* sp = spans_host + (size_t)s * SCREEN_SPAN_FIELDS;
-      if (sp[0] < 0 || sp[0] > 2 || sp[1] < 0 || sp[2] <= 0 || sp[2] > L - sp[1]) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: span %ld: kind %ld, bases [%ld, +%ld) of %ld", (long)s, (long)sp[0], (long)sp[1], (long)sp[2], (long)L);
-      if (sp[0] == 0 && (sp[3] < 0 || sp[2] > n_payload - sp[3])) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: span %ld: payload [%ld, +%ld) of %ld", (long)s, (long)sp[3], (long)sp[2], (long)n_payload);
-      if (s > e[3] && sp[1] < sp[-SCREEN_SPAN_FIELDS + 1] + sp[-SCREEN_SPAN_FIELDS + 2]) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: spans %ld and %ld of snippet %d overlap or are not sorted by pos", (long)s - 1, (long)s, k);
-    }
-    off += e[2];
-  }
-  if (off != total) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: the snippets hold %ld bases, out holds %ld", (long)off, (long)total);
-  HIPCHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(screen_edit_codes_multi_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, window, (long)L,
-                     reinterpret_cast<const long long*>(table), n_snippets, reinterpret_cast<const long long*>(spans), (long)n_spans, payload, (long)n_payload, out,
-                     (long)total);
-  LAUNCHCHECK("screen_edit_codes_multi_kernel");
-  return ORCA_OK;
-}
-
-extern "C" int orca_screen_splice_rows_multi(orca_ctx* ctx, const float* ref, int64_t n5, const float* fresh, int64_t n_fresh, const int64_t* segments,
-                                             const int64_t* segments_host, int64_t n_segments, const int64_t* seg_off, const int64_t* seg_off_host, int B,
-                                             float* out) {
-  if (!ctx || !ref || !seg_off || !seg_off_host || !out) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: NULL argument");
-  if (B < 0 || n5 < 0 || n_fresh < 0 || n_segments < 0)
-    return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: %d images of %ld rows, %ld fresh rows, %ld segments", B, (long)n5, (long)n_fresh, (long)n_segments);
-  if (n_fresh > 0 && !fresh) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: NULL fresh rows");
-  if (n_segments > 0 && (!segments || !segments_host)) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: NULL segment table");
-  if (seg_off_host[0] != 0 || seg_off_host[B] != n_segments)
-    return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: segment offsets run from %ld to %ld, the table holds %ld segments", (long)seg_off_host[0], (long)seg_off_host[B], (long)n_segments);
-  for (int b = 0; b < B; ++b)       // monotone from 0 to n_segments: every offset is inside the table before a segment is read
-    if (seg_off_host[b + 1] < seg_off_host[b]) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: segment offsets decrease at image %d", b);
-  for (int b = 0; b < B; ++b) {
-    for (int64_t s = seg_off_host[b]; s < seg_off_host[b + 1]; ++s) {
-      const int64_t* g = segments_host + 3 * (size_t)s;
-      if (g[0] < 0 || g[1] <= 0 || g[1] > n5 - g[0] || g[2] < 0 || g[1] > n_fresh - g[2])
-        return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: segment %ld = rows [%ld, +%ld) of %ld from fresh row %ld of %ld", (long)s, (long)g[0], (long)g[1], (long)n5, (long)g[2], (long)n_fresh);
-      if (s > seg_off_host[b] && g[0] < g[-3] + g[-2]) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: segments %ld and %ld of image %d overlap or are not sorted by row_lo", (long)s - 1, (long)s, b);
-    }
-  }
-  if (B == 0 || n5 == 0) return ORCA_OK;
-  if (!al16(ref) || !al16(out) || (fresh && !al16(fresh))) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: rows must be 16-byte aligned");
-  HIPCHECK(hipSetDevice(ctx->device));
-  const long units = (long)B * n5 * 32;
-  hipLaunchKernelGGL(screen_splice_rows_multi_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, ctx->stream, reinterpret_cast<const f32x4*>(ref), (long)n5,
-                     reinterpret_cast<const f32x4*>(fresh), (long)n_fresh, reinterpret_cast<const long long*>(segments), (long)n_segments,
-                     reinterpret_cast<const long long*>(seg_off), B, reinterpret_cast<f32x4*>(out));
-  LAUNCHCHECK("screen_splice_rows_multi_kernel");
-  return ORCA_OK;
-}
-
-extern "C" int orca_screen_region_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* rects,
-                                         const int32_t* rects_host, int K, float* mean_signed, float* mean_abs) {
-  if (!ctx || !alt || !ref || !rects || !rects_host || !mean_signed || !mean_abs) return fail(ORCA_EINVAL, "orca_screen_region_scores: NULL argument");
-  if (B < 0 || n <= 0 || K <= 0 || K > 64 || map_bs < 0) return fail(ORCA_EINVAL, "orca_screen_region_scores: %d maps of %d bins, %d rectangles (1..64)", B, n, K);
-  for (int k = 0; k < K; ++k) {
-    const int32_t* r = rects_host + 4 * k;
-    if (r[0] < 0 || r[0] >= r[1] || r[1] > n || r[2] < 0 || r[2] >= r[3] || r[3] > n)
-      return fail(ORCA_EINVAL, "orca_screen_region_scores: rectangle %d = rows [%d, %d) x columns [%d, %d) outside [0, %d) or empty", k, r[0], r[1], r[2], r[3], n);
-  }
-  if (B == 0) return ORCA_OK;
-  HIPCHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(screen_region_scores_kernel, dim3((unsigned)B, (unsigned)K), dim3(256), 0, ctx->stream, alt, (long)map_bs, ref, n, rects, K, mean_signed, mean_abs);
-  LAUNCHCHECK("screen_region_scores_kernel");
-  return ORCA_OK;
-}
-
-// insertions and deletions: the edited bases of a batch from piece lists over the context (window + right flank), and the row images from the reference
-// rows, the recomputed rows and the stage-4 phase entries.  Tables as above: a device copy for the kernel, a host copy checked here before any launch.
-extern "C" int orca_screen_assemble_codes(orca_ctx* ctx, const uint8_t* context, int64_t C, const int64_t* table, const int64_t* table_host, int n_snippets,
-                                          const int64_t* pieces, const int64_t* pieces_host, int64_t n_pieces, const uint8_t* payload, int64_t n_payload,
-                                          uint8_t* out, int64_t total) {
-  if (!ctx || !context || !table || !table_host || !out) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: NULL argument");
-  if (n_snippets <= 0 || n_pieces < 0 || n_payload < 0 || total < 0 || C <= 0)
-    return fail(ORCA_EINVAL, "orca_screen_assemble_codes: %d snippets, %ld pieces, %ld payload codes, %ld output bases, context of %ld", n_snippets, (long)n_pieces,
-                (long)n_payload, (long)total, (long)C);
-  if (n_pieces > 0 && (!pieces || !pieces_host)) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: NULL piece table");
-  if (n_payload > 0 && !payload) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: NULL payload");
-  const int64_t kmax = INT64_MAX / 4;               // every coordinate stays far below the sums the kernel forms
-  int64_t off = 0;
-  for (int k = 0; k < n_snippets; ++k) {
-    const int64_t* e = table_host + (size_t)k * SCREEN_EDIT_FIELDS;
-    if (e[0] != off || e[2] <= 0) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: snippet %d starts at output base %ld with %ld bases, expected %ld (out_off ascending, no gaps)",
-                                               k, (long)e[0], (long)e[2], (long)off);
-    if (e[1] < 0 || e[1] > kmax || e[2] > kmax) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: snippet %d = alt bases [%ld, +%ld)", k, (long)e[1], (long)e[2]);
-    if (e[3] < 0 || e[4] < 0 || e[4] > n_pieces - e[3]) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: snippet %d has pieces [%ld, +%ld) of %ld", k, (long)e[3], (long)e[4], (long)n_pieces);
-    for (int64_t s = e[3]; s < e[3] + e[4]; ++s) {
-      const int64_t* pc = pieces_host + (size_t)s * SCREEN_PIECE_FIELDS;
-      if (pc[1] < 0 || pc[1] > 3 || pc[0] < 0 || pc[0] > kmax || pc[3] <= 0 || pc[3] > kmax || pc[2] < 0 || pc[2] > kmax)
-        return fail(ORCA_EINVAL, "orca_screen_assemble_codes: piece %ld: alt base %ld, kind %ld, source %ld, %ld bases", (long)s, (long)pc[0], (long)pc[1], (long)pc[2], (long)pc[3]);
-      if (pc[1] == 2 && pc[3] > n_payload - pc[2]) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: piece %ld: payload [%ld, +%ld) of %ld", (long)s, (long)pc[2], (long)pc[3], (long)n_payload);
-      if (s > e[3] && pc[0] < pc[-SCREEN_PIECE_FIELDS] + pc[-SCREEN_PIECE_FIELDS + 3])
-        return fail(ORCA_EINVAL, "orca_screen_assemble_codes: pieces %ld and %ld of snippet %d overlap or are not sorted by dst", (long)s - 1, (long)s, k);
-    }
-    off += e[2];
-  }
-  if (off != total) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: the snippets hold %ld bases, out holds %ld", (long)off, (long)total);
-  if (total == 0) return ORCA_OK;
-  HIPCHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(screen_assemble_codes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, context, (long)C,
-                     reinterpret_cast<const long long*>(table), n_snippets, reinterpret_cast<const long long*>(pieces), (long)n_pieces, payload, (long)n_payload, out,
-                     (long)total);
-  LAUNCHCHECK("screen_assemble_codes_kernel");
-  return ORCA_OK;
-}
-
-extern "C" int orca_screen_gather_rows(orca_ctx* ctx, const float* ref, int64_t n5, const float* fresh, int64_t n_fresh, const float* const* entries,
-                                       const int64_t* entry_rows, const int64_t* entry_rows_host, int P, const int64_t* segments, const int64_t* segments_host,
-                                       int64_t n_segments, const int64_t* seg_off, const int64_t* seg_off_host, int B, float* out) {
-  if (!ctx || !ref || !seg_off || !seg_off_host || !out) return fail(ORCA_EINVAL, "orca_screen_gather_rows: NULL argument");
-  if (B < 0 || n5 < 0 || n_fresh < 0 || n_segments < 0 || P < 0)
-    return fail(ORCA_EINVAL, "orca_screen_gather_rows: %d images of %ld rows, %ld fresh rows, %d phase entries, %ld segments", B, (long)n5, (long)n_fresh, P, (long)n_segments);
-  if (n_fresh > 0 && !fresh) return fail(ORCA_EINVAL, "orca_screen_gather_rows: NULL fresh rows");
-  if (P > 0 && (!entries || !entry_rows || !entry_rows_host)) return fail(ORCA_EINVAL, "orca_screen_gather_rows: NULL phase entries");
-  if (n_segments > 0 && (!segments || !segments_host)) return fail(ORCA_EINVAL, "orca_screen_gather_rows: NULL segment table");
-  for (int p = 0; p < P; ++p)
-    if (entry_rows_host[p] < 0) return fail(ORCA_EINVAL, "orca_screen_gather_rows: phase entry %d has %ld rows", p, (long)entry_rows_host[p]);
-  if (seg_off_host[0] != 0 || seg_off_host[B] != n_segments)
-    return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment offsets run from %ld to %ld, the table holds %ld segments", (long)seg_off_host[0], (long)seg_off_host[B], (long)n_segments);
-  for (int b = 0; b < B; ++b)       // monotone from 0 to n_segments: every offset is inside the table before a segment is read
-    if (seg_off_host[b + 1] < seg_off_host[b]) return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment offsets decrease at image %d", b);
-  for (int b = 0; b < B; ++b) {
-    for (int64_t s = seg_off_host[b]; s < seg_off_host[b + 1]; ++s) {
-      const int64_t* g = segments_host + SCREEN_GATHER_FIELDS * (size_t)s;
-      if (g[0] < 0 || g[1] <= 0 || g[1] > n5 - g[0]) return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment %ld = rows [%ld, +%ld) of %ld", (long)s, (long)g[0], (long)g[1], (long)n5);
-      if (g[2] < -2 || g[2] >= P) return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment %ld has source %ld (-1 fresh, -2 ref, or a phase entry below %d)", (long)s, (long)g[2], P);
-      const int64_t have = g[2] == -1 ? n_fresh : g[2] == -2 ? n5 : entry_rows_host[g[2]], step = g[2] >= 0 ? 5 : 1;      // a pooled row reads 5 of its entry's
-      if (g[3] < 0 || g[3] > have || g[1] > (have - g[3]) / step)
-        return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment %ld reads %ld rows from row %ld of source %ld, which cannot give them", (long)s, (long)g[1], (long)g[3], (long)g[2]);
-      if (s > seg_off_host[b] && g[0] < g[-SCREEN_GATHER_FIELDS] + g[-SCREEN_GATHER_FIELDS + 1])
-        return fail(ORCA_EINVAL, "orca_screen_gather_rows: segments %ld and %ld of image %d overlap or are not sorted by row_lo", (long)s - 1, (long)s, b);
-    }
-  }
-  if (B == 0 || n5 == 0) return ORCA_OK;
-  if (!al16(ref) || !al16(out) || (fresh && !al16(fresh))) return fail(ORCA_EINVAL, "orca_screen_gather_rows: rows must be 16-byte aligned");
-  HIPCHECK(hipSetDevice(ctx->device));
-  const long units = (long)B * n5 * 32;
-  hipLaunchKernelGGL(screen_gather_rows_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, ctx->stream, reinterpret_cast<const f32x4*>(ref), (long)n5,
-                     reinterpret_cast<const f32x4*>(fresh), (long)n_fresh, reinterpret_cast<const f32x4* const*>(entries),
-                     reinterpret_cast<const long long*>(entry_rows), P, reinterpret_cast<const long long*>(segments), (long)n_segments,
-                     reinterpret_cast<const long long*>(seg_off), B, reinterpret_cast<f32x4*>(out));
-  LAUNCHCHECK("screen_gather_rows_kernel");
-  return ORCA_OK;
-}
 
 extern "C" int orca_pack_sequence(orca_ctx* ctx, const float* x, int64_t sx_c, int64_t sx_l, int64_t L, uint8_t* codes, int* packable) {
   if (!ctx || !x || !codes || !packable) return fail(ORCA_EINVAL, "orca_pack_sequence: NULL argument");

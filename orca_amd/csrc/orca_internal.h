@@ -3,6 +3,7 @@
 //   orca_encoder.hip       Conv1d launchers, the Encoder (orca_modules.py:929-980) and the U-net encoders (:1151-1169, :1388-1406)
 //   orca_decoder.hip       Conv2d launchers, Decoder / Decoder_1m (:461-488, :782-800), strand merge, background block means, the observed-data
 //                          smoother, the 2-bit genome expander
+//   orca_screen.hip        entry points of the 1 Mb mutagenesis screen (screen.h): table validation + one launch each
 //   orca_comm.hip          the RCCL communicator of the sharded Encoder (dlopen'ed)
 //   orca_test_entries.hip  single-layer entry points for the kernel tests
 // Kernels live in the *.h files next to these; every non-template kernel there is `static`, so a header may be included by several units.
@@ -69,6 +70,11 @@ struct orca_ctx {
 
 int ws_ensure(orca_ctx* ctx, size_t bytes);        // start of a call: the arena holds at least `bytes` (waits for an earlier call on another stream)
 float* ws_take(orca_ctx* ctx, size_t nfloats);     // next 256-byte aligned piece of the arena (NULL when it is exhausted)
+static inline int ws_three(orca_ctx* ctx, size_t nfloats, float* buf[3]) {   // start of a call that works in three equal buffers (the Encoder's)
+  const int rc = ws_ensure(ctx, 3 * ru256(nfloats * sizeof(float)));
+  for (int i = 0; rc == ORCA_OK && i < 3; ++i) buf[i] = ws_take(ctx, nfloats);
+  return rc;
+}
 
 #ifndef ORCA_MAX_TARGETS
 #define ORCA_MAX_TARGETS 8   // num_2d of the multi-target decoders (orca_leukemia.py:512-990); hidden width F = max(5, T) (also misc_kernels.h)
@@ -116,6 +122,44 @@ int make_layer(const orca_conv_desc& d, ConvLayer* out);                        
 int make_layer17(int cin, int cout, const std::vector<double>& w17, const std::vector<double>& b17, ConvLayer* out);   // a composed 17-tap group
 void compose_pair(const orca_conv_desc& c1, const orca_conv_desc& c2, std::vector<double>* w17, std::vector<double>* b17);
 void free_layer(ConvLayer& L);
+
+// ---- launch helpers ---------------------------------------------------------------------------------------------------------------------
+static inline int device_cus() {   // compute units of the current device (queried once)
+  static int ncu = [] { int dev = 0, v = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v; }();
+  return ncu;
+}
+// the grid of a persistent kernel: CUs x resident workgroups of KERNEL at THREADS threads (queried once per kernel instantiation)
+template <auto KERNEL, int THREADS>
+static int resident_workgroups() {
+  static int resident = [] {
+    int per_cu = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERNEL, THREADS, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+    return device_cus() * per_cu;
+  }();
+  return resident;
+}
+// one launch (or fused group) timed into ctx->timed when the context asks for it and the launch is long enough:
+//   LaunchTimer t(ctx, n); ORCA_TRY(t.open()); <launch> ORCA_TRY(t.close(cout, cin, tile, batch, n, ksize));
+struct LaunchTimer {
+  orca_ctx* ctx;
+  bool on;
+  TimedLaunch tl;
+  LaunchTimer(orca_ctx* c, long n, bool wanted = true) : ctx(c), on(c->timing && n >= 65536 && wanted) {}
+  int open() {
+    if (!on) return ORCA_OK;
+    HIPCHECK(hipEventCreate(&tl.e0));
+    HIPCHECK(hipEventCreate(&tl.e1));
+    HIPCHECK(hipEventRecord(tl.e0, ctx->stream));
+    return ORCA_OK;
+  }
+  int close(int cout, int cin, int tile, int batch, long n, int ksize) {   // `tile`: the tags of orca_kernel_time (include/orca_hip.h)
+    if (!on) return ORCA_OK;
+    HIPCHECK(hipEventRecord(tl.e1, ctx->stream));
+    tl.rec.cout = cout; tl.rec.cin = cin; tl.rec.tile = tile; tl.rec.batch = batch; tl.rec.n = n; tl.rec.ms = 0.f; tl.rec.ksize = ksize;
+    ctx->timed.push_back(tl);
+    return ORCA_OK;
+  }
+};
 
 // ---- launchers used across units -------------------------------------------------------------------------------------------------------
 static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

@@ -1,0 +1,197 @@
+// orca_screen.hip - entry points of the 1 Mb mutagenesis screen (orca_amd/screen.py; kernels in screen.h): table validation on the host, one launch each
+// Part of liborca_hip.so (include/orca_hip.h is the ABI; orca_internal.h what the units share).
+#include "orca_internal.h"
+
+#include "screen.h"
+
+extern "C" int orca_screen_edit_codes(orca_ctx* ctx, const uint8_t* window, int64_t L, const int64_t* table, int n_snippets, const uint8_t* payload,
+                                      int64_t n_payload, uint8_t* out, int64_t total) {
+  if (!ctx || !window || !table || !out || n_snippets <= 0) return fail(ORCA_EINVAL, "orca_screen_edit_codes: NULL / empty argument");
+  if (n_payload > 0 && !payload) return fail(ORCA_EINVAL, "orca_screen_edit_codes: NULL payload");
+  if (total <= 0) return ORCA_OK;
+  HIPCHECK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(screen_edit_codes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, window, (long)L,
+                     reinterpret_cast<const long long*>(table), n_snippets, payload, (long)n_payload, out, (long)total);
+  LAUNCHCHECK("screen_edit_codes_kernel");
+  return ORCA_OK;
+}
+
+extern "C" int orca_screen_splice_rows(orca_ctx* ctx, const float* ref, int64_t n5, const float* fresh, int64_t n_fresh, const int64_t* table, int B, float* out) {
+  if (!ctx || !ref || !table || !out || (n_fresh > 0 && !fresh)) return fail(ORCA_EINVAL, "orca_screen_splice_rows: NULL argument");
+  if (B <= 0 || n5 <= 0) return ORCA_OK;
+  if (!al16(ref) || !al16(out) || (fresh && !al16(fresh))) return fail(ORCA_EINVAL, "orca_screen_splice_rows: rows must be 16-byte aligned");
+  HIPCHECK(hipSetDevice(ctx->device));
+  const long units = (long)B * n5 * 32;
+  hipLaunchKernelGGL(screen_splice_rows_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, ctx->stream, reinterpret_cast<const f32x4*>(ref), (long)n5,
+                     reinterpret_cast<const f32x4*>(fresh), (long)n_fresh, reinterpret_cast<const long long*>(table), B, reinterpret_cast<f32x4*>(out));
+  LAUNCHCHECK("screen_splice_rows_kernel");
+  return ORCA_OK;
+}
+extern "C" int orca_screen_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, float* profile, float* mean, float* amax) {
+  if (!ctx || !alt || !ref || !profile || !mean || !amax) return fail(ORCA_EINVAL, "orca_screen_scores: NULL argument");
+  if (B <= 0 || n <= 0) return ORCA_OK;
+  HIPCHECK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(screen_scores_kernel, dim3((unsigned)B), dim3(512), 0, ctx->stream, alt, (long)map_bs, ref, n, profile, mean, amax);
+  LAUNCHCHECK("screen_scores_kernel");
+  return ORCA_OK;
+}
+
+// compound edits: the small tables come twice, on the device for the kernels and on the host for the checks made here before any launch (the
+// kernels clip every table-derived index all the same, so the two copies differing cannot make them leave their buffers)
+extern "C" int orca_screen_edit_codes_multi(orca_ctx* ctx, const uint8_t* window, int64_t L, const int64_t* table, const int64_t* table_host, int n_snippets,
+                                            const int64_t* spans, const int64_t* spans_host, int64_t n_spans, const uint8_t* payload, int64_t n_payload,
+                                            uint8_t* out, int64_t total) {
+  if (!ctx || !window || !table || !table_host || !out) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: NULL argument");
+  if (n_snippets <= 0 || n_spans < 0 || n_payload < 0 || total < 0 || L <= 0)
+    return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: %d snippets, %ld spans, %ld payload codes, %ld output bases, window of %ld", n_snippets, (long)n_spans,
+                (long)n_payload, (long)total, (long)L);
+  if (n_spans > 0 && (!spans || !spans_host)) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: NULL span table");
+  if (n_payload > 0 && !payload) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: NULL payload");
+  int64_t off = 0;
+  for (int k = 0; k < n_snippets; ++k) {
+    const int64_t* e = table_host + (size_t)k * SCREEN_EDIT_FIELDS;
+    if (e[0] != off || e[2] <= 0) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: snippet %d starts at output base %ld with %ld bases, expected %ld (out_off ascending, no gaps)",
+                                               k, (long)e[0], (long)e[2], (long)off);
+    if (e[1] < 0 || e[2] > L - e[1]) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: snippet %d = window bases [%ld, +%ld) outside the window of %ld", k, (long)e[1], (long)e[2], (long)L);
+    if (e[3] < 0 || e[4] < 0 || e[4] > n_spans - e[3]) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: snippet %d has spans [%ld, +%ld) of %ld", k, (long)e[3], (long)e[4], (long)n_spans);
+    for (int64_t s = e[3]; s < e[3] + e[4]; ++s) {
+      const int64_t* sp = spans_host + (size_t)s * SCREEN_SPAN_FIELDS;
+      if (sp[0] < 0 || sp[0] > 2 || sp[1] < 0 || sp[2] <= 0 || sp[2] > L - sp[1]) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: span %ld: kind %ld, bases [%ld, +%ld) of %ld", (long)s, (long)sp[0], (long)sp[1], (long)sp[2], (long)L);
+      if (sp[0] == 0 && (sp[3] < 0 || sp[2] > n_payload - sp[3])) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: span %ld: payload [%ld, +%ld) of %ld", (long)s, (long)sp[3], (long)sp[2], (long)n_payload);
+      if (s > e[3] && sp[1] < sp[-SCREEN_SPAN_FIELDS + 1] + sp[-SCREEN_SPAN_FIELDS + 2]) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: spans %ld and %ld of snippet %d overlap or are not sorted by pos", (long)s - 1, (long)s, k);
+    }
+    off += e[2];
+  }
+  if (off != total) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: the snippets hold %ld bases, out holds %ld", (long)off, (long)total);
+  HIPCHECK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(screen_edit_codes_multi_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, window, (long)L,
+                     reinterpret_cast<const long long*>(table), n_snippets, reinterpret_cast<const long long*>(spans), (long)n_spans, payload, (long)n_payload, out,
+                     (long)total);
+  LAUNCHCHECK("screen_edit_codes_multi_kernel");
+  return ORCA_OK;
+}
+
+extern "C" int orca_screen_splice_rows_multi(orca_ctx* ctx, const float* ref, int64_t n5, const float* fresh, int64_t n_fresh, const int64_t* segments,
+                                             const int64_t* segments_host, int64_t n_segments, const int64_t* seg_off, const int64_t* seg_off_host, int B,
+                                             float* out) {
+  if (!ctx || !ref || !seg_off || !seg_off_host || !out) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: NULL argument");
+  if (B < 0 || n5 < 0 || n_fresh < 0 || n_segments < 0)
+    return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: %d images of %ld rows, %ld fresh rows, %ld segments", B, (long)n5, (long)n_fresh, (long)n_segments);
+  if (n_fresh > 0 && !fresh) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: NULL fresh rows");
+  if (n_segments > 0 && (!segments || !segments_host)) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: NULL segment table");
+  if (seg_off_host[0] != 0 || seg_off_host[B] != n_segments)
+    return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: segment offsets run from %ld to %ld, the table holds %ld segments", (long)seg_off_host[0], (long)seg_off_host[B], (long)n_segments);
+  for (int b = 0; b < B; ++b)       // monotone from 0 to n_segments: every offset is inside the table before a segment is read
+    if (seg_off_host[b + 1] < seg_off_host[b]) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: segment offsets decrease at image %d", b);
+  for (int b = 0; b < B; ++b) {
+    for (int64_t s = seg_off_host[b]; s < seg_off_host[b + 1]; ++s) {
+      const int64_t* g = segments_host + 3 * (size_t)s;
+      if (g[0] < 0 || g[1] <= 0 || g[1] > n5 - g[0] || g[2] < 0 || g[1] > n_fresh - g[2])
+        return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: segment %ld = rows [%ld, +%ld) of %ld from fresh row %ld of %ld", (long)s, (long)g[0], (long)g[1], (long)n5, (long)g[2], (long)n_fresh);
+      if (s > seg_off_host[b] && g[0] < g[-3] + g[-2]) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: segments %ld and %ld of image %d overlap or are not sorted by row_lo", (long)s - 1, (long)s, b);
+    }
+  }
+  if (B == 0 || n5 == 0) return ORCA_OK;
+  if (!al16(ref) || !al16(out) || (fresh && !al16(fresh))) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: rows must be 16-byte aligned");
+  HIPCHECK(hipSetDevice(ctx->device));
+  const long units = (long)B * n5 * 32;
+  hipLaunchKernelGGL(screen_splice_rows_multi_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, ctx->stream, reinterpret_cast<const f32x4*>(ref), (long)n5,
+                     reinterpret_cast<const f32x4*>(fresh), (long)n_fresh, reinterpret_cast<const long long*>(segments), (long)n_segments,
+                     reinterpret_cast<const long long*>(seg_off), B, reinterpret_cast<f32x4*>(out));
+  LAUNCHCHECK("screen_splice_rows_multi_kernel");
+  return ORCA_OK;
+}
+
+extern "C" int orca_screen_region_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* rects,
+                                         const int32_t* rects_host, int K, float* mean_signed, float* mean_abs) {
+  if (!ctx || !alt || !ref || !rects || !rects_host || !mean_signed || !mean_abs) return fail(ORCA_EINVAL, "orca_screen_region_scores: NULL argument");
+  if (B < 0 || n <= 0 || K <= 0 || K > 64 || map_bs < 0) return fail(ORCA_EINVAL, "orca_screen_region_scores: %d maps of %d bins, %d rectangles (1..64)", B, n, K);
+  for (int k = 0; k < K; ++k) {
+    const int32_t* r = rects_host + 4 * k;
+    if (r[0] < 0 || r[0] >= r[1] || r[1] > n || r[2] < 0 || r[2] >= r[3] || r[3] > n)
+      return fail(ORCA_EINVAL, "orca_screen_region_scores: rectangle %d = rows [%d, %d) x columns [%d, %d) outside [0, %d) or empty", k, r[0], r[1], r[2], r[3], n);
+  }
+  if (B == 0) return ORCA_OK;
+  HIPCHECK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(screen_region_scores_kernel, dim3((unsigned)B, (unsigned)K), dim3(256), 0, ctx->stream, alt, (long)map_bs, ref, n, rects, K, mean_signed, mean_abs);
+  LAUNCHCHECK("screen_region_scores_kernel");
+  return ORCA_OK;
+}
+
+// insertions and deletions: the edited bases of a batch from piece lists over the context (window + right flank), and the row images from the reference
+// rows, the recomputed rows and the stage-4 phase entries.  Tables as above: a device copy for the kernel, a host copy checked here before any launch.
+extern "C" int orca_screen_assemble_codes(orca_ctx* ctx, const uint8_t* context, int64_t C, const int64_t* table, const int64_t* table_host, int n_snippets,
+                                          const int64_t* pieces, const int64_t* pieces_host, int64_t n_pieces, const uint8_t* payload, int64_t n_payload,
+                                          uint8_t* out, int64_t total) {
+  if (!ctx || !context || !table || !table_host || !out) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: NULL argument");
+  if (n_snippets <= 0 || n_pieces < 0 || n_payload < 0 || total < 0 || C <= 0)
+    return fail(ORCA_EINVAL, "orca_screen_assemble_codes: %d snippets, %ld pieces, %ld payload codes, %ld output bases, context of %ld", n_snippets, (long)n_pieces,
+                (long)n_payload, (long)total, (long)C);
+  if (n_pieces > 0 && (!pieces || !pieces_host)) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: NULL piece table");
+  if (n_payload > 0 && !payload) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: NULL payload");
+  const int64_t kmax = INT64_MAX / 4;               // every coordinate stays far below the sums the kernel forms
+  int64_t off = 0;
+  for (int k = 0; k < n_snippets; ++k) {
+    const int64_t* e = table_host + (size_t)k * SCREEN_EDIT_FIELDS;
+    if (e[0] != off || e[2] <= 0) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: snippet %d starts at output base %ld with %ld bases, expected %ld (out_off ascending, no gaps)",
+                                               k, (long)e[0], (long)e[2], (long)off);
+    if (e[1] < 0 || e[1] > kmax || e[2] > kmax) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: snippet %d = alt bases [%ld, +%ld)", k, (long)e[1], (long)e[2]);
+    if (e[3] < 0 || e[4] < 0 || e[4] > n_pieces - e[3]) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: snippet %d has pieces [%ld, +%ld) of %ld", k, (long)e[3], (long)e[4], (long)n_pieces);
+    for (int64_t s = e[3]; s < e[3] + e[4]; ++s) {
+      const int64_t* pc = pieces_host + (size_t)s * SCREEN_PIECE_FIELDS;
+      if (pc[1] < 0 || pc[1] > 3 || pc[0] < 0 || pc[0] > kmax || pc[3] <= 0 || pc[3] > kmax || pc[2] < 0 || pc[2] > kmax)
+        return fail(ORCA_EINVAL, "orca_screen_assemble_codes: piece %ld: alt base %ld, kind %ld, source %ld, %ld bases", (long)s, (long)pc[0], (long)pc[1], (long)pc[2], (long)pc[3]);
+      if (pc[1] == 2 && pc[3] > n_payload - pc[2]) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: piece %ld: payload [%ld, +%ld) of %ld", (long)s, (long)pc[2], (long)pc[3], (long)n_payload);
+      if (s > e[3] && pc[0] < pc[-SCREEN_PIECE_FIELDS] + pc[-SCREEN_PIECE_FIELDS + 3])
+        return fail(ORCA_EINVAL, "orca_screen_assemble_codes: pieces %ld and %ld of snippet %d overlap or are not sorted by dst", (long)s - 1, (long)s, k);
+    }
+    off += e[2];
+  }
+  if (off != total) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: the snippets hold %ld bases, out holds %ld", (long)off, (long)total);
+  if (total == 0) return ORCA_OK;
+  HIPCHECK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(screen_assemble_codes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, context, (long)C,
+                     reinterpret_cast<const long long*>(table), n_snippets, reinterpret_cast<const long long*>(pieces), (long)n_pieces, payload, (long)n_payload, out,
+                     (long)total);
+  LAUNCHCHECK("screen_assemble_codes_kernel");
+  return ORCA_OK;
+}
+
+extern "C" int orca_screen_gather_rows(orca_ctx* ctx, const float* ref, int64_t n5, const float* fresh, int64_t n_fresh, const float* const* entries,
+                                       const int64_t* entry_rows, const int64_t* entry_rows_host, int P, const int64_t* segments, const int64_t* segments_host,
+                                       int64_t n_segments, const int64_t* seg_off, const int64_t* seg_off_host, int B, float* out) {
+  if (!ctx || !ref || !seg_off || !seg_off_host || !out) return fail(ORCA_EINVAL, "orca_screen_gather_rows: NULL argument");
+  if (B < 0 || n5 < 0 || n_fresh < 0 || n_segments < 0 || P < 0)
+    return fail(ORCA_EINVAL, "orca_screen_gather_rows: %d images of %ld rows, %ld fresh rows, %d phase entries, %ld segments", B, (long)n5, (long)n_fresh, P, (long)n_segments);
+  if (n_fresh > 0 && !fresh) return fail(ORCA_EINVAL, "orca_screen_gather_rows: NULL fresh rows");
+  if (P > 0 && (!entries || !entry_rows || !entry_rows_host)) return fail(ORCA_EINVAL, "orca_screen_gather_rows: NULL phase entries");
+  if (n_segments > 0 && (!segments || !segments_host)) return fail(ORCA_EINVAL, "orca_screen_gather_rows: NULL segment table");
+  for (int p = 0; p < P; ++p)
+    if (entry_rows_host[p] < 0) return fail(ORCA_EINVAL, "orca_screen_gather_rows: phase entry %d has %ld rows", p, (long)entry_rows_host[p]);
+  if (seg_off_host[0] != 0 || seg_off_host[B] != n_segments)
+    return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment offsets run from %ld to %ld, the table holds %ld segments", (long)seg_off_host[0], (long)seg_off_host[B], (long)n_segments);
+  for (int b = 0; b < B; ++b)       // monotone from 0 to n_segments: every offset is inside the table before a segment is read
+    if (seg_off_host[b + 1] < seg_off_host[b]) return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment offsets decrease at image %d", b);
+  for (int b = 0; b < B; ++b) {
+    for (int64_t s = seg_off_host[b]; s < seg_off_host[b + 1]; ++s) {
+      const int64_t* g = segments_host + SCREEN_GATHER_FIELDS * (size_t)s;
+      if (g[0] < 0 || g[1] <= 0 || g[1] > n5 - g[0]) return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment %ld = rows [%ld, +%ld) of %ld", (long)s, (long)g[0], (long)g[1], (long)n5);
+      if (g[2] < -2 || g[2] >= P) return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment %ld has source %ld (-1 fresh, -2 ref, or a phase entry below %d)", (long)s, (long)g[2], P);
+      const int64_t have = g[2] == -1 ? n_fresh : g[2] == -2 ? n5 : entry_rows_host[g[2]], step = g[2] >= 0 ? 5 : 1;      // a pooled row reads 5 of its entry's
+      if (g[3] < 0 || g[3] > have || g[1] > (have - g[3]) / step)
+        return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment %ld reads %ld rows from row %ld of source %ld, which cannot give them", (long)s, (long)g[1], (long)g[3], (long)g[2]);
+      if (s > seg_off_host[b] && g[0] < g[-SCREEN_GATHER_FIELDS] + g[-SCREEN_GATHER_FIELDS + 1])
+        return fail(ORCA_EINVAL, "orca_screen_gather_rows: segments %ld and %ld of image %d overlap or are not sorted by row_lo", (long)s - 1, (long)s, b);
+    }
+  }
+  if (B == 0 || n5 == 0) return ORCA_OK;
+  if (!al16(ref) || !al16(out) || (fresh && !al16(fresh))) return fail(ORCA_EINVAL, "orca_screen_gather_rows: rows must be 16-byte aligned");
+  HIPCHECK(hipSetDevice(ctx->device));
+  const long units = (long)B * n5 * 32;
+  hipLaunchKernelGGL(screen_gather_rows_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, ctx->stream, reinterpret_cast<const f32x4*>(ref), (long)n5,
+                     reinterpret_cast<const f32x4*>(fresh), (long)n_fresh, reinterpret_cast<const f32x4* const*>(entries),
+                     reinterpret_cast<const long long*>(entry_rows), P, reinterpret_cast<const long long*>(segments), (long)n_segments,
+                     reinterpret_cast<const long long*>(seg_off), B, reinterpret_cast<f32x4*>(out));
+  LAUNCHCHECK("screen_gather_rows_kernel");
+  return ORCA_OK;
+}
