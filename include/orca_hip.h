@@ -162,6 +162,10 @@ int orca_net_set_precision(orca_net* net, int precision);
 #define ORCA_ENCODER_FORM_LCONV1_ONLY 2
 #define ORCA_ENCODER_FORM_TWO_CONV 3
 int orca_net_set_encoder_form(orca_net* net, int form);
+/* ORCA_NET_DECODER / _DECODER_1M only: with ORCA_PRECISION_F16X2 each run of residual blocks of dilation 16, 32, 64 is ONE launch
+ * (conv2d_dblock_run_kernel, bit-identical to the three per-block launches); on by default, 0 = one launch per block.  The other precisions
+ * always launch per block.  ORCA_EINVAL on any other net. */
+int orca_net_set_decoder_block_runs(orca_net* net, int on);
 /* ORCA_PRECISION_F16X2 only: the kernels raise a device flag when an activation leaves the fp16
  * range (the result of that forward is then invalid).  This call waits for the context's stream,
  * returns the flag in *flag and clears it - the host falls back to ORCA_PRECISION_BF16X3. */
@@ -475,6 +479,11 @@ int orca_conv2d_m16_forward(orca_ctx* ctx, const orca_conv_desc* conv, int preci
  * makes a round trip through the M16 storage and the launch has the grid of the Decoder forward.  ORCA_EINVAL, before any launch, on
  * anything else. */
 int orca_conv2d_dblock_forward(orca_ctx* ctx, const orca_conv_desc* convs, int precision, const float* x, float* y, int B, int n);
+/* A run of nblk = 2 or 3 consecutive blocks of dilations d0, 2 d0 (, 4 d0) <= 64, wrapped for tests: convs[4 nblk] block by block as above,
+ * precision ORCA_PRECISION_F16X2 only.  The map is converted to M16 ONCE, then fused != 0: one conv2d_dblock_run_kernel launch, fused == 0: nblk
+ * conv2d_dblock_kernel launches on the same M16 buffer, and converted back once - the two must agree bit for bit. */
+int orca_conv2d_dblock_run_forward(orca_ctx* ctx, const orca_conv_desc* convs, int nblk, int precision, const float* x, float* y, int B, int n,
+                                   int fused);
 /* y[c][m] = max_{j<k} x[c][k*m+j]  (nn.MaxPool1d(k,k)); x: [rows][ldx], y: [rows][ldy]. */
 int orca_maxpool1d_forward(orca_ctx* ctx, const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows,
                            int64_t n_out, int k);

@@ -49,6 +49,7 @@ SIGNATURES = {
     "orca_net_free": (c_int, [c_void_p]),
     "orca_net_set_precision": (c_int, [c_void_p, c_int]),
     "orca_net_set_encoder_form": (c_int, [c_void_p, c_int]),
+    "orca_net_set_decoder_block_runs": (c_int, [c_void_p, c_int]),
     "orca_encoder_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_int64,
                                      c_int64, c_void_p, c_int64, c_int64, c_int64]),
     "orca_p16_plane_units": (c_int64, [c_int64]),
@@ -109,6 +110,7 @@ SIGNATURES = {
     "orca_conv2d_forward": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]),
     "orca_conv2d_m16_forward": (c_int, [c_void_p, POINTER(ConvDesc), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]),
     "orca_conv2d_dblock_forward": (c_int, [c_void_p, POINTER(ConvDesc), c_int, c_void_p, c_void_p, c_int, c_int]),
+    "orca_conv2d_dblock_run_forward": (c_int, [c_void_p, POINTER(ConvDesc), c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int]),
     "orca_maxpool1d_forward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int]),
     "orca_pointwise1d_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64,
                                           c_int64, c_int, c_int64, c_int]),

@@ -610,6 +610,12 @@ extern "C" int orca_net_set_encoder_form(orca_net* net, int form) {
   return ORCA_OK;
 }
 
+extern "C" int orca_net_set_decoder_block_runs(orca_net* net, int on) {
+  if (!net || (net->kind != ORCA_NET_DECODER && net->kind != ORCA_NET_DECODER_1M)) return fail(ORCA_EINVAL, "orca_net_set_decoder_block_runs: not a Decoder net");
+  net->dec_block_runs = on ? 1 : 0;
+  return ORCA_OK;
+}
+
 extern "C" int orca_net_free(orca_net* net) {
   if (!net) return ORCA_OK;
   if (net->ctx) (void)hipSetDevice(net->ctx->device);

@@ -227,6 +227,24 @@ static int decoder_m16(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx_c,
         // the whole block (oth = lm(cur) + cur; cur = m(oth) + oth) in one launch, in place (conv2d_dblock.h)
         if (!(dil == 16 || dil == 32 || dil == 64) || p[1].dil != dil || p[2].dil != dil || p[3].dil != dil)
           return fail(ORCA_EINVAL, "decoder block %d: dilation %d unsupported", i, dil);
+        // f16x2: a run 16, 32, 64 is ONE launch (conv2d_dblock_run_kernel, bit-identical) unless a probe stops behind its first or second block
+        if constexpr (NS == 2 && DT == 1) {
+          bool is_run = net->dec_block_runs && dil == 16 && i + 2 < npairs && !(probe && (probe->stage == 3 + i || probe->stage == 3 + i + 1));
+          for (int k = 0; is_run && k < 8; ++k) is_run = p[4 + k].dil == (k < 4 ? 32 : 64);
+          if (is_run) {
+            DBlockRunArgs ra{};
+            ra.cur = cur; ra.bs = sz64; ra.H = n; ra.W = n; ra.dil0 = 16; ra.nblk = 3; ra.flag = ctx->d_flag;
+            for (int k = 0; k < 12; ++k) {
+              if (!p[k].f16_ok) return fail(ORCA_EINVAL, "layer weights exceed the fp16 range");
+              ra.w[k] = p[k].d_wf16;
+              ra.bias[k] = p[k].d_bias;
+            }
+            hipLaunchKernelGGL((conv2d_dblock_run_kernel<2, 1>), dim3(256, (unsigned)nb), dim3(512), 0, ctx->stream, ra);
+            LAUNCHCHECK("conv2d_dblock_run_kernel");
+            i += 2;
+            continue;
+          }
+        }
         DBlockArgs da;
         da.cur = cur; da.bs = sz64; da.H = n; da.W = n; da.dil = dil; da.flag = ctx->d_flag;
         for (int k = 0; k < 4; ++k) {

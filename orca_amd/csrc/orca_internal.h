@@ -97,6 +97,7 @@ struct orca_net {
   orca_ctx* ctx = nullptr;
   int kind = 0;
   int precision = ORCA_PRECISION_F32;
+  int dec_block_runs = 1;   // Decoders, f16x2: each run of blocks of dilation 16, 32, 64 is ONE launch (orca_net_set_decoder_block_runs, conv2d_dblock.h)
   int enc_form = ORCA_ENCODER_FORM_DEFAULT;   // Encoder: which of the algebraically equal forms of stage 1-3's linear groups runs (orca_net_set_encoder_form)
   float* d_first_w = nullptr;   // Encoder: folded [64][4][9] weights of the first layer, unpacked (conv1d_first_p16_kernel)
   void* d_first_w16 = nullptr;  // same as a K=48 fp16 split pack [2][3][2][64][8] (conv1d_first_mfma_p16_kernel)

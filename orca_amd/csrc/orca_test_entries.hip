@@ -214,6 +214,58 @@ extern "C" int orca_conv2d_dblock_forward(orca_ctx* ctx, const orca_conv_desc* c
   return rc;
 }
 
+// a run of nblk blocks (conv2d_dblock_run_kernel) against the chain of per-block launches, BOTH on one M16 buffer between one conversion in and one
+// out: chained orca_conv2d_dblock_forward calls would re-split hi + lo through fp32 between the blocks, which can differ from the stored units by a
+// rounding tie
+extern "C" int orca_conv2d_dblock_run_forward(orca_ctx* ctx, const orca_conv_desc* convs, int nblk, int precision, const float* x, float* y, int B,
+                                              int n, int fused) {
+  if (!ctx || !convs || !x || !y) return fail(ORCA_EINVAL, "orca_conv2d_dblock_run_forward: NULL argument");
+  if (n <= 0 || n > ORCA_LDW || B <= 0 || B > 65535) return fail(ORCA_EINVAL, "orca_conv2d_dblock_run_forward: map size %d / batch %d unsupported", n, B);
+  if (precision != ORCA_PRECISION_F16X2) return fail(ORCA_EINVAL, "orca_conv2d_dblock_run_forward: precision %d has no run kernel (f16x2 only)", precision);
+  if (nblk != 2 && nblk != 3) return fail(ORCA_EINVAL, "orca_conv2d_dblock_run_forward: %d blocks (2 or 3)", nblk);
+  const int d0 = convs[0].dilation;
+  if (!(d0 == 16 || d0 == 32) || (d0 << (nblk - 1)) > 64) return fail(ORCA_EINVAL, "orca_conv2d_dblock_run_forward: %d blocks from dilation %d (16, 32 (, 64) or 32, 64)", nblk, d0);
+  for (int k = 0; k < 4 * nblk; ++k) {
+    const int cin = k & 1 ? 32 : 64, cout = k & 1 ? 64 : 32, d = d0 << (k >> 2);
+    if (convs[k].ksize != 3 || convs[k].cin != cin || convs[k].cout != cout || convs[k].dilation != d)
+      return fail(ORCA_EINVAL, "orca_conv2d_dblock_run_forward: conv %d must be 3x3, %d -> %d, dilation %d", k, cin, cout, d);
+  }
+  HIPCHECK(hipSetDevice(ctx->device));
+  ConvLayer L[12];
+  int rc = ORCA_OK, made = 0;
+  for (; made < 4 * nblk && rc == ORCA_OK; ++made) {
+    rc = make_layer(convs[made], &L[made]);
+    if (rc == ORCA_OK && !L[made].f16_ok) rc = fail(ORCA_EINVAL, "layer weights exceed the fp16 range");
+  }
+  const size_t sz64 = (size_t)2 * n * ORCA_LDW * 8;
+  if (rc == ORCA_OK) rc = ws_ensure(ctx, ru256(B * sz64 * 16));
+  if (rc == ORCA_OK) {
+    f32x4* cur = reinterpret_cast<f32x4*>(ws_take(ctx, B * sz64 * 4));
+    hipStream_t s = ctx->stream;
+    for (int b = 0; b < B; ++b)
+      hipLaunchKernelGGL((nchw_to_m16_kernel<2, 1>), dim3((unsigned)n), dim3(ORCA_LDW), 0, s, x + (size_t)b * 64 * n * n, 64, n, cur + b * sz64, 8);
+    if (fused) {
+      DBlockRunArgs ra{};
+      ra.cur = cur; ra.bs = (long)sz64; ra.H = n; ra.W = n; ra.dil0 = d0; ra.nblk = nblk; ra.flag = ctx->d_flag;
+      for (int k = 0; k < 4 * nblk; ++k) { ra.w[k] = L[k].d_wf16; ra.bias[k] = L[k].d_bias; }
+      hipLaunchKernelGGL((conv2d_dblock_run_kernel<2, 1>), dim3(256, (unsigned)B), dim3(512), 0, s, ra);
+    } else {
+      for (int blk = 0; blk < nblk; ++blk) {
+        DBlockArgs da;
+        da.cur = cur; da.bs = (long)sz64; da.H = n; da.W = n; da.dil = d0 << blk; da.flag = ctx->d_flag;
+        for (int k = 0; k < 4; ++k) { da.w[k] = L[4 * blk + k].d_wf16; da.bias[k] = L[4 * blk + k].d_bias; }
+        hipLaunchKernelGGL((conv2d_dblock_kernel<2, 1>), dim3(256, (unsigned)B), dim3(512), 0, s, da);
+      }
+    }
+    for (int b = 0; b < B; ++b)
+      hipLaunchKernelGGL((m16_to_nchw_kernel<2, 1>), dim3((unsigned)n), dim3(ORCA_LDW), 0, s, cur + b * sz64, 64, n, y + (size_t)b * 64 * n * n);
+    if (hipGetLastError() != hipSuccess) rc = fail(ORCA_EHIP, "conv2d_dblock_run test path: launch failed");
+  }
+  (void)hipStreamSynchronize(ctx->stream);
+  for (int k = 0; k < made; ++k) free_layer(L[k]);
+  return rc;
+}
+
 extern "C" int orca_pointwise1d_forward(orca_ctx* ctx, const float* w_dev, const float* bias_dev, int cout, int cin, const float* x,
                                         int64_t x_bs, int64_t ldx, float* y, int64_t y_bs, int64_t ldy, int B, int64_t n, int act) {
   if (!ctx || !w_dev || !bias_dev || !x || !y) return fail(ORCA_EINVAL, "orca_pointwise1d_forward: NULL argument");

@@ -346,6 +346,10 @@ class Net:
             raise ValueError(f"form must be one of {sorted(_lib.ENCODER_FORMS)}, got {name!r}")
         check(_lib.load().orca_net_set_encoder_form(self.handle, _lib.ENCODER_FORMS[name]), "orca_net_set_encoder_form")
 
+    def set_decoder_block_runs(self, on):
+        """Decoder nets, f16x2: run each dilation 16-32-64 block run as one launch (default) or block by block (bit-identical; conv2d_dblock.h)."""
+        check(_lib.load().orca_net_set_decoder_block_runs(self.handle, 1 if on else 0), "orca_net_set_decoder_block_runs")
+
 
 # ---------------------------------------------------------------------------
 # forward wrappers
@@ -1077,6 +1081,27 @@ def conv2d_dblock(x, convs, dilation, precision="f16x2"):
     y = torch.empty_like(x)
     ctx = get_context(x.device)
     check(_lib.load().orca_conv2d_dblock_forward(ctx.handle, d, _lib.PRECISIONS[precision], _p(x), _p(y), B, n), "orca_conv2d_dblock_forward")
+    return y
+
+
+def conv2d_dblock_run(x, convs, d0, fused=True, precision="f16x2"):
+    """A run of 2 or 3 consecutive Decoder blocks of dilations d0, 2 d0 (, 4 d0) <= 64 (test wrapper): convs = [(w, b)] * 4 per block.  One
+    round trip through the M16 storage; fused: one conv2d_dblock_run_kernel launch, else one conv2d_dblock_kernel launch per block on the
+    same M16 buffer."""
+    x = _f32_cuda(x, "x").contiguous()
+    B, _, n, _ = x.shape
+    if len(convs) not in (8, 12):
+        raise ValueError("conv2d_dblock_run: four convs (lm.a, lm.b, m.a, m.b) for each of 2 or 3 blocks")
+    layers = []
+    for k, (w, b) in enumerate(convs):
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        layers.append({"w": w, "b": np.ascontiguousarray(b, dtype=np.float32), "cout": w.shape[0], "cin": w.shape[1], "k": w.shape[2],
+                       "dil": int(d0) << (k // 4)})
+    d = make_descs(layers)
+    y = torch.empty_like(x)
+    ctx = get_context(x.device)
+    check(_lib.load().orca_conv2d_dblock_run_forward(ctx.handle, d, len(convs) // 4, _lib.PRECISIONS[precision], _p(x), _p(y), B, n,
+                                                     1 if fused else 0), "orca_conv2d_dblock_run_forward")
     return y
 
 
