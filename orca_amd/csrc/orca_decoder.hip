@@ -2,6 +2,8 @@
 // Part of liborca_hip.so (include/orca_hip.h is the ABI; orca_internal.h what the units share).
 #include "orca_internal.h"
 
+#include <type_traits>
+
 #include "conv2d_m16.h"
 #include "conv2d_m16q.h"
 #include "conv2d_dblock.h"
@@ -22,6 +24,18 @@ int launch_conv2d(orca_ctx* ctx, const ConvLayer& L, const float* x, long x_bs, 
   else hipLaunchKernelGGL((conv2d_3x3_kernel<32>), grid, dim3(512), 0, ctx->stream, a);
   LAUNCHCHECK("conv2d_3x3_kernel");
   return ORCA_OK;
+}
+
+// the <COUT, NS, DT> variant of an M16 kernel for (mode, cout): f(COUT, NS, DT) with the three as integral constants
+template <class F>
+static void m16_variant(int mode, int cout, F f) {
+  auto by_cout = [&](auto ns, auto dt) {
+    if (cout == 64) f(std::integral_constant<int, 64>(), ns, dt);
+    else f(std::integral_constant<int, 32>(), ns, dt);
+  };
+  if (mode == 1) by_cout(std::integral_constant<int, 1>(), std::integral_constant<int, 0>());
+  else if (mode == 2) by_cout(std::integral_constant<int, 1>(), std::integral_constant<int, 1>());
+  else by_cout(std::integral_constant<int, 2>(), std::integral_constant<int, 1>());
 }
 
 // dilated 3x3 conv on M16 maps (conv2d_m16.h); maps are unit arrays [octets][NS][n][256]; strides in units
@@ -63,34 +77,47 @@ int launch_conv2d_m16(orca_ctx* ctx, const ConvLayer& L, const f32x4* x, long x_
     if (a.nchunks % 2 == 0 && gx * B > res) gy = res / gx > 1 ? res / gx : 1;
     if (gy > B) gy = B;
     dim3 gridq((unsigned)gx, (unsigned)gy);
-    if (bf16) {
-      if (L.cout == 64) hipLaunchKernelGGL((conv2d_3x3_m16q_kernel<64, 1, 0>), gridq, dim3(512), 0, ctx->stream, aq);
-      else hipLaunchKernelGGL((conv2d_3x3_m16q_kernel<32, 1, 0>), gridq, dim3(512), 0, ctx->stream, aq);
-    } else if (mode == 2) {
-      if (L.cout == 64) hipLaunchKernelGGL((conv2d_3x3_m16q_kernel<64, 1, 1>), gridq, dim3(512), 0, ctx->stream, aq);
-      else hipLaunchKernelGGL((conv2d_3x3_m16q_kernel<32, 1, 1>), gridq, dim3(512), 0, ctx->stream, aq);
-    } else {
-      if (L.cout == 64) hipLaunchKernelGGL((conv2d_3x3_m16q_kernel<64, 2, 1>), gridq, dim3(512), 0, ctx->stream, aq);
-      else hipLaunchKernelGGL((conv2d_3x3_m16q_kernel<32, 2, 1>), gridq, dim3(512), 0, ctx->stream, aq);
-    }
+    m16_variant(mode, L.cout, [&](auto co, auto ns, auto dt) {
+      hipLaunchKernelGGL((conv2d_3x3_m16q_kernel<decltype(co)::value, decltype(ns)::value, decltype(dt)::value>), gridq, dim3(512), 0, ctx->stream, aq);
+    });
     LAUNCHCHECK("conv2d_3x3_m16q_kernel");
     return ORCA_OK;
   }
   a.banded = n >= 64 ? 1 : 0;
   dim3 grid((unsigned)(a.banded ? 8 * ((n + 7) / 8) : n), (unsigned)B);
-  if (bf16) {
-    if (L.cout == 64) hipLaunchKernelGGL((conv2d_3x3_m16_kernel<64, 1, 0>), grid, dim3(512), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((conv2d_3x3_m16_kernel<32, 1, 0>), grid, dim3(512), 0, ctx->stream, a);
-  } else if (mode == 2) {
-    if (L.cout == 64) hipLaunchKernelGGL((conv2d_3x3_m16_kernel<64, 1, 1>), grid, dim3(512), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((conv2d_3x3_m16_kernel<32, 1, 1>), grid, dim3(512), 0, ctx->stream, a);
-  } else {
-    if (L.cout == 64) hipLaunchKernelGGL((conv2d_3x3_m16_kernel<64, 2, 1>), grid, dim3(512), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((conv2d_3x3_m16_kernel<32, 2, 1>), grid, dim3(512), 0, ctx->stream, a);
-  }
+  m16_variant(mode, L.cout, [&](auto co, auto ns, auto dt) {
+    hipLaunchKernelGGL((conv2d_3x3_m16_kernel<decltype(co)::value, decltype(ns)::value, decltype(dt)::value>), grid, dim3(512), 0, ctx->stream, a);
+  });
   LAUNCHCHECK("conv2d_3x3_m16_kernel");
   return ORCA_OK;
 }
+
+// `nblk` whole residual blocks of dilations d, 2 d (, 4 d) out of 16, 32, 64, in place on the M16 maps `cur` (conv2d_dblock.h); p: their 4 nblk
+// layers.  One block: conv2d_dblock_kernel; a run of 2 or 3 (f16x2 only): conv2d_dblock_run_kernel, bit-identical to its blocks one by one.
+template <int NS, int DT>
+int launch_dblocks(orca_ctx* ctx, f32x4* cur, long bs, int B, int n, const ConvLayer* p, int nblk) {
+  if (nblk < 1 || nblk > (NS == 2 && DT == 1 ? 3 : 1)) return fail(ORCA_EINVAL, "launch_dblocks: %d blocks in one launch", nblk);
+  DBlockArgs a{};
+  a.cur = cur; a.bs = bs; a.H = n; a.W = n; a.dil = p[0].dil; a.nblk = nblk; a.flag = ctx->d_flag;
+  for (int k = 0; k < 4 * nblk; ++k) {
+    const int dil = a.dil << (k >> 2);
+    if (!(dil == 16 || dil == 32 || dil == 64) || p[k].dil != dil) return fail(ORCA_EINVAL, "decoder block: dilation %d unsupported", p[k].dil);
+    if (DT == 1 && !p[k].f16_ok) return fail(ORCA_EINVAL, "layer weights exceed the fp16 range");
+    a.w[k] = DT == 0 ? p[k].d_wb16p : p[k].d_wf16;
+    a.bias[k] = p[k].d_bias;
+  }
+  if (nblk == 1) {
+    hipLaunchKernelGGL((conv2d_dblock_kernel<NS, DT>), dim3(256, (unsigned)B), dim3(512), 0, ctx->stream, a);
+    LAUNCHCHECK("conv2d_dblock_kernel");
+  } else if constexpr (NS == 2 && DT == 1) {
+    hipLaunchKernelGGL((conv2d_dblock_run_kernel<2, 1>), dim3(256, (unsigned)B), dim3(512), 0, ctx->stream, a);
+    LAUNCHCHECK("conv2d_dblock_run_kernel");
+  }
+  return ORCA_OK;
+}
+template int launch_dblocks<2, 1>(orca_ctx*, f32x4*, long, int, int, const ConvLayer*, int);
+template int launch_dblocks<1, 0>(orca_ctx*, f32x4*, long, int, int, const ConvLayer*, int);
+template int launch_dblocks<1, 1>(orca_ctx*, f32x4*, long, int, int, const ConvLayer*, int);
 
 // ---------------------------------------------------------------------------
 // Decoder / Decoder_1m (orca_modules.py:461-488, :782-800)
@@ -104,16 +131,15 @@ struct RowSrc {
   explicit operator bool() const { return rows || base; }
 };
 
-static int launch_final(orca_ctx* ctx, orca_net* net, const float* cur, long cur_bs, float* out, int B, int n, int accumulate) {
+// the last two 1x1 convs + symmetrisation: final_sym_kernel on fp32 maps, final_sym_m16_kernel<NS, DT> on M16 maps (cur_bs in floats / units)
+static FinalArgs final_args(const orca_net* net, const float* cur, long cur_bs, float* out, int n, int accumulate) {
   const ConvLayer& fa = net->convs[net->convs.size() - 2];
   const ConvLayer& fb = net->convs[net->convs.size() - 1];
   FinalArgs a;
   a.cur = cur; a.w1 = fa.d_w; a.b1 = fa.d_bias; a.w2 = fb.d_w; a.b2 = fb.d_bias; a.out = out;
   a.cur_bs = cur_bs; a.out_bs = (long)net->num_2d * n * n; a.n = n; a.accumulate = accumulate;
   a.T = net->num_2d; a.F = fa.cout;
-  hipLaunchKernelGGL(final_sym_kernel, dim3((unsigned)n, (unsigned)B), dim3(256), 0, ctx->stream, a);
-  LAUNCHCHECK("final_sym_kernel");
-  return ORCA_OK;
+  return a;
 }
 
 // orca_decoder_probe: the forward stops behind the launches that complete `stage` and hands out that map as fp32 [B][channels][n][n].
@@ -123,13 +149,69 @@ struct DecoderProbe {
   float* out;
 };
 
-// Decoder / Decoder_1m on the 16-bit matrix cores, feature maps in M16 (conv2d_m16.h)
+// ---- the chain of both Decoders, written once for the M16 and the fp32 maps ----
+// a batch of feature maps: fp32 planes [channels][n][256] (P = float) or M16 units [octets][NS][n][256] (P = f32x4); bs = batch stride, oct = channel octets
+template <class P>
+struct DecMaps {
+  P* p;
+  long bs;
+  int oct;
+};
+constexpr int DEC_STOP = 1;   // what a callable of decoder_chain returns to end the forward without an error (a probe has its map)
+
+// one residual block behind the first: oth = lm(cur) + cur; cur = m(oth) + oth, layer by layer (p = lm.a, lm.b, m.a, m.b; T: the 32-channel map)
+template <class M, class Conv>
+static int residual_block(Conv& conv, const ConvLayer* p, const M& cur, const M& oth, const M& T) {
+  ORCA_TRY(conv(p[0], cur, T, nullptr, 0));
+  ORCA_TRY(conv(p[1], T, oth, &cur, 0));
+  ORCA_TRY(conv(p[2], oth, T, nullptr, 1));
+  return conv(p[3], T, cur, &oth, 1);
+}
+
+// Decoder: lcombinerD / combinerD -> A (64 channels; the caller has put the coarse prediction y behind them) -> lcombiner / combiner (with y) or
+// block 0 (without) -> blocks 1..27 at L + 8.  Decoder_1m: blocks 0..18 at L.  Block 0's lm has no residual (:477).
+//   conv(layer, src, dst, residual or nullptr, relu)   one 3x3 conv
+//   block(i, cur, oth)                                  block i >= 1, result in cur
+// Both return ORCA_OK, an error or DEC_STOP.  *last = the map that holds the residual stream at the end.
+template <class M, class Conv, class Block>
+static int decoder_chain(const orca_net* net, bool with_y, const M& IN, const M& A, const M& Bf, const M& Cf, const M& Df, const M& T, Conv conv,
+                         Block block, M* last) {
+  const bool is1m = net->kind == ORCA_NET_DECODER_1M;
+  const ConvLayer* L = net->convs.data();
+  const ConvLayer* pairs = is1m ? L : L + 8;
+  const int npairs = is1m ? 19 : 28;
+  if (!is1m) {
+    ORCA_TRY(conv(L[0], IN, Bf, nullptr, 0));
+    ORCA_TRY(conv(L[1], Bf, Cf, nullptr, 0));      // Cf = lcombinerD(mat)
+    ORCA_TRY(conv(L[2], Cf, Bf, nullptr, 1));
+    ORCA_TRY(conv(L[3], Bf, A, &Cf, 1));           // A[0:64] = combinerD(.) + .
+  }
+  if (!is1m && with_y) {
+    ORCA_TRY(conv(L[4], A, Bf, nullptr, 0));
+    ORCA_TRY(conv(L[5], Bf, Cf, nullptr, 0));      // Cf = lcombiner(cat)
+    ORCA_TRY(conv(L[6], Cf, Bf, nullptr, 1));
+    ORCA_TRY(conv(L[7], Bf, Df, &Cf, 1));          // Df = combiner(.) + .
+  } else {
+    ORCA_TRY(conv(pairs[0], is1m ? IN : A, T, nullptr, 0));
+    ORCA_TRY(conv(pairs[1], T, Cf, nullptr, 0));   // Cf = lm0(mat)
+    ORCA_TRY(conv(pairs[2], Cf, T, nullptr, 1));
+    ORCA_TRY(conv(pairs[3], T, Df, &Cf, 1));
+  }
+  for (int i = 1; i < npairs; ++i) ORCA_TRY(block(i, Df, Cf));
+  *last = Df;
+  return ORCA_OK;
+}
+
+// Decoder / Decoder_1m on the 16-bit matrix cores, feature maps in M16 (conv2d_m16.h).  A Decoder is a chain of ~90 dependent launches per map; a
+// launch carries the WHOLE batch (conv2d_m16q.h: both strands of a level are 252-256 workgroups = one round on 256 CUs).  Half-batches on two
+// streams were measured twice (rounds 3 and 5: slower or noise) and are gone.
 template <int NS, int DT>
 static int decoder_m16(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx_c, long sx_l, const RowSrc& de,
                        long sd_c, long sd_h, long sd_w, const RowSrc& y, long sy_c, long sy_h, long sy_w, int B, int n,
                        float* out, int accumulate, const DecoderProbe* probe = nullptr) {
+  typedef DecMaps<f32x4> M;
   const int nt2 = net->num_2d;
-  const bool is1m = net->kind == ORCA_NET_DECODER_1M, bf16 = DT == 0;
+  const bool is1m = net->kind == ORCA_NET_DECODER_1M;
   const int mode = DT == 0 ? 1 : (NS == 1 ? 2 : 0);
   // channel octets: Decoder_1m 128 channels of outer sum; Decoder: ONLY the distenc chunk (16 channels) - the 128 outer-sum channels of
   // lcombinerD.a never exist as a map (separable, see orca_net_create); A: 80 (64 + coarse prediction)
@@ -139,143 +221,76 @@ static int decoder_m16(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx_c,
   const size_t szIN = upo * oIN, szA = upo * oA, sz64 = upo * 8, sz32 = upo * 4;   // units
   const size_t need = ru256(B * szIN * 16) + ru256(B * szA * 16) + 3 * ru256(B * sz64 * 16) + ru256(B * sz32 * 16) + ru256(B * tabsz * 4);
   ORCA_TRY(ws_ensure(ctx, need));
-  auto take = [&](size_t units) { return reinterpret_cast<f32x4*>(ws_take(ctx, units * 4)); };
-  float* const TAB0 = is1m ? nullptr : ws_take(ctx, B * tabsz);
-  f32x4* const IN0 = take(B * szIN);
-  f32x4* const A0 = take(B * szA);
-  f32x4* const Bf0 = take(B * sz64);
-  f32x4* const Cf0 = take(B * sz64);
-  f32x4* const Df0 = take(B * sz64);
-  f32x4* const T0 = take(B * sz32);
-  // maps [b0, b0 + nb) of the batch, on ctx->stream
-  auto run = [&](int b0, int nb) -> int {
-    f32x4* IN = IN0 + b0 * szIN;
-    f32x4* A = A0 + b0 * szA;
-    f32x4* Bf = Bf0 + b0 * sz64;
-    f32x4* Cf = Cf0 + b0 * sz64;
-    f32x4* Df = Df0 + b0 * sz64;
-    f32x4* T = T0 + b0 * sz32;
-    hipStream_t s = ctx->stream;
-    float* TAB = is1m ? nullptr : TAB0 + b0 * tabsz;
-    // probe: map `buf` (batch stride bs units) is what stage k leaves - convert it and stop
-    auto emit = [&](const f32x4* buf, size_t bs) -> int {
-      for (int b = 0; b < nb; ++b)
-        hipLaunchKernelGGL((m16_to_nchw_kernel<NS, DT>), dim3((unsigned)n), dim3(ORCA_LDW), 0, s, buf + b * bs, probe->channels, n,
-                           probe->out + (size_t)(b0 + b) * probe->channels * n * n);
-      LAUNCHCHECK("m16_to_nchw_kernel");
-      return ORCA_OK;
-    };
-#define PROBE(k, buf, bs) \
-  if (probe && probe->stage == (k)) return emit(buf, bs)
-    // everything computed from the inputs alone - IN (outer sum / distenc chunk), the separable tables, the upsampled coarse prediction - in one
-    // launch per 8 maps (decoder_head_m16_kernel)
-    for (int c0 = 0; c0 < nb; c0 += 8) {
-      const int nc = nb - c0 < 8 ? nb - c0 : 8;
-      M16HeadArgs ha{};
-      for (int b = 0; b < nc; ++b) { ha.x[b] = x.at(b0 + c0 + b); ha.de[b] = de.at(b0 + c0 + b); ha.y[b] = (!is1m && y) ? y.at(b0 + c0 + b) : nullptr; }
-      ha.sx_c = sx_c; ha.sx_l = sx_l; ha.sd_c = sd_c; ha.sd_h = sd_h; ha.sd_w = sd_w; ha.sy_c = sy_c; ha.sy_h = sy_h; ha.sy_w = sy_w;
-      ha.in = IN + c0 * szIN; ha.in_bs = (long)szIN;
-      ha.tab = is1m ? nullptr : TAB + c0 * tabsz; ha.tab_bs = (long)tabsz;
-      ha.a = A + c0 * szA; ha.a_bs = (long)szA;
-      ha.wsep = net->d_sep; ha.nt = nt2; ha.n = n; ha.o0 = is1m ? 0 : 16; ha.noct = oIN; ha.nsep = is1m ? 0 : 6;
-      ha.bilinear = net->upsample_mode == ORCA_UPSAMPLE_BILINEAR ? 1 : 0; ha.flag = ctx->d_flag;
-      const unsigned roles = (unsigned)(oIN + ha.nsep + ((!is1m && y) ? 1 : 0));
-      hipLaunchKernelGGL((decoder_head_m16_kernel<NS, DT>), dim3((unsigned)n, roles, (unsigned)nc), dim3(256), 0, s, ha);
-      LAUNCHCHECK("decoder_head_m16_kernel");
-    }
-    PROBE(0, IN, szIN);
-    const ConvLayer* L = net->convs.data();
-    const ConvLayer* pairs;
-    int npairs;
-#define C2(layer, src, sbs, so, dst, dbs, dso, res, rbs, relu) \
-  ORCA_TRY(launch_conv2d_m16(ctx, layer, src, sbs, so, dst, dbs, dso, res, rbs, nb, n, relu, mode))
-    if (!is1m) {
-      // lcombinerD.a = (MFMA conv over the distenc chunk) + (separable outer-sum part from the tables, added in the epilogue)
-      ORCA_TRY(launch_conv2d_m16(ctx, L[0], IN, szIN, oIN, Bf, sz64, 8, nullptr, 0, nb, n, 0, mode, 8, 1, TAB, (long)tabsz));
-      PROBE(1, Bf, sz64);
-      C2(L[1], Bf, sz64, 8, Cf, sz64, 8, nullptr, 0, 0);
-      C2(L[2], Cf, sz64, 8, Bf, sz64, 8, nullptr, 0, 1);
-      C2(L[3], Bf, sz64, 8, A, szA, oA, Cf, sz64, 1);           // A[octets 0..7] = combinerD(.) + .
-      PROBE(2, A, szA);
-      pairs = L + 8; npairs = 28;
-      if (y) {
-        // (octets 8, 9 of A - the upsampled coarse prediction - were written by the head launch)
-        C2(L[4], A, szA, oA, Bf, sz64, 8, nullptr, 0, 0);
-        C2(L[5], Bf, sz64, 8, Cf, sz64, 8, nullptr, 0, 0);
-        C2(L[6], Cf, sz64, 8, Bf, sz64, 8, nullptr, 0, 1);
-        C2(L[7], Bf, sz64, 8, Df, sz64, 8, Cf, sz64, 1);
-      } else {
-        C2(pairs[0], A, szA, oA, T, sz32, 4, nullptr, 0, 0);
-        C2(pairs[1], T, sz32, 4, Cf, sz64, 8, nullptr, 0, 0);
-        C2(pairs[2], Cf, sz64, 8, T, sz32, 4, nullptr, 0, 1);
-        C2(pairs[3], T, sz32, 4, Df, sz64, 8, Cf, sz64, 1);
-      }
-    } else {
-      pairs = L; npairs = 19;
-      C2(pairs[0], IN, szIN, oIN, T, sz32, 4, nullptr, 0, 0);
-      C2(pairs[1], T, sz32, 4, Cf, sz64, 8, nullptr, 0, 0);
-      C2(pairs[2], Cf, sz64, 8, T, sz32, 4, nullptr, 0, 1);
-      C2(pairs[3], T, sz32, 4, Df, sz64, 8, Cf, sz64, 1);
-    }
-    f32x4* cur = Df;
-    f32x4* oth = Cf;
-    for (int i = 1; i < npairs; ++i) {
-      PROBE(3 + i - 1, cur, sz64);
-      const ConvLayer* p = pairs + 4 * i;
-      const int dil = p[0].dil;
-      if (dil >= 16) {
-        // the whole block (oth = lm(cur) + cur; cur = m(oth) + oth) in one launch, in place (conv2d_dblock.h)
-        if (!(dil == 16 || dil == 32 || dil == 64) || p[1].dil != dil || p[2].dil != dil || p[3].dil != dil)
-          return fail(ORCA_EINVAL, "decoder block %d: dilation %d unsupported", i, dil);
-        // f16x2: a run 16, 32, 64 is ONE launch (conv2d_dblock_run_kernel, bit-identical) unless a probe stops behind its first or second block
-        if constexpr (NS == 2 && DT == 1) {
-          bool is_run = net->dec_block_runs && dil == 16 && i + 2 < npairs && !(probe && (probe->stage == 3 + i || probe->stage == 3 + i + 1));
-          for (int k = 0; is_run && k < 8; ++k) is_run = p[4 + k].dil == (k < 4 ? 32 : 64);
-          if (is_run) {
-            DBlockRunArgs ra{};
-            ra.cur = cur; ra.bs = sz64; ra.H = n; ra.W = n; ra.dil0 = 16; ra.nblk = 3; ra.flag = ctx->d_flag;
-            for (int k = 0; k < 12; ++k) {
-              if (!p[k].f16_ok) return fail(ORCA_EINVAL, "layer weights exceed the fp16 range");
-              ra.w[k] = p[k].d_wf16;
-              ra.bias[k] = p[k].d_bias;
-            }
-            hipLaunchKernelGGL((conv2d_dblock_run_kernel<2, 1>), dim3(256, (unsigned)nb), dim3(512), 0, ctx->stream, ra);
-            LAUNCHCHECK("conv2d_dblock_run_kernel");
-            i += 2;
-            continue;
-          }
-        }
-        DBlockArgs da;
-        da.cur = cur; da.bs = sz64; da.H = n; da.W = n; da.dil = dil; da.flag = ctx->d_flag;
-        for (int k = 0; k < 4; ++k) {
-          if (!bf16 && !p[k].f16_ok) return fail(ORCA_EINVAL, "layer weights exceed the fp16 range");
-          da.w[k] = bf16 ? p[k].d_wb16p : p[k].d_wf16;
-          da.bias[k] = p[k].d_bias;
-        }
-        hipLaunchKernelGGL((conv2d_dblock_kernel<NS, DT>), dim3(256, (unsigned)nb), dim3(512), 0, ctx->stream, da);
-        LAUNCHCHECK("conv2d_dblock_kernel");
-        continue;
-      }
-      C2(p[0], cur, sz64, 8, T, sz32, 4, nullptr, 0, 0);
-      C2(p[1], T, sz32, 4, oth, sz64, 8, cur, sz64, 0);
-      C2(p[2], oth, sz64, 8, T, sz32, 4, nullptr, 0, 1);
-      C2(p[3], T, sz32, 4, cur, sz64, 8, oth, sz64, 1);
-    }
-#undef C2
-    PROBE(3 + npairs - 1, cur, sz64);
-#undef PROBE
-    const ConvLayer& fa = net->convs[net->convs.size() - 2];
-    const ConvLayer& fb = net->convs[net->convs.size() - 1];
-    FinalArgs fa_;
-    fa_.cur = reinterpret_cast<const float*>(cur); fa_.w1 = fa.d_w; fa_.b1 = fa.d_bias; fa_.w2 = fb.d_w; fa_.b2 = fb.d_bias; fa_.out = out + (size_t)b0 * nt2 * n * n;
-    fa_.cur_bs = sz64; fa_.out_bs = (long)nt2 * n * n; fa_.n = n; fa_.accumulate = accumulate; fa_.T = nt2; fa_.F = fa.cout;
-    hipLaunchKernelGGL((final_sym_m16_kernel<NS, DT>), dim3(136u, (unsigned)nb), dim3(256), 0, s, fa_);   // 16 x 16 tile pairs of the upper triangle
-    LAUNCHCHECK("final_sym_m16_kernel");
+  auto take = [&](size_t units, int oct) { return M{reinterpret_cast<f32x4*>(ws_take(ctx, B * units * 4)), (long)units, oct}; };
+  float* const TAB = is1m ? nullptr : ws_take(ctx, B * tabsz);
+  const M IN = take(szIN, oIN), A = take(szA, oA), Bf = take(sz64, 8), Cf = take(sz64, 8), Df = take(sz64, 8), T = take(sz32, 4);
+  hipStream_t s = ctx->stream;
+  // probe: map `m` is what stage k leaves - convert it and stop
+  auto emit = [&](const M& m) -> int {
+    for (int b = 0; b < B; ++b)
+      hipLaunchKernelGGL((m16_to_nchw_kernel<NS, DT>), dim3((unsigned)n), dim3(ORCA_LDW), 0, s, m.p + b * m.bs, probe->channels, n,
+                         probe->out + (size_t)b * probe->channels * n * n);
+    LAUNCHCHECK("m16_to_nchw_kernel");
+    return DEC_STOP;
+  };
+#define PROBE(k, m) \
+  if (probe && probe->stage == (k)) return emit(m)
+  // everything computed from the inputs alone - IN (outer sum / distenc chunk), the separable tables, the upsampled coarse prediction - in one
+  // launch per 8 maps (decoder_head_m16_kernel)
+  for (int c0 = 0; c0 < B; c0 += 8) {
+    const int nc = B - c0 < 8 ? B - c0 : 8;
+    M16HeadArgs ha{};
+    for (int b = 0; b < nc; ++b) { ha.x[b] = x.at(c0 + b); ha.de[b] = de.at(c0 + b); ha.y[b] = (!is1m && y) ? y.at(c0 + b) : nullptr; }
+    ha.sx_c = sx_c; ha.sx_l = sx_l; ha.sd_c = sd_c; ha.sd_h = sd_h; ha.sd_w = sd_w; ha.sy_c = sy_c; ha.sy_h = sy_h; ha.sy_w = sy_w;
+    ha.in = IN.p + c0 * szIN; ha.in_bs = (long)szIN;
+    ha.tab = is1m ? nullptr : TAB + c0 * tabsz; ha.tab_bs = (long)tabsz;
+    ha.a = A.p + c0 * szA; ha.a_bs = (long)szA;
+    ha.wsep = net->d_sep; ha.nt = nt2; ha.n = n; ha.o0 = is1m ? 0 : 16; ha.noct = oIN; ha.nsep = is1m ? 0 : 6;
+    ha.bilinear = net->upsample_mode == ORCA_UPSAMPLE_BILINEAR ? 1 : 0; ha.flag = ctx->d_flag;
+    const unsigned roles = (unsigned)(oIN + ha.nsep + ((!is1m && y) ? 1 : 0));
+    hipLaunchKernelGGL((decoder_head_m16_kernel<NS, DT>), dim3((unsigned)n, roles, (unsigned)nc), dim3(256), 0, s, ha);
+    LAUNCHCHECK("decoder_head_m16_kernel");
+  }
+  const auto stop = [](int rc) { return rc == DEC_STOP ? ORCA_OK : rc; };
+  if (probe && probe->stage == 0) return stop(emit(IN));
+  const ConvLayer* L = net->convs.data();
+  const ConvLayer* pairs = is1m ? L : L + 8;
+  const int npairs = is1m ? 19 : 28;
+  auto conv = [&](const ConvLayer& l, const M& src, const M& dst, const M* res, int relu) -> int {
+    // lcombinerD.a = (MFMA conv over the distenc chunk) + (separable outer-sum part from the tables, added in the epilogue)
+    const bool sep = !is1m && &l == L;
+    ORCA_TRY(launch_conv2d_m16(ctx, l, src.p, src.bs, src.oct, dst.p, dst.bs, dst.oct, res ? res->p : nullptr, res ? res->bs : 0, B, n, relu, mode,
+                               sep ? 8 : 0, sep ? 1 : 0, sep ? TAB : nullptr, sep ? (long)tabsz : 0));
+    if (sep) PROBE(1, dst);
+    if (!is1m && &l == L + 3) PROBE(2, dst);     // A[octets 0..7]; octets 8, 9 - the upsampled coarse prediction - were written by the head launch
     return ORCA_OK;
   };
-  // A Decoder is a chain of ~90 dependent launches per map; a launch carries the WHOLE batch (conv2d_m16q.h: both strands of a level are
-  // 252-256 workgroups = one round on 256 CUs).  Half-batches on two streams were measured twice (rounds 3 and 5: slower or noise) and are gone.
-  return run(0, B);
+  int run_end = 0;   // blocks below it went out with the run that an earlier call of `block` launched
+  auto block = [&](int i, const M& cur, const M& oth) -> int {
+    if (i < run_end) return ORCA_OK;
+    PROBE(3 + i - 1, cur);
+    const ConvLayer* p = pairs + 4 * i;
+    if (p[0].dil < 16) return residual_block(conv, p, cur, oth, T);
+    // the whole block in one launch, in place (conv2d_dblock.h); f16x2: a run 16, 32, 64 is ONE launch unless a probe stops behind its first or
+    // second block
+    int nblk = 1;
+    if constexpr (NS == 2 && DT == 1) {
+      bool is_run = net->dec_block_runs && p[0].dil == 16 && i + 2 < npairs && !(probe && (probe->stage == 3 + i || probe->stage == 3 + i + 1));
+      for (int k = 0; is_run && k < 12; ++k) is_run = p[k].dil == 16 << (k >> 2);
+      if (is_run) nblk = 3;
+    }
+    run_end = i + nblk;
+    return launch_dblocks<NS, DT>(ctx, cur.p, cur.bs, B, n, p, nblk);
+  };
+  M cur;
+  int rc = decoder_chain(net, (bool)y, IN, A, Bf, Cf, Df, T, conv, block, &cur);
+  if (rc == ORCA_OK && probe && probe->stage == 3 + npairs - 1) rc = emit(cur);
+#undef PROBE
+  if (rc != ORCA_OK) return stop(rc);
+  const FinalArgs fa = final_args(net, reinterpret_cast<const float*>(cur.p), cur.bs, out, n, accumulate);
+  hipLaunchKernelGGL((final_sym_m16_kernel<NS, DT>), dim3(136u, (unsigned)B), dim3(256), 0, s, fa);   // 16 x 16 tile pairs of the upper triangle
+  LAUNCHCHECK("final_sym_m16_kernel");
+  return ORCA_OK;
 }
 
 static int decoder_common(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx_c, long sx_l, const RowSrc& de,
@@ -292,66 +307,41 @@ static int decoder_common(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx
   if (net->precision == ORCA_PRECISION_F16)
     return decoder_m16<1, 1>(ctx, net, x, sx_c, sx_l, de, sd_c, sd_h, sd_w, y, sy_c, sy_h, sy_w, B, n, out, accumulate, probe);
   if (probe) return fail(ORCA_EINVAL, "orca_decoder_probe: an f32 net has no M16 stages (its convs are conv2d_3x3_kernel)");
+  // exact fp32: maps as planes [channels][n][256], conv2d_3x3_kernel layer by layer
+  typedef DecMaps<float> M;
   const bool is1m = net->kind == ORCA_NET_DECODER_1M;
   const size_t plane = (size_t)n * ORCA_LDW;
   const int cin0 = is1m ? 128 : 136;
   const size_t szIN = plane * cin0, szA = plane * 72, sz64 = plane * 64, sz32 = plane * 32;
   const size_t need = ru256(B * szIN * 4) + ru256(B * szA * 4) + 3 * ru256(B * sz64 * 4) + ru256(B * sz32 * 4);
   ORCA_TRY(ws_ensure(ctx, need));
-  float* IN = ws_take(ctx, B * szIN);
-  float* A = ws_take(ctx, B * szA);
-  float* Bf = ws_take(ctx, B * sz64);
-  float* Cf = ws_take(ctx, B * sz64);
-  float* Df = ws_take(ctx, B * sz64);
-  float* T = ws_take(ctx, B * sz32);
+  auto take = [&](size_t floats) { return M{ws_take(ctx, B * floats), (long)floats, 0}; };
+  const M IN = take(szIN), A = take(szA), Bf = take(sz64), Cf = take(sz64), Df = take(sz64), T = take(sz32);
   hipStream_t s = ctx->stream;
   for (int b = 0; b < B; ++b) {
     hipLaunchKernelGGL(outer_sum_kernel, dim3((unsigned)n, (unsigned)cin0), dim3(64), 0, s, x.at(b), sx_c, sx_l,
-                       de.at(b), sd_c, sd_h, sd_w, nt2, IN + b * szIN, n, cin0);
+                       de.at(b), sd_c, sd_h, sd_w, nt2, IN.p + b * szIN, n, cin0);
     LAUNCHCHECK("outer_sum_kernel");
   }
   const ConvLayer* L = net->convs.data();
-  const ConvLayer* pairs;
-  int npairs;
-  if (!is1m) {
-    ORCA_TRY(launch_conv2d(ctx, L[0], IN, szIN, Bf, sz64, nullptr, 0, B, n, 0));
-    ORCA_TRY(launch_conv2d(ctx, L[1], Bf, sz64, Cf, sz64, nullptr, 0, B, n, 0));     // Cf = lcombinerD(mat)
-    ORCA_TRY(launch_conv2d(ctx, L[2], Cf, sz64, Bf, sz64, nullptr, 0, B, n, 1));
-    ORCA_TRY(launch_conv2d(ctx, L[3], Bf, sz64, A, szA, Cf, sz64, B, n, 1));         // A[0:64] = combinerD(.)+.
-    pairs = L + 8; npairs = 28;
-    if (y) {
-      for (int b = 0; b < B; ++b) {
-        hipLaunchKernelGGL(upsample2d_x2_kernel, dim3((unsigned)n, 8), dim3(ORCA_LDW), 0, s, y.at(b), sy_c, sy_h, sy_w, nt2,
-                           A + b * szA + 64 * plane, n, net->upsample_mode == ORCA_UPSAMPLE_BILINEAR ? 1 : 0, 8);
-        LAUNCHCHECK("upsample2d_x2_kernel");
-      }
-      ORCA_TRY(launch_conv2d(ctx, L[4], A, szA, Bf, sz64, nullptr, 0, B, n, 0));
-      ORCA_TRY(launch_conv2d(ctx, L[5], Bf, sz64, Cf, sz64, nullptr, 0, B, n, 0));   // Cf = lcombiner(cat)
-      ORCA_TRY(launch_conv2d(ctx, L[6], Cf, sz64, Bf, sz64, nullptr, 0, B, n, 1));
-      ORCA_TRY(launch_conv2d(ctx, L[7], Bf, sz64, Df, sz64, Cf, sz64, B, n, 1));     // Df = combiner(.)+.
-    } else {
-      ORCA_TRY(launch_conv2d(ctx, pairs[0], A, szA, T, sz32, nullptr, 0, B, n, 0));
-      ORCA_TRY(launch_conv2d(ctx, pairs[1], T, sz32, Cf, sz64, nullptr, 0, B, n, 0));  // Cf = lm0(mat) (no residual, :477)
-      ORCA_TRY(launch_conv2d(ctx, pairs[2], Cf, sz64, T, sz32, nullptr, 0, B, n, 1));
-      ORCA_TRY(launch_conv2d(ctx, pairs[3], T, sz32, Df, sz64, Cf, sz64, B, n, 1));
+  auto conv = [&](const ConvLayer& l, const M& src, const M& dst, const M* res, int relu) -> int {
+    ORCA_TRY(launch_conv2d(ctx, l, src.p, src.bs, dst.p, dst.bs, res ? res->p : nullptr, res ? res->bs : 0, B, n, relu));
+    if (is1m || !y || &l != L + 3) return ORCA_OK;
+    for (int b = 0; b < B; ++b) {   // behind combinerD: the upsampled coarse prediction into channels 64.. of A
+      hipLaunchKernelGGL(upsample2d_x2_kernel, dim3((unsigned)n, 8), dim3(ORCA_LDW), 0, s, y.at(b), sy_c, sy_h, sy_w, nt2,
+                         A.p + b * szA + 64 * plane, n, net->upsample_mode == ORCA_UPSAMPLE_BILINEAR ? 1 : 0, 8);
+      LAUNCHCHECK("upsample2d_x2_kernel");
     }
-  } else {
-    pairs = L; npairs = 19;
-    ORCA_TRY(launch_conv2d(ctx, pairs[0], IN, szIN, T, sz32, nullptr, 0, B, n, 0));
-    ORCA_TRY(launch_conv2d(ctx, pairs[1], T, sz32, Cf, sz64, nullptr, 0, B, n, 0));
-    ORCA_TRY(launch_conv2d(ctx, pairs[2], Cf, sz64, T, sz32, nullptr, 0, B, n, 1));
-    ORCA_TRY(launch_conv2d(ctx, pairs[3], T, sz32, Df, sz64, Cf, sz64, B, n, 1));
-  }
-  float* cur = Df;
-  float* oth = Cf;
-  for (int i = 1; i < npairs; ++i) {
-    const ConvLayer* p = pairs + 4 * i;
-    ORCA_TRY(launch_conv2d(ctx, p[0], cur, sz64, T, sz32, nullptr, 0, B, n, 0));
-    ORCA_TRY(launch_conv2d(ctx, p[1], T, sz32, oth, sz64, cur, sz64, B, n, 0));   // oth = lm(cur)+cur
-    ORCA_TRY(launch_conv2d(ctx, p[2], oth, sz64, T, sz32, nullptr, 0, B, n, 1));
-    ORCA_TRY(launch_conv2d(ctx, p[3], T, sz32, cur, sz64, oth, sz64, B, n, 1));   // cur = m(oth)+oth
-  }
-  return launch_final(ctx, net, cur, sz64, out, B, n, accumulate);
+    return ORCA_OK;
+  };
+  const ConvLayer* pairs = is1m ? L : L + 8;
+  auto block = [&](int i, const M& cur, const M& oth) -> int { return residual_block(conv, pairs + 4 * i, cur, oth, T); };
+  M cur;
+  ORCA_TRY(decoder_chain(net, (bool)y, IN, A, Bf, Cf, Df, T, conv, block, &cur));
+  const FinalArgs fa = final_args(net, cur.p, cur.bs, out, n, accumulate);
+  hipLaunchKernelGGL(final_sym_kernel, dim3((unsigned)n, (unsigned)B), dim3(256), 0, s, fa);
+  LAUNCHCHECK("final_sym_kernel");
+  return ORCA_OK;
 }
 
 extern "C" int orca_decoder_forward(orca_ctx* ctx, orca_net* net, const float* x, int64_t sx_b, int64_t sx_c, int64_t sx_l,

@@ -183,3 +183,7 @@ int launch_conv2d(orca_ctx* ctx, const ConvLayer& L, const float* x, long x_bs, 
 // dilated 3x3 conv on M16 maps; mode 0 = f16x2, 1 = bf16, 2 = f16 (see the definition)
 int launch_conv2d_m16(orca_ctx* ctx, const ConvLayer& L, const f32x4* x, long x_bs, int x_oct, f32x4* y, long y_bs, int y_oct, const f32x4* r, long r_bs, int B,
                       int n, int relu, int mode, int chunk0 = 0, int nchunks_ = 0, const float* tab = nullptr, long tab_bs = 0);
+// nblk whole residual blocks of dilations d, 2 d (, 4 d) out of 16, 32, 64 in ONE launch, in place on the M16 maps cur (conv2d_dblock.h); p: their
+// 4 nblk layers; nblk > 1: f16x2 only.  Instantiated for <NS, DT> = <2, 1> (f16x2), <1, 0> (bf16), <1, 1> (f16)
+template <int NS, int DT>
+int launch_dblocks(orca_ctx* ctx, f32x4* cur, long bs, int B, int n, const ConvLayer* p, int nblk);

@@ -4,7 +4,6 @@
 
 #include "conv_p16.h"        // nlc <-> P16 / B16 conversions
 #include "conv2d_m16.h"      // nchw <-> M16 conversions
-#include "conv2d_dblock.h"
 #include "misc_kernels.h"
 
 // ---------------------------------------------------------------------------
@@ -172,13 +171,7 @@ static int conv2d_dblock_test(orca_ctx* ctx, const ConvLayer* L, const float* x,
   hipStream_t s = ctx->stream;
   for (int b = 0; b < B; ++b)
     hipLaunchKernelGGL((nchw_to_m16_kernel<NS, DT>), dim3((unsigned)n), dim3(ORCA_LDW), 0, s, x + (size_t)b * 64 * n * n, 64, n, cur + b * sz64, 8);
-  DBlockArgs da;
-  da.cur = cur; da.bs = (long)sz64; da.H = n; da.W = n; da.dil = L[0].dil; da.flag = ctx->d_flag;
-  for (int k = 0; k < 4; ++k) {
-    da.w[k] = DT == 0 ? L[k].d_wb16p : L[k].d_wf16;
-    da.bias[k] = L[k].d_bias;
-  }
-  hipLaunchKernelGGL((conv2d_dblock_kernel<NS, DT>), dim3(256, (unsigned)B), dim3(512), 0, s, da);
+  ORCA_TRY((launch_dblocks<NS, DT>(ctx, cur, (long)sz64, B, n, L, 1)));
   for (int b = 0; b < B; ++b)
     hipLaunchKernelGGL((m16_to_nchw_kernel<NS, DT>), dim3((unsigned)n), dim3(ORCA_LDW), 0, s, cur + b * sz64, 64, n, y + (size_t)b * 64 * n * n);
   LAUNCHCHECK("conv2d_dblock test path");
@@ -244,22 +237,12 @@ extern "C" int orca_conv2d_dblock_run_forward(orca_ctx* ctx, const orca_conv_des
     hipStream_t s = ctx->stream;
     for (int b = 0; b < B; ++b)
       hipLaunchKernelGGL((nchw_to_m16_kernel<2, 1>), dim3((unsigned)n), dim3(ORCA_LDW), 0, s, x + (size_t)b * 64 * n * n, 64, n, cur + b * sz64, 8);
-    if (fused) {
-      DBlockRunArgs ra{};
-      ra.cur = cur; ra.bs = (long)sz64; ra.H = n; ra.W = n; ra.dil0 = d0; ra.nblk = nblk; ra.flag = ctx->d_flag;
-      for (int k = 0; k < 4 * nblk; ++k) { ra.w[k] = L[k].d_wf16; ra.bias[k] = L[k].d_bias; }
-      hipLaunchKernelGGL((conv2d_dblock_run_kernel<2, 1>), dim3(256, (unsigned)B), dim3(512), 0, s, ra);
-    } else {
-      for (int blk = 0; blk < nblk; ++blk) {
-        DBlockArgs da;
-        da.cur = cur; da.bs = (long)sz64; da.H = n; da.W = n; da.dil = d0 << blk; da.flag = ctx->d_flag;
-        for (int k = 0; k < 4; ++k) { da.w[k] = L[4 * blk + k].d_wf16; da.bias[k] = L[4 * blk + k].d_bias; }
-        hipLaunchKernelGGL((conv2d_dblock_kernel<2, 1>), dim3(256, (unsigned)B), dim3(512), 0, s, da);
-      }
-    }
+    if (fused) rc = launch_dblocks<2, 1>(ctx, cur, (long)sz64, B, n, L, nblk);
+    else
+      for (int blk = 0; blk < nblk && rc == ORCA_OK; ++blk) rc = launch_dblocks<2, 1>(ctx, cur, (long)sz64, B, n, L + 4 * blk, 1);
     for (int b = 0; b < B; ++b)
       hipLaunchKernelGGL((m16_to_nchw_kernel<2, 1>), dim3((unsigned)n), dim3(ORCA_LDW), 0, s, cur + b * sz64, 64, n, y + (size_t)b * 64 * n * n);
-    if (hipGetLastError() != hipSuccess) rc = fail(ORCA_EHIP, "conv2d_dblock_run test path: launch failed");
+    if (rc == ORCA_OK && hipGetLastError() != hipSuccess) rc = fail(ORCA_EHIP, "conv2d_dblock_run test path: launch failed");
   }
   (void)hipStreamSynchronize(ctx->stream);
   for (int k = 0; k < made; ++k) free_layer(L[k]);

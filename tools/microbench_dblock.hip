@@ -1,5 +1,6 @@
 // Ablation micro-benchmark of conv2d_dblock_kernel (one Decoder residual block per launch) and, with DBLOCK_RUN=1, of conv2d_dblock_run_kernel (a run of
-// blocks 16, 32, 64 per launch) against the chain of per-block launches.
+// blocks 16, 32, 64 per launch) against the chain of per-block launches.  DBLOCK_BLOCKS=1: only the per-block launches of the three 16-bit modes;
+// DBLOCK_V1_ABL=1 / DBLOCK_V2_ABL=1: the ablation ladders of the block kernel / of tools/parked/conv2d_dblock2.h.
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -w -I orca_amd/csrc -I include -I tools tools/microbench_dblock.hip -o tools/microbench_dblock
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -47,7 +48,7 @@ static void same(DBlockArgs a, int B, const std::vector<unsigned short>& h, size
 }
 // ---- a run of blocks 16, 32, 64 in one launch (conv2d_dblock_run_kernel) against the chain of three per-block launches (DBLOCK_RUN=1) ----
 template <int ABL>
-static float run_fused(DBlockRunArgs ra, int B, const char* what) {
+static float run_fused(DBlockArgs ra, int B, const char* what) {
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   float best = 1e9;
   for (int r = 0; r < 6; ++r) {
@@ -56,7 +57,7 @@ static float run_fused(DBlockRunArgs ra, int B, const char* what) {
     hipEventRecord(e1, 0); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1); if (r > 0 && ms < best) best = ms;
   }
-  printf("run d0=%d nblk=%d B=%d ABL=%d (%s): %.1f us per run  [%s]\n", ra.dil0, ra.nblk, B, ABL, what, best * 100.f, hipGetErrorString(hipGetLastError()));
+  printf("run d0=%d nblk=%d B=%d ABL=%d (%s): %.1f us per run  [%s]\n", ra.dil, ra.nblk, B, ABL, what, best * 100.f, hipGetErrorString(hipGetLastError()));
   return best * 100.f;
 }
 static void launch_chain(DBlockArgs a, int nblk, int B) {
@@ -76,7 +77,7 @@ static float run_chain(DBlockArgs a, int nblk, int B) {
   return best * 100.f;
 }
 // the chain and the run from the same input: the maps must be bit-identical
-static void same_run(DBlockArgs a, DBlockRunArgs ra, int B, const std::vector<unsigned short>& h, size_t map_units) {
+static void same_run(DBlockArgs a, DBlockArgs ra, int B, const std::vector<unsigned short>& h, size_t map_units) {
   const size_t bytes = map_units * 16 * B;
   std::vector<unsigned short> o1(bytes / 2), o2(bytes / 2);
   hipMemcpy(a.cur, h.data(), bytes, hipMemcpyHostToDevice);
@@ -87,7 +88,7 @@ static void same_run(DBlockArgs a, DBlockRunArgs ra, int B, const std::vector<un
   hipMemcpy(o2.data(), a.cur, bytes, hipMemcpyDeviceToHost);
   size_t diff = 0, nz = 0;
   for (size_t i = 0; i < o1.size(); ++i) { diff += o1[i] != o2[i]; nz += o1[i] != 0; }
-  printf("same? run d0=%d nblk=%d B=%d: %zu of %zu halfwords differ (%zu nonzero)  [%s]\n", ra.dil0, ra.nblk, B, diff, o1.size(), nz, hipGetErrorString(hipGetLastError()));
+  printf("same? run d0=%d nblk=%d B=%d: %zu of %zu halfwords differ (%zu nonzero)  [%s]\n", ra.dil, ra.nblk, B, diff, o1.size(), nz, hipGetErrorString(hipGetLastError()));
   hipMemcpy(a.cur, h.data(), bytes, hipMemcpyHostToDevice);
 }
 int main() {
@@ -108,8 +109,13 @@ int main() {
   DBlockArgs a{}; a.cur = cur; a.bs = map; a.H = n; a.W = n; a.flag = nullptr;
   for (int k = 0; k < 4; ++k) { a.w[k] = w[k]; a.bias[k] = b[k]; }
   a.bs = map;
+  if (getenv("DBLOCK_BLOCKS")) {   // the per-block launches of the three 16-bit modes: f16x2 at B = 2, f16 and bf16 at B = 8
+    for (int rep = 0; rep < 6; ++rep)   // the first repetition warms up (clocks, L2): the figures settle from the second on
+      for (int d : {16, 32, 64}) { a.dil = d; run<2, 1, 0>(a, 2, "f16x2"); run<1, 1, 0>(a, 8, "f16"); run<1, 0, 0>(a, 8, "bf16"); }
+    return 0;
+  }
   if (getenv("DBLOCK_RUN")) {
-    DBlockRunArgs ra{}; ra.cur = cur; ra.bs = map; ra.H = n; ra.W = n; ra.flag = nullptr;
+    DBlockArgs ra{}; ra.cur = cur; ra.bs = map; ra.H = n; ra.W = n; ra.flag = nullptr;
     for (int k = 0; k < 12; ++k) { ra.w[k] = w[k & 3]; ra.bias[k] = b[k & 3]; }
     // the pad pixels (columns n .. 255) must hold zero as every Decoder kernel leaves them: the run kernel keeps 0 for the grid pixels outside the
     // map where the per-block launches gather pad pixel 255 of row 0 again
@@ -117,11 +123,11 @@ int main() {
     for (size_t u = 0; u < hz.size() / 8; ++u)
       if ((int)(u & 255) >= n) for (int e = 0; e < 8; ++e) hz[u * 8 + e] = 0;
     for (int d0 : {16, 32}) {
-      a.dil = d0; ra.dil0 = d0; ra.nblk = d0 == 16 ? 3 : 2;
+      a.dil = d0; ra.dil = d0; ra.nblk = d0 == 16 ? 3 : 2;
       same_run(a, ra, 2, hz, map);
     }
     hipMemcpy(cur, h.data(), h.size() * 2, hipMemcpyHostToDevice);
-    a.dil = 16; ra.dil0 = 16; ra.nblk = 3;
+    a.dil = 16; ra.dil = 16; ra.nblk = 3;
     for (int rep = 0; rep < 3; ++rep)
       for (int B : {1, 2, 4, 8}) {
         const float tc = run_chain(a, 3, B), tf = run_fused<0>(ra, B, "full");
