@@ -1165,6 +1165,7 @@ struct EdgeLayerArgs {
   float* sout;                 // scratch [2 * half][128] (may be NULL for the last layer)
   f32x4* y; long y_plen; int out_fmt;   // planar tensor receiving the outermost store_half positions per end (NULL: none);
                                         // out_fmt 0: P16, 1: B16, 2: fp32 channel-major [cout][y_plen] (the exact-fp32 mode; y_plen = row stride in floats), 3: fp32 channel-last [n][cout]
+  unsigned* flag;              // fp16-range guard of the P16 stores (out_fmt 0): the exact end values are not the composed conv's, whose guard saw only its own
 };
 
 template <int KC>
@@ -1220,6 +1221,7 @@ static __global__ __launch_bounds__(512) void lconv_edge_layer_kernel(EdgeLayerA
       } else if (a.out_fmt == 0) {
         const _Float16 h = (_Float16)acc;
         const _Float16 l = (_Float16)(acc - (float)h);
+        if (!(fabsf(acc) <= 65504.f) && a.flag) *a.flag = 1u;      // (a NaN raises it too)
         reinterpret_cast<_Float16*>(a.y + (long)(co >> 3) * 2 * a.y_plen + P16_GUARD + p)[co & 7] = h;
         reinterpret_cast<_Float16*>(a.y + ((long)(co >> 3) * 2 + 1) * a.y_plen + P16_GUARD + p)[co & 7] = l;
       } else {
@@ -1301,6 +1303,7 @@ struct EdgePoolArgs {
   const float* sl; int half_l;     // lout1 at the first / last half_l positions            [2 half_l][128]
   long n; int cout;
   f32x4* y; long y_plen; int out_fmt;
+  unsigned* flag;                  // fp16-range guard of the P16 stores (out_fmt 0), as in EdgeLayerArgs
 };
 static __global__ __launch_bounds__(128) void lconv_edge_pool_kernel(EdgePoolArgs a) {
   const long nw = a.n / 4;
@@ -1323,6 +1326,7 @@ static __global__ __launch_bounds__(128) void lconv_edge_pool_kernel(EdgePoolArg
   if (a.out_fmt == 0) {
     const _Float16 h = (_Float16)m;
     const _Float16 l = (_Float16)(m - (float)h);
+    if (!(fabsf(m) <= 65504.f) && a.flag) *a.flag = 1u;
     reinterpret_cast<_Float16*>(a.y + (long)(co >> 3) * 2 * a.y_plen + P16_GUARD + w)[co & 7] = h;
     reinterpret_cast<_Float16*>(a.y + ((long)(co >> 3) * 2 + 1) * a.y_plen + P16_GUARD + w)[co & 7] = l;
   } else {

@@ -398,7 +398,7 @@ static int launch_edge_chain(orca_ctx* ctx, const ConvLayer* Ls, int depth, int 
     a.sin = l > 0 ? ctx->d_edge + (l - 1) * ORCA_EDGE_SLAB : nullptr;
     a.sout = ctx->d_edge + l * ORCA_EDGE_SLAB;
     float* const y = l == 1 ? lo : l == 2 ? t : nullptr;
-    a.y = reinterpret_cast<f32x4*>(y); a.y_plen = fmt == 2 ? ld_f32 : p16_plen(n); a.out_fmt = fmt;
+    a.y = reinterpret_cast<f32x4*>(y); a.y_plen = fmt == 2 ? ld_f32 : p16_plen(n); a.out_fmt = fmt; a.flag = ctx->d_flag;
     a.store_half = !y ? 0 : l == 1 ? 4 : 8;
     hipLaunchKernelGGL(lconv_edge_layer_kernel, dim3((unsigned)(2 * a.half)), dim3(512), 0, ctx->stream, a);
   }
@@ -549,7 +549,7 @@ static int enc_stage1_last_from_bases(orca_ctx* ctx, const orca_net* net, const 
   ORCA_TRY(launch_p16_zero_pads(ctx, buf[kS], Lb.cout, n / 4, r.fmt));
   EdgePoolArgs ep{};
   ep.sc = ctx->d_edge + 3 * ORCA_EDGE_SLAB; ep.half_c = 8; ep.sl = ctx->d_edge + 1 * ORCA_EDGE_SLAB; ep.half_l = 16; ep.n = n; ep.cout = Lb.cout;
-  ep.y = reinterpret_cast<f32x4*>(buf[kS]); ep.y_plen = p16_plen(n / 4); ep.out_fmt = r.fmt;
+  ep.y = reinterpret_cast<f32x4*>(buf[kS]); ep.y_plen = p16_plen(n / 4); ep.out_fmt = r.fmt; ep.flag = ctx->d_flag;
   if (n / 4 > 0) hipLaunchKernelGGL(lconv_edge_pool_kernel, dim3(3), dim3(128), 0, ctx->stream, ep);
   LAUNCHCHECK("lconv_edge_pool_kernel");
   return ORCA_OK;
