@@ -315,6 +315,22 @@ int orca_screen_gather_rows(orca_ctx* ctx, const float* ref, int64_t n5, const f
                             const int64_t* entry_rows, const int64_t* entry_rows_host, int P, const int64_t* segments, const int64_t* segments_host,
                             int64_t n_segments, const int64_t* seg_off, const int64_t* seg_off_host, int B, float* out);
 
+/* Aligned scores (screen.bin_map): behind an unbalanced insertion or deletion the alt map is displaced against ref, so alt bin i is compared with the
+ * reference bin it stands for.  `bin_map` (B x n int32, n <= 256; device copy for the kernel, host copy checked here, as above): bin_map[b][i] = the
+ * reference bin of alt bin i of map b, or -1 for none (inserted bases, refill); any value outside -1 .. n - 1 is refused (and reads as -1 in the kernel).
+ * With M_b = {i : bin_map[b][i] >= 0}, c = |M_b| and d(i, j) = |alt[b][i][j] - ref[map i][map j]|, every result indexed by ALT bin:
+ *   orca_screen_aligned_scores         profile[b][i] = sum_{j in M} d(i, j) / c (NaN for i outside M), mean[b] = sum_{i, j in M} d / c^2, amax[b] = max over
+ *                                      M x M; all NaN when c = 0.  Differences and sums in fp64; a NaN at a mapped pair gives NaN, one at an unmapped
+ *                                      pair is never read.  A map's results are bit for bit the same whatever B and its place in the batch
+ *   orca_screen_aligned_region_scores  `rects` as for orca_screen_region_scores but in REFERENCE bins: rectangle k takes the alt pairs (i, j) with
+ *                                      map i in [i0, i1) and map j in [j0, j1); mean_signed[b][k] = mean of alt[i][j] - ref[map i][map j], mean_abs[b][k]
+ *                                      = mean of its absolute value; both NaN when no pair qualifies (the region was deleted) */
+int orca_screen_aligned_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* bin_map,
+                               const int32_t* bin_map_host, float* profile, float* mean, float* amax);
+int orca_screen_aligned_region_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* bin_map,
+                                      const int32_t* bin_map_host, const int32_t* rects, const int32_t* rects_host, int K, float* mean_signed,
+                                      float* mean_abs);
+
 /* Number of 4 kb bins Encoder emits for an L-bp input (floor through the
  * 4,4,5,5,5,2 pooling chain). */
 int64_t orca_encoder_num_bins(int64_t L);

@@ -118,6 +118,50 @@ extern "C" int orca_screen_region_scores(orca_ctx* ctx, const float* alt, int64_
   return ORCA_OK;
 }
 
+// aligned scores: the bin map (B x n int32, -1 .. n - 1) comes twice like every small table; `what` names the entry point in the message
+static int check_bin_map(const char* what, const int32_t* bin_map_host, int B, int n) {
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < n; ++i) {
+      const int32_t m = bin_map_host[(size_t)b * n + i];
+      if (m < -1 || m >= n) return fail(ORCA_EINVAL, "%s: map %d sends alt bin %d to reference bin %d, outside -1 .. %d", what, b, i, m, n - 1);
+    }
+  return ORCA_OK;
+}
+
+extern "C" int orca_screen_aligned_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* bin_map,
+                                          const int32_t* bin_map_host, float* profile, float* mean, float* amax) {
+  if (!ctx || !alt || !ref || !bin_map || !bin_map_host || !profile || !mean || !amax) return fail(ORCA_EINVAL, "orca_screen_aligned_scores: NULL argument");
+  if (B < 0 || n <= 0 || n > SCREEN_ALIGNED_MAX_BINS || map_bs < 0)
+    return fail(ORCA_EINVAL, "orca_screen_aligned_scores: %d maps of %d bins (1..%d), batch stride %ld", B, n, SCREEN_ALIGNED_MAX_BINS, (long)map_bs);
+  if (int rc = check_bin_map("orca_screen_aligned_scores", bin_map_host, B, n)) return rc;
+  if (B == 0) return ORCA_OK;
+  HIPCHECK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(screen_aligned_scores_kernel, dim3((unsigned)B), dim3(512), 0, ctx->stream, alt, (long)map_bs, ref, n, bin_map, profile, mean, amax);
+  LAUNCHCHECK("screen_aligned_scores_kernel");
+  return ORCA_OK;
+}
+
+extern "C" int orca_screen_aligned_region_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* bin_map,
+                                                 const int32_t* bin_map_host, const int32_t* rects, const int32_t* rects_host, int K, float* mean_signed,
+                                                 float* mean_abs) {
+  if (!ctx || !alt || !ref || !bin_map || !bin_map_host || !rects || !rects_host || !mean_signed || !mean_abs)
+    return fail(ORCA_EINVAL, "orca_screen_aligned_region_scores: NULL argument");
+  if (B < 0 || n <= 0 || n > SCREEN_ALIGNED_MAX_BINS || K <= 0 || K > 64 || map_bs < 0)
+    return fail(ORCA_EINVAL, "orca_screen_aligned_region_scores: %d maps of %d bins (1..%d), %d rectangles (1..64)", B, n, SCREEN_ALIGNED_MAX_BINS, K);
+  for (int k = 0; k < K; ++k) {
+    const int32_t* r = rects_host + 4 * k;
+    if (r[0] < 0 || r[0] >= r[1] || r[1] > n || r[2] < 0 || r[2] >= r[3] || r[3] > n)
+      return fail(ORCA_EINVAL, "orca_screen_aligned_region_scores: rectangle %d = rows [%d, %d) x columns [%d, %d) outside [0, %d) or empty", k, r[0], r[1], r[2], r[3], n);
+  }
+  if (int rc = check_bin_map("orca_screen_aligned_region_scores", bin_map_host, B, n)) return rc;
+  if (B == 0) return ORCA_OK;
+  HIPCHECK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(screen_aligned_region_scores_kernel, dim3((unsigned)B, (unsigned)K), dim3(256), 0, ctx->stream, alt, (long)map_bs, ref, n, bin_map, rects, K,
+                     mean_signed, mean_abs);
+  LAUNCHCHECK("screen_aligned_region_scores_kernel");
+  return ORCA_OK;
+}
+
 // insertions and deletions: the edited bases of a batch from piece lists over the context (window + right flank), and the row images from the reference
 // rows, the recomputed rows and the stage-4 phase entries.  Tables as above: a device copy for the kernel, a host copy checked here before any launch.
 extern "C" int orca_screen_assemble_codes(orca_ctx* ctx, const uint8_t* context, int64_t C, const int64_t* table, const int64_t* table_host, int n_snippets,

@@ -1,5 +1,5 @@
 // screen.h - the small kernels of the 1 Mb in-silico mutagenesis screen (orca_amd/screen.py): edited snippets straight from the window's
-// codes, the per-edit stage-5 row images, the [B][n][128] -> [B][128][n] hand-over of batched stages 5-7, and the map scores.
+// codes, the per-edit stage-5 row images, the [B][n][128] -> [B][128][n] hand-over of batched stages 5-7, and the map scores (bin with bin, and on aligned bins).
 // All of them are HBM-bound and tiny next to the Decoder_1m they feed; each is ONE launch for a whole batch of edits.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -336,4 +336,144 @@ static __global__ void screen_gather_rows_kernel(const f32x4* __restrict__ ref, 
     }
   }
   out[u] = v;
+}
+
+// ---- aligned scores (screen.bin_map): alt bin i stands for reference bin map[i], or for none (-1) -------------------------------------------------------
+// bin map (int32 per alt bin, [B][n]; include/orca_hip.h: orca_screen_aligned_scores): values -1 .. n - 1 - the host entry point checks it; any other value
+// reads as -1 here.  Every result is indexed by ALT bin (two alt bins may stand for one reference bin).  At most SCREEN_ALIGNED_MAX_BINS bins: the map of a
+// workgroup's alt map lives in LDS.
+#define SCREEN_ALIGNED_MAX_BINS 256
+
+// map b's entries into LDS, clipped to -1 .. n - 1 (entries past n are -1); the caller synchronises
+static __device__ __forceinline__ int screen_load_bin_map(const int* __restrict__ map, int n, int* s_map) {
+  int m = -1;
+  if ((int)threadIdx.x < n) {
+    m = map[threadIdx.x];
+    m = (m >= 0 && m < n) ? m : -1;
+  }
+  if (threadIdx.x < SCREEN_ALIGNED_MAX_BINS) s_map[threadIdx.x] = m;
+  return m;
+}
+
+// screen_scores_kernel over the mapped bins M = {i : map[i] >= 0}, c = |M|: d(i, j) = |alt[i][j] - ref[map i][map j]| for i, j in M (difference in fp64);
+// profile[b][i] = sum_j d / c (NaN for i outside M), mean[b] = sum_ij d / c^2, amax[b] = max d; all NaN when c = 0.  One workgroup per map, one wave
+// per alt row at a time: the alt row is read along its columns, the reference row `map i` at columns `map j` (near-contiguous runs, the map ascends).
+// Only mapped pairs are read, so a NaN elsewhere does not show; one at a mapped pair propagates as in screen_scores_kernel.  The order of every sum is
+// fixed by (n, the map) alone: a map's results do not depend on B or on its place in the batch.
+static __global__ void __launch_bounds__(512) screen_aligned_scores_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, int n,
+                                                                           const int* __restrict__ bin_map, float* __restrict__ profile,
+                                                                           float* __restrict__ mean, float* __restrict__ amax) {
+  __shared__ int s_map[SCREEN_ALIGNED_MAX_BINS];
+  __shared__ double s_sum[8], s_max[8];
+  __shared__ int s_nan[8];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  n = n > SCREEN_ALIGNED_MAX_BINS ? SCREEN_ALIGNED_MAX_BINS : n;
+  const int mine = screen_load_bin_map(bin_map + (long)b * n, n, s_map);
+  const int c = __syncthreads_count(mine >= 0);
+  const float* a = alt + (long)b * map_bs;
+  const float qnan = __int_as_float(0x7fc00000);
+  double wsum = 0.0, wmax = 0.0;
+  bool wnan = false;
+  for (int i = wv; i < n; i += 8) {
+    const int mi = s_map[i];                         // wave-uniform
+    if (mi < 0) {
+      if (lane == 0) profile[(long)b * n + i] = qnan;
+      continue;
+    }
+    double rs = 0.0;
+    for (int j = lane; j < n; j += 64) {
+      const int mj = s_map[j];
+      if (mj < 0) continue;
+      const double d = fabs((double)a[(long)i * n + j] - (double)ref[(long)mi * n + mj]);
+      rs += d;
+      wnan |= d != d;
+      wmax = fmax(wmax, d);
+    }
+    for (int o = 32; o > 0; o >>= 1) rs += __shfl_xor(rs, o, 64);
+    if (lane == 0) profile[(long)b * n + i] = (float)(rs / (double)c);
+    wsum += rs;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    wmax = fmax(wmax, __shfl_xor(wmax, o, 64));
+    wnan |= __shfl_xor((int)wnan, o, 64) != 0;
+  }
+  if (lane == 0) {
+    s_sum[wv] = wsum;
+    s_max[wv] = wmax;
+    s_nan[wv] = wnan ? 1 : 0;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0, m = 0.0;
+    bool nan = c == 0;
+    for (int k = 0; k < 8; ++k) {
+      t += s_sum[k];
+      nan |= s_nan[k] != 0;
+      m = fmax(m, s_max[k]);
+    }
+    mean[b] = nan ? qnan : (float)(t / ((double)c * (double)c));
+    amax[b] = nan ? qnan : (float)m;
+  }
+}
+
+// the bins i (ascending) with lo <= s_map[i] < hi into list[]; one wave, returns their number (the same in every lane)
+static __device__ __forceinline__ int screen_bins_in(const int* s_map, int n, int lo, int hi, int* list, int lane) {
+  int cnt = 0;
+  for (int i0 = 0; i0 < n; i0 += 64) {
+    const int i = i0 + lane;
+    const bool in = i < n && s_map[i] >= lo && s_map[i] < hi;
+    const unsigned long long mask = __ballot(in);
+    if (in) list[cnt + __popcll(mask & ((1ull << lane) - 1ull))] = i;
+    cnt += __popcll(mask);
+  }
+  return cnt;
+}
+
+// screen_region_scores_kernel with the rectangles in REFERENCE bins: rectangle k = (i0, i1, j0, j1) takes the alt pairs (i, j) with map i in [i0, i1) and
+// map j in [j0, j1); signed[b][k] = mean of alt[i][j] - ref[map i][map j] over them, absm[b][k] = mean of its absolute value, both NaN when no pair
+// qualifies (the region was deleted).  One workgroup per (map, rectangle): wave 0 lists the qualifying alt rows, wave 1 the columns (ascending, in LDS),
+// then all four waves walk the pairs.  fp64 differences and sums in a fixed order, as there.
+static __global__ void __launch_bounds__(256) screen_aligned_region_scores_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, int n,
+                                                                                  const int* __restrict__ bin_map, const int* __restrict__ rects, int K,
+                                                                                  float* __restrict__ signed_out, float* __restrict__ abs_out) {
+  __shared__ int s_map[SCREEN_ALIGNED_MAX_BINS], s_rows[SCREEN_ALIGNED_MAX_BINS], s_cols[SCREEN_ALIGNED_MAX_BINS];
+  __shared__ int s_cnt[2];
+  __shared__ double s_sum[4], s_abs[4];
+  const int b = blockIdx.x, k = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  n = n > SCREEN_ALIGNED_MAX_BINS ? SCREEN_ALIGNED_MAX_BINS : n;
+  int i0 = rects[4 * k], i1 = rects[4 * k + 1], j0 = rects[4 * k + 2], j1 = rects[4 * k + 3];
+  i0 = i0 < 0 ? 0 : i0; j0 = j0 < 0 ? 0 : j0;
+  i1 = i1 > n ? n : i1; j1 = j1 > n ? n : j1;
+  screen_load_bin_map(bin_map + (long)b * n, n, s_map);
+  __syncthreads();
+  if (wv == 0) {
+    const int h = screen_bins_in(s_map, n, i0, i1, s_rows, lane);
+    if (lane == 0) s_cnt[0] = h;
+  } else if (wv == 1) {
+    const int w = screen_bins_in(s_map, n, j0, j1, s_cols, lane);
+    if (lane == 0) s_cnt[1] = w;
+  }
+  __syncthreads();
+  const int h = s_cnt[0], w = s_cnt[1];
+  const float* a = alt + (long)b * map_bs;
+  double sum = 0.0, asum = 0.0;
+  for (int e = threadIdx.x; e < h * w; e += 256) {
+    const int i = s_rows[e / w], j = s_cols[e % w];
+    const double d = (double)a[(long)i * n + j] - (double)ref[(long)s_map[i] * n + s_map[j]];
+    sum += d;
+    asum += fabs(d);
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    sum += __shfl_xor(sum, o, 64);
+    asum += __shfl_xor(asum, o, 64);
+  }
+  if (lane == 0) { s_sum[wv] = sum; s_abs[wv] = asum; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double cnt = (double)h * (double)w;
+    const double t = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]), ta = (s_abs[0] + s_abs[1]) + (s_abs[2] + s_abs[3]);
+    const float qnan = __int_as_float(0x7fc00000);
+    signed_out[(long)b * K + k] = h * w > 0 ? (float)(t / cnt) : qnan;
+    abs_out[(long)b * K + k] = h * w > 0 ? (float)(ta / cnt) : qnan;
+  }
 }

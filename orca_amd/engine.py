@@ -787,6 +787,56 @@ def screen_region_scores(ctx, alt, ref, rects_host):
     return sg, ab
 
 
+# aligned scores (orca_screen_aligned_scores, orca_screen_aligned_region_scores): the bin map is one more small table
+SCREEN_ALIGNED_MAX_BINS = 256
+
+
+def _aligned_args(alt, ref, bin_map_host, bin_map):
+    alt, ref = _f32_cuda(alt, "alt"), _f32_cuda(ref, "ref").contiguous()
+    n = ref.shape[0]
+    if alt.dim() != 3 or ref.dim() != 2 or tuple(alt.shape[1:]) != (n, n) or alt.stride(2) != 1 or alt.stride(1) != n or tuple(ref.shape) != (n, n):
+        raise ValueError(f"alt [B,{n},{n}] with contiguous maps, ref [{n},{n}]")
+    m = _host_table(bin_map_host, np.int32, n, "bin map")
+    if m.shape[0] != alt.shape[0]:
+        raise ValueError(f"bin map: [{alt.shape[0]},{n}] int32, one row per alt map")
+    md = torch.from_numpy(m).to(alt.device) if bin_map is None else _on_device(bin_map, "bin_map", torch.int32)
+    if tuple(md.shape) != m.shape or md.device != alt.device:
+        raise ValueError("bin map: host and device copies differ in shape")
+    return alt, ref, m, md
+
+
+def screen_aligned_scores(ctx, alt, ref, bin_map_host, bin_map=None):
+    """alt [B, n, n] (any batch stride, rows contiguous) against ref [n, n] on aligned bins (orca_screen_aligned_scores): ``bin_map_host`` [B, n] int32
+    numpy, the reference bin of every alt bin or -1 (``bin_map``: its device copy, uploaded here when None).  (profile [B, n], mean [B], max [B]) of
+    |alt[i, j] - ref[map i, map j]| over the mapped bins, NaN where nothing is mapped."""
+    alt, ref, m, md = _aligned_args(alt, ref, bin_map_host, bin_map)
+    B, n = m.shape
+    profile = torch.empty((B, n), dtype=torch.float32, device=alt.device)
+    mean = torch.empty((B,), dtype=torch.float32, device=alt.device)
+    amax = torch.empty((B,), dtype=torch.float32, device=alt.device)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_aligned_scores(ctx.handle, _dev_p(alt), alt.stride(0), _p(ref), B, n, _dev_p(md), _np_p(m), _dev_p(profile), _dev_p(mean),
+                                                 _dev_p(amax)), "orca_screen_aligned_scores")
+    return profile, mean, amax
+
+
+def screen_aligned_region_scores(ctx, alt, ref, bin_map_host, rects_host, bin_map=None):
+    """`screen_region_scores` on aligned bins (orca_screen_aligned_region_scores): the K rectangles ``rects_host`` [K, 4] = (i0, i1, j0, j1) are in
+    REFERENCE bins, and rectangle k takes the alt pairs (i, j) with map i in [i0, i1) and map j in [j0, j1): (mean of alt[i, j] - ref[map i, map j]
+    [B, K], mean of its absolute value [B, K]), NaN where no pair qualifies."""
+    alt, ref, m, md = _aligned_args(alt, ref, bin_map_host, bin_map)
+    B, n = m.shape
+    r = _host_table(rects_host, np.int32, 4, "rectangles")
+    K = r.shape[0]
+    rd = torch.from_numpy(r).to(alt.device)
+    sg = torch.empty((B, K), dtype=torch.float32, device=alt.device)
+    ab = torch.empty((B, K), dtype=torch.float32, device=alt.device)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_aligned_region_scores(ctx.handle, _dev_p(alt), alt.stride(0), _p(ref), B, n, _dev_p(md), _np_p(m), _dev_p(rd), _np_p(r), K,
+                                                        _dev_p(sg), _dev_p(ab)), "orca_screen_aligned_region_scores")
+    return sg, ab
+
+
 def encoder_forward_2bit(net, two, nmask, start, L, reverse=False, bin_lo=0, bin_hi=0, chunk_bp=0, out=None):
     """Encoder on bases [start, start + L) of a chromosome stored as 2 bits per base + N mask in HBM (genome.TwoBitGenome planes): no
     unpacked window is made (orca_encoder_forward_2bit).  Returns [1,128,bins]."""

@@ -29,6 +29,11 @@ the 80-base grid, so their rows are the MaxPool1d(5) of stage 4's output on the 
 (`sv.Stage4Cache`), or plainly the reference's rows s / 400 further on when 400 divides s; only the junctions and the alt window's right
 end go through the front again.  A batch that holds such an item takes its bases from piece lists (orca_screen_assemble_codes) and its rows
 from a table of sources (orca_screen_gather_rows); `plan_batch` states the rule.
+
+Behind an unbalanced indel the alt map is displaced against the reference map, and the bin-with-bin scores hold that displacement.
+``screen_1m(..., aligned=True)`` adds scores on ALIGNED bins: `bin_map` says which reference bin an alt bin stands for, and alt pair (i, j) is
+compared with reference pair (map i, map j) (orca_screen_aligned_scores, orca_screen_aligned_region_scores).  `deletion_scan` and `tandem_dup`
+generate the large edits this is for, and ``flank_bp`` reads enough genome behind the window to refill them.
 """
 from dataclasses import dataclass, field
 from typing import Optional
@@ -331,6 +336,70 @@ def indel(codes, pos, ref, alt, name=None):
         return rest
     sub = Edit("sub", pos, m, a[:m])
     return sub if rest is None else EditSet([sub, rest], name)
+
+
+def deletion_scan(width, step, start, end):
+    """Deletions of ``width`` bases every ``step`` bases, each inside [start, end): ``Edit("del", p, width)`` for p = max(start, 1), p + step, ...
+    (a deletion starts at base 1 or later: the alt window keeps the window's first base).  Score them with ``screen_1m(..., aligned=True)``."""
+    if width <= 0 or step <= 0:
+        raise ValueError("deletion_scan: width and step must be positive")
+    return [Edit("del", p, width) for p in range(max(int(start), 1), int(end) - width + 1, step)]
+
+
+def tandem_dup(codes, pos, length):
+    """A tandem duplication of window bases [pos, pos + length) as the insertion of their copy right behind them:
+    ``Edit("ins", pos + length, codes[pos: pos + length])``.  In `bin_map` the inserted copy stands for no reference bin (-1)."""
+    c = np.asarray(codes.cpu() if isinstance(codes, torch.Tensor) else codes)
+    pos, length = int(pos), int(length)
+    if length <= 0 or not 0 <= pos <= pos + length <= c.size:
+        raise ValueError(f"duplication of [{pos}, {pos + length}): non-empty and inside the window of {c.size} bases")
+    return Edit("ins", pos + length, c[pos: pos + length])
+
+
+# ---- aligned bins ---------------------------------------------------------------------------------------------------------------------------
+BIN_BP = 4000
+
+
+def bin_map(item, L, F=0):
+    """The reference bin every bin of the item's alt map stands for: np.int32 [n], n = L // 4000, -1 for none.  An alt bin is placed by its
+    midpoint base a = 4000 i + 2000.  Walking the item's members in their sorted order with cum = bases inserted - removed so far, a surviving
+    reference base p sits at alt position p + cum.  If a is a surviving base of the window (p < L), ``bin_map[i] = p // 4000``; ``sub``, ``mask``
+    and ``inv`` spans stand where they stood (p = a - cum, not mirrored for ``inv``).  -1: a is an inserted base, was refilled from the flank
+    (p >= L; ``F``, the flank's length, 0 <= F <= L, therefore changes nothing: the refill stands for no reference bin whatever fills it) or is
+    N fill beyond the context.
+
+    A length-preserving item maps every bin to itself, and a shift below 2 000 bases leaves the map the identity wherever no midpoint crosses a
+    bin edge.  All pieces are forward and in order, so the mapped values never decrease with i; next to an insertion two alt bins may share a
+    reference bin, which is why every aligned result is indexed by ALT bin.  A mapped bin's midpoint lies inside its reference bin by
+    construction; what remains is a misregistration below half a bin, inherent to a 4 kb map: behind a shift that is no multiple of 4 000 the
+    aligned score of an otherwise silent edit is not zero."""
+    members = members_of(item)
+    if L % BIN_BP or not 0 <= int(F) <= L:
+        raise ValueError(f"bin_map: a window of {L} bases (a multiple of {BIN_BP}) with a flank of {F} (0 .. {L})")
+    item.check(L)
+    mid = BIN_BP * np.arange(L // BIN_BP, dtype=np.int64) + BIN_BP // 2
+    out = np.full(mid.size, -1, dtype=np.int32)
+    p, cum = 0, 0
+    runs = []                                            # (first surviving base, one past the last, cum): alt [p0 + cum, p1 + cum)
+    for e in members:
+        if e.kind in LEN_KINDS:
+            runs.append((p, e.pos, cum))
+            cum += e.inserted - e.removed
+            p = e.end
+    runs.append((p, L, cum))
+    for p0, p1, s in runs:
+        m = (mid >= p0 + s) & (mid < p1 + s)
+        out[m] = (mid[m] - s) // BIN_BP
+    return out
+
+
+def _bin_maps(bin_map_, E, n):
+    m = np.asarray(bin_map_)
+    if m.ndim == 1:
+        m = np.repeat(m[None], E, axis=0)
+    if m.shape != (E, n) or not np.issubdtype(m.dtype, np.integer) or (m.size and (m.min() < -1 or m.max() >= n)):
+        raise ValueError(f"bin_map: [{E}, {n}] integers -1 .. {n - 1}")
+    return m.astype(np.int64)
 
 
 # ---- planning (pure; tests/test_screen_cpu.py checks it against the fp64 oracle) -----------------------------------------------------------
@@ -775,6 +844,42 @@ def region_scores_host(maps, ref_map, regions):
     return sg, ab
 
 
+def aligned_scores_host(maps, ref_map, bin_map):
+    """The aligned scores of `ScreenResult` from alt maps [E, n, n], the reference map [n, n] and the bin maps [E, n] (or one [n] for all; fp64 host
+    restatement of orca_screen_aligned_scores).  With M = the alt bins whose ``bin_map`` is >= 0, c = |M| and d[i, j] = |alt[i, j] - ref[map i,
+    map j]| for i, j in M: (aligned_profile [E, n], aligned_abs_mean [E], aligned_abs_max [E]) = (sum_j d[i, j] / c, NaN outside M;
+    sum_ij d / c^2; max d), all NaN for an item with c = 0."""
+    alt, ref = np.asarray(maps, dtype=np.float64), np.asarray(ref_map, dtype=np.float64)
+    E, n = alt.shape[0], ref.shape[0]
+    bm = _bin_maps(bin_map, E, n)
+    prof, mean, amax = np.full((E, n), np.nan), np.full(E, np.nan), np.full(E, np.nan)
+    for e in range(E):
+        M = np.flatnonzero(bm[e] >= 0)
+        if M.size:
+            r = bm[e, M]
+            d = np.abs(alt[e][np.ix_(M, M)] - ref[np.ix_(r, r)])
+            prof[e, M], mean[e], amax[e] = d.sum(axis=1) / M.size, d.sum() / M.size ** 2, d.max()
+    return prof, mean, amax
+
+
+def aligned_region_scores_host(maps, ref_map, bin_map, regions):
+    """The aligned region scores of `ScreenResult` (fp64 host restatement of orca_screen_aligned_region_scores): the rectangles are in REFERENCE
+    bins, and rectangle (i0, i1, j0, j1) takes the alt pairs (i, j) with map i in [i0, i1) and map j in [j0, j1).  (aligned_region [E, K],
+    aligned_region_abs [E, K]) = the means of alt[i, j] - ref[map i, map j] and of its absolute value over them, NaN where no pair qualifies."""
+    alt, ref = np.asarray(maps, dtype=np.float64), np.asarray(ref_map, dtype=np.float64)
+    E, n = alt.shape[0], ref.shape[0]
+    bm = _bin_maps(bin_map, E, n)
+    rects = check_regions(regions, n)
+    sg, ab = np.full((E, len(rects)), np.nan), np.full((E, len(rects)), np.nan)
+    for e in range(E):
+        for k, (i0, i1, j0, j1) in enumerate(rects):
+            rows, cols = np.flatnonzero((bm[e] >= i0) & (bm[e] < i1)), np.flatnonzero((bm[e] >= j0) & (bm[e] < j1))
+            if rows.size and cols.size:
+                d = alt[e][np.ix_(rows, cols)] - ref[np.ix_(bm[e, rows], bm[e, cols])]
+                sg[e, k], ab[e, k] = d.mean(), np.abs(d).mean()
+    return sg, ab
+
+
 @dataclass
 class ScreenResult:
     """Result of `screen_1m` (device tensors).  Maps are the model's output, the log observed / expected map of ``_Orca1M.forward`` (the
@@ -789,9 +894,20 @@ class ScreenResult:
       delta_region_abs [E, K]         mean of |alt - ref| over rectangle k (None without regions)
       shift            [E] int64      bases removed minus bases inserted by the item (0 without ``del`` / ``ins``).  The alt window is anchored at
                                       the window's first base, so what lies behind the item's last member sits ``shift`` bases (shift / 4000
-                                      bins) earlier in the alt map than in ``ref_map``: the scores compare bin with bin all the same, and behind
-                                      an unbalanced indel they therefore also hold that displacement
-    `scores_host` computes the three map scores from maps on the host, `region_scores_host` the two region scores."""
+                                      bins) earlier in the alt map than in ``ref_map``.  The ``delta_*`` scores above compare bin with bin all the
+                                      same, so behind an unbalanced indel they also hold that displacement; the ``aligned_*`` fields below do not
+    With ``aligned=True`` (None otherwise), all indexed by ALT bin; M = the alt bins of item e that stand for a reference bin, c = |M|,
+    d[i, j] = |alt map[i, j] - ref_map[map i, map j]| for i, j in M:
+      bin_map            [E, n] int32 the reference bin alt bin i stands for, -1 for none (`bin_map` states the rule)
+      aligned_bins       [E] int64    c, the number of mapped bins
+      aligned_profile    [E, n]       sum_{j in M} d[i, j] / c; NaN for i outside M
+      aligned_abs_mean   [E]          sum_{i, j in M} d / c^2 (NaN when c = 0)
+      aligned_abs_max    [E]          max over M x M (NaN when c = 0)
+      aligned_region     [E, K]       with ``regions``, read as REFERENCE bins: the mean of alt[i, j] - ref[map i, map j] (signed) over the alt
+                                      pairs with map i in [i0, i1) and map j in [j0, j1); NaN when none qualifies (the region was deleted)
+      aligned_region_abs [E, K]       the mean of its absolute value over the same pairs
+    `scores_host` computes the three map scores from maps on the host, `region_scores_host` the two region scores, `aligned_scores_host` and
+    `aligned_region_scores_host` the aligned ones."""
     ref_map: torch.Tensor
     ref_1d: Optional[torch.Tensor]
     delta_profile: torch.Tensor
@@ -803,6 +919,13 @@ class ScreenResult:
     delta_region: Optional[torch.Tensor] = None
     delta_region_abs: Optional[torch.Tensor] = None
     shift: Optional[torch.Tensor] = None
+    bin_map: Optional[torch.Tensor] = None
+    aligned_bins: Optional[torch.Tensor] = None
+    aligned_profile: Optional[torch.Tensor] = None
+    aligned_abs_mean: Optional[torch.Tensor] = None
+    aligned_abs_max: Optional[torch.Tensor] = None
+    aligned_region: Optional[torch.Tensor] = None
+    aligned_region_abs: Optional[torch.Tensor] = None
 
 
 # ---- the screen -----------------------------------------------------------------------------------------------------------------------------
@@ -835,16 +958,16 @@ def _net_of(model):
     return net
 
 
-def _flank_codes(window, flank, win):
+def _flank_codes(window, flank, win, flank_bp=None):
     """The right flank of the window as a [F] uint8 tensor on the window's device (0 <= F <= L): ``flank`` as given, else read from the genome
-    of a ``(genome, chrom, start[, L])`` window (`FLANK_BP` bases, fewer at the chromosome's end), else empty."""
+    of a ``(genome, chrom, start[, L])`` window (``flank_bp`` bases, `FLANK_BP` by default, fewer at the chromosome's end), else empty."""
     L = win.numel()
     if flank is None:
-        if not isinstance(window, tuple):
+        if not isinstance(window, tuple) or flank_bp == 0:
             return win[:0]
         genome, chrom, start = window[:3]
         n = dict(genome.get_chr_lens())[chrom]
-        flank = genome.get_codes_from_coords(chrom, int(start) + L, min(int(start) + L + min(FLANK_BP, L), n))
+        flank = genome.get_codes_from_coords(chrom, int(start) + L, min(int(start) + L + (min(FLANK_BP, L) if flank_bp is None else flank_bp), n))
     if not isinstance(flank, torch.Tensor):
         raise TypeError("flank: a [F] uint8 codes tensor on the MI355X")
     if not flank.is_cuda:
@@ -967,7 +1090,7 @@ class _Screen:
         return self._decode(out)
 
 
-def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regions=None, flank=None):
+def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regions=None, flank=None, aligned=False, flank_bp=None):
     """Score ``edits`` (a list of `Edit` and `EditSet`, one row of every result tensor each) of one window with the 1 Mb model: a `ScreenResult`.
 
     ``model``: an ``H1esc_1M`` / ``Hff_1M`` container or a bare ``orca_modules.Net``.  ``window``: the window's base codes, a [L] uint8 tensor on
@@ -985,9 +1108,26 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
     (`FLANK_BP` bases, fewer at the chromosome's end); bases beyond it are N.  It is validated and otherwise ignored when no item changes
     length.  `ScreenResult.shift` says how far each item displaces what follows it.  More ``stats``: ``indel_items`` (items with a ``del`` /
     ``ins`` member), ``take_rows`` (stage-5 rows pooled from stage-4 cache entries on the two-part route), ``cache_phases`` (entries built: 512
-    bytes per context base for all 80; they are built with the reference, inside its deferred range check)."""
+    bytes per context base for all 80; they are built with the reference, inside its deferred range check).
+
+    ``flank_bp``: for a ``(genome, chrom, start[, L])`` window without ``flank``, the number of bases to read behind the window, 0 <= flank_bp <= L
+    (`FLANK_BP` by default; fewer at the chromosome's end).  Without it a 100 kb deletion is refilled with 8 kb of genome and 92 kb of N.  Given
+    together with ``flank`` or with a tensor window it is a ValueError.
+
+    ``aligned=True`` adds the scores on aligned bins (`ScreenResult.bin_map`, ``aligned_bins``, ``aligned_profile``, ``aligned_abs_mean``,
+    ``aligned_abs_max`` and, with ``regions``, ``aligned_region`` / ``aligned_region_abs``): alt pair (i, j) against reference pair (map i, map j)
+    with map = `bin_map` of the item, taken from the batch's maps whichever route produced them.  The rectangles of ``regions`` keep their
+    meaning for ``delta_region`` and are read as REFERENCE bins for the aligned pair.  With ``aligned=False`` nothing more is launched and those
+    fields are None.  ``stats`` gains ``aligned_items``: the items whose bin map is not the identity (0 without ``aligned``)."""
     net = _net_of(model)
+    if flank_bp is not None:
+        if flank is not None or not isinstance(window, tuple):
+            raise ValueError("flank_bp: for a (genome, chrom, start[, L]) window without an explicit flank")
     win = _window_codes(window)
+    if flank_bp is not None:
+        flank_bp = int(flank_bp)
+        if not 0 <= flank_bp <= win.numel():
+            raise ValueError(f"flank_bp of {flank_bp}: 0 .. {win.numel()} bases")
     edits = list(edits)
     for e in edits:
         if not isinstance(e, (Edit, EditSet)):
@@ -998,8 +1138,8 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
     rects = None if regions is None else check_regions(regions, win.numel() // 4000)
     st = {"route": None, "two_part_batches": 0, "whole_window_batches": 0, "range_fallback_batches": 0, "range_fallback_reference": False,
           "front_runs": 0, "front_bases": 0, "edits": len(edits), "set_items": sum(isinstance(e, EditSet) for e in edits), "segments": 0,
-          "indel_items": sum(changes_length(e) for e in edits), "take_rows": 0, "cache_phases": 0}
-    fl = _flank_codes(window, flank, win) if (flank is not None or st["indel_items"]) else None
+          "indel_items": sum(changes_length(e) for e in edits), "take_rows": 0, "cache_phases": 0, "aligned_items": 0}
+    fl = _flank_codes(window, flank, win, flank_bp) if (flank is not None or st["indel_items"]) else None
     sc = _Screen(net, win, st, fl if st["indel_items"] else None)
     E, n, dev = len(edits), sc.n, sc.dev
     two_part = net._enc.two_part_ok()
@@ -1036,6 +1176,18 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
         if rects is not None:
             res.delta_region = torch.zeros((E, len(rects)), dtype=torch.float32, device=dev)
             res.delta_region_abs = torch.zeros((E, len(rects)), dtype=torch.float32, device=dev)
+        bmaps = None
+        if aligned:
+            bmaps = np.stack([bin_map(e, sc.L, sc.F) for e in edits]) if E else np.zeros((0, n), dtype=np.int32)
+            st["aligned_items"] = int((bmaps != np.arange(n, dtype=np.int32)[None]).any(axis=1).sum())
+            res.bin_map = sc._upload(bmaps, torch.int32)
+            res.aligned_bins = sc._upload((bmaps >= 0).sum(axis=1), torch.int64)
+            res.aligned_profile = torch.zeros((E, n), dtype=torch.float32, device=dev)
+            res.aligned_abs_mean = torch.zeros(E, dtype=torch.float32, device=dev)
+            res.aligned_abs_max = torch.zeros(E, dtype=torch.float32, device=dev)
+            if rects is not None:
+                res.aligned_region = torch.zeros((E, len(rects)), dtype=torch.float32, device=dev)
+                res.aligned_region_abs = torch.zeros((E, len(rects)), dtype=torch.float32, device=dev)
         for i0 in range(0, E, batch):
             chunk = edits[i0: i0 + batch]
             if two_part:
@@ -1061,6 +1213,12 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
             res.delta_abs_max[i0:i1] = amax
             if rects is not None:
                 res.delta_region[i0:i1], res.delta_region_abs[i0:i1] = engine.screen_region_scores(sc.ctx, maps, ref_map, rects)
+            if aligned:
+                res.aligned_profile[i0:i1], res.aligned_abs_mean[i0:i1], res.aligned_abs_max[i0:i1] = engine.screen_aligned_scores(
+                    sc.ctx, maps, ref_map, bmaps[i0:i1], res.bin_map[i0:i1])
+                if rects is not None:
+                    res.aligned_region[i0:i1], res.aligned_region_abs[i0:i1] = engine.screen_aligned_region_scores(
+                        sc.ctx, maps, ref_map, bmaps[i0:i1], rects, res.bin_map[i0:i1])
             if h is not None:
                 torch.sub(h, ref_1d[None], out=res.delta_1d[i0:i1])
             if keep_maps:

@@ -18,6 +18,10 @@ Compound edits (screen.EditSet), items per second against the same edited window
 Insertions and deletions, into profiles/screen_1m_indels.json:
   --indels N     N random indels of 1-50 bases (half deletions, half insertions, anywhere in the window, 8 000 bases of right flank) at B = 64,
                  against the same alt windows through model.net and against N SNVs at the same positions through the screen, in the same run
+
+Aligned scores, into profiles/screen_1m_aligned.json:
+  --aligned      the 3 250-edit workload above through screen_1m with aligned=True and with aligned=False, alternated in the same run (B from
+                 --batches): what the bin maps and the aligned-score kernels add
 """
 import argparse
 import json
@@ -140,6 +144,24 @@ def time_indels(a, model, win, c, dev):
     return {"device": torch.cuda.get_device_name(dev), f"indels_{a.indels}_of_1_to_50_bp": row}
 
 
+def time_aligned(a, model, win, edits, dev):
+    """The --aligned workload: screen_1m on the same edits with and without aligned=True, alternated, per batch size."""
+    rep = {"device": torch.cuda.get_device_name(dev), "edits": len(edits)}
+    st = {}
+    S.screen_1m(model, win, edits[:64], batch=64, stats=st, aligned=True)                     # warm-up
+    S.screen_1m(model, win, edits[:64], batch=64)
+    rep["route"] = st["route"]
+    for B in [int(b) for b in a.batches.split(",")]:
+        ta, tp = [], []
+        for _ in range(a.reps):
+            tp.append(timed(lambda: S.screen_1m(model, win, edits, batch=B))[0])
+            ta.append(timed(lambda: S.screen_1m(model, win, edits, batch=B, aligned=True))[0])
+        rep[f"B{B}"] = {"plain_s": [round(t, 3) for t in tp], "aligned_s": [round(t, 3) for t in ta], "plain_edits_per_s": round(len(edits) / min(tp), 1),
+                        "aligned_edits_per_s": round(len(edits) / min(ta), 1), "aligned_over_plain": round(min(ta) / min(tp), 4)}
+        print(json.dumps({f"B{B}": rep[f"B{B}"]}), flush=True)
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="16,64")
@@ -151,6 +173,7 @@ def main():
     ap.add_argument("--haplotypes", type=int, default=64)
     ap.add_argument("--haplotype-span", type=int, default=L)
     ap.add_argument("--indels", type=int, default=0, help="N: time N random 1-50-base indels at B = 64")
+    ap.add_argument("--aligned", action="store_true", help="time the 3 250-edit workload with aligned=True against aligned=False")
     ap.add_argument("--commit", default="", help="recorded in the report")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -181,6 +204,17 @@ def main():
                 json.dump(rep, f, indent=1)
         return
     edits = S.saturation_edits(c, 499_500, 500_500) + S.tile_edits("mask", 4000, 4000, 0, L)
+    if a.aligned:
+        rep = {"workload": f"H1esc_1M synthetic, 1 Mb window, {len(edits)} edits (saturation SNVs of 1 kb + 250 4 kb mask tiles); screen_1m with "
+                           "aligned=True against aligned=False, alternated (every call includes its reference)", "commit": a.commit}
+        rep.update(time_aligned(a, model, win, edits, dev))
+        print(json.dumps(rep))
+        out = a.out if a.out != ap.get_default("out") else os.path.join(os.path.dirname(a.out), "screen_1m_aligned.json")
+        if out:
+            os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+            with open(out, "w") as f:
+                json.dump(rep, f, indent=1)
+        return
     rep = {"workload": f"H1esc_1M synthetic, 1 Mb window, {len(edits)} edits (saturation SNVs of 1 kb + 250 4 kb mask tiles)", "edits": len(edits)}
     # warm-up (library load, nets, workspaces) and the cross-check of both routes' maps
     st = {}
