@@ -4,40 +4,102 @@
 
 #include "screen.h"
 
+static inline const f32x4* f4(const float* p) { return reinterpret_cast<const f32x4*>(p); }
+static inline const long long* i64(const int64_t* p) { return reinterpret_cast<const long long*>(p); }
+static inline dim3 grid256(long threads) { return dim3((unsigned)((threads + 255) / 256)); }
+
+// the end of every entry point: one launch on the context's stream
+template <class... P, class... A>
+static int launch(orca_ctx* ctx, const char* name, void (*kernel)(P...), dim3 grid, int threads, A... args) {
+  HIPCHECK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, ctx->stream, args...);
+  LAUNCHCHECK(name);
+  return ORCA_OK;
+}
+
+// ---- the checks of the small tables.  A table comes twice, on the device for the kernel and on the host for the checks made here before any launch (the
+// kernels clip every table-derived index all the same, so the two copies differing cannot make them leave their buffers).  `what` names the entry point
+// in the shared messages; wording that differs between the formats is in the entry point's own `snip` / `row` / `seg` check.
+
+// a packed snippet table over a sub-table of 4-field `rows` ("spans" / "pieces"; `key` names column K, LEN is the length's column): out_off ascending
+// without gaps, snip(k, e), the sub-table range inside its table, then per row row(s, r) and sorted / disjoint against the row before
+template <class Snip, class Row>
+static int walk_snippets(const char* what, const char* rows, const char* key, int K, int LEN, const int64_t* table_host, int n_snippets, const int64_t* sub_host,
+                         int64_t n_sub, int64_t total, Snip snip, Row row) {
+  int64_t off = 0;
+  for (int k = 0; k < n_snippets; ++k) {
+    const int64_t* e = table_host + (size_t)k * SCREEN_EDIT_FIELDS;
+    if (e[0] != off || e[2] <= 0)
+      return fail(ORCA_EINVAL, "%s: snippet %d starts at output base %ld with %ld bases, expected %ld (out_off ascending, no gaps)", what, k, (long)e[0], (long)e[2], (long)off);
+    ORCA_TRY(snip(k, e));
+    if (e[3] < 0 || e[4] < 0 || e[4] > n_sub - e[3]) return fail(ORCA_EINVAL, "%s: snippet %d has %s [%ld, +%ld) of %ld", what, k, rows, (long)e[3], (long)e[4], (long)n_sub);
+    for (int64_t s = e[3]; s < e[3] + e[4]; ++s) {
+      const int64_t* r = sub_host + (size_t)s * 4;
+      ORCA_TRY(row(s, r));
+      if (s > e[3] && r[K] < r[K - 4] + r[LEN - 4])
+        return fail(ORCA_EINVAL, "%s: %s %ld and %ld of snippet %d overlap or are not sorted by %s", what, rows, (long)s - 1, (long)s, k, key);
+    }
+    off += e[2];
+  }
+  return off == total ? ORCA_OK : fail(ORCA_EINVAL, "%s: the snippets hold %ld bases, out holds %ld", what, (long)off, (long)total);
+}
+
+// a segment table of FIELDS columns [row_lo, row_cnt, ..] with offsets: monotone from 0 to n_segments (every offset is inside the table before a segment
+// is read), then per segment seg(s, g) and sorted / disjoint against the segment before
+template <class Seg>
+static int walk_segments(const char* what, int FIELDS, const int64_t* segments_host, int64_t n_segments, const int64_t* seg_off_host, int B, Seg seg) {
+  if (seg_off_host[0] != 0 || seg_off_host[B] != n_segments)
+    return fail(ORCA_EINVAL, "%s: segment offsets run from %ld to %ld, the table holds %ld segments", what, (long)seg_off_host[0], (long)seg_off_host[B], (long)n_segments);
+  for (int b = 0; b < B; ++b)
+    if (seg_off_host[b + 1] < seg_off_host[b]) return fail(ORCA_EINVAL, "%s: segment offsets decrease at image %d", what, b);
+  for (int b = 0; b < B; ++b)
+    for (int64_t s = seg_off_host[b]; s < seg_off_host[b + 1]; ++s) {
+      const int64_t* g = segments_host + FIELDS * (size_t)s;
+      ORCA_TRY(seg(s, g));
+      if (s > seg_off_host[b] && g[0] < g[-FIELDS] + g[1 - FIELDS])
+        return fail(ORCA_EINVAL, "%s: segments %ld and %ld of image %d overlap or are not sorted by row_lo", what, (long)s - 1, (long)s, b);
+    }
+  return ORCA_OK;
+}
+
+static int check_rects(const char* what, const int32_t* rects_host, int K, int n) {
+  for (int k = 0; k < K; ++k) {
+    const int32_t* r = rects_host + 4 * k;
+    if (r[0] < 0 || r[0] >= r[1] || r[1] > n || r[2] < 0 || r[2] >= r[3] || r[3] > n)
+      return fail(ORCA_EINVAL, "%s: rectangle %d = rows [%d, %d) x columns [%d, %d) outside [0, %d) or empty", what, k, r[0], r[1], r[2], r[3], n);
+  }
+  return ORCA_OK;
+}
+
+// the bin map of the aligned scores: B x n int32, -1 .. n - 1
+static int check_bin_map(const char* what, const int32_t* bin_map_host, int B, int n) {
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < n; ++i) {
+      const int32_t m = bin_map_host[(size_t)b * n + i];
+      if (m < -1 || m >= n) return fail(ORCA_EINVAL, "%s: map %d sends alt bin %d to reference bin %d, outside -1 .. %d", what, b, i, m, n - 1);
+    }
+  return ORCA_OK;
+}
+
+// ---- bare edits: one span per snippet, one segment per image; the tables are on the device only (the kernels clip) ------------------------------------------
 extern "C" int orca_screen_edit_codes(orca_ctx* ctx, const uint8_t* window, int64_t L, const int64_t* table, int n_snippets, const uint8_t* payload,
                                       int64_t n_payload, uint8_t* out, int64_t total) {
   if (!ctx || !window || !table || !out || n_snippets <= 0) return fail(ORCA_EINVAL, "orca_screen_edit_codes: NULL / empty argument");
   if (n_payload > 0 && !payload) return fail(ORCA_EINVAL, "orca_screen_edit_codes: NULL payload");
   if (total <= 0) return ORCA_OK;
-  HIPCHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(screen_edit_codes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, window, (long)L,
-                     reinterpret_cast<const long long*>(table), n_snippets, payload, (long)n_payload, out, (long)total);
-  LAUNCHCHECK("screen_edit_codes_kernel");
-  return ORCA_OK;
+  return launch(ctx, "screen_edit_codes_kernel", screen_edit_codes_kernel, grid256(total), 256, window, (long)L, i64(table), n_snippets, payload, (long)n_payload, out,
+                (long)total);
 }
 
 extern "C" int orca_screen_splice_rows(orca_ctx* ctx, const float* ref, int64_t n5, const float* fresh, int64_t n_fresh, const int64_t* table, int B, float* out) {
   if (!ctx || !ref || !table || !out || (n_fresh > 0 && !fresh)) return fail(ORCA_EINVAL, "orca_screen_splice_rows: NULL argument");
   if (B <= 0 || n5 <= 0) return ORCA_OK;
   if (!al16(ref) || !al16(out) || (fresh && !al16(fresh))) return fail(ORCA_EINVAL, "orca_screen_splice_rows: rows must be 16-byte aligned");
-  HIPCHECK(hipSetDevice(ctx->device));
-  const long units = (long)B * n5 * 32;
-  hipLaunchKernelGGL(screen_splice_rows_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, ctx->stream, reinterpret_cast<const f32x4*>(ref), (long)n5,
-                     reinterpret_cast<const f32x4*>(fresh), (long)n_fresh, reinterpret_cast<const long long*>(table), B, reinterpret_cast<f32x4*>(out));
-  LAUNCHCHECK("screen_splice_rows_kernel");
-  return ORCA_OK;
-}
-extern "C" int orca_screen_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, float* profile, float* mean, float* amax) {
-  if (!ctx || !alt || !ref || !profile || !mean || !amax) return fail(ORCA_EINVAL, "orca_screen_scores: NULL argument");
-  if (B <= 0 || n <= 0) return ORCA_OK;
-  HIPCHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(screen_scores_kernel, dim3((unsigned)B), dim3(512), 0, ctx->stream, alt, (long)map_bs, ref, n, profile, mean, amax);
-  LAUNCHCHECK("screen_scores_kernel");
-  return ORCA_OK;
+  return launch(ctx, "screen_splice_rows_kernel", screen_splice_rows_kernel, grid256((long)B * n5 * 32), 256, f4(ref), (long)n5, f4(fresh), (long)n_fresh, i64(table), B,
+                reinterpret_cast<f32x4*>(out));
 }
 
-// compound edits: the small tables come twice, on the device for the kernels and on the host for the checks made here before any launch (the
-// kernels clip every table-derived index all the same, so the two copies differing cannot make them leave their buffers)
+// ---- compound edits: spans per snippet, segments per image ---------------------------------------------------------------------------------------------------
 extern "C" int orca_screen_edit_codes_multi(orca_ctx* ctx, const uint8_t* window, int64_t L, const int64_t* table, const int64_t* table_host, int n_snippets,
                                             const int64_t* spans, const int64_t* spans_host, int64_t n_spans, const uint8_t* payload, int64_t n_payload,
                                             uint8_t* out, int64_t total) {
@@ -47,28 +109,19 @@ extern "C" int orca_screen_edit_codes_multi(orca_ctx* ctx, const uint8_t* window
                 (long)n_payload, (long)total, (long)L);
   if (n_spans > 0 && (!spans || !spans_host)) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: NULL span table");
   if (n_payload > 0 && !payload) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: NULL payload");
-  int64_t off = 0;
-  for (int k = 0; k < n_snippets; ++k) {
-    const int64_t* e = table_host + (size_t)k * SCREEN_EDIT_FIELDS;
-    if (e[0] != off || e[2] <= 0) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: snippet %d starts at output base %ld with %ld bases, expected %ld (out_off ascending, no gaps)",
-                                               k, (long)e[0], (long)e[2], (long)off);
-    if (e[1] < 0 || e[2] > L - e[1]) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: snippet %d = window bases [%ld, +%ld) outside the window of %ld", k, (long)e[1], (long)e[2], (long)L);
-    if (e[3] < 0 || e[4] < 0 || e[4] > n_spans - e[3]) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: snippet %d has spans [%ld, +%ld) of %ld", k, (long)e[3], (long)e[4], (long)n_spans);
-    for (int64_t s = e[3]; s < e[3] + e[4]; ++s) {
-      const int64_t* sp = spans_host + (size_t)s * SCREEN_SPAN_FIELDS;
-      if (sp[0] < 0 || sp[0] > 2 || sp[1] < 0 || sp[2] <= 0 || sp[2] > L - sp[1]) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: span %ld: kind %ld, bases [%ld, +%ld) of %ld", (long)s, (long)sp[0], (long)sp[1], (long)sp[2], (long)L);
-      if (sp[0] == 0 && (sp[3] < 0 || sp[2] > n_payload - sp[3])) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: span %ld: payload [%ld, +%ld) of %ld", (long)s, (long)sp[3], (long)sp[2], (long)n_payload);
-      if (s > e[3] && sp[1] < sp[-SCREEN_SPAN_FIELDS + 1] + sp[-SCREEN_SPAN_FIELDS + 2]) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: spans %ld and %ld of snippet %d overlap or are not sorted by pos", (long)s - 1, (long)s, k);
-    }
-    off += e[2];
-  }
-  if (off != total) return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: the snippets hold %ld bases, out holds %ld", (long)off, (long)total);
-  HIPCHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(screen_edit_codes_multi_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, window, (long)L,
-                     reinterpret_cast<const long long*>(table), n_snippets, reinterpret_cast<const long long*>(spans), (long)n_spans, payload, (long)n_payload, out,
-                     (long)total);
-  LAUNCHCHECK("screen_edit_codes_multi_kernel");
-  return ORCA_OK;
+  ORCA_TRY(walk_snippets("orca_screen_edit_codes_multi", "spans", "pos", 1, 2, table_host, n_snippets, spans_host, n_spans, total,
+    [&](int k, const int64_t* e) -> int {
+      if (e[1] >= 0 && e[2] <= L - e[1]) return ORCA_OK;
+      return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: snippet %d = window bases [%ld, +%ld) outside the window of %ld", k, (long)e[1], (long)e[2], (long)L);
+    },
+    [&](int64_t s, const int64_t* sp) -> int {
+      if (sp[0] < 0 || sp[0] > 2 || sp[1] < 0 || sp[2] <= 0 || sp[2] > L - sp[1])
+        return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: span %ld: kind %ld, bases [%ld, +%ld) of %ld", (long)s, (long)sp[0], (long)sp[1], (long)sp[2], (long)L);
+      if (sp[0] != 0 || (sp[3] >= 0 && sp[2] <= n_payload - sp[3])) return ORCA_OK;
+      return fail(ORCA_EINVAL, "orca_screen_edit_codes_multi: span %ld: payload [%ld, +%ld) of %ld", (long)s, (long)sp[3], (long)sp[2], (long)n_payload);
+    }));
+  return launch(ctx, "screen_edit_codes_multi_kernel", screen_edit_codes_multi_kernel, grid256(total), 256, window, (long)L, i64(table), n_snippets, i64(spans),
+                (long)n_spans, payload, (long)n_payload, out, (long)total);
 }
 
 extern "C" int orca_screen_splice_rows_multi(orca_ctx* ctx, const float* ref, int64_t n5, const float* fresh, int64_t n_fresh, const int64_t* segments,
@@ -79,91 +132,18 @@ extern "C" int orca_screen_splice_rows_multi(orca_ctx* ctx, const float* ref, in
     return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: %d images of %ld rows, %ld fresh rows, %ld segments", B, (long)n5, (long)n_fresh, (long)n_segments);
   if (n_fresh > 0 && !fresh) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: NULL fresh rows");
   if (n_segments > 0 && (!segments || !segments_host)) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: NULL segment table");
-  if (seg_off_host[0] != 0 || seg_off_host[B] != n_segments)
-    return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: segment offsets run from %ld to %ld, the table holds %ld segments", (long)seg_off_host[0], (long)seg_off_host[B], (long)n_segments);
-  for (int b = 0; b < B; ++b)       // monotone from 0 to n_segments: every offset is inside the table before a segment is read
-    if (seg_off_host[b + 1] < seg_off_host[b]) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: segment offsets decrease at image %d", b);
-  for (int b = 0; b < B; ++b) {
-    for (int64_t s = seg_off_host[b]; s < seg_off_host[b + 1]; ++s) {
-      const int64_t* g = segments_host + 3 * (size_t)s;
-      if (g[0] < 0 || g[1] <= 0 || g[1] > n5 - g[0] || g[2] < 0 || g[1] > n_fresh - g[2])
-        return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: segment %ld = rows [%ld, +%ld) of %ld from fresh row %ld of %ld", (long)s, (long)g[0], (long)g[1], (long)n5, (long)g[2], (long)n_fresh);
-      if (s > seg_off_host[b] && g[0] < g[-3] + g[-2]) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: segments %ld and %ld of image %d overlap or are not sorted by row_lo", (long)s - 1, (long)s, b);
-    }
-  }
+  ORCA_TRY(walk_segments("orca_screen_splice_rows_multi", 3, segments_host, n_segments, seg_off_host, B, [&](int64_t s, const int64_t* g) -> int {
+    if (g[0] >= 0 && g[1] > 0 && g[1] <= n5 - g[0] && g[2] >= 0 && g[1] <= n_fresh - g[2]) return ORCA_OK;
+    return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: segment %ld = rows [%ld, +%ld) of %ld from fresh row %ld of %ld", (long)s, (long)g[0], (long)g[1], (long)n5, (long)g[2], (long)n_fresh);
+  }));
   if (B == 0 || n5 == 0) return ORCA_OK;
   if (!al16(ref) || !al16(out) || (fresh && !al16(fresh))) return fail(ORCA_EINVAL, "orca_screen_splice_rows_multi: rows must be 16-byte aligned");
-  HIPCHECK(hipSetDevice(ctx->device));
-  const long units = (long)B * n5 * 32;
-  hipLaunchKernelGGL(screen_splice_rows_multi_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, ctx->stream, reinterpret_cast<const f32x4*>(ref), (long)n5,
-                     reinterpret_cast<const f32x4*>(fresh), (long)n_fresh, reinterpret_cast<const long long*>(segments), (long)n_segments,
-                     reinterpret_cast<const long long*>(seg_off), B, reinterpret_cast<f32x4*>(out));
-  LAUNCHCHECK("screen_splice_rows_multi_kernel");
-  return ORCA_OK;
+  return launch(ctx, "screen_splice_rows_multi_kernel", screen_splice_rows_multi_kernel, grid256((long)B * n5 * 32), 256, f4(ref), (long)n5, f4(fresh), (long)n_fresh,
+                i64(segments), (long)n_segments, i64(seg_off), B, reinterpret_cast<f32x4*>(out));
 }
 
-extern "C" int orca_screen_region_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* rects,
-                                         const int32_t* rects_host, int K, float* mean_signed, float* mean_abs) {
-  if (!ctx || !alt || !ref || !rects || !rects_host || !mean_signed || !mean_abs) return fail(ORCA_EINVAL, "orca_screen_region_scores: NULL argument");
-  if (B < 0 || n <= 0 || K <= 0 || K > 64 || map_bs < 0) return fail(ORCA_EINVAL, "orca_screen_region_scores: %d maps of %d bins, %d rectangles (1..64)", B, n, K);
-  for (int k = 0; k < K; ++k) {
-    const int32_t* r = rects_host + 4 * k;
-    if (r[0] < 0 || r[0] >= r[1] || r[1] > n || r[2] < 0 || r[2] >= r[3] || r[3] > n)
-      return fail(ORCA_EINVAL, "orca_screen_region_scores: rectangle %d = rows [%d, %d) x columns [%d, %d) outside [0, %d) or empty", k, r[0], r[1], r[2], r[3], n);
-  }
-  if (B == 0) return ORCA_OK;
-  HIPCHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(screen_region_scores_kernel, dim3((unsigned)B, (unsigned)K), dim3(256), 0, ctx->stream, alt, (long)map_bs, ref, n, rects, K, mean_signed, mean_abs);
-  LAUNCHCHECK("screen_region_scores_kernel");
-  return ORCA_OK;
-}
-
-// aligned scores: the bin map (B x n int32, -1 .. n - 1) comes twice like every small table; `what` names the entry point in the message
-static int check_bin_map(const char* what, const int32_t* bin_map_host, int B, int n) {
-  for (int b = 0; b < B; ++b)
-    for (int i = 0; i < n; ++i) {
-      const int32_t m = bin_map_host[(size_t)b * n + i];
-      if (m < -1 || m >= n) return fail(ORCA_EINVAL, "%s: map %d sends alt bin %d to reference bin %d, outside -1 .. %d", what, b, i, m, n - 1);
-    }
-  return ORCA_OK;
-}
-
-extern "C" int orca_screen_aligned_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* bin_map,
-                                          const int32_t* bin_map_host, float* profile, float* mean, float* amax) {
-  if (!ctx || !alt || !ref || !bin_map || !bin_map_host || !profile || !mean || !amax) return fail(ORCA_EINVAL, "orca_screen_aligned_scores: NULL argument");
-  if (B < 0 || n <= 0 || n > SCREEN_ALIGNED_MAX_BINS || map_bs < 0)
-    return fail(ORCA_EINVAL, "orca_screen_aligned_scores: %d maps of %d bins (1..%d), batch stride %ld", B, n, SCREEN_ALIGNED_MAX_BINS, (long)map_bs);
-  if (int rc = check_bin_map("orca_screen_aligned_scores", bin_map_host, B, n)) return rc;
-  if (B == 0) return ORCA_OK;
-  HIPCHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(screen_aligned_scores_kernel, dim3((unsigned)B), dim3(512), 0, ctx->stream, alt, (long)map_bs, ref, n, bin_map, profile, mean, amax);
-  LAUNCHCHECK("screen_aligned_scores_kernel");
-  return ORCA_OK;
-}
-
-extern "C" int orca_screen_aligned_region_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* bin_map,
-                                                 const int32_t* bin_map_host, const int32_t* rects, const int32_t* rects_host, int K, float* mean_signed,
-                                                 float* mean_abs) {
-  if (!ctx || !alt || !ref || !bin_map || !bin_map_host || !rects || !rects_host || !mean_signed || !mean_abs)
-    return fail(ORCA_EINVAL, "orca_screen_aligned_region_scores: NULL argument");
-  if (B < 0 || n <= 0 || n > SCREEN_ALIGNED_MAX_BINS || K <= 0 || K > 64 || map_bs < 0)
-    return fail(ORCA_EINVAL, "orca_screen_aligned_region_scores: %d maps of %d bins (1..%d), %d rectangles (1..64)", B, n, SCREEN_ALIGNED_MAX_BINS, K);
-  for (int k = 0; k < K; ++k) {
-    const int32_t* r = rects_host + 4 * k;
-    if (r[0] < 0 || r[0] >= r[1] || r[1] > n || r[2] < 0 || r[2] >= r[3] || r[3] > n)
-      return fail(ORCA_EINVAL, "orca_screen_aligned_region_scores: rectangle %d = rows [%d, %d) x columns [%d, %d) outside [0, %d) or empty", k, r[0], r[1], r[2], r[3], n);
-  }
-  if (int rc = check_bin_map("orca_screen_aligned_region_scores", bin_map_host, B, n)) return rc;
-  if (B == 0) return ORCA_OK;
-  HIPCHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(screen_aligned_region_scores_kernel, dim3((unsigned)B, (unsigned)K), dim3(256), 0, ctx->stream, alt, (long)map_bs, ref, n, bin_map, rects, K,
-                     mean_signed, mean_abs);
-  LAUNCHCHECK("screen_aligned_region_scores_kernel");
-  return ORCA_OK;
-}
-
-// insertions and deletions: the edited bases of a batch from piece lists over the context (window + right flank), and the row images from the reference
-// rows, the recomputed rows and the stage-4 phase entries.  Tables as above: a device copy for the kernel, a host copy checked here before any launch.
+// ---- insertions and deletions: the edited bases of a batch from piece lists over the context (window + right flank), and the row images from the
+// reference rows, the recomputed rows and the stage-4 phase entries
 extern "C" int orca_screen_assemble_codes(orca_ctx* ctx, const uint8_t* context, int64_t C, const int64_t* table, const int64_t* table_host, int n_snippets,
                                           const int64_t* pieces, const int64_t* pieces_host, int64_t n_pieces, const uint8_t* payload, int64_t n_payload,
                                           uint8_t* out, int64_t total) {
@@ -174,31 +154,19 @@ extern "C" int orca_screen_assemble_codes(orca_ctx* ctx, const uint8_t* context,
   if (n_pieces > 0 && (!pieces || !pieces_host)) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: NULL piece table");
   if (n_payload > 0 && !payload) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: NULL payload");
   const int64_t kmax = INT64_MAX / 4;               // every coordinate stays far below the sums the kernel forms
-  int64_t off = 0;
-  for (int k = 0; k < n_snippets; ++k) {
-    const int64_t* e = table_host + (size_t)k * SCREEN_EDIT_FIELDS;
-    if (e[0] != off || e[2] <= 0) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: snippet %d starts at output base %ld with %ld bases, expected %ld (out_off ascending, no gaps)",
-                                               k, (long)e[0], (long)e[2], (long)off);
-    if (e[1] < 0 || e[1] > kmax || e[2] > kmax) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: snippet %d = alt bases [%ld, +%ld)", k, (long)e[1], (long)e[2]);
-    if (e[3] < 0 || e[4] < 0 || e[4] > n_pieces - e[3]) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: snippet %d has pieces [%ld, +%ld) of %ld", k, (long)e[3], (long)e[4], (long)n_pieces);
-    for (int64_t s = e[3]; s < e[3] + e[4]; ++s) {
-      const int64_t* pc = pieces_host + (size_t)s * SCREEN_PIECE_FIELDS;
+  ORCA_TRY(walk_snippets("orca_screen_assemble_codes", "pieces", "dst", 0, 3, table_host, n_snippets, pieces_host, n_pieces, total,
+    [&](int k, const int64_t* e) -> int {
+      return (e[1] < 0 || e[1] > kmax || e[2] > kmax) ? fail(ORCA_EINVAL, "orca_screen_assemble_codes: snippet %d = alt bases [%ld, +%ld)", k, (long)e[1], (long)e[2]) : ORCA_OK;
+    },
+    [&](int64_t s, const int64_t* pc) -> int {
       if (pc[1] < 0 || pc[1] > 3 || pc[0] < 0 || pc[0] > kmax || pc[3] <= 0 || pc[3] > kmax || pc[2] < 0 || pc[2] > kmax)
         return fail(ORCA_EINVAL, "orca_screen_assemble_codes: piece %ld: alt base %ld, kind %ld, source %ld, %ld bases", (long)s, (long)pc[0], (long)pc[1], (long)pc[2], (long)pc[3]);
-      if (pc[1] == 2 && pc[3] > n_payload - pc[2]) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: piece %ld: payload [%ld, +%ld) of %ld", (long)s, (long)pc[2], (long)pc[3], (long)n_payload);
-      if (s > e[3] && pc[0] < pc[-SCREEN_PIECE_FIELDS] + pc[-SCREEN_PIECE_FIELDS + 3])
-        return fail(ORCA_EINVAL, "orca_screen_assemble_codes: pieces %ld and %ld of snippet %d overlap or are not sorted by dst", (long)s - 1, (long)s, k);
-    }
-    off += e[2];
-  }
-  if (off != total) return fail(ORCA_EINVAL, "orca_screen_assemble_codes: the snippets hold %ld bases, out holds %ld", (long)off, (long)total);
+      if (pc[1] != 2 || pc[3] <= n_payload - pc[2]) return ORCA_OK;
+      return fail(ORCA_EINVAL, "orca_screen_assemble_codes: piece %ld: payload [%ld, +%ld) of %ld", (long)s, (long)pc[2], (long)pc[3], (long)n_payload);
+    }));
   if (total == 0) return ORCA_OK;
-  HIPCHECK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(screen_assemble_codes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, context, (long)C,
-                     reinterpret_cast<const long long*>(table), n_snippets, reinterpret_cast<const long long*>(pieces), (long)n_pieces, payload, (long)n_payload, out,
-                     (long)total);
-  LAUNCHCHECK("screen_assemble_codes_kernel");
-  return ORCA_OK;
+  return launch(ctx, "screen_assemble_codes_kernel", screen_assemble_codes_kernel, grid256(total), 256, context, (long)C, i64(table), n_snippets, i64(pieces),
+                (long)n_pieces, payload, (long)n_payload, out, (long)total);
 }
 
 extern "C" int orca_screen_gather_rows(orca_ctx* ctx, const float* ref, int64_t n5, const float* fresh, int64_t n_fresh, const float* const* entries,
@@ -212,30 +180,56 @@ extern "C" int orca_screen_gather_rows(orca_ctx* ctx, const float* ref, int64_t 
   if (n_segments > 0 && (!segments || !segments_host)) return fail(ORCA_EINVAL, "orca_screen_gather_rows: NULL segment table");
   for (int p = 0; p < P; ++p)
     if (entry_rows_host[p] < 0) return fail(ORCA_EINVAL, "orca_screen_gather_rows: phase entry %d has %ld rows", p, (long)entry_rows_host[p]);
-  if (seg_off_host[0] != 0 || seg_off_host[B] != n_segments)
-    return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment offsets run from %ld to %ld, the table holds %ld segments", (long)seg_off_host[0], (long)seg_off_host[B], (long)n_segments);
-  for (int b = 0; b < B; ++b)       // monotone from 0 to n_segments: every offset is inside the table before a segment is read
-    if (seg_off_host[b + 1] < seg_off_host[b]) return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment offsets decrease at image %d", b);
-  for (int b = 0; b < B; ++b) {
-    for (int64_t s = seg_off_host[b]; s < seg_off_host[b + 1]; ++s) {
-      const int64_t* g = segments_host + SCREEN_GATHER_FIELDS * (size_t)s;
-      if (g[0] < 0 || g[1] <= 0 || g[1] > n5 - g[0]) return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment %ld = rows [%ld, +%ld) of %ld", (long)s, (long)g[0], (long)g[1], (long)n5);
-      if (g[2] < -2 || g[2] >= P) return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment %ld has source %ld (-1 fresh, -2 ref, or a phase entry below %d)", (long)s, (long)g[2], P);
-      const int64_t have = g[2] == -1 ? n_fresh : g[2] == -2 ? n5 : entry_rows_host[g[2]], step = g[2] >= 0 ? 5 : 1;      // a pooled row reads 5 of its entry's
-      if (g[3] < 0 || g[3] > have || g[1] > (have - g[3]) / step)
-        return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment %ld reads %ld rows from row %ld of source %ld, which cannot give them", (long)s, (long)g[1], (long)g[3], (long)g[2]);
-      if (s > seg_off_host[b] && g[0] < g[-SCREEN_GATHER_FIELDS] + g[-SCREEN_GATHER_FIELDS + 1])
-        return fail(ORCA_EINVAL, "orca_screen_gather_rows: segments %ld and %ld of image %d overlap or are not sorted by row_lo", (long)s - 1, (long)s, b);
-    }
-  }
+  ORCA_TRY(walk_segments("orca_screen_gather_rows", SCREEN_GATHER_FIELDS, segments_host, n_segments, seg_off_host, B, [&](int64_t s, const int64_t* g) -> int {
+    if (g[0] < 0 || g[1] <= 0 || g[1] > n5 - g[0]) return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment %ld = rows [%ld, +%ld) of %ld", (long)s, (long)g[0], (long)g[1], (long)n5);
+    if (g[2] < -2 || g[2] >= P) return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment %ld has source %ld (-1 fresh, -2 ref, or a phase entry below %d)", (long)s, (long)g[2], P);
+    const int64_t have = g[2] == -1 ? n_fresh : g[2] == -2 ? n5 : entry_rows_host[g[2]], step = g[2] >= 0 ? 5 : 1;      // a pooled row reads 5 of its entry's
+    if (g[3] >= 0 && g[3] <= have && g[1] <= (have - g[3]) / step) return ORCA_OK;
+    return fail(ORCA_EINVAL, "orca_screen_gather_rows: segment %ld reads %ld rows from row %ld of source %ld, which cannot give them", (long)s, (long)g[1], (long)g[3], (long)g[2]);
+  }));
   if (B == 0 || n5 == 0) return ORCA_OK;
   if (!al16(ref) || !al16(out) || (fresh && !al16(fresh))) return fail(ORCA_EINVAL, "orca_screen_gather_rows: rows must be 16-byte aligned");
-  HIPCHECK(hipSetDevice(ctx->device));
-  const long units = (long)B * n5 * 32;
-  hipLaunchKernelGGL(screen_gather_rows_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, ctx->stream, reinterpret_cast<const f32x4*>(ref), (long)n5,
-                     reinterpret_cast<const f32x4*>(fresh), (long)n_fresh, reinterpret_cast<const f32x4* const*>(entries),
-                     reinterpret_cast<const long long*>(entry_rows), P, reinterpret_cast<const long long*>(segments), (long)n_segments,
-                     reinterpret_cast<const long long*>(seg_off), B, reinterpret_cast<f32x4*>(out));
-  LAUNCHCHECK("screen_gather_rows_kernel");
-  return ORCA_OK;
+  return launch(ctx, "screen_gather_rows_kernel", screen_gather_rows_kernel, grid256((long)B * n5 * 32), 256, f4(ref), (long)n5, f4(fresh), (long)n_fresh,
+                reinterpret_cast<const f32x4* const*>(entries), i64(entry_rows), P, i64(segments), (long)n_segments, i64(seg_off), B, reinterpret_cast<f32x4*>(out));
+}
+
+// ---- scores ----------------------------------------------------------------------------------------------------------------------------------------------------
+extern "C" int orca_screen_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, float* profile, float* mean, float* amax) {
+  if (!ctx || !alt || !ref || !profile || !mean || !amax) return fail(ORCA_EINVAL, "orca_screen_scores: NULL argument");
+  if (B <= 0 || n <= 0) return ORCA_OK;
+  return launch(ctx, "screen_scores_kernel", screen_scores_kernel, dim3((unsigned)B), 512, alt, (long)map_bs, ref, n, profile, mean, amax);
+}
+
+extern "C" int orca_screen_region_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* rects,
+                                         const int32_t* rects_host, int K, float* mean_signed, float* mean_abs) {
+  if (!ctx || !alt || !ref || !rects || !rects_host || !mean_signed || !mean_abs) return fail(ORCA_EINVAL, "orca_screen_region_scores: NULL argument");
+  if (B < 0 || n <= 0 || K <= 0 || K > 64 || map_bs < 0) return fail(ORCA_EINVAL, "orca_screen_region_scores: %d maps of %d bins, %d rectangles (1..64)", B, n, K);
+  ORCA_TRY(check_rects("orca_screen_region_scores", rects_host, K, n));
+  if (B == 0) return ORCA_OK;
+  return launch(ctx, "screen_region_scores_kernel", screen_region_scores_kernel, dim3((unsigned)B, (unsigned)K), 256, alt, (long)map_bs, ref, n, rects, K, mean_signed,
+                mean_abs);
+}
+
+extern "C" int orca_screen_aligned_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* bin_map,
+                                          const int32_t* bin_map_host, float* profile, float* mean, float* amax) {
+  if (!ctx || !alt || !ref || !bin_map || !bin_map_host || !profile || !mean || !amax) return fail(ORCA_EINVAL, "orca_screen_aligned_scores: NULL argument");
+  if (B < 0 || n <= 0 || n > SCREEN_ALIGNED_MAX_BINS || map_bs < 0)
+    return fail(ORCA_EINVAL, "orca_screen_aligned_scores: %d maps of %d bins (1..%d), batch stride %ld", B, n, SCREEN_ALIGNED_MAX_BINS, (long)map_bs);
+  ORCA_TRY(check_bin_map("orca_screen_aligned_scores", bin_map_host, B, n));
+  if (B == 0) return ORCA_OK;
+  return launch(ctx, "screen_aligned_scores_kernel", screen_aligned_scores_kernel, dim3((unsigned)B), 512, alt, (long)map_bs, ref, n, bin_map, profile, mean, amax);
+}
+
+extern "C" int orca_screen_aligned_region_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* bin_map,
+                                                 const int32_t* bin_map_host, const int32_t* rects, const int32_t* rects_host, int K, float* mean_signed,
+                                                 float* mean_abs) {
+  if (!ctx || !alt || !ref || !bin_map || !bin_map_host || !rects || !rects_host || !mean_signed || !mean_abs)
+    return fail(ORCA_EINVAL, "orca_screen_aligned_region_scores: NULL argument");
+  if (B < 0 || n <= 0 || n > SCREEN_ALIGNED_MAX_BINS || K <= 0 || K > 64 || map_bs < 0)
+    return fail(ORCA_EINVAL, "orca_screen_aligned_region_scores: %d maps of %d bins (1..%d), %d rectangles (1..64)", B, n, SCREEN_ALIGNED_MAX_BINS, K);
+  ORCA_TRY(check_rects("orca_screen_aligned_region_scores", rects_host, K, n));
+  ORCA_TRY(check_bin_map("orca_screen_aligned_region_scores", bin_map_host, B, n));
+  if (B == 0) return ORCA_OK;
+  return launch(ctx, "screen_aligned_region_scores_kernel", screen_aligned_region_scores_kernel, dim3((unsigned)B, (unsigned)K), 256, alt, (long)map_bs, ref, n, bin_map,
+                rects, K, mean_signed, mean_abs);
 }

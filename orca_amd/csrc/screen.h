@@ -5,61 +5,176 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// ---- edit table (int64 per snippet, SCREEN_EDIT_FIELDS fields; include/orca_hip.h: orca_screen_edit_codes) ---------------------------------------------
-//   [0] out_off  first output base of this snippet in the packed output
-//   [1] b0       first window base of the snippet
-//   [2] nb       bases in the snippet
-//   [3] kind     0 substitution (payload), 1 N-mask, 2 in-place reverse complement
-//   [4] pos      first window base of the edited span
-//   [5] len      bases in the edited span
-//   [6] pay_off  first payload code of a substitution
-//   [7] (unused)
-// Snippets are packed back to back in table order (out_off ascending, no gaps).
+// ---- the edited bases: three table formats over one snippet table (include/orca_hip.h: orca_screen_edit_codes, _edit_codes_multi, _assemble_codes) -------
+// snippet table (int64 per snippet, SCREEN_EDIT_FIELDS fields): [0] out_off  first output base of this snippet in the packed output  [1] b0  its first
+// base in the source's coordinates  [2] nb  its bases; snippets are packed back to back in table order (out_off ascending, no gaps).  The other fields:
+//   single span (screen.Edit):     [3] kind  [4] pos  [5] len  [6] pay_off - the one span of the snippet, fields as in the span table
+//   spans (screen.EditSet):        [3] span_lo  first span of this snippet in the span table  [4] span_cnt
+//   pieces ("del" / "ins" edits):  [3] piece_lo  first piece of this snippet in the piece table  [4] piece_cnt; b0 is an ALT base
+// span table (int64 per span, SCREEN_SPAN_FIELDS fields): [0] kind  0 substitution (payload), 1 N-mask, 2 in-place reverse complement  [1] pos  first
+// window base of the span  [2] len  [3] pay_off  first payload code of a substitution - a snippet's spans are sorted by pos and pairwise disjoint, so a
+// binary search finds the one span that can hold a base.  An inversion reads its source from the unedited window.
+// piece table (int64 per piece, SCREEN_PIECE_FIELDS fields): [0] dst  first alt base  [1] kind  [2] src  [3] len - the alt window of an item is a list of
+// pieces in alt coordinates over the CONTEXT (the window followed by its right flank); a snippet's pieces are sorted by dst and pairwise disjoint.
+// kind 0: context bases [src, src + len) forward; 1: their reverse complement (alt base dst + t is the complement of context[src + len - 1 - t]);
+// 2: payload codes [src, src + len); 3: N.  A base no piece covers is N.
+// Every kernel is one thread per output base: binary search of its snippet, of the snippet's spans / pieces, then the base.  A sub-table range is clipped
+// to its table and every read is bounds-checked (an out-of-range index reads as N), so a malformed table cannot make a kernel leave its buffers.
 #define SCREEN_EDIT_FIELDS 8
+#define SCREEN_SPAN_FIELDS 4
+#define SCREEN_PIECE_FIELDS 4
 
-// one thread per output base: binary search of its snippet, then the window base with the edit applied.  Every read is bounds-checked
-// against L / npay (an out-of-range index reads as N), so a malformed table cannot make the kernel leave its buffers.
+// the last snippet with out_off <= t (the first one when none is)
+static __device__ __forceinline__ const long long* screen_snippet_of(const long long* __restrict__ tab, int ns, long t) {
+  int lo = 0, hi = ns - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[(long)mid * SCREEN_EDIT_FIELDS] <= t) lo = mid; else hi = mid - 1;
+  }
+  return tab + (long)lo * SCREEN_EDIT_FIELDS;
+}
+
+// of rows [lo, hi) (clipped to the n rows) of an int64 table with FIELDS columns, the last one whose column K is <= x (the first one when none is);
+// NULL for an empty range
+template <int FIELDS, int K>
+static __device__ __forceinline__ const long long* screen_row_of(const long long* __restrict__ tab, long n, long lo, long hi, long x) {
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > n ? n : hi;
+  if (lo >= hi) return nullptr;
+  long a = lo, z = hi - 1;
+  while (a < z) {
+    const long mid = (a + z + 1) >> 1;
+    if ((long)tab[mid * FIELDS + K] <= x) a = mid; else z = mid - 1;
+  }
+  return tab + a * FIELDS;
+}
+
+static __device__ __forceinline__ unsigned screen_code(const unsigned char* __restrict__ buf, long n, long i) { return (i >= 0 && i < n) ? buf[i] : 4u; }
+static __device__ __forceinline__ unsigned screen_complement(unsigned s) { return s < 4u ? 3u - s : 4u; }      // A<->T, C<->G; N stays N
+
+// window base w (unedited: c) under the span (kind, pos, len, pay_off)
+static __device__ __forceinline__ unsigned screen_span_code(unsigned c, long w, long long kind, long pos, long len, long pay_off, const unsigned char* __restrict__ win,
+                                                            long L, const unsigned char* __restrict__ pay, long npay) {
+  const long k = w - pos;
+  if (w < pos || k >= len) return c;
+  if (kind == 0) return screen_code(pay, npay, pay_off + k);
+  if (kind == 1) return 4u;
+  return screen_complement(screen_code(win, L, pos + len - 1 - k));
+}
+
 static __global__ void screen_edit_codes_kernel(const unsigned char* __restrict__ win, long L, const long long* __restrict__ tab, int ns,
                                                 const unsigned char* __restrict__ pay, long npay, unsigned char* __restrict__ out, long total) {
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total) return;
-  int lo = 0, hi = ns - 1;
-  while (lo < hi) {                                  // last snippet with out_off <= t
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[(long)mid * SCREEN_EDIT_FIELDS] <= t) lo = mid; else hi = mid - 1;
-  }
-  const long long* e = tab + (long)lo * SCREEN_EDIT_FIELDS;
+  const long long* e = screen_snippet_of(tab, ns, t);
   const long w = (long)e[1] + (t - (long)e[0]);
-  unsigned c = (w >= 0 && w < L) ? win[w] : 4u;
-  const long pos = (long)e[4], len = (long)e[5];
-  if (w >= pos && w < pos + len) {
-    const long k = w - pos;
-    if (e[3] == 0) {
-      const long p = (long)e[6] + k;
-      c = (p >= 0 && p < npay) ? pay[p] : 4u;
-    } else if (e[3] == 1) {
-      c = 4u;
-    } else {
-      const long src = pos + len - 1 - k;
-      const unsigned s = (src >= 0 && src < L) ? win[src] : 4u;
-      c = s < 4u ? 3u - s : 4u;                        // A<->T, C<->G; N stays N
+  const unsigned c = screen_span_code(screen_code(win, L, w), w, e[3], (long)e[4], (long)e[5], (long)e[6], win, L, pay, npay);
+  out[t] = (unsigned char)(c > 4u ? 4u : c);
+}
+
+static __global__ void screen_edit_codes_multi_kernel(const unsigned char* __restrict__ win, long L, const long long* __restrict__ tab, int ns,
+                                                      const long long* __restrict__ spans, long nspans, const unsigned char* __restrict__ pay, long npay,
+                                                      unsigned char* __restrict__ out, long total) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const long long* e = screen_snippet_of(tab, ns, t);
+  const long w = (long)e[1] + (t - (long)e[0]);
+  unsigned c = screen_code(win, L, w);
+  if (const long long* sp = screen_row_of<SCREEN_SPAN_FIELDS, 1>(spans, nspans, (long)e[3], (long)e[3] + (long)e[4], w))
+    c = screen_span_code(c, w, sp[0], (long)sp[1], (long)sp[2], (long)sp[3], win, L, pay, npay);
+  out[t] = (unsigned char)(c > 4u ? 4u : c);
+}
+
+static __global__ void screen_assemble_codes_kernel(const unsigned char* __restrict__ cx, long C, const long long* __restrict__ tab, int ns,
+                                                    const long long* __restrict__ pieces, long npieces, const unsigned char* __restrict__ pay, long npay,
+                                                    unsigned char* __restrict__ out, long total) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const long long* e = screen_snippet_of(tab, ns, t);
+  const long w = (long)e[1] + (t - (long)e[0]);
+  unsigned c = 4u;
+  if (const long long* pc = screen_row_of<SCREEN_PIECE_FIELDS, 0>(pieces, npieces, (long)e[3], (long)e[3] + (long)e[4], w)) {
+    const long dst = (long)pc[0], src = (long)pc[2], len = (long)pc[3], k = w - dst;
+    if (w >= dst && k < len) {
+      if (pc[1] == 0) c = screen_code(cx, C, src + k);
+      else if (pc[1] == 1) c = screen_complement(screen_code(cx, C, src + len - 1 - k));
+      else if (pc[1] == 2) c = screen_code(pay, npay, src + k);
     }
   }
   out[t] = (unsigned char)(c > 4u ? 4u : c);
 }
 
-// splice table (int64 per edit, 3 fields): [row_lo, row_cnt, src_row] - rows [row_lo, row_lo + row_cnt) of edit b's image come from rows
-// [src_row, ..) of `fresh`, every other row from `ref`.  One thread per 16-byte unit of the output [B][n5][128].
-static __global__ void screen_splice_rows_kernel(const f32x4* __restrict__ ref, long n5, const f32x4* __restrict__ fresh, long nfresh,
-                                                 const long long* __restrict__ tab, int B, f32x4* __restrict__ out) {
+// ---- the row images: three segment formats (orca_screen_splice_rows, _splice_rows_multi, _gather_rows) -----------------------------------------------------
+// A segment says that rows [row_lo, row_lo + row_cnt) of an image come from elsewhere; a row in no segment is `ref` at its own index.
+//   splice table (int64 per image, 3 fields): [row_lo, row_cnt, src_row] - image b has the one segment b, from rows [src_row, ..) of `fresh`
+//   segment table (3 fields, the same) with offsets: image b owns segments [seg_off[b], seg_off[b + 1]), sorted by row_lo and disjoint
+//   gather table (SCREEN_GATHER_FIELDS fields) with offsets: [row_lo, row_cnt, source, src_row] - source -1: rows [src_row, ..) of `fresh`; -2: rows
+//   [src_row, ..) of `ref`; p >= 0: row row_lo + t is the MaxPool1d(5) of rows src_row + 5 t .. + 4 of phase entry p (`entries[p]`, `entry_rows[p]` rows
+//   of 128 floats).  The pooling expression is rows_pool5_into_kernel's (p16_planes.h): the same bits.
+// One thread per 16-byte unit of the output [B][n5][128]: binary search of the image's segments for the last one with row_lo <= r.  The segment range
+// is clipped to the table, every source row to its buffer (a row that would leave it is `ref` at its own index).
+#define SCREEN_GATHER_FIELDS 4
+
+// FIELDS columns per segment, src_row the last; RANGED: image b's segments by seg_off, else segment b; SOURCES: the source column, else all from `fresh`
+template <int FIELDS, bool RANGED, bool SOURCES>
+static __device__ __forceinline__ void screen_row_images(const f32x4* __restrict__ ref, long n5, const f32x4* __restrict__ fresh, long nfresh,
+                                                         const f32x4* const* __restrict__ entries, const long long* __restrict__ entry_rows, int P,
+                                                         const long long* __restrict__ seg, long nseg, const long long* __restrict__ seg_off, int B,
+                                                         f32x4* __restrict__ out) {
   const long u = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long per = n5 * 32;
   if (u >= (long)B * per) return;
   const int b = (int)(u / per);
   const long r = (u - (long)b * per) >> 5, q = u & 31;
-  const long r0 = (long)tab[3 * b], cnt = (long)tab[3 * b + 1], s0 = (long)tab[3 * b + 2];
-  const long s = s0 + (r - r0);
-  out[u] = (r >= r0 && r < r0 + cnt && s >= 0 && s < nfresh) ? fresh[s * 32 + q] : ref[r * 32 + q];
+  const long long* g = seg + (long)FIELDS * b;
+  if constexpr (RANGED) g = screen_row_of<FIELDS, 0>(seg, nseg, (long)seg_off[b], (long)seg_off[b + 1], r);
+  const f32x4* from = ref + r * 32 + q;
+  bool pool = false;
+  if (g) {
+    const long r0 = (long)g[0], cnt = (long)g[1], k = r - r0;
+    long source = -1;
+    if constexpr (SOURCES) source = (long)g[2];
+    const long s = (long)g[FIELDS - 1] + (source >= 0 ? 5 : 1) * k;
+    if (r >= r0 && k < cnt) {
+      if (source == -1) {
+        if (s >= 0 && s < nfresh) from = fresh + s * 32 + q;
+      } else if constexpr (SOURCES) {
+        if (source == -2) {
+          if (s >= 0 && s < n5) from = ref + s * 32 + q;
+        } else if (source >= 0 && source < P && s >= 0 && s + 5 <= (long)entry_rows[source]) {
+          from = entries[source] + s * 32 + q;
+          pool = true;
+        }
+      }
+    }
+  }
+  f32x4 v = from[0];
+  if (pool) {
+#pragma unroll
+    for (int j = 1; j < 5; ++j) {
+      const f32x4 x = from[j * 32];
+      v.x = fmaxf(v.x, x.x); v.y = fmaxf(v.y, x.y); v.z = fmaxf(v.z, x.z); v.w = fmaxf(v.w, x.w);
+    }
+  }
+  out[u] = v;
+}
+
+static __global__ void screen_splice_rows_kernel(const f32x4* __restrict__ ref, long n5, const f32x4* __restrict__ fresh, long nfresh,
+                                                 const long long* __restrict__ tab, int B, f32x4* __restrict__ out) {
+  screen_row_images<3, false, false>(ref, n5, fresh, nfresh, nullptr, nullptr, 0, tab, B, nullptr, B, out);
+}
+
+static __global__ void screen_splice_rows_multi_kernel(const f32x4* __restrict__ ref, long n5, const f32x4* __restrict__ fresh, long nfresh,
+                                                       const long long* __restrict__ seg, long nseg, const long long* __restrict__ seg_off, int B,
+                                                       f32x4* __restrict__ out) {
+  screen_row_images<3, true, false>(ref, n5, fresh, nfresh, nullptr, nullptr, 0, seg, nseg, seg_off, B, out);
+}
+
+static __global__ void screen_gather_rows_kernel(const f32x4* __restrict__ ref, long n5, const f32x4* __restrict__ fresh, long nfresh,
+                                                 const f32x4* const* __restrict__ entries, const long long* __restrict__ entry_rows, int P,
+                                                 const long long* __restrict__ seg, long nseg, const long long* __restrict__ seg_off, int B,
+                                                 f32x4* __restrict__ out) {
+  screen_row_images<SCREEN_GATHER_FIELDS, true, true>(ref, n5, fresh, nfresh, entries, entry_rows, P, seg, nseg, seg_off, B, out);
 }
 
 // channel-last rows [B][n][128] -> out[b * so_b + c * so_c + j]
@@ -117,83 +232,6 @@ static __global__ void __launch_bounds__(512) screen_scores_kernel(const float* 
   }
 }
 
-// ---- compound edits (screen.EditSet): several disjoint spans applied to one snippet, several (snippet, row range) segments per image -------------------
-// snippet table (int64 per snippet, SCREEN_EDIT_FIELDS fields; include/orca_hip.h: orca_screen_edit_codes_multi)
-//   [0] out_off  [1] b0  [2] nb  as above     [3] span_lo  first span of this snippet in the span table     [4] span_cnt  spans of this snippet
-// span table (int64 per span, SCREEN_SPAN_FIELDS fields): [0] kind  [1] pos  [2] len  [3] pay_off - a snippet's spans are sorted by pos and
-// pairwise disjoint, so a binary search finds the one span that can hold a base.  An inversion reads its source from the unedited window.
-#define SCREEN_SPAN_FIELDS 4
-
-// one thread per output base: binary search of its snippet, binary search of the snippet's spans, then the window base with that span's
-// edit applied.  The span range is clipped to the table and every read is bounds-checked against L / npay (an out-of-range index reads as N).
-static __global__ void screen_edit_codes_multi_kernel(const unsigned char* __restrict__ win, long L, const long long* __restrict__ tab, int ns,
-                                                      const long long* __restrict__ spans, long nspans, const unsigned char* __restrict__ pay, long npay,
-                                                      unsigned char* __restrict__ out, long total) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  int lo = 0, hi = ns - 1;
-  while (lo < hi) {                                  // last snippet with out_off <= t
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[(long)mid * SCREEN_EDIT_FIELDS] <= t) lo = mid; else hi = mid - 1;
-  }
-  const long long* e = tab + (long)lo * SCREEN_EDIT_FIELDS;
-  const long w = (long)e[1] + (t - (long)e[0]);
-  unsigned c = (w >= 0 && w < L) ? win[w] : 4u;
-  long s0 = (long)e[3], s1 = (long)e[3] + (long)e[4];
-  s0 = s0 < 0 ? 0 : s0;
-  s1 = s1 > nspans ? nspans : s1;
-  if (s0 < s1) {
-    long a = s0, b = s1 - 1;
-    while (a < b) {                                  // last span with pos <= w (the first one when none is)
-      const long mid = (a + b + 1) >> 1;
-      if ((long)spans[mid * SCREEN_SPAN_FIELDS + 1] <= w) a = mid; else b = mid - 1;
-    }
-    const long long* sp = spans + a * SCREEN_SPAN_FIELDS;
-    const long pos = (long)sp[1], len = (long)sp[2];
-    if (w >= pos && w - pos < len) {
-      const long k = w - pos;
-      if (sp[0] == 0) {
-        const long p = (long)sp[3] + k;
-        c = (p >= 0 && p < npay) ? pay[p] : 4u;
-      } else if (sp[0] == 1) {
-        c = 4u;
-      } else {
-        const long src = pos + len - 1 - k;
-        const unsigned s = (src >= 0 && src < L) ? win[src] : 4u;
-        c = s < 4u ? 3u - s : 4u;                        // A<->T, C<->G; N stays N
-      }
-    }
-  }
-  out[t] = (unsigned char)(c > 4u ? 4u : c);
-}
-
-// segment table (int64 per segment, 3 fields): [row_lo, row_cnt, src_row] as the splice table above; image b owns segments
-// [seg_off[b], seg_off[b + 1]), sorted by row_lo and disjoint.  One thread per 16-byte unit of the output [B][n5][128]: binary search of the
-// image's segments for the last one with row_lo <= r.  The segment range is clipped to the table, the source row to `fresh`.
-static __global__ void screen_splice_rows_multi_kernel(const f32x4* __restrict__ ref, long n5, const f32x4* __restrict__ fresh, long nfresh,
-                                                       const long long* __restrict__ seg, long nseg, const long long* __restrict__ seg_off, int B,
-                                                       f32x4* __restrict__ out) {
-  const long u = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long per = n5 * 32;
-  if (u >= (long)B * per) return;
-  const int b = (int)(u / per);
-  const long r = (u - (long)b * per) >> 5, q = u & 31;
-  long s0 = (long)seg_off[b], s1 = (long)seg_off[b + 1];
-  s0 = s0 < 0 ? 0 : s0;
-  s1 = s1 > nseg ? nseg : s1;
-  f32x4 v = ref[r * 32 + q];
-  if (s0 < s1) {
-    long a = s0, z = s1 - 1;
-    while (a < z) {
-      const long mid = (a + z + 1) >> 1;
-      if ((long)seg[3 * mid] <= r) a = mid; else z = mid - 1;
-    }
-    const long r0 = (long)seg[3 * a], cnt = (long)seg[3 * a + 1], s = (long)seg[3 * a + 2] + (r - r0);
-    if (r >= r0 && r - r0 < cnt && s >= 0 && s < nfresh) v = fresh[s * 32 + q];
-  }
-  out[u] = v;
-}
-
 // region scores of B alt maps [B][n][n] (batch stride map_bs) against ref [n][n]: for rectangle k = (i0, i1, j0, j1) (int32, half open, inside
 // [0, n) - the host entry point checks it; clipped here all the same) signed[b][k] = mean of alt - ref, absm[b][k] = mean of |alt - ref|.
 // One workgroup per (map, rectangle).  The differences and both sums are fp64 (an fp32 difference is exact in fp64, so the signed mean keeps
@@ -227,115 +265,6 @@ static __global__ void __launch_bounds__(256) screen_region_scores_kernel(const 
     signed_out[(long)b * K + k] = (float)(t / cnt);
     abs_out[(long)b * K + k] = (float)(ta / cnt);
   }
-}
-
-// ---- insertions and deletions (screen.Edit "del" / "ins"): the edited bases from a piece list, the row images from several sources ---------------------
-// The alt window of an item is a list of PIECES in alt coordinates; the context is the window followed by its right flank.
-// snippet table (int64 per snippet, SCREEN_EDIT_FIELDS fields; include/orca_hip.h: orca_screen_assemble_codes)
-//   [0] out_off  [1] a0  first ALT base of the snippet  [2] nb  [3] piece_lo  first piece of this snippet in the piece table  [4] piece_cnt
-// piece table (int64 per piece, SCREEN_PIECE_FIELDS fields): [0] dst  first alt base  [1] kind  [2] src  [3] len - a snippet's pieces are sorted by
-// dst and pairwise disjoint.  kind 0: context bases [src, src + len) forward; 1: their reverse complement (alt base dst + t is the complement of
-// context[src + len - 1 - t], N stays N); 2: payload codes [src, src + len); 3: N.
-#define SCREEN_PIECE_FIELDS 4
-
-// one thread per output base: binary search of its snippet, binary search of the snippet's pieces.  The piece range is clipped to the table; a base no
-// piece covers and a read outside the context / the payload give N.
-static __global__ void screen_assemble_codes_kernel(const unsigned char* __restrict__ cx, long C, const long long* __restrict__ tab, int ns,
-                                                    const long long* __restrict__ pieces, long npieces, const unsigned char* __restrict__ pay, long npay,
-                                                    unsigned char* __restrict__ out, long total) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  int lo = 0, hi = ns - 1;
-  while (lo < hi) {                                  // last snippet with out_off <= t
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[(long)mid * SCREEN_EDIT_FIELDS] <= t) lo = mid; else hi = mid - 1;
-  }
-  const long long* e = tab + (long)lo * SCREEN_EDIT_FIELDS;
-  const long w = (long)e[1] + (t - (long)e[0]);
-  unsigned c = 4u;
-  long s0 = (long)e[3], s1 = (long)e[3] + (long)e[4];
-  s0 = s0 < 0 ? 0 : s0;
-  s1 = s1 > npieces ? npieces : s1;
-  if (s0 < s1) {
-    long a = s0, b = s1 - 1;
-    while (a < b) {                                  // last piece with dst <= w (the first one when none is)
-      const long mid = (a + b + 1) >> 1;
-      if ((long)pieces[mid * SCREEN_PIECE_FIELDS] <= w) a = mid; else b = mid - 1;
-    }
-    const long long* pc = pieces + a * SCREEN_PIECE_FIELDS;
-    const long dst = (long)pc[0], src = (long)pc[2], len = (long)pc[3];
-    if (w >= dst && w - dst < len) {
-      const long k = w - dst;
-      if (pc[1] == 0) {
-        const long p = src + k;
-        c = (p >= 0 && p < C) ? cx[p] : 4u;
-      } else if (pc[1] == 1) {
-        const long p = src + len - 1 - k;
-        const unsigned s = (p >= 0 && p < C) ? cx[p] : 4u;
-        c = s < 4u ? 3u - s : 4u;                        // A<->T, C<->G; N stays N
-      } else if (pc[1] == 2) {
-        const long p = src + k;
-        c = (p >= 0 && p < npay) ? pay[p] : 4u;
-      }
-    }
-  }
-  out[t] = (unsigned char)(c > 4u ? 4u : c);
-}
-
-// segment table (int64 per segment, SCREEN_GATHER_FIELDS fields): [row_lo, row_cnt, source, src_row]; image b owns segments [seg_off[b], seg_off[b + 1]),
-// sorted by row_lo and disjoint.  source -1: rows [src_row, ..) of `fresh`; -2: rows [src_row, ..) of `ref`; p >= 0: row row_lo + t is the MaxPool1d(5) of
-// rows src_row + 5 t .. + 4 of phase entry p (`entries[p]`, `entry_rows[p]` rows of 128 floats).  A row in no segment is `ref` at its own index.
-// One thread per 16-byte unit of the output [B][n5][128].  The segment range is clipped to the table, every source row to its buffer (a row that
-// would leave it is `ref` at its own index).  The pooling expression is rows_pool5_into_kernel's (p16_planes.h): the same bits.
-#define SCREEN_GATHER_FIELDS 4
-
-static __global__ void screen_gather_rows_kernel(const f32x4* __restrict__ ref, long n5, const f32x4* __restrict__ fresh, long nfresh,
-                                                 const f32x4* const* __restrict__ entries, const long long* __restrict__ entry_rows, int P,
-                                                 const long long* __restrict__ seg, long nseg, const long long* __restrict__ seg_off, int B,
-                                                 f32x4* __restrict__ out) {
-  const long u = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long per = n5 * 32;
-  if (u >= (long)B * per) return;
-  const int b = (int)(u / per);
-  const long r = (u - (long)b * per) >> 5, q = u & 31;
-  long s0 = (long)seg_off[b], s1 = (long)seg_off[b + 1];
-  s0 = s0 < 0 ? 0 : s0;
-  s1 = s1 > nseg ? nseg : s1;
-  const f32x4* from = ref + r * 32 + q;
-  bool pool = false;
-  if (s0 < s1) {
-    long a = s0, z = s1 - 1;
-    while (a < z) {
-      const long mid = (a + z + 1) >> 1;
-      if ((long)seg[SCREEN_GATHER_FIELDS * mid] <= r) a = mid; else z = mid - 1;
-    }
-    const long long* g = seg + SCREEN_GATHER_FIELDS * a;
-    const long r0 = (long)g[0], cnt = (long)g[1], source = (long)g[2], k = r - r0;
-    if (r >= r0 && k < cnt) {
-      if (source == -1) {
-        const long s = (long)g[3] + k;
-        if (s >= 0 && s < nfresh) from = fresh + s * 32 + q;
-      } else if (source == -2) {
-        const long s = (long)g[3] + k;
-        if (s >= 0 && s < n5) from = ref + s * 32 + q;
-      } else if (source >= 0 && source < P) {
-        const long s = (long)g[3] + 5 * k;
-        if (s >= 0 && s + 5 <= (long)entry_rows[source]) {
-          from = entries[source] + s * 32 + q;
-          pool = true;
-        }
-      }
-    }
-  }
-  f32x4 v = from[0];
-  if (pool) {
-#pragma unroll
-    for (int j = 1; j < 5; ++j) {
-      const f32x4 x = from[j * 32];
-      v.x = fmaxf(v.x, x.x); v.y = fmaxf(v.y, x.y); v.z = fmaxf(v.z, x.z); v.w = fmaxf(v.w, x.w);
-    }
-  }
-  out[u] = v;
 }
 
 // ---- aligned scores (screen.bin_map): alt bin i stands for reference bin map[i], or for none (-1) -------------------------------------------------------

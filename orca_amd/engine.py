@@ -634,15 +634,24 @@ def encoder_back5_batch(net, rows, out=None):
     return out
 
 
+def _maps_args(alt, ref):
+    """alt [B, n, n] (any batch stride, rows contiguous) and ref [n, n] of the score entry points: (alt, ref, n)."""
+    alt, ref = _f32_cuda(alt, "alt"), _f32_cuda(ref, "ref").contiguous()
+    n = ref.shape[0]
+    if alt.dim() != 3 or ref.dim() != 2 or tuple(alt.shape[1:]) != (n, n) or alt.stride(2) != 1 or alt.stride(1) != n or tuple(ref.shape) != (n, n):
+        raise ValueError(f"alt [B,{n},{n}] with contiguous maps, ref [{n},{n}]")
+    return alt, ref, n
+
+
+def _f32_outputs(device, *shapes):
+    return tuple(torch.empty(s, dtype=torch.float32, device=device) for s in shapes)
+
+
 def screen_scores(ctx, alt, ref):
     """alt [B, n, n] (any batch stride, rows contiguous) against ref [n, n]: (profile [B, n], mean [B], max [B]) of |alt - ref|."""
-    alt, ref = _f32_cuda(alt, "alt"), _f32_cuda(ref, "ref").contiguous()
-    B, n = alt.shape[0], ref.shape[0]
-    if alt.dim() != 3 or tuple(alt.shape[1:]) != (n, n) or alt.stride(2) != 1 or alt.stride(1) != n or tuple(ref.shape) != (n, n):
-        raise ValueError(f"alt [B,{n},{n}] with contiguous maps, ref [{n},{n}]")
-    profile = torch.empty((B, n), dtype=torch.float32, device=alt.device)
-    mean = torch.empty((B,), dtype=torch.float32, device=alt.device)
-    amax = torch.empty((B,), dtype=torch.float32, device=alt.device)
+    alt, ref, n = _maps_args(alt, ref)
+    B = alt.shape[0]
+    profile, mean, amax = _f32_outputs(alt.device, (B, n), (B,), (B,))
     ctx.sync_stream()
     check(_lib.load().orca_screen_scores(ctx.handle, _p(alt), alt.stride(0), _p(ref), B, n, _p(profile), _p(mean), _p(amax)), "orca_screen_scores")
     return profile, mean, amax
@@ -678,21 +687,39 @@ def _dev_p(t):
     return ctypes.c_void_p(t.data_ptr() if t.numel() else 0)
 
 
+def _screen_codes(entry, ctx, src, name, size, table_host, sub_host, sub_name, payload, out):
+    """The call of orca_screen_edit_codes_multi / _assemble_codes: bases of ``src`` (``name``, [``size``] uint8) into ``out`` by the snippet table and its
+    4-field sub-table ``sub_name``, both numpy on the host and uploaded here."""
+    src, out = _on_device(src, name, torch.uint8), _on_device(out, "out", torch.uint8)
+    if src.dim() != 1 or out.dim() != 1:
+        raise ValueError(f"{name}, out: [{size}] and [total] uint8")
+    if payload is not None:
+        payload = _on_device(payload, "payload", torch.uint8)
+    t, s = _host_table(table_host, np.int64, SCREEN_EDIT_FIELDS, "snippet table"), _host_table(sub_host, np.int64, 4, sub_name)
+    td, sd = torch.from_numpy(t).to(src.device), torch.from_numpy(s).to(src.device)
+    ctx.sync_stream()
+    check(getattr(_lib.load(), entry)(ctx.handle, _dev_p(src), src.numel(), _dev_p(td), _np_p(t), t.shape[0], _dev_p(sd), _np_p(s), s.shape[0],
+                                      ctypes.c_void_p(0) if payload is None else _dev_p(payload), 0 if payload is None else payload.numel(),
+                                      _dev_p(out), out.numel()), entry)
+    return out
+
+
 def screen_edit_codes_multi(ctx, window, table_host, spans_host, payload, out):
     """Edited snippets of ``window`` [L] uint8 into ``out`` [total] with any number of spans per snippet (orca_screen_edit_codes_multi).
     ``table_host`` [k, 8] int64 numpy = [out_off, b0, nb, span_lo, span_cnt, 0, 0, 0]; ``spans_host`` [s, 4] int64 numpy = [kind, pos, len, pay_off]."""
-    window, out = _on_device(window, "window", torch.uint8), _on_device(out, "out", torch.uint8)
-    if window.dim() != 1 or out.dim() != 1:
-        raise ValueError("window, out: [L] and [total] uint8")
-    if payload is not None:
-        payload = _on_device(payload, "payload", torch.uint8)
-    t, s = _host_table(table_host, np.int64, SCREEN_EDIT_FIELDS, "snippet table"), _host_table(spans_host, np.int64, SCREEN_SPAN_FIELDS, "span table")
-    td, sd = torch.from_numpy(t).to(window.device), torch.from_numpy(s).to(window.device)
-    ctx.sync_stream()
-    check(_lib.load().orca_screen_edit_codes_multi(ctx.handle, _p(window), window.numel(), _dev_p(td), _np_p(t), t.shape[0], _dev_p(sd), _np_p(s), s.shape[0],
-                                                   ctypes.c_void_p(0) if payload is None else _dev_p(payload), 0 if payload is None else payload.numel(),
-                                                   _dev_p(out), out.numel()), "orca_screen_edit_codes_multi")
-    return out
+    return _screen_codes("orca_screen_edit_codes_multi", ctx, window, "window", "L", table_host, spans_host, "span table", payload, out)
+
+
+def _segment_args(segments_host, cols, seg_off_host, out, n5):
+    """A segment table of ``cols`` fields with its offsets, and the images ``out`` they describe: (table, offsets, B)."""
+    g = _host_table(segments_host, np.int64, cols, "segment table")
+    o = np.ascontiguousarray(seg_off_host, dtype=np.int64)
+    if o.ndim != 1 or o.size < 1:
+        raise ValueError("segment offsets: [B + 1] int64")
+    B = o.size - 1
+    if out.dim() != 3 or tuple(out.shape) != (B, n5, 128):
+        raise ValueError(f"out: a contiguous [{B},{n5},128] float32 ROCm tensor, B + 1 = the number of segment offsets")
+    return g, o, B
 
 
 def screen_splice_rows_multi(ctx, ref, fresh, segments_host, seg_off_host, out):
@@ -702,13 +729,7 @@ def screen_splice_rows_multi(ctx, ref, fresh, segments_host, seg_off_host, out):
     if ref.dim() != 2 or ref.shape[1] != 128 or fresh.dim() != 2 or fresh.shape[1] != 128:
         raise ValueError("ref, fresh: [n,128] float32")
     n5 = ref.shape[0]
-    g = _host_table(segments_host, np.int64, 3, "segment table")
-    o = np.ascontiguousarray(seg_off_host, dtype=np.int64)
-    if o.ndim != 1 or o.size < 1:
-        raise ValueError("segment offsets: [B + 1] int64")
-    B = o.size - 1
-    if out.dim() != 3 or tuple(out.shape) != (B, n5, 128):
-        raise ValueError(f"out: a contiguous [{B},{n5},128] float32 ROCm tensor, B + 1 = the number of segment offsets")
+    g, o, B = _segment_args(segments_host, 3, seg_off_host, out, n5)
     gd, od = torch.from_numpy(g).to(ref.device), torch.from_numpy(o).to(ref.device)
     ctx.sync_stream()
     check(_lib.load().orca_screen_splice_rows_multi(ctx.handle, _dev_p(ref), n5, _dev_p(fresh), fresh.shape[0], _dev_p(gd), _np_p(g), g.shape[0], _dev_p(od), _np_p(o),
@@ -727,18 +748,7 @@ def screen_assemble_codes(ctx, context, table_host, pieces_host, payload, out):
     """Alt bases from piece lists over ``context`` [C] uint8 (the window followed by its right flank) into ``out`` [total]
     (orca_screen_assemble_codes).  ``table_host`` [k, 8] int64 numpy = [out_off, a0, nb, piece_lo, piece_cnt, 0, 0, 0] (a0 in alt coordinates);
     ``pieces_host`` [n, 4] int64 numpy = [dst, kind, src, len], kind 0 context forward, 1 its reverse complement, 2 payload, 3 N."""
-    context, out = _on_device(context, "context", torch.uint8), _on_device(out, "out", torch.uint8)
-    if context.dim() != 1 or out.dim() != 1:
-        raise ValueError("context, out: [C] and [total] uint8")
-    if payload is not None:
-        payload = _on_device(payload, "payload", torch.uint8)
-    t, s = _host_table(table_host, np.int64, SCREEN_EDIT_FIELDS, "snippet table"), _host_table(pieces_host, np.int64, SCREEN_PIECE_FIELDS, "piece table")
-    td, sd = torch.from_numpy(t).to(context.device), torch.from_numpy(s).to(context.device)
-    ctx.sync_stream()
-    check(_lib.load().orca_screen_assemble_codes(ctx.handle, _dev_p(context), context.numel(), _dev_p(td), _np_p(t), t.shape[0], _dev_p(sd), _np_p(s), s.shape[0],
-                                                 ctypes.c_void_p(0) if payload is None else _dev_p(payload), 0 if payload is None else payload.numel(),
-                                                 _dev_p(out), out.numel()), "orca_screen_assemble_codes")
-    return out
+    return _screen_codes("orca_screen_assemble_codes", ctx, context, "context", "C", table_host, pieces_host, "piece table", payload, out)
 
 
 def screen_gather_rows(ctx, ref, fresh, entries, segments_host, seg_off_host, out):
@@ -753,13 +763,7 @@ def screen_gather_rows(ctx, ref, fresh, entries, segments_host, seg_off_host, ou
     if any(e.dim() != 2 or e.shape[1] != 128 or e.data_ptr() % 16 for e in entries):
         raise ValueError("phase entries: [n,128] float32, 16-byte aligned")
     n5 = ref.shape[0]
-    g = _host_table(segments_host, np.int64, SCREEN_GATHER_FIELDS, "segment table")
-    o = np.ascontiguousarray(seg_off_host, dtype=np.int64)
-    if o.ndim != 1 or o.size < 1:
-        raise ValueError("segment offsets: [B + 1] int64")
-    B = o.size - 1
-    if out.dim() != 3 or tuple(out.shape) != (B, n5, 128):
-        raise ValueError(f"out: a contiguous [{B},{n5},128] float32 ROCm tensor, B + 1 = the number of segment offsets")
+    g, o, B = _segment_args(segments_host, SCREEN_GATHER_FIELDS, seg_off_host, out, n5)
     ptrs = np.array([e.data_ptr() for e in entries], dtype=np.int64)
     cnts = np.array([e.shape[0] for e in entries], dtype=np.int64)
     gd, od, pd, cd = (torch.from_numpy(a).to(ref.device) for a in (g, o, ptrs, cnts))
@@ -772,15 +776,11 @@ def screen_gather_rows(ctx, ref, fresh, entries, segments_host, seg_off_host, ou
 def screen_region_scores(ctx, alt, ref, rects_host):
     """alt [B, n, n] (any batch stride, rows contiguous) against ref [n, n] over the K rectangles ``rects_host`` [K, 4] = (i0, i1, j0, j1), half open:
     (mean of alt - ref [B, K], mean of |alt - ref| [B, K]) (orca_screen_region_scores)."""
-    alt, ref = _f32_cuda(alt, "alt"), _f32_cuda(ref, "ref").contiguous()
-    n = ref.shape[0]
-    if alt.dim() != 3 or ref.dim() != 2 or tuple(alt.shape[1:]) != (n, n) or alt.stride(2) != 1 or alt.stride(1) != n or tuple(ref.shape) != (n, n):
-        raise ValueError(f"alt [B,{n},{n}] with contiguous maps, ref [{n},{n}]")
+    alt, ref, n = _maps_args(alt, ref)
     r = _host_table(rects_host, np.int32, 4, "rectangles")
     B, K = alt.shape[0], r.shape[0]
     rd = torch.from_numpy(r).to(alt.device)
-    sg = torch.empty((B, K), dtype=torch.float32, device=alt.device)
-    ab = torch.empty((B, K), dtype=torch.float32, device=alt.device)
+    sg, ab = _f32_outputs(alt.device, (B, K), (B, K))
     ctx.sync_stream()
     check(_lib.load().orca_screen_region_scores(ctx.handle, _dev_p(alt), alt.stride(0), _p(ref), B, n, _dev_p(rd), _np_p(r), K, _dev_p(sg), _dev_p(ab)),
           "orca_screen_region_scores")
@@ -792,10 +792,7 @@ SCREEN_ALIGNED_MAX_BINS = 256
 
 
 def _aligned_args(alt, ref, bin_map_host, bin_map):
-    alt, ref = _f32_cuda(alt, "alt"), _f32_cuda(ref, "ref").contiguous()
-    n = ref.shape[0]
-    if alt.dim() != 3 or ref.dim() != 2 or tuple(alt.shape[1:]) != (n, n) or alt.stride(2) != 1 or alt.stride(1) != n or tuple(ref.shape) != (n, n):
-        raise ValueError(f"alt [B,{n},{n}] with contiguous maps, ref [{n},{n}]")
+    alt, ref, n = _maps_args(alt, ref)
     m = _host_table(bin_map_host, np.int32, n, "bin map")
     if m.shape[0] != alt.shape[0]:
         raise ValueError(f"bin map: [{alt.shape[0]},{n}] int32, one row per alt map")
@@ -811,9 +808,7 @@ def screen_aligned_scores(ctx, alt, ref, bin_map_host, bin_map=None):
     |alt[i, j] - ref[map i, map j]| over the mapped bins, NaN where nothing is mapped."""
     alt, ref, m, md = _aligned_args(alt, ref, bin_map_host, bin_map)
     B, n = m.shape
-    profile = torch.empty((B, n), dtype=torch.float32, device=alt.device)
-    mean = torch.empty((B,), dtype=torch.float32, device=alt.device)
-    amax = torch.empty((B,), dtype=torch.float32, device=alt.device)
+    profile, mean, amax = _f32_outputs(alt.device, (B, n), (B,), (B,))
     ctx.sync_stream()
     check(_lib.load().orca_screen_aligned_scores(ctx.handle, _dev_p(alt), alt.stride(0), _p(ref), B, n, _dev_p(md), _np_p(m), _dev_p(profile), _dev_p(mean),
                                                  _dev_p(amax)), "orca_screen_aligned_scores")
@@ -829,8 +824,7 @@ def screen_aligned_region_scores(ctx, alt, ref, bin_map_host, rects_host, bin_ma
     r = _host_table(rects_host, np.int32, 4, "rectangles")
     K = r.shape[0]
     rd = torch.from_numpy(r).to(alt.device)
-    sg = torch.empty((B, K), dtype=torch.float32, device=alt.device)
-    ab = torch.empty((B, K), dtype=torch.float32, device=alt.device)
+    sg, ab = _f32_outputs(alt.device, (B, K), (B, K))
     ctx.sync_stream()
     check(_lib.load().orca_screen_aligned_region_scores(ctx.handle, _dev_p(alt), alt.stride(0), _p(ref), B, n, _dev_p(md), _np_p(m), _dev_p(rd), _np_p(r), K,
                                                         _dev_p(sg), _dev_p(ab)), "orca_screen_aligned_region_scores")

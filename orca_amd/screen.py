@@ -510,23 +510,35 @@ def set_clusters(item, L, margin=MARGIN_BP):
     return [(a, b) for a, b in out]
 
 
+def _item_table(items, rows_of):
+    """Every item's rows of a 4-field sub-table (spans / pieces), item by item: (table [n, 4] int64, first row of every item [E + 1], payload,
+    per-item row lists).  ``rows_of(item, pay_off)`` = (the item's rows, its payload codes), ``pay_off`` its first code's place in the payload."""
+    rows, lists, pay, npay = [], [], [], 0
+    base = np.zeros(len(items) + 1, dtype=np.int64)
+    for i, it in enumerate(items):
+        mine, py = rows_of(it, npay)
+        lists.append(mine)
+        rows += mine
+        pay.append(py)
+        npay += py.size
+        base[i + 1] = len(rows)
+    return np.array(rows, dtype=np.int64).reshape(-1, 4), base, (np.concatenate(pay) if pay else np.zeros(0, dtype=np.uint8)), lists
+
+
+def _item_spans(item, pay_off=0):
+    """The members of ``item`` as spans: ([(kind, pos, len, pay_off)], payload codes)."""
+    out, pay = [], [np.zeros(0, dtype=np.uint8)]
+    for e in members_of(item):
+        out.append((engine.SCREEN_KINDS[e.kind], e.pos, e.length, pay_off if e.kind == "sub" else 0))
+        if e.kind == "sub":
+            pay.append(e.seq)
+            pay_off += e.length
+    return out, np.concatenate(pay)
+
+
 def _span_table(items):
     """(span table [n, 4] int64, first span of every item [E + 1], payload): every item's members, item by item."""
-    n = sum(len(members_of(it)) for it in items)
-    spans = np.zeros((n, engine.SCREEN_SPAN_FIELDS), dtype=np.int64)
-    base = np.zeros(len(items) + 1, dtype=np.int64)
-    payload, npay, k = [], 0, 0
-    for i, it in enumerate(items):
-        for e in members_of(it):
-            po = 0
-            if e.kind == "sub":
-                po = npay
-                payload.append(e.seq)
-                npay += e.length
-            spans[k] = (engine.SCREEN_KINDS[e.kind], e.pos, e.length, po)
-            k += 1
-        base[i + 1] = k
-    return spans, base, (np.concatenate(payload) if payload else np.zeros(0, dtype=np.uint8))
+    return _item_table(items, _item_spans)[:3]
 
 
 def _spans_meeting(spans, lo, hi, b0, b1):
@@ -635,17 +647,7 @@ def _pieces_meeting(pieces, lo, hi, a0, a1):
 
 def _piece_table(items, L, F):
     """(piece table [n, 4] int64, first piece of every item [E + 1], payload, per-item piece lists): every item's pieces, item by item."""
-    rows, lists, pay, npay = [], [], [], 0
-    base = np.zeros(len(items) + 1, dtype=np.int64)
-    for i, it in enumerate(items):
-        pcs, py = item_pieces(it, L, F, npay)
-        lists.append(pcs)
-        rows += pcs
-        pay.append(py)
-        npay += py.size
-        base[i + 1] = len(rows)
-    return (np.array(rows, dtype=np.int64).reshape(-1, engine.SCREEN_PIECE_FIELDS), base,
-            (np.concatenate(pay) if pay else np.zeros(0, dtype=np.uint8)), lists)
+    return _item_table(items, lambda it, pay_off: item_pieces(it, L, F, pay_off))
 
 
 def _pack(snips, rows, L, run_max):
@@ -670,6 +672,27 @@ def _pack(snips, rows, L, run_max):
     return order, out_off, fresh, n_fresh, runs
 
 
+def _layout(fresh_runs, L, pad, min_snippet, run_max, sub, base, meeting):
+    """The layout both planners share, from every item's runs of rows that go through the front (``fresh_runs[i]`` = [(r0, r1)] ascending): one
+    snippet per run, item by item, packed into front runs (`_pack`); the snippet table in buffer order, snippet k carrying the rows of ``sub``
+    (item i's at [base[i], base[i + 1])) that ``meeting`` finds on its bases; and the fresh segments.  The `BatchPlan` fields of all that."""
+    rows_l = [r for mine in fresh_runs for r in mine]
+    item_of = [i for i, mine in enumerate(fresh_runs) for _ in mine]
+    snips = [edit_snippet(r0, r1, L, pad, min_snippet) for r0, r1 in rows_l]
+    S = len(snips)
+    rows = np.array(rows_l, dtype=np.int64).reshape(S, 2)
+    order, out_off, fresh, n_fresh, runs = _pack(snips, rows, L, run_max)
+    snippet_table = np.zeros((S, engine.SCREEN_EDIT_FIELDS), dtype=np.int64)
+    for k, i in enumerate(order):
+        it = item_of[i]
+        lo, cnt = meeting(sub, int(base[it]), int(base[it + 1]), snips[i][0], snips[i][1])
+        snippet_table[k, :5] = (out_off[i], snips[i][0], snips[i][1] - snips[i][0], lo, cnt)
+    return dict(L=L, snippet=np.array([(b0, b1 - b0) for b0, b1 in snips], dtype=np.int64).reshape(S, 2), rows=rows, order=order, runs=runs, fresh=fresh,
+                n_fresh=n_fresh, item_of=np.array(item_of, dtype=np.int64), snippet_table=snippet_table,
+                segments=np.stack([rows[:, 0], rows[:, 1] - rows[:, 0], fresh], axis=1).astype(np.int64).reshape(S, 3),
+                seg_off=np.cumsum([0] + [len(mine) for mine in fresh_runs], dtype=np.int64))
+
+
 def _plan_indels(edits, L, F, pad, margin, min_snippet, run_max):
     """`plan_batch` for a batch that holds a length-changing item: every item, the length-preserving ones too, as pieces and row sources.  A
     length-preserving item gets the clusters, snippets and fresh rows it gets alone (its pieces all have s = 0, so the rows outside every
@@ -677,39 +700,22 @@ def _plan_indels(edits, L, F, pad, margin, min_snippet, run_max):
     whichever run it lands."""
     E = len(edits)
     pieces, piece_off, payload, lists = _piece_table(edits, L, F)
-    rows_l, snips, item_of, served = [], [], [], []
-    seg_off = np.zeros(E + 1, dtype=np.int64)
-    for i, e in enumerate(edits):
-        segs, fresh_runs = item_sources(lists[i], L, F, margin)
-        served.append(segs)
-        for r0, r1 in fresh_runs:
-            rows_l.append((r0, r1))
-            snips.append(edit_snippet(r0, r1, L, pad, min_snippet))
-            item_of.append(i)
-        seg_off[i + 1] = len(snips)
-    S = len(snips)
-    rows = np.array(rows_l, dtype=np.int64).reshape(S, 2)
-    order, out_off, fresh, n_fresh, runs = _pack(snips, rows, L, run_max)
-    snippet_table = np.zeros((S, engine.SCREEN_EDIT_FIELDS), dtype=np.int64)
-    for k, i in enumerate(order):
-        it = item_of[i]
-        lo, cnt = _pieces_meeting(pieces, int(piece_off[it]), int(piece_off[it + 1]), snips[i][0], snips[i][1])
-        snippet_table[k, :5] = (out_off[i], snips[i][0], snips[i][1] - snips[i][0], lo, cnt)
-    segments = np.stack([rows[:, 0], rows[:, 1] - rows[:, 0], fresh], axis=1).astype(np.int64).reshape(S, 3)
+    sources = [item_sources(pcs, L, F, margin) for pcs in lists]
+    served = [segs for segs, _ in sources]
+    p = _layout([mine for _, mine in sources], L, pad, min_snippet, run_max, pieces, piece_off, _pieces_meeting)
     phases = sorted({g[2] for segs in served for g in segs if g[2] >= 0})
     index = {ph: k for k, ph in enumerate(phases)}
     gather, gather_off, take_rows = [], np.zeros(E + 1, dtype=np.int64), 0
     for i in range(E):
-        mine = [(int(r0), int(cnt), engine.SCREEN_SRC_FRESH, int(src)) for r0, cnt, src in segments[seg_off[i]: seg_off[i + 1]]]
+        mine = [(int(r0), int(cnt), engine.SCREEN_SRC_FRESH, int(src)) for r0, cnt, src in p["segments"][p["seg_off"][i]: p["seg_off"][i + 1]]]
         for r0, cnt, source, src in served[i]:
             mine.append((r0, cnt, index[source] if source >= 0 else source, src))
             take_rows += cnt if source >= 0 else 0
         gather += sorted(mine)
         gather_off[i + 1] = len(gather)
-    return BatchPlan(L, np.array([(b0, b1 - b0) for b0, b1 in snips], dtype=np.int64).reshape(S, 2), rows, order, runs, fresh, n_fresh, None, None,
-                     payload, np.array(item_of, dtype=np.int64), snippet_table, None, segments, seg_off, True, F, pieces, piece_off,
-                     np.array(gather, dtype=np.int64).reshape(-1, engine.SCREEN_GATHER_FIELDS), gather_off, phases,
-                     [entry_rows(L + F, ph) for ph in phases], take_rows, np.array([shift_of(e) for e in edits], dtype=np.int64))
+    return BatchPlan(edit_table=None, splice_table=None, payload=payload, indel=True, flank=F, piece_table=pieces, piece_off=piece_off,
+                     gather_segments=np.array(gather, dtype=np.int64).reshape(-1, engine.SCREEN_GATHER_FIELDS), gather_off=gather_off, phases=phases,
+                     entry_rows=[entry_rows(L + F, ph) for ph in phases], take_rows=take_rows, shift=np.array([shift_of(e) for e in edits], dtype=np.int64), **p)
 
 
 def plan_batch(edits, L, pad=PAD_BP, margin=MARGIN_BP, min_snippet=MIN_SNIPPET_BP, run_max=RUN_MAX_BP, flank=0):
@@ -721,93 +727,46 @@ def plan_batch(edits, L, pad=PAD_BP, margin=MARGIN_BP, min_snippet=MIN_SNIPPET_B
         raise ValueError("pad must cover the margin and be a multiple of 400")
     if not 0 <= int(flank) <= L:
         raise ValueError(f"flank of {flank} bases: 0 .. {L}")
-    if any(changes_length(e) for e in edits):
-        for e in edits:
-            e.check(L)
-        return _plan_indels(edits, L, int(flank), pad, margin, min_snippet, run_max)
-    E = len(edits)
-    rows_l, snips, item_of = [], [], []
-    seg_off = np.zeros(E + 1, dtype=np.int64)
-    for i, e in enumerate(edits):
+    indel = any(changes_length(e) for e in edits)
+    for e in edits:
         e.check(L)
-        for r0, r1 in set_clusters(e, L, margin):
-            rows_l.append((r0, r1))
-            snips.append(edit_snippet(r0, r1, L, pad, min_snippet))
-            item_of.append(i)
-        seg_off[i + 1] = len(snips)
-    S = len(snips)
-    rows = np.array(rows_l, dtype=np.int64).reshape(S, 2)
-    runs_idx = _runs(snips, L, run_max)
-    order = [i for r in runs_idx for i in r]
-    out_off = {}
-    off = 0
-    for i in order:
-        out_off[i] = off
-        off += snips[i][1] - snips[i][0]
-    fresh = np.zeros(S, dtype=np.int64)
-    n_fresh = 0
-    for i in order:
-        fresh[i] = n_fresh
-        n_fresh += int(rows[i, 1] - rows[i, 0])
-    runs = []
-    for r in runs_idx:
-        o0 = out_off[r[0]]
-        nb = sum(snips[i][1] - snips[i][0] for i in r)
-        ranges = [(int(out_off[i] - o0 + rows[i, 0] * ROW_BP - snips[i][0]) // ROW_BP, int(rows[i, 1] - rows[i, 0]), int(fresh[i])) for i in r]
-        runs.append((o0, nb, ranges))
+    if indel:
+        return _plan_indels(edits, L, int(flank), pad, margin, min_snippet, run_max)
     spans, span_base, payload = _span_table(edits)
-    snippet_table = np.zeros((S, engine.SCREEN_EDIT_FIELDS), dtype=np.int64)
-    for k, i in enumerate(order):
-        it = item_of[i]
-        lo, cnt = _spans_meeting(spans, int(span_base[it]), int(span_base[it + 1]), snips[i][0], snips[i][1])
-        snippet_table[k, :5] = (out_off[i], snips[i][0], snips[i][1] - snips[i][0], lo, cnt)
-    segments = np.stack([rows[:, 0], rows[:, 1] - rows[:, 0], fresh], axis=1).astype(np.int64).reshape(S, 3)
+    p = _layout([set_clusters(e, L, margin) for e in edits], L, pad, min_snippet, run_max, spans, span_base, _spans_meeting)
     table = splice = None
-    if len(spans) == E:                              # one member per item: the tables of the single-span kernels
-        table = np.zeros((E, engine.SCREEN_EDIT_FIELDS), dtype=np.int64)
-        for k, i in enumerate(order):
-            table[k, :7] = (out_off[i], snips[i][0], snips[i][1] - snips[i][0], *spans[i])
-        splice = segments.copy()
-    return BatchPlan(L, np.array([(b0, b1 - b0) for b0, b1 in snips], dtype=np.int64).reshape(S, 2), rows, order, runs, fresh, n_fresh, table, splice,
-                     payload, np.array(item_of, dtype=np.int64), snippet_table, spans, segments, seg_off)
+    if len(spans) == len(edits):                     # one member per item: the tables of the single-span kernels, snippet i = item i with its span
+        table, splice = p["snippet_table"].copy(), p["segments"].copy()
+        table[:, 3:7] = spans[p["order"]]
+    return BatchPlan(edit_table=table, splice_table=splice, payload=payload, span_table=spans, **p)
+
+
+def _whole_window(items, L, sub_table):
+    """The tables of the whole-window route: item i's complete edited window at bases [i L, (i + 1) L) of the output, one [0, L) snippet with all of
+    the item's rows of ``sub_table(items)`` = (sub-table, first row of every item, payload, ..) - (snippet table, sub-table, payload)."""
+    for it in items:
+        it.check(L)
+    sub, base, payload = sub_table(items)[:3]
+    table = np.zeros((len(items), engine.SCREEN_EDIT_FIELDS), dtype=np.int64)
+    table[:, 0], table[:, 2], table[:, 3], table[:, 4] = L * np.arange(len(items)), L, base[:-1], np.diff(base)
+    return table, sub, payload
 
 
 def whole_window_table(edits, L):
     """Edit table of the whole-window route: edit i's complete edited window at bases [i L, (i + 1) L) of the output."""
-    payload, npay, table = [], 0, np.zeros((len(edits), engine.SCREEN_EDIT_FIELDS), dtype=np.int64)
-    for i, e in enumerate(edits):
-        e.check(L)
-        po = 0
-        if e.kind == "sub":
-            po = npay
-            payload.append(e.seq)
-            npay += e.length
-        table[i, :7] = (i * L, 0, L, engine.SCREEN_KINDS[e.kind], e.pos, e.length, po)
-    return table, (np.concatenate(payload) if payload else np.zeros(0, dtype=np.uint8))
+    table, spans, payload = _whole_window(edits, L, _span_table)
+    table[:, 3:7] = spans                            # bare edits: the one span in the snippet's own row
+    return table, payload
 
 
 def whole_window_piece_tables(items, L, F):
-    """`whole_window_set_tables` for a batch with a length-changing item: (snippet table, piece table, payload) of orca_screen_assemble_codes -
-    item i's complete alt window at bases [i L, (i + 1) L) of the output, one [0, L) snippet with all of the item's pieces."""
-    for it in items:
-        it.check(L)
-    pieces, base, payload, _ = _piece_table(items, L, F)
-    table = np.zeros((len(items), engine.SCREEN_EDIT_FIELDS), dtype=np.int64)
-    for i in range(len(items)):
-        table[i, :5] = (i * L, 0, L, base[i], base[i + 1] - base[i])
-    return table, pieces, payload
+    """`whole_window_set_tables` for a batch with a length-changing item: (snippet table, piece table, payload) of orca_screen_assemble_codes."""
+    return _whole_window(items, L, lambda its: _piece_table(its, L, F))
 
 
 def whole_window_set_tables(items, L):
-    """`whole_window_table` for `Edit`s and `EditSet`s: (snippet table, span table, payload) of orca_screen_edit_codes_multi - item i's complete
-    edited window at bases [i L, (i + 1) L) of the output, carrying all of the item's spans."""
-    for it in items:
-        it.check(L)
-    spans, base, payload = _span_table(items)
-    table = np.zeros((len(items), engine.SCREEN_EDIT_FIELDS), dtype=np.int64)
-    for i in range(len(items)):
-        table[i, :5] = (i * L, 0, L, base[i], base[i + 1] - base[i])
-    return table, spans, payload
+    """`whole_window_table` for `Edit`s and `EditSet`s: (snippet table, span table, payload) of orca_screen_edit_codes_multi."""
+    return _whole_window(items, L, _span_table)
 
 
 # ---- scores ---------------------------------------------------------------------------------------------------------------------------------
@@ -1041,37 +1000,20 @@ class _Screen:
         self.stats["cache_phases"] = self.cache.builds
         return out
 
-    def two_part_indels(self, edits, s5_ref, p):
-        """`two_part` for a batch with a length-changing item: the bases of every snippet from the items' pieces, the row images from the
-        reference rows, the recomputed rows and the cache entries."""
-        enc = self.net._enc
-        total = int(p.snippet[:, 1].sum())
-        codes = torch.empty(total, dtype=torch.uint8, device=self.dev)
-        pay = self._upload(p.payload, torch.uint8) if p.payload.size else None
-        if total:                                        # no snippet at all: every row of every item is served (an ``ins`` behind the last base)
-            engine.screen_assemble_codes(self.ctx, self.context, p.snippet_table, p.piece_table, pay, codes)
-        fresh = torch.empty((p.n_fresh, 128), dtype=torch.float32, device=self.dev)
-        for o0, nb, ranges in p.runs:
-            enc.front4_ranges(codes[o0: o0 + nb], False, ranges, fresh)
-        rows = torch.empty((len(edits), self.n5, 128), dtype=torch.float32, device=self.dev)
-        engine.screen_gather_rows(self.ctx, s5_ref, fresh, self.build_entries(p.phases), p.gather_segments, p.gather_off, rows)
-        out = enc.back5_batch(rows)
-        self.stats["segments"] += len(p.segments)
-        self.stats["front_runs"] += len(p.runs)
-        self.stats["front_bases"] += total
-        self.stats["take_rows"] += p.take_rows
-        return self._decode(out)
-
     def two_part(self, edits, s5_ref, plan=None):
+        """Maps of a batch on the two-part route.  ``plan``: the batch's plan if it holds a length-changing item (`screen_1m` made it with the
+        reference) - then the bases of every snippet come from the items' pieces and the row images from the reference rows, the recomputed rows
+        and the cache entries; a list of bare `Edit`s runs the single-span kernels, as ever."""
         enc = self.net._enc
-        if plan is not None:
-            return self.two_part_indels(edits, s5_ref, plan)
-        p = plan_batch(edits, self.L)
+        p = plan_batch(edits, self.L) if plan is None else plan
         total = int(p.snippet[:, 1].sum())
         codes = torch.empty(total, dtype=torch.uint8, device=self.dev)
         pay = self._upload(p.payload, torch.uint8) if p.payload.size else None
-        single = all(isinstance(e, Edit) for e in edits)             # bare edits: the single-span kernels, as ever
-        if single:
+        single = all(isinstance(e, Edit) for e in edits)
+        if p.indel:
+            if total:                                    # no snippet at all: every row of every item is served (an ``ins`` behind the last base)
+                engine.screen_assemble_codes(self.ctx, self.context, p.snippet_table, p.piece_table, pay, codes)
+        elif single:
             engine.screen_edit_codes(self.ctx, self.window, p.edit_table, self._upload(p.edit_table, torch.int64), pay, codes)
         else:
             engine.screen_edit_codes_multi(self.ctx, self.window, p.snippet_table, p.span_table, pay, codes)
@@ -1079,7 +1021,9 @@ class _Screen:
         for o0, nb, ranges in p.runs:
             enc.front4_ranges(codes[o0: o0 + nb], False, ranges, fresh)
         rows = torch.empty((len(edits), self.n5, 128), dtype=torch.float32, device=self.dev)
-        if single:
+        if p.indel:
+            engine.screen_gather_rows(self.ctx, s5_ref, fresh, self.build_entries(p.phases), p.gather_segments, p.gather_off, rows)
+        elif single:
             engine.screen_splice_rows(self.ctx, s5_ref, fresh, self._upload(p.splice_table, torch.int64), rows)
         else:
             engine.screen_splice_rows_multi(self.ctx, s5_ref, fresh, p.segments, p.seg_off, rows)
@@ -1087,6 +1031,7 @@ class _Screen:
         self.stats["segments"] += len(p.segments)
         self.stats["front_runs"] += len(p.runs)
         self.stats["front_bases"] += total
+        self.stats["take_rows"] += p.take_rows
         return self._decode(out)
 
 
