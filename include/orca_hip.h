@@ -331,6 +331,18 @@ int orca_screen_aligned_region_scores(orca_ctx* ctx, const float* alt, int64_t m
                                       const int32_t* bin_map_host, const int32_t* rects, const int32_t* rects_host, int K, float* mean_signed,
                                       float* mean_abs);
 
+/* Both strands (screen.screen_1m(..., strands="both")): B maps of the '+' strand fwd[b * fwd_bs + i * n + j] and of the '-' strand rev[b * rev_bs + ..]
+ * (1 <= n <= 256, B >= 1, batch strides >= n * n) merged as genomepredict merges them (orca_predict.py:514-523):
+ *   out[b][i][j] = 0.5f * fwd[b][i][j] + 0.5f * rev[b][n-1-i][n-1-j]     bit for bit orca_strand_merge on each map
+ *   gap[b]       = mean_ij |(fwd[b] - ref_fwd)[i][j] - (rev[b] - ref_rev)[n-1-i][n-1-j]|   with the two strands' reference maps ref_fwd, ref_rev [n][n]:
+ *                  how far the strands disagree about the item's effect.  Differences and sums in fp64 in an order fixed by n alone (no atomics): a
+ *                  map's gap does not depend on B or on its place in the batch
+ * gap == NULL or ref_fwd == NULL: only `out` is written and no reference is read (the form that merges the reference itself, B = 1).  A NaN propagates
+ * into out and gap.  `out` may be `fwd` (every element is read and written by one thread); `rev` must not overlap `out`.  Anything else is ORCA_EINVAL
+ * before any launch. */
+int orca_screen_merge_strands(orca_ctx* ctx, const float* fwd, int64_t fwd_bs, const float* rev, int64_t rev_bs, const float* ref_fwd, const float* ref_rev,
+                              int B, int n, float* out, int64_t out_bs, float* gap);
+
 /* Number of 4 kb bins Encoder emits for an L-bp input (floor through the
  * 4,4,5,5,5,2 pooling chain). */
 int64_t orca_encoder_num_bins(int64_t L);

@@ -233,3 +233,22 @@ extern "C" int orca_screen_aligned_region_scores(orca_ctx* ctx, const float* alt
   return launch(ctx, "screen_aligned_region_scores_kernel", screen_aligned_region_scores_kernel, dim3((unsigned)B, (unsigned)K), 256, alt, (long)map_bs, ref, n, bin_map,
                 rects, K, mean_signed, mean_abs);
 }
+
+// ---- both strands --------------------------------------------------------------------------------------------------------------------------------------------
+extern "C" int orca_screen_merge_strands(orca_ctx* ctx, const float* fwd, int64_t fwd_bs, const float* rev, int64_t rev_bs, const float* ref_fwd, const float* ref_rev,
+                                         int B, int n, float* out, int64_t out_bs, float* gap) {
+  if (!ctx || !fwd || !rev || !out) return fail(ORCA_EINVAL, "orca_screen_merge_strands: NULL argument");
+  if (n < 1 || n > 256 || B < 1) return fail(ORCA_EINVAL, "orca_screen_merge_strands: %d maps (>= 1) of %d bins (1..256)", B, n);
+  const int64_t nn = (int64_t)n * n;
+  if (fwd_bs < nn || rev_bs < nn || out_bs < nn)
+    return fail(ORCA_EINVAL, "orca_screen_merge_strands: batch strides %ld (fwd), %ld (rev), %ld (out) below the map's %ld floats", (long)fwd_bs, (long)rev_bs, (long)out_bs, (long)nn);
+  if (!ref_fwd) gap = nullptr;                       // the form that merges the reference itself
+  if (gap && !ref_rev) return fail(ORCA_EINVAL, "orca_screen_merge_strands: the gap needs both strands' reference maps (ref_rev is NULL)");
+  const float* rev_end = rev + (size_t)(B - 1) * rev_bs + nn;
+  const float* out_end = out + (size_t)(B - 1) * out_bs + nn;
+  if (rev < out_end && out < rev_end) return fail(ORCA_EINVAL, "orca_screen_merge_strands: rev overlaps out (out may be fwd, an element's thread reads and writes it; rev is read mirrored)");
+  auto al8 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; };
+  const int vec = n % 2 == 0 && fwd_bs % 2 == 0 && rev_bs % 2 == 0 && out_bs % 2 == 0 && al8(fwd) && al8(rev) && al8(out) && (!gap || (al8(ref_fwd) && al8(ref_rev)));
+  return launch(ctx, "screen_merge_strands_kernel", screen_merge_strands_kernel, dim3((unsigned)B), 512, fwd, (long)fwd_bs, rev, (long)rev_bs, ref_fwd, ref_rev, n, out,
+                (long)out_bs, gap, vec);
+}

@@ -406,3 +406,68 @@ static __global__ void __launch_bounds__(256) screen_aligned_region_scores_kerne
     abs_out[(long)b * K + k] = h * w > 0 ? (float)(ta / cnt) : qnan;
   }
 }
+
+// ---- both strands (screen.screen_1m(..., strands="both")): the '-' strand's map is merged into the '+' strand's as genomepredict merges them ------------
+// out[b][i][j] = 0.5 fwd[b][i][j] + 0.5 rev[b][n-1-i][n-1-j] (the expression of strand_merge_kernel: the same bits), and with the two strands' reference maps
+// gap[b] = mean_ij |(fwd - ref_fwd)[i][j] - (rev - ref_rev)[n-1-i][n-1-j]| - how far the strands disagree about the item's effect.  One workgroup per map, one
+// wave per row at a time, 128 columns per step: lane l holds columns j0 + 2l and j0 + 2l + 1.  The mirrored row n-1-i of `rev` is read FORWARDS - lane m reads
+// columns c, c + 1 with c = n - j0 - 128 + 2m - and lane l takes the pair of lane 63 - l, swapped.  `vec` (wave-uniform; n even, every base and batch stride
+// 8-byte aligned - rows of 250 floats are no more than that): the pairs are float2 accesses, else two scalar ones; the assignment of columns to lanes, and
+// with it the order of the sum, is the same.  Differences and sums in fp64: per lane along its columns, shuffles across the wave, the waves' sums serially -
+// fixed by n alone, so a map's gap does not depend on B or on its place in the batch.  A NaN propagates into out and, through the sums, into gap.
+// `out` may be `fwd` (an element is read and written by the same thread); `rev` may not overlap `out`.  gap == NULL: no references are read.
+static __device__ __forceinline__ float2 screen_load2(const float* row, int c, int n, bool vec) {
+  if (vec) return (c >= 0 && c + 1 < n) ? *reinterpret_cast<const float2*>(row + c) : make_float2(0.f, 0.f);
+  return make_float2((c >= 0 && c < n) ? row[c] : 0.f, (c + 1 >= 0 && c + 1 < n) ? row[c + 1] : 0.f);
+}
+
+static __global__ void __launch_bounds__(512) screen_merge_strands_kernel(const float* fwd, long fwd_bs, const float* __restrict__ rev, long rev_bs,
+                                                                          const float* __restrict__ ref_fwd, const float* __restrict__ ref_rev, int n,
+                                                                          float* out, long out_bs, float* __restrict__ gap, int vec) {
+  __shared__ double s_sum[8];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float* f = fwd + (long)b * fwd_bs;
+  const float* r = rev + (long)b * rev_bs;
+  float* o = out + (long)b * out_bs;
+  const bool v2 = vec != 0;
+  double wsum = 0.0;
+  for (int i = wv; i < n; i += 8) {
+    const long at = (long)i * n, mat = (long)(n - 1 - i) * n;
+    double rs = 0.0;
+    for (int j0 = 0; j0 < n; j0 += 128) {
+      const int j = j0 + 2 * lane, c = n - j0 - 128 + 2 * lane;
+      const float2 mine = screen_load2(r + mat, c, n, v2);        // columns c, c + 1 of the mirrored row: output columns n-1-c, n-2-c
+      double e0 = 0.0, e1 = 0.0;
+      if (gap) {
+        const float2 rr = screen_load2(ref_rev + mat, c, n, v2);
+        e0 = (double)mine.x - (double)rr.x;
+        e1 = (double)mine.y - (double)rr.y;
+      }
+      const float m0 = __shfl(mine.y, 63 - lane, 64), m1 = __shfl(mine.x, 63 - lane, 64);      // rev[n-1-i][n-1-j], rev[n-1-i][n-2-j]
+      const double g0 = __shfl(e1, 63 - lane, 64), g1 = __shfl(e0, 63 - lane, 64);
+      const float2 a = screen_load2(f + at, j, n, v2);
+      const float2 res = make_float2(a.x * 0.5f + m0 * 0.5f, a.y * 0.5f + m1 * 0.5f);
+      if (gap) {
+        const float2 rf = screen_load2(ref_fwd + at, j, n, v2);
+        if (j < n) rs += fabs(((double)a.x - (double)rf.x) - g0);
+        if (j + 1 < n) rs += fabs(((double)a.y - (double)rf.y) - g1);
+      }
+      if (v2) {
+        if (j + 1 < n) *reinterpret_cast<float2*>(o + at + j) = res;
+      } else {
+        if (j < n) o[at + j] = res.x;
+        if (j + 1 < n) o[at + j + 1] = res.y;
+      }
+    }
+    for (int k = 32; k > 0; k >>= 1) rs += __shfl_xor(rs, k, 64);
+    wsum += rs;
+  }
+  if (!gap) return;
+  if (lane == 0) s_sum[wv] = wsum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int k = 0; k < 8; ++k) t += s_sum[k];
+    gap[b] = (float)(t / ((double)n * (double)n));
+  }
+}

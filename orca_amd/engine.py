@@ -831,6 +831,42 @@ def screen_aligned_region_scores(ctx, alt, ref, bin_map_host, rects_host, bin_ma
     return sg, ab
 
 
+# both strands (orca_screen_merge_strands)
+def screen_merge_strands(ctx, fwd, rev, ref_fwd=None, ref_rev=None, out=None):
+    """The '+' strand's maps ``fwd`` [B, n, n] and the '-' strand's ``rev`` [B, n, n] (any batch stride, rows contiguous) merged as genomepredict merges
+    them (orca_screen_merge_strands): (out [B, n, n] = 0.5 fwd + 0.5 rev.flip(-1, -2), gap [B] or None).  With both strands' reference maps ``ref_fwd``,
+    ``ref_rev`` [n, n], gap[b] = mean |(fwd[b] - ref_fwd) - (rev[b] - ref_rev).flip(-1, -2)|; without them it is None.  ``out`` may be ``fwd`` itself (merged
+    in place); it must not overlap ``rev``."""
+    if (ref_fwd is None) != (ref_rev is None):
+        raise ValueError("ref_fwd and ref_rev: both strands' reference maps, or neither")
+    fwd, rev = _f32_cuda(fwd, "fwd"), _f32_cuda(rev, "rev")
+    if fwd.dim() != 3 or fwd.shape[0] < 1 or fwd.shape[1] != fwd.shape[2] or not 1 <= fwd.shape[1] <= SCREEN_ALIGNED_MAX_BINS:
+        raise ValueError(f"fwd: [B,n,n] with B >= 1 and 1 <= n <= {SCREEN_ALIGNED_MAX_BINS}, got {tuple(fwd.shape)}")
+    B, n = fwd.shape[0], fwd.shape[1]
+    if out is None:
+        out = torch.empty((B, n, n), dtype=torch.float32, device=fwd.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32):
+        raise ValueError("out: a float32 tensor (it is written in place)")
+    for t, name in ((fwd, "fwd"), (rev, "rev"), (out, "out")):
+        if tuple(t.shape) != (B, n, n) or t.stride(2) != 1 or t.stride(1) != n or (B > 1 and t.stride(0) < n * n) or t.device != fwd.device:
+            raise ValueError(f"{name}: [{B},{n},{n}] float32 beside fwd with contiguous maps and a batch stride >= {n * n}")
+    refs = []
+    for t, name in ((ref_fwd, "ref_fwd"), (ref_rev, "ref_rev")):
+        if t is not None:
+            t = _f32_cuda(t, name).contiguous()
+            if tuple(t.shape) != (n, n) or t.device != fwd.device:
+                raise ValueError(f"{name}: [{n},{n}] beside fwd")
+        refs.append(t)
+    gap = None if refs[0] is None else torch.empty(B, dtype=torch.float32, device=fwd.device)
+    bs = [max(t.stride(0), n * n) for t in (fwd, rev, out)]          # B = 1: torch may report any stride for the one map
+    null = ctypes.c_void_p(0)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_merge_strands(ctx.handle, _p(fwd), bs[0], _p(rev), bs[1], null if refs[0] is None else _p(refs[0]),
+                                                null if refs[1] is None else _p(refs[1]), B, n, _p(out), bs[2], null if gap is None else _p(gap)),
+          "orca_screen_merge_strands")
+    return out, gap
+
+
 def encoder_forward_2bit(net, two, nmask, start, L, reverse=False, bin_lo=0, bin_hi=0, chunk_bp=0, out=None):
     """Encoder on bases [start, start + L) of a chromosome stored as 2 bits per base + N mask in HBM (genome.TwoBitGenome planes): no
     unpacked window is made (orca_encoder_forward_2bit).  Returns [1,128,bins]."""

@@ -34,8 +34,14 @@ Behind an unbalanced indel the alt map is displaced against the reference map, a
 ``screen_1m(..., aligned=True)`` adds scores on ALIGNED bins: `bin_map` says which reference bin an alt bin stands for, and alt pair (i, j) is
 compared with reference pair (map i, map j) (orca_screen_aligned_scores, orca_screen_aligned_region_scores).  `deletion_scan` and `tandem_dup`
 generate the large edits this is for, and ``flank_bp`` reads enough genome behind the window to refill them.
+
+``screen_1m(..., strands="both")`` scores every item on both strands, merged as ``genomepredict`` merges them: every map returned or scored is
+0.5 plus + 0.5 flip(minus), minus being the model's map of the reverse complement of the item's alt window.  The snippets are generated once, in
+forward coordinates; the front reads the same buffer reverse-complemented, and the '-' strand's plan is the mirror of the '+' strand's
+(`mirror_plan`: '+' row r is '-' row n5 - 1 - r).  One kernel merges a batch's two strands and measures how far they disagree
+(orca_screen_merge_strands, `ScreenResult.strand_gap`); the scores then run unchanged on the merged maps.
 """
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Optional
 
 import numpy as np
@@ -448,6 +454,8 @@ class BatchPlan:
     entry_rows: list = None
     take_rows: int = 0
     shift: np.ndarray = None
+    reverse: bool = False                     # `mirror_plan`: the row tables are the '-' strand's (the codes tables never change)
+    both_strands: bool = False                # a ``del`` / ``ins`` batch planned so that `mirror_plan` applies (`item_sources`)
 
 
 def edit_rows(edit, L, margin=MARGIN_BP):
@@ -585,7 +593,7 @@ def item_pieces(item, L, F, pay_off=0):
     return out, (np.concatenate(pay) if pay else np.zeros(0, dtype=np.uint8))
 
 
-def item_sources(pieces, L, F, margin=MARGIN_BP):
+def item_sources(pieces, L, F, margin=MARGIN_BP, both_strands=False):
     """Where the stage-5 rows of an alt window come from: (segments, fresh) with segments = [(row_lo, row_cnt, source, src_row)] for source -2
     (reference rows [src_row, ..)) and source = a phase 0..79 (pooled from that cache entry's stage-4 row src_row on), and fresh = [(r0, r1)]
     the maximal runs of rows that go through the front.  Rows in neither keep the reference's row of their own index.  The rule, with the
@@ -595,7 +603,11 @@ def item_sources(pieces, L, F, margin=MARGIN_BP):
       * s = 0: the reference's row r.  400 | s: the reference's row r + s / 400 if that row's cone lies inside the window [0, L) (the
         reference rows saw zero padding there).  Otherwise entry s mod 80, stage-4 rows (400 r + s - phase) / 80 .. + 4, if the cone in
         context coordinates lies inside the entry's run (the cache saw zero padding at its ends);
-      * everything else is fresh: junctions, payload, inversions, N fill, and the alt window's right end whenever s != 0 there."""
+      * everything else is fresh: junctions, payload, inversions, N fill, and the alt window's right end whenever s != 0 there.
+    ``both_strands`` (``strands="both"``; off by default, and then every plan is what it ever was): the '-' strand serves the same rows from the
+    '-' cache - on that strand the row is pooled from entry (C - s) mod 80 of the reverse-complemented context, whose run ends elsewhere, within
+    a few rows of the context's ends - so a take is kept only where the cone lies inside the run of BOTH entries (`mirror_plan` then is a
+    pure table transform); the rest is fresh."""
     n5, C = L // ROW_BP, L + F
     segs, served = [], np.zeros(n5, dtype=bool)
     for d0, kind, src, ln in pieces:
@@ -619,9 +631,12 @@ def item_sources(pieces, L, F, margin=MARGIN_BP):
                 served[a:b] = True
                 cuts = [(lo, a), (b, hi)]
         ph = s % sv.S4_GRID
-        run1 = ph + sv.S4_GRID * entry_rows(C, ph)
+        run0, run1 = ph, ph + sv.S4_GRID * entry_rows(C, ph)
+        if both_strands:                                 # the '-' entry's run, in context coordinates
+            pm = (C - s) % sv.S4_GRID
+            run0, run1 = max(run0, C - pm - sv.S4_GRID * entry_rows(C, pm)), min(run1, C - pm)
         for x, y in cuts:
-            a, b = max(x, -(-(ph + margin - s) // ROW_BP)), min(y, (run1 - margin - s) // ROW_BP)
+            a, b = max(x, -(-(run0 + margin - s) // ROW_BP)), min(y, (run1 - margin - s) // ROW_BP)
             if b > a:
                 segs.append((a, b - a, ph, (ROW_BP * a + s - ph) // sv.S4_GRID))
                 served[a:b] = True
@@ -629,13 +644,20 @@ def item_sources(pieces, L, F, margin=MARGIN_BP):
     return sorted(segs), [(int(a), int(b)) for a, b in zip(edge[0::2], edge[1::2])]
 
 
-def needed_phases(items, L, F, margin=MARGIN_BP):
-    """The stage-4 cache entries (phases 0..79, ascending) the two-part route of ``items`` pools rows from."""
+def needed_phases(items, L, F, margin=MARGIN_BP, both_strands=False):
+    """The stage-4 cache entries (phases 0..79, ascending) the two-part route of ``items`` pools rows from on the '+' strand (`mirror_phases`
+    gives the '-' strand's)."""
     ph = set()
     for it in items:
         if changes_length(it):
-            ph.update(g[2] for g in item_sources(item_pieces(it, L, F)[0], L, F, margin)[0] if g[2] >= 0)
+            ph.update(g[2] for g in item_sources(item_pieces(it, L, F)[0], L, F, margin, both_strands)[0] if g[2] >= 0)
     return sorted(ph)
+
+
+def mirror_phases(phases, C):
+    """The '-' strand's cache entries for the '+' strand's ``phases`` over a context of C bases: a row that starts at context base x = phase mod 80
+    starts at base C - x - 400 of the reverse-complemented context, phase (C - phase) mod 80.  Ascending; its own inverse."""
+    return sorted({(C - ph) % sv.S4_GRID for ph in phases})
 
 
 def _pieces_meeting(pieces, lo, hi, a0, a1):
@@ -693,14 +715,14 @@ def _layout(fresh_runs, L, pad, min_snippet, run_max, sub, base, meeting):
                 seg_off=np.cumsum([0] + [len(mine) for mine in fresh_runs], dtype=np.int64))
 
 
-def _plan_indels(edits, L, F, pad, margin, min_snippet, run_max):
+def _plan_indels(edits, L, F, pad, margin, min_snippet, run_max, both_strands=False):
     """`plan_batch` for a batch that holds a length-changing item: every item, the length-preserving ones too, as pieces and row sources.  A
     length-preserving item gets the clusters, snippets and fresh rows it gets alone (its pieces all have s = 0, so the rows outside every
     member's cone are served and the others are not: `set_clusters`' rule), and the front runs give a snippet's rows bit for bit in
     whichever run it lands."""
     E = len(edits)
     pieces, piece_off, payload, lists = _piece_table(edits, L, F)
-    sources = [item_sources(pcs, L, F, margin) for pcs in lists]
+    sources = [item_sources(pcs, L, F, margin, both_strands) for pcs in lists]
     served = [segs for segs, _ in sources]
     p = _layout([mine for _, mine in sources], L, pad, min_snippet, run_max, pieces, piece_off, _pieces_meeting)
     phases = sorted({g[2] for segs in served for g in segs if g[2] >= 0})
@@ -715,12 +737,13 @@ def _plan_indels(edits, L, F, pad, margin, min_snippet, run_max):
         gather_off[i + 1] = len(gather)
     return BatchPlan(edit_table=None, splice_table=None, payload=payload, indel=True, flank=F, piece_table=pieces, piece_off=piece_off,
                      gather_segments=np.array(gather, dtype=np.int64).reshape(-1, engine.SCREEN_GATHER_FIELDS), gather_off=gather_off, phases=phases,
-                     entry_rows=[entry_rows(L + F, ph) for ph in phases], take_rows=take_rows, shift=np.array([shift_of(e) for e in edits], dtype=np.int64), **p)
+                     entry_rows=[entry_rows(L + F, ph) for ph in phases], take_rows=take_rows, shift=np.array([shift_of(e) for e in edits], dtype=np.int64), both_strands=both_strands, **p)
 
 
-def plan_batch(edits, L, pad=PAD_BP, margin=MARGIN_BP, min_snippet=MIN_SNIPPET_BP, run_max=RUN_MAX_BP, flank=0):
+def plan_batch(edits, L, pad=PAD_BP, margin=MARGIN_BP, min_snippet=MIN_SNIPPET_BP, run_max=RUN_MAX_BP, flank=0, both_strands=False):
     """The `BatchPlan` of ``edits`` (`Edit`s and `EditSet`s) on an L-base window (L a multiple of 400) followed by ``flank`` bases of right flank
-    (only a batch with a ``del`` / ``ins`` member looks at it; such a batch is planned by the row-source rule of `item_sources`)."""
+    (only a batch with a ``del`` / ``ins`` member looks at it; such a batch is planned by the row-source rule of `item_sources`, with
+    ``both_strands`` in the form that `mirror_plan` can mirror; a batch without such a member plans the same either way)."""
     if L % ROW_BP:
         raise ValueError(f"window length must be a multiple of {ROW_BP}")
     if pad < margin or pad % ROW_BP:
@@ -731,7 +754,7 @@ def plan_batch(edits, L, pad=PAD_BP, margin=MARGIN_BP, min_snippet=MIN_SNIPPET_B
     for e in edits:
         e.check(L)
     if indel:
-        return _plan_indels(edits, L, int(flank), pad, margin, min_snippet, run_max)
+        return _plan_indels(edits, L, int(flank), pad, margin, min_snippet, run_max, both_strands)
     spans, span_base, payload = _span_table(edits)
     p = _layout([set_clusters(e, L, margin) for e in edits], L, pad, min_snippet, run_max, spans, span_base, _spans_meeting)
     table = splice = None
@@ -739,6 +762,56 @@ def plan_batch(edits, L, pad=PAD_BP, margin=MARGIN_BP, min_snippet=MIN_SNIPPET_B
         table, splice = p["snippet_table"].copy(), p["segments"].copy()
         table[:, 3:7] = spans[p["order"]]
     return BatchPlan(edit_table=table, splice_table=splice, payload=payload, span_table=spans, **p)
+
+
+def mirror_plan(plan):
+    """The plan of the same batch on the '-' strand (``strands="both"``): a pure table transform, its own inverse.  The edited snippets are
+    generated once, in forward coordinates - ``edit_table``, ``snippet_table``, ``span_table``, ``payload``, ``order`` and the buffer offsets in
+    ``runs`` stay as they are - and the front reads the same buffer with ``reverse=True``: it reverse-complements the whole run, so the pooled
+    rows come out in '-' order.  L is a multiple of 400 and every snippet bound is a multiple of 400 or a window end, so the '-' strand's
+    400-base grid is the mirror of the '+' grid and '+' row r is '-' row n5 - 1 - r:
+      * a run of nr pooled rows sends the range (skip, count, dst) to (nr - skip - count, count, dst): a snippet keeps its place in the
+        recomputed rows, and its rows lie there ascending in '-' row index;
+      * a segment (row_lo, cnt, src_row) becomes (n5 - row_lo - cnt, cnt, src_row), each item's segments re-sorted by row_lo;
+      * ``rows`` and ``snippet`` are restated in '-' coordinates ((n5 - r1, n5 - r0) and (L - b0 - nb, nb)).
+    A run that a window-start snippet opens is, reversed, a run that a window-end snippet closes: `_runs`' rule holds on the '-' strand.
+    A plan with row sources (``indel``; it must have been made with ``both_strands``, so that every take lies inside the run of the '-' entry
+    too) mirrors its gather segments [row_lo, row_cnt, source, src_row] the same way, with C = L + flank: a fresh source keeps src_row; a
+    reference source (-2) reads the '-' reference rows [n5 - src_row - cnt, ..); a take from entry ``phases[p]`` starts at context base
+    x = 80 src_row + phase and becomes a take from the '-' entry of phase (C - phase) mod 80 (`mirror_phases`) at stage-4 row
+    (C - x - 400 cnt - that phase) / 80.  ``phases`` and ``entry_rows`` are then the '-' cache's."""
+    if plan.indel and not plan.both_strands:
+        raise ValueError("mirror_plan: a del / ins batch must be planned with both_strands=True (its takes must lie inside the '-' entries' runs too)")
+    L, n5 = plan.L, plan.L // ROW_BP
+    more = {}
+    if plan.indel:
+        C = L + plan.flank
+        phases = mirror_phases(plan.phases, C)
+        index = {ph: k for k, ph in enumerate(phases)}
+        g = plan.gather_segments.copy()
+        for k, (a, cnt, source, src) in enumerate(plan.gather_segments):
+            if source == engine.SCREEN_SRC_REF:
+                src = n5 - src - cnt
+            elif source >= 0:
+                ph = plan.phases[source]
+                pm = (C - ph) % sv.S4_GRID
+                source, src = index[pm], (C - (sv.S4_GRID * src + ph) - ROW_BP * cnt - pm) // sv.S4_GRID
+            g[k] = (n5 - a - cnt, cnt, source, src)
+        for i in range(len(plan.gather_off) - 1):
+            a, b = int(plan.gather_off[i]), int(plan.gather_off[i + 1])
+            g[a:b] = g[a:b][::-1]
+        more = dict(gather_segments=g, phases=phases, entry_rows=[entry_rows(C, ph) for ph in phases])
+
+    def seg(t):
+        return None if t is None else np.stack([n5 - t[:, 0] - t[:, 1], t[:, 1], t[:, 2]], axis=1).astype(np.int64).reshape(-1, 3)
+    segments = seg(plan.segments)
+    for i in range(len(plan.seg_off) - 1):
+        a, b = int(plan.seg_off[i]), int(plan.seg_off[i + 1])
+        segments[a:b] = segments[a:b][::-1]              # ascending and disjoint before: descending after the mirror
+    runs = [(o0, nb, [(nb // ROW_BP - skip - count, count, dst) for skip, count, dst in ranges]) for o0, nb, ranges in plan.runs]
+    return replace(plan, reverse=not plan.reverse, runs=runs, segments=segments, splice_table=seg(plan.splice_table), **more,
+                   rows=np.stack([n5 - plan.rows[:, 1], n5 - plan.rows[:, 0]], axis=1).astype(np.int64).reshape(-1, 2),
+                   snippet=np.stack([L - plan.snippet[:, 0] - plan.snippet[:, 1], plan.snippet[:, 1]], axis=1).astype(np.int64).reshape(-1, 2))
 
 
 def _whole_window(items, L, sub_table):
@@ -839,6 +912,18 @@ def aligned_region_scores_host(maps, ref_map, bin_map, regions):
     return sg, ab
 
 
+def merge_strands_host(plus, minus, ref_plus=None, ref_minus=None):
+    """The merged maps of ``strands="both"`` (fp64 host restatement of orca_screen_merge_strands): ``plus``, ``minus`` [E, n, n] (or [n, n]) the two
+    strands' maps, ``minus`` in the '-' strand's own orientation.  (merged, gap) with merged = 0.5 plus + 0.5 flip(minus), flip reversing both bin
+    axes, and - with the two strands' reference maps [n, n] - gap[e] = mean |(plus[e] - ref_plus) - flip(minus[e] - ref_minus)|, else None."""
+    p, m = np.asarray(plus, dtype=np.float64), np.asarray(minus, dtype=np.float64)
+    merged = 0.5 * p + 0.5 * m[..., ::-1, ::-1]
+    if ref_plus is None or ref_minus is None:
+        return merged, None
+    d = (p - np.asarray(ref_plus, dtype=np.float64)) - (m - np.asarray(ref_minus, dtype=np.float64))[..., ::-1, ::-1]
+    return merged, np.abs(d).mean(axis=(-1, -2))
+
+
 @dataclass
 class ScreenResult:
     """Result of `screen_1m` (device tensors).  Maps are the model's output, the log observed / expected map of ``_Orca1M.forward`` (the
@@ -865,6 +950,12 @@ class ScreenResult:
       aligned_region     [E, K]       with ``regions``, read as REFERENCE bins: the mean of alt[i, j] - ref[map i, map j] (signed) over the alt
                                       pairs with map i in [i0, i1) and map j in [j0, j1); NaN when none qualifies (the region was deleted)
       aligned_region_abs [E, K]       the mean of its absolute value over the same pairs
+    With ``strands="both"`` every map above is the MERGED map 0.5 plus + 0.5 flip(minus) (minus = the model's map of the reverse complement of the
+    item's alt window, flip reverses both bin axes; forward orientation, so bins, regions and `bin_map` keep their meaning), every score is taken
+    from merged maps against the merged ``ref_map``, the 1-D heads are 0.5 h_plus + 0.5 h_minus.flip(-1), and (None with ``strands="+"``):
+      strand_gap         [E]          mean over the map of |(alt+ - ref+) - flip(alt- - ref-)|: how far the two strands disagree about the item's
+                                      effect - set it beside ``delta_abs_mean``: an effect well above its gap is one both strands see
+      ref_strand_gap     0-dim        mean |ref+ - flip(ref-)|: the model's strand asymmetry on the unedited window
     `scores_host` computes the three map scores from maps on the host, `region_scores_host` the two region scores, `aligned_scores_host` and
     `aligned_region_scores_host` the aligned ones."""
     ref_map: torch.Tensor
@@ -885,6 +976,8 @@ class ScreenResult:
     aligned_abs_max: Optional[torch.Tensor] = None
     aligned_region: Optional[torch.Tensor] = None
     aligned_region_abs: Optional[torch.Tensor] = None
+    strand_gap: Optional[torch.Tensor] = None
+    ref_strand_gap: Optional[torch.Tensor] = None
 
 
 # ---- the screen -----------------------------------------------------------------------------------------------------------------------------
@@ -960,10 +1053,11 @@ class _Screen:
     def _upload(self, a, dtype):
         return torch.from_numpy(np.ascontiguousarray(a)).to(self.dev, dtype)
 
-    def whole(self, edits):
-        """Maps of the edited windows through Net's own Encoder and Decoder_1m (the module guards apply as in Net.forward)."""
+    def whole(self, edits, reverse=False):
+        """Maps of the edited windows through Net's own Encoder and Decoder_1m (the module guards apply as in Net.forward); ``reverse``: of their
+        reverse complements (the '-' strand's maps, in its own orientation)."""
         if not edits:
-            return self._decode(self.net._enc.forward_codes(self.window[None]))
+            return self._decode(self.net._enc.forward_codes(self.window[None], reverse=reverse))
         codes = torch.empty(len(edits) * self.L, dtype=torch.uint8, device=self.dev)
         if any(changes_length(e) for e in edits):
             table, pieces, payload = whole_window_piece_tables(edits, self.L, self.F)
@@ -977,21 +1071,22 @@ class _Screen:
             table, spans, payload = whole_window_set_tables(edits, self.L)
             pay = self._upload(payload, torch.uint8) if payload.size else None
             engine.screen_edit_codes_multi(self.ctx, self.window, table, spans, pay, codes)
-        return self._decode(self.net._enc.forward_codes(codes.view(len(edits), self.L)))
+        return self._decode(self.net._enc.forward_codes(codes.view(len(edits), self.L), reverse=reverse))
 
-    def reference_rows(self):
+    def reference_rows(self, reverse=False):
         enc = self.net._enc
         s5 = torch.empty((self.n5, 128), dtype=torch.float32, device=self.dev)
-        enc.front4_ranges(self.window, False, [(0, self.n5, 0)], s5)
+        enc.front4_ranges(self.window, reverse, [(0, self.n5, 0)], s5)
         return s5
 
-    def build_entries(self, phases):
-        """The stage-4 cache entries of ``phases`` over the context ('+' strand; `sv.Stage4Cache` builds a phase's group of five)."""
+    def build_entries(self, phases, strand="+"):
+        """The stage-4 cache entries of ``phases`` over the context on ``strand`` ('-': over its reverse complement; `sv.Stage4Cache` builds a
+        phase's group of five)."""
         if self.cache is None:
             self.cache = sv.Stage4Cache(self.net._enc, self.context)
         out = []
         for ph in phases:
-            e = self.cache.get("+", ph)
+            e = self.cache.get(strand, ph)
             if e is None:
                 raise OrcaHipError(f"screen_1m: stage-4 cache entry {ph} unavailable (fp16 range)")
             if e.shape[0] != entry_rows(self.L + self.F, ph):
@@ -1000,48 +1095,62 @@ class _Screen:
         self.stats["cache_phases"] = self.cache.builds
         return out
 
-    def two_part(self, edits, s5_ref, plan=None):
-        """Maps of a batch on the two-part route.  ``plan``: the batch's plan if it holds a length-changing item (`screen_1m` made it with the
-        reference) - then the bases of every snippet come from the items' pieces and the row images from the reference rows, the recomputed rows
-        and the cache entries; a list of bare `Edit`s runs the single-span kernels, as ever."""
-        enc = self.net._enc
-        p = plan_batch(edits, self.L) if plan is None else plan
+    def _snippet_codes(self, p, edits):
+        """The packed buffer of the plan's edited snippets, in forward coordinates (both strands read it)."""
         total = int(p.snippet[:, 1].sum())
         codes = torch.empty(total, dtype=torch.uint8, device=self.dev)
         pay = self._upload(p.payload, torch.uint8) if p.payload.size else None
-        single = all(isinstance(e, Edit) for e in edits)
         if p.indel:
             if total:                                    # no snippet at all: every row of every item is served (an ``ins`` behind the last base)
                 engine.screen_assemble_codes(self.ctx, self.context, p.snippet_table, p.piece_table, pay, codes)
-        elif single:
+        elif p.edit_table is not None and all(isinstance(e, Edit) for e in edits):
             engine.screen_edit_codes(self.ctx, self.window, p.edit_table, self._upload(p.edit_table, torch.int64), pay, codes)
         else:
             engine.screen_edit_codes_multi(self.ctx, self.window, p.snippet_table, p.span_table, pay, codes)
+        return codes
+
+    def _strand_enc(self, p, edits, codes, s5_ref, reverse=False):
+        """The encodings [B, 128, n] of one strand of a batch from the snippets' bases: the front on every run, the row images, stages 5-7.
+        ``reverse``: ``p`` is the mirrored plan, ``s5_ref`` the '-' strand's reference rows, and the front reverse-complements every run."""
+        enc = self.net._enc
         fresh = torch.empty((p.n_fresh, 128), dtype=torch.float32, device=self.dev)
         for o0, nb, ranges in p.runs:
-            enc.front4_ranges(codes[o0: o0 + nb], False, ranges, fresh)
+            enc.front4_ranges(codes[o0: o0 + nb], reverse, ranges, fresh)
         rows = torch.empty((len(edits), self.n5, 128), dtype=torch.float32, device=self.dev)
         if p.indel:
-            engine.screen_gather_rows(self.ctx, s5_ref, fresh, self.build_entries(p.phases), p.gather_segments, p.gather_off, rows)
-        elif single:
+            engine.screen_gather_rows(self.ctx, s5_ref, fresh, self.build_entries(p.phases, "-" if reverse else "+"), p.gather_segments, p.gather_off, rows)
+        elif p.splice_table is not None and all(isinstance(e, Edit) for e in edits):
             engine.screen_splice_rows(self.ctx, s5_ref, fresh, self._upload(p.splice_table, torch.int64), rows)
         else:
             engine.screen_splice_rows_multi(self.ctx, s5_ref, fresh, p.segments, p.seg_off, rows)
-        out = enc.back5_batch(rows)
+        return enc.back5_batch(rows)
+
+    def two_part(self, edits, s5_ref, plan=None, s5_ref_minus=None):
+        """Maps of a batch on the two-part route.  ``plan``: the batch's plan if it holds a length-changing item (`screen_1m` made it with the
+        reference, and for both strands if they are wanted) - then the bases of every snippet come from the items' pieces and the row images
+        from the reference rows, the recomputed rows and the cache entries; a list of bare `Edit`s runs the single-span kernels, as ever.  With
+        ``s5_ref_minus`` (the '-' strand's reference rows) the result is the pair ('+' strand, '-' strand) of (maps, 1-D head), the second in
+        the '-' strand's own orientation: the front reads the same buffer reverse-complemented, run by run, and the mirrored plan
+        (`mirror_plan`) says where its rows go."""
+        p = plan_batch(edits, self.L) if plan is None else plan
+        codes = self._snippet_codes(p, edits)
+        out = self._strand_enc(p, edits, codes, s5_ref)
         self.stats["segments"] += len(p.segments)
         self.stats["front_runs"] += len(p.runs)
-        self.stats["front_bases"] += total
+        self.stats["front_bases"] += int(codes.numel())
         self.stats["take_rows"] += p.take_rows
-        return self._decode(out)
+        if s5_ref_minus is None:
+            return self._decode(out)
+        return self._decode(out), self._decode(self._strand_enc(mirror_plan(p), edits, codes, s5_ref_minus, True))
 
 
-def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regions=None, flank=None, aligned=False, flank_bp=None):
+def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regions=None, flank=None, aligned=False, flank_bp=None, strands="+"):
     """Score ``edits`` (a list of `Edit` and `EditSet`, one row of every result tensor each) of one window with the 1 Mb model: a `ScreenResult`.
 
     ``model``: an ``H1esc_1M`` / ``Hff_1M`` container or a bare ``orca_modules.Net``.  ``window``: the window's base codes, a [L] uint8 tensor on
     the MI355X, or ``(genome, chrom, start)`` / ``(genome, chrom, start, L)`` for a `genome.PackedGenome` / `TwoBitGenome` resident there
     (L = 1 000 000 by default, as the reference's 1 Mb model).  L: a multiple of 4 000 with at most 256 bins.  Forward strand only (as the
-    reference's ``pred_1m``).  ``batch``: edits per batch.  ``keep_maps``: also return every alt map.  ``stats``: a dict that receives
+    reference's ``pred_1m``) by default; ``strands`` below.  ``batch``: edits per batch.  ``keep_maps``: also return every alt map.  ``stats``: a dict that receives
     counters - ``route`` ("two_part" / "whole_window"), ``two_part_batches``, ``whole_window_batches``, ``range_fallback_batches`` (batches
     redone on the whole-window route in the range-safe arithmetic after the fp16-range check fired), ``range_fallback_reference`` (the
     reference itself tripped: every batch went that way), ``front_runs``, ``front_bases``, ``edits``, ``set_items`` (items that are an
@@ -1063,7 +1172,22 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
     ``aligned_abs_max`` and, with ``regions``, ``aligned_region`` / ``aligned_region_abs``): alt pair (i, j) against reference pair (map i, map j)
     with map = `bin_map` of the item, taken from the batch's maps whichever route produced them.  The rectangles of ``regions`` keep their
     meaning for ``delta_region`` and are read as REFERENCE bins for the aligned pair.  With ``aligned=False`` nothing more is launched and those
-    fields are None.  ``stats`` gains ``aligned_items``: the items whose bin map is not the identity (0 without ``aligned``)."""
+    fields are None.  ``stats`` gains ``aligned_items``: the items whose bin map is not the identity (0 without ``aligned``).
+
+    ``strands``: "+" (the default: nothing below is launched, every field is what it ever was) or "both": every map returned or scored is the
+    merged map 0.5 plus + 0.5 flip(minus), as ``genomepredict`` merges its two strands - minus is the model's map of the REVERSE COMPLEMENT of the
+    item's alt window (for a ``del`` / ``ins`` item the L-base alt window with its refill and N fill applied), flip reverses both bin axes.  Merged
+    maps are in forward orientation, so ``ref_map``, ``maps``, every ``delta_*`` and ``aligned_*`` field, ``regions``, `bin_map` and ``shift`` keep
+    their meaning, now on merged maps against the merged reference (orca_screen_merge_strands, then the same score kernels); the 1-D heads are
+    0.5 h_plus + 0.5 h_minus.flip(-1).  `ScreenResult.strand_gap` and ``ref_strand_gap`` say how far the strands disagree.  On the two-part route
+    the snippets are generated once and the front reads them a second time reverse-complemented (`mirror_plan`); a ``del`` / ``ins`` item
+    pools its '-' rows from the '-' strand's stage-4 cache entries (built with the reference too; ``cache_phases`` counts both strands').  One
+    deferred range check covers both strands of a batch (and of the reference).  The screen is decode-bound, so expect about twice the time
+    per item.  More ``stats``: ``strands``, ``reverse_two_part_items`` / ``reverse_whole_items`` (items whose '-' strand ran two-part /
+    through the whole-window Encoder: the whole-window route and the range-safe redo)."""
+    if strands not in ("+", "both"):
+        raise ValueError(f"strands must be '+' or 'both', got {strands!r}")
+    both = strands == "both"
     net = _net_of(model)
     if flank_bp is not None:
         if flank is not None or not isinstance(window, tuple):
@@ -1083,40 +1207,62 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
     rects = None if regions is None else check_regions(regions, win.numel() // 4000)
     st = {"route": None, "two_part_batches": 0, "whole_window_batches": 0, "range_fallback_batches": 0, "range_fallback_reference": False,
           "front_runs": 0, "front_bases": 0, "edits": len(edits), "set_items": sum(isinstance(e, EditSet) for e in edits), "segments": 0,
-          "indel_items": sum(changes_length(e) for e in edits), "take_rows": 0, "cache_phases": 0, "aligned_items": 0}
+          "indel_items": sum(changes_length(e) for e in edits), "take_rows": 0, "cache_phases": 0, "aligned_items": 0,
+          "strands": strands, "reverse_two_part_items": 0, "reverse_whole_items": 0}
     fl = _flank_codes(window, flank, win, flank_bp) if (flank is not None or st["indel_items"]) else None
     sc = _Screen(net, win, st, fl if st["indel_items"] else None)
     E, n, dev = len(edits), sc.n, sc.dev
     two_part = net._enc.two_part_ok()
     plans = {}
     with torch.no_grad():
-        s5_ref = None
+        s5_ref = s5_ref_minus = ref_minus = None
         if two_part:
             with engine.defer_overflow_guard():
                 s5_ref = sc.reference_rows()
                 enc_ref = torch.empty((1, 128, n), dtype=torch.float32, device=dev)
                 net._enc.back5(s5_ref, enc_ref[0])
                 ref_map, ref_1d = sc._decode(enc_ref)
+                if both:                                 # the '-' strand's reference, under the same range check
+                    s5_ref_minus = sc.reference_rows(True)
+                    enc_minus = torch.empty((1, 128, n), dtype=torch.float32, device=dev)
+                    net._enc.back5(s5_ref_minus, enc_minus[0])
+                    ref_minus = sc._decode(enc_minus)
                 if st["indel_items"]:                    # the cache entries the batches will pool from, under the reference's range check
                     for i0 in range(0, E, batch):        # every indel batch is planned once, here; the phases built are the phases used
                         if any(changes_length(e) for e in edits[i0: i0 + batch]):
-                            plans[i0] = plan_batch(edits[i0: i0 + batch], sc.L, flank=sc.F)
-                    sc.build_entries(sorted({ph for p in plans.values() for ph in p.phases}))
+                            plans[i0] = plan_batch(edits[i0: i0 + batch], sc.L, flank=sc.F, both_strands=both)
+                    phases = sorted({ph for p in plans.values() for ph in p.phases})
+                    sc.build_entries(phases)
+                    if both:
+                        sc.build_entries(mirror_phases(phases, sc.L + sc.F), "-")
             if sc.ctx.take_overflow():
                 two_part = False
                 st["range_fallback_reference"] = True
         if not two_part and not st["range_fallback_reference"]:
             ref_map, ref_1d = sc.whole([])
+            ref_minus = sc.whole([], reverse=True) if both else None
         elif st["range_fallback_reference"]:
             with engine.force_safe_precision():
                 ref_map, ref_1d = sc.whole([])
+                ref_minus = sc.whole([], reverse=True) if both else None
         st["route"] = "two_part" if two_part else "whole_window"
         ref_map = ref_map[0].contiguous()
         ref_1d = None if ref_1d is None else ref_1d[0].contiguous()
+        ref_gap = ref_plus = None
+        if both:                                         # the reference merged as every batch will be; zero "references" make the gap mean |ref+ - flip(ref-)|
+            ref_plus, ref_minus, ref_1d_minus = ref_map, ref_minus[0][0].contiguous(), ref_minus[1]
+            zero = torch.zeros_like(ref_plus)
+            merged, ref_gap = engine.screen_merge_strands(sc.ctx, ref_plus[None], ref_minus[None], zero, zero)
+            ref_map = merged[0]
+            if ref_1d is not None:
+                ref_1d = 0.5 * ref_1d + 0.5 * ref_1d_minus[0].flip(-1)
         res = ScreenResult(ref_map, ref_1d, torch.zeros((E, n), dtype=torch.float32, device=dev), torch.zeros(E, dtype=torch.float32, device=dev),
                            torch.zeros(E, dtype=torch.float32, device=dev),
                            torch.zeros((E, sc.num_1d, n), dtype=torch.float32, device=dev) if sc.num_1d else None,
                            torch.zeros((E, n, n), dtype=torch.float32, device=dev) if keep_maps else None, edits)
+        if both:
+            res.ref_strand_gap = ref_gap[0]
+            res.strand_gap = torch.zeros(E, dtype=torch.float32, device=dev)
         res.shift = torch.tensor([shift_of(e) for e in edits], dtype=torch.int64, device=dev)
         if rects is not None:
             res.delta_region = torch.zeros((E, len(rects)), dtype=torch.float32, device=dev)
@@ -1133,25 +1279,39 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
             if rects is not None:
                 res.aligned_region = torch.zeros((E, len(rects)), dtype=torch.float32, device=dev)
                 res.aligned_region_abs = torch.zeros((E, len(rects)), dtype=torch.float32, device=dev)
+        def whole(chunk):                                # a batch on the whole-window route: the '+' strand, or the pair of strands
+            if not both:
+                return sc.whole(chunk)
+            st["reverse_whole_items"] += len(chunk)
+            return sc.whole(chunk), sc.whole(chunk, reverse=True)
         for i0 in range(0, E, batch):
             chunk = edits[i0: i0 + batch]
             if two_part:
-                with engine.defer_overflow_guard():
-                    maps, h = sc.two_part(chunk, s5_ref, plans.get(i0))
+                with engine.defer_overflow_guard():      # one check for both strands of the batch
+                    out = sc.two_part(chunk, s5_ref, plans.get(i0), s5_ref_minus)
                 if sc.ctx.take_overflow():
                     st["range_fallback_batches"] += 1
                     with engine.force_safe_precision():
-                        maps, h = sc.whole(chunk)
+                        out = whole(chunk)
                 else:
                     st["two_part_batches"] += 1
+                    if both:
+                        st["reverse_two_part_items"] += len(chunk)
             elif st["range_fallback_reference"]:
                 st["range_fallback_batches"] += 1
                 with engine.force_safe_precision():
-                    maps, h = sc.whole(chunk)
+                    out = whole(chunk)
             else:
                 st["whole_window_batches"] += 1
-                maps, h = sc.whole(chunk)
+                out = whole(chunk)
             i1 = i0 + len(chunk)
+            if both:
+                (maps, h), (maps_minus, h_minus) = out
+                maps, res.strand_gap[i0:i1] = engine.screen_merge_strands(sc.ctx, maps, maps_minus, ref_plus, ref_minus, out=maps)
+                if h is not None:
+                    h = 0.5 * h + 0.5 * h_minus.flip(-1)
+            else:
+                maps, h = out
             prof, mean, amax = engine.screen_scores(sc.ctx, maps, ref_map)
             res.delta_profile[i0:i1] = prof
             res.delta_abs_mean[i0:i1] = mean

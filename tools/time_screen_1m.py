@@ -22,6 +22,10 @@ Insertions and deletions, into profiles/screen_1m_indels.json:
 Aligned scores, into profiles/screen_1m_aligned.json:
   --aligned      the 3 250-edit workload above through screen_1m with aligned=True and with aligned=False, alternated in the same run (B from
                  --batches): what the bin maps and the aligned-score kernels add
+
+Both strands, into profiles/screen_1m_strands.json:
+  --strands both the 3 250-edit workload at B = 64 through screen_1m with strands="both", and alternated in the same run with strands="+" and the
+                 naive both-strand route (the edited windows through Net on both strands, merged by orca_screen_merge_strands, the same scores)
 """
 import argparse
 import json
@@ -162,6 +166,46 @@ def time_aligned(a, model, win, edits, dev):
     return rep
 
 
+def naive_both(model, win, edits, batch, keep_maps=False):
+    """`naive` on both strands: every batch's edited windows through Net's Encoder and Decoder_1m forwards and reverse-complemented, merged."""
+    sc = S._Screen(model.net, win, {})
+    ref_map, _ = engine.screen_merge_strands(sc.ctx, sc.whole([])[0], sc.whole([], reverse=True)[0])
+    ref_map = ref_map[0].contiguous()
+    out, maps_all = [], []
+    with torch.no_grad():
+        for i0 in range(0, len(edits), batch):
+            maps, _ = engine.screen_merge_strands(sc.ctx, sc.whole(edits[i0: i0 + batch])[0], sc.whole(edits[i0: i0 + batch], reverse=True)[0])
+            out.append(engine.screen_scores(sc.ctx, maps, ref_map)[1])
+            if keep_maps:
+                maps_all.append(maps.clone())
+    return torch.cat(out), (torch.cat(maps_all) if keep_maps else None)
+
+
+def time_strands(a, model, win, edits, dev):
+    """The --strands both workload: screen_1m with strands="both", with strands="+" and the naive both-strand route, alternated, at B = 64."""
+    B = 64
+    rep = {"device": torch.cuda.get_device_name(dev), "edits": len(edits), "batch": B}
+    st = {}
+    rs_ = S.screen_1m(model, win, edits[:B], batch=B, keep_maps=True, stats=st, strands="both")          # warm-up and cross-check
+    S.screen_1m(model, win, edits[:B], batch=B)
+    _, mn = naive_both(model, win, edits[:B], B, keep_maps=True)
+    rep.update({"route": st["route"], "reverse_two_part_items": st["reverse_two_part_items"], "reverse_whole_items": st["reverse_whole_items"],
+                "front_bases_per_item": round(st["front_bases"] / B), "maps_maxabs_screen_vs_naive": float((rs_.maps - mn).abs().max()),
+                "ref_strand_gap": float(rs_.ref_strand_gap), "strand_gap_over_delta_abs_mean_median": float((rs_.strand_gap / rs_.delta_abs_mean).median())})
+    assert rep["maps_maxabs_screen_vs_naive"] < 2e-5, rep
+    del rs_, mn
+    tb, tp, tn = [], [], []
+    for _ in range(a.reps):
+        tb.append(timed(lambda: S.screen_1m(model, win, edits, batch=B, strands="both"))[0])
+        tp.append(timed(lambda: S.screen_1m(model, win, edits, batch=B))[0])
+        tn.append(timed(lambda: naive_both(model, win, edits, B))[0])
+    rep.update({"both_s": [round(t, 3) for t in tb], "plus_s": [round(t, 3) for t in tp], "naive_both_s": [round(t, 3) for t in tn],
+                "both_edits_per_s": round(len(edits) / min(tb), 1), "plus_edits_per_s": round(len(edits) / min(tp), 1),
+                "naive_both_edits_per_s": round(len(edits) / min(tn), 1), "both_over_plus": round(min(tb) / min(tp), 3),
+                "speedup_over_naive_both": round(min(tn) / min(tb), 2)})
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="16,64")
@@ -174,6 +218,7 @@ def main():
     ap.add_argument("--haplotype-span", type=int, default=L)
     ap.add_argument("--indels", type=int, default=0, help="N: time N random 1-50-base indels at B = 64")
     ap.add_argument("--aligned", action="store_true", help="time the 3 250-edit workload with aligned=True against aligned=False")
+    ap.add_argument("--strands", default="+", choices=("+", "both"), help="both: time the 3 250-edit workload on both strands at B = 64")
     ap.add_argument("--commit", default="", help="recorded in the report")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -210,6 +255,18 @@ def main():
         rep.update(time_aligned(a, model, win, edits, dev))
         print(json.dumps(rep))
         out = a.out if a.out != ap.get_default("out") else os.path.join(os.path.dirname(a.out), "screen_1m_aligned.json")
+        if out:
+            os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+            with open(out, "w") as f:
+                json.dump(rep, f, indent=1)
+        return
+    if a.strands == "both":
+        rep = {"workload": f"H1esc_1M synthetic, 1 Mb window, {len(edits)} edits (saturation SNVs of 1 kb + 250 4 kb mask tiles); screen_1m with "
+                           "strands='both' against strands='+' and against the edited windows through Net on both strands, merged; alternated "
+                           "(every call includes its reference)", "commit": a.commit}
+        rep.update(time_strands(a, model, win, edits, dev))
+        print(json.dumps(rep))
+        out = a.out if a.out != ap.get_default("out") else os.path.join(os.path.dirname(a.out), "screen_1m_strands.json")
         if out:
             os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
             with open(out, "w") as f:
