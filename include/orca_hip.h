@@ -331,6 +331,25 @@ int orca_screen_aligned_region_scores(orca_ctx* ctx, const float* alt, int64_t m
                                       const int32_t* bin_map_host, const int32_t* rects, const int32_t* rects_host, int K, float* mean_signed,
                                       float* mean_abs);
 
+/* Tracks (screen.screen_1m(..., insulation=, viewpoints=)): 1-D readouts of B maps alt[b * map_bs + i * n + j] (B >= 1, 1 <= n <= 256, map_bs >= n * n)
+ * against ref[n][n], bin with bin and - with `bin_map` as above (device copy and checked host copy) - on aligned bins, indexed by ALT bin.  The small
+ * tables `widths` (W int32, 1 <= W <= 8, each 1..128) and `views` (V int32, 1 <= V <= 64, each 0 .. n - 1) come twice like every table.  The diamond of
+ * bin i at width w is rows [i - w, i) x columns (i, i + w]; it fits when w <= i < n - w, and ins_w(m)[i] = the mean of m over it (w^2 terms, fp64), NaN
+ * where it does not fit (a width with 2 w + 1 > n is legal and gives NaN everywhere).  Each diamond is summed on its own, in an order fixed by (n, w).
+ *   orca_screen_insulation  track[b][k][i] = ins_wk(alt b)[i]; delta[b][k][i] = ins(alt b)[i] - ins(ref)[i]; aligned[b][k][i] = ins(alt b)[i] -
+ *                           ins(ref)[map i] where map i >= 0 and both diamonds fit, else NaN (only the centre bin has to be mapped; where map i == i it
+ *                           is delta's expression, the same bits).  The differences are fp64, rounded once.  `delta` may be NULL; `aligned` is
+ *                           non-NULL exactly when `bin_map` is; ref == NULL writes the track only (delta, aligned, bin_map NULL: the form for the
+ *                           reference map itself, B = 1).  A NaN pixel shows in the bins whose diamond holds it and in no other
+ *   orca_screen_viewpoints  delta[b][v][j] = alt[b][view v][j] - ref[view v][j] (fp32).  aligned[b][v][j]: the viewpoint is a REFERENCE bin, R = the alt
+ *                           bins i with map i == view v (ascending), c = |R|: (sum_{i in R} alt[b][i][j]) / c - ref[view v][map j] in fp64 where c >= 1
+ *                           and map j >= 0 (c = 1: the fp32 subtraction), else NaN.  `aligned` is non-NULL exactly when `bin_map` is
+ * A map's results are bit for bit the same whatever B and its place in the batch.  Anything else is ORCA_EINVAL before any launch. */
+int orca_screen_insulation(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* widths, const int32_t* widths_host,
+                           int W, const int32_t* bin_map, const int32_t* bin_map_host, float* track, float* delta, float* aligned);
+int orca_screen_viewpoints(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* views, const int32_t* views_host,
+                           int V, const int32_t* bin_map, const int32_t* bin_map_host, float* delta, float* aligned);
+
 /* Both strands (screen.screen_1m(..., strands="both")): B maps of the '+' strand fwd[b * fwd_bs + i * n + j] and of the '-' strand rev[b * rev_bs + ..]
  * (1 <= n <= 256, B >= 1, batch strides >= n * n) merged as genomepredict merges them (orca_predict.py:514-523):
  *   out[b][i][j] = 0.5f * fwd[b][i][j] + 0.5f * rev[b][n-1-i][n-1-j]     bit for bit orca_strand_merge on each map

@@ -234,6 +234,41 @@ extern "C" int orca_screen_aligned_region_scores(orca_ctx* ctx, const float* alt
                 rects, K, mean_signed, mean_abs);
 }
 
+// ---- tracks ----------------------------------------------------------------------------------------------------------------------------------------------------
+// what the two track entry points share: the maps, and the bin map that comes exactly with the aligned output
+static int check_track_maps(const char* what, int64_t map_bs, int B, int n, const int32_t* bin_map, const int32_t* bin_map_host, const float* aligned) {
+  if (B < 1 || n < 1 || n > SCREEN_ALIGNED_MAX_BINS || map_bs < (int64_t)n * n)
+    return fail(ORCA_EINVAL, "%s: %d maps (>= 1) of %d bins (1..%d), batch stride %ld (>= n * n)", what, B, n, SCREEN_ALIGNED_MAX_BINS, (long)map_bs);
+  if ((aligned != nullptr) != (bin_map != nullptr)) return fail(ORCA_EINVAL, "%s: the aligned output and the bin map come together or not at all", what);
+  if (bin_map && !bin_map_host) return fail(ORCA_EINVAL, "%s: NULL host copy of the bin map", what);
+  return bin_map ? check_bin_map(what, bin_map_host, B, n) : ORCA_OK;
+}
+
+extern "C" int orca_screen_insulation(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* widths,
+                                      const int32_t* widths_host, int W, const int32_t* bin_map, const int32_t* bin_map_host, float* track, float* delta,
+                                      float* aligned) {
+  if (!ctx || !alt || !widths || !widths_host || !track) return fail(ORCA_EINVAL, "orca_screen_insulation: NULL argument");
+  if (!ref && (delta || aligned || bin_map)) return fail(ORCA_EINVAL, "orca_screen_insulation: without ref only the track is written (delta, aligned and bin_map must be NULL)");
+  ORCA_TRY(check_track_maps("orca_screen_insulation", map_bs, B, n, bin_map, bin_map_host, aligned));
+  if (W < 1 || W > SCREEN_INSULATION_MAX_WIDTHS) return fail(ORCA_EINVAL, "orca_screen_insulation: %d widths (1..%d)", W, SCREEN_INSULATION_MAX_WIDTHS);
+  for (int k = 0; k < W; ++k)
+    if (widths_host[k] < 1 || widths_host[k] > SCREEN_INSULATION_MAX_WIDTH)
+      return fail(ORCA_EINVAL, "orca_screen_insulation: width %d is %d bins, outside 1 .. %d", k, widths_host[k], SCREEN_INSULATION_MAX_WIDTH);
+  const unsigned chunks = (unsigned)((n + SCREEN_INSULATION_BINS - 1) / SCREEN_INSULATION_BINS);
+  return launch(ctx, "screen_insulation_kernel", screen_insulation_kernel, dim3((unsigned)B, (unsigned)W, chunks), 256, alt, (long)map_bs, ref, n, widths, W, bin_map, track,
+                delta, aligned);
+}
+
+extern "C" int orca_screen_viewpoints(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* views,
+                                      const int32_t* views_host, int V, const int32_t* bin_map, const int32_t* bin_map_host, float* delta, float* aligned) {
+  if (!ctx || !alt || !ref || !views || !views_host || !delta) return fail(ORCA_EINVAL, "orca_screen_viewpoints: NULL argument");
+  ORCA_TRY(check_track_maps("orca_screen_viewpoints", map_bs, B, n, bin_map, bin_map_host, aligned));
+  if (V < 1 || V > SCREEN_VIEWPOINTS_MAX) return fail(ORCA_EINVAL, "orca_screen_viewpoints: %d viewpoints (1..%d)", V, SCREEN_VIEWPOINTS_MAX);
+  for (int v = 0; v < V; ++v)
+    if (views_host[v] < 0 || views_host[v] >= n) return fail(ORCA_EINVAL, "orca_screen_viewpoints: viewpoint %d is bin %d, outside 0 .. %d", v, views_host[v], n - 1);
+  return launch(ctx, "screen_viewpoints_kernel", screen_viewpoints_kernel, dim3((unsigned)B, (unsigned)V), 256, alt, (long)map_bs, ref, n, views, V, bin_map, delta, aligned);
+}
+
 // ---- both strands --------------------------------------------------------------------------------------------------------------------------------------------
 extern "C" int orca_screen_merge_strands(orca_ctx* ctx, const float* fwd, int64_t fwd_bs, const float* rev, int64_t rev_bs, const float* ref_fwd, const float* ref_rev,
                                          int B, int n, float* out, int64_t out_bs, float* gap) {

@@ -407,6 +407,111 @@ static __global__ void __launch_bounds__(256) screen_aligned_region_scores_kerne
   }
 }
 
+// ---- tracks (screen.screen_1m(..., insulation=, viewpoints=)): 1-D readouts per map, bin with bin and on aligned bins -----------------------------------
+// The diamond of bin i at width w is rows [i - w, i) x columns (i, i + w] of a map: it fits when w <= i < n - w, and ins_w(m)[i] is the mean of m over it
+// (lower = more insulated), NaN where it does not fit.  Every diamond is summed on its own - no running update from bin to bin - so a NaN pixel shows in
+// the bins whose diamond holds it and in no other, and the order of every sum is fixed by (n, w) alone.
+#define SCREEN_INSULATION_MAX_WIDTHS 8
+#define SCREEN_INSULATION_MAX_WIDTH 128
+#define SCREEN_INSULATION_BINS 32          // bins per workgroup: 4 waves, 8 bins each
+#define SCREEN_VIEWPOINTS_MAX 64
+
+// the sum of the diamond of bin i (which fits) over map m, in every lane of the wave: element e = row * w + column goes to lane e % 64, so consecutive
+// lanes read consecutive columns; fp64 per lane in ascending e, then the shuffles
+static __device__ __forceinline__ double screen_diamond_sum(const float* __restrict__ m, int n, int i, int w, int lane) {
+  const float* d = m + (long)(i - w) * n + (i + 1);
+  double s = 0.0;
+  int r = lane / w, c = lane - r * w;
+  const int dr = 64 / w, dc = 64 - dr * w;             // e += 64 moves (r, c) by (dr, dc), carrying once
+  for (int e = lane; e < w * w; e += 64) {
+    s += (double)d[(long)r * n + c];
+    r += dr;
+    c += dc;
+    if (c >= w) { c -= w; ++r; }
+  }
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  return s;
+}
+
+// insulation tracks of B alt maps [B][n][n] (batch stride map_bs) at W widths (int32, 1 .. SCREEN_INSULATION_MAX_WIDTH - the host entry point checks
+// them; any other width reads as one that fits nowhere): track[b][k][i] = ins_wk(alt b)[i]; with ref [n][n], delta[b][k][i] = ins(alt b)[i] - ins(ref)[i]
+// (the difference of the two fp64 means, rounded once); with the bin map, aligned[b][k][i] = ins(alt b)[i] - ins(ref)[map i] where map i >= 0 and the
+// reference diamond fits at map i, else NaN - only the centre bin has to be mapped.  ref, delta, aligned and bin_map may each be NULL (the host entry
+// point says which combinations).  One workgroup per (map, width, SCREEN_INSULATION_BINS bins), one wave per bin at a time; the pixels come from global
+// memory (a map does not fit LDS; neighbouring diamonds overlap, so the re-reads hit L2).  Where map i == i the aligned value is the delta's expression.
+static __global__ void __launch_bounds__(256) screen_insulation_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, int n,
+                                                                       const int* __restrict__ widths, int W, const int* __restrict__ bin_map,
+                                                                       float* __restrict__ track, float* __restrict__ delta, float* __restrict__ aligned) {
+  __shared__ int s_map[SCREEN_ALIGNED_MAX_BINS];
+  const int b = blockIdx.x, k = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  n = n > SCREEN_ALIGNED_MAX_BINS ? SCREEN_ALIGNED_MAX_BINS : n;
+  if (bin_map) screen_load_bin_map(bin_map + (long)b * n, n, s_map);
+  __syncthreads();
+  int w = widths[k];
+  w = (w >= 1 && w <= SCREEN_INSULATION_MAX_WIDTH) ? w : n;          // n fits nowhere
+  const double ww = (double)w * (double)w;
+  const float* a = alt + (long)b * map_bs;
+  const float qnan = __int_as_float(0x7fc00000);
+  const int i0 = blockIdx.z * SCREEN_INSULATION_BINS;
+  for (int i = i0 + wv; i < i0 + SCREEN_INSULATION_BINS && i < n; i += 4) {         // wave-uniform
+    const long at = ((long)b * W + k) * n + i;
+    const bool fits = i >= w && i < n - w;
+    const double ia = fits ? screen_diamond_sum(a, n, i, w, lane) / ww : 0.0;
+    const double ir = (fits && ref && (delta || aligned)) ? screen_diamond_sum(ref, n, i, w, lane) / ww : 0.0;
+    float al = qnan;
+    if (aligned && fits) {
+      const int r = bin_map ? s_map[i] : -1;
+      if (r == i) al = (float)(ia - ir);
+      else if (r >= w && r < n - w && ref) al = (float)(ia - screen_diamond_sum(ref, n, r, w, lane) / ww);
+    }
+    if (lane == 0) {
+      track[at] = fits ? (float)ia : qnan;
+      if (delta) delta[at] = (fits && ref) ? (float)(ia - ir) : qnan;
+      if (aligned) aligned[at] = al;
+    }
+  }
+}
+
+// viewpoint profiles (virtual 4C) of B alt maps [B][n][n] (batch stride map_bs) against ref [n][n] at V viewpoint bins (int32, 0 .. n - 1 - the host
+// entry point checks them; clipped here all the same): delta[b][v][j] = alt[b][view][j] - ref[view][j], an fp32 subtraction.  With the bin map the
+// viewpoint is a REFERENCE bin: R = the alt bins i with map i == view, ascending, c = |R|; aligned[b][v][j] = (sum_{i in R} alt[b][i][j]) / c -
+// ref[view][map j] in fp64 where c >= 1 and map j >= 0 (for c = 1 the fp32 subtraction itself), else NaN - the viewpoint was deleted, or column j stands
+// for nothing.  One workgroup per (map, viewpoint), one thread per column: wave 0 lists R in LDS, then every thread walks R down its own column
+// (coalesced along the row) and gathers the reference row through the LDS bin map.  bin_map and aligned are NULL together.
+static __global__ void __launch_bounds__(256) screen_viewpoints_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, int n,
+                                                                       const int* __restrict__ views, int V, const int* __restrict__ bin_map,
+                                                                       float* __restrict__ delta, float* __restrict__ aligned) {
+  __shared__ int s_map[SCREEN_ALIGNED_MAX_BINS], s_rows[SCREEN_ALIGNED_MAX_BINS];
+  __shared__ int s_cnt;
+  const int b = blockIdx.x, v = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = threadIdx.x;
+  n = n > SCREEN_ALIGNED_MAX_BINS ? SCREEN_ALIGNED_MAX_BINS : n;
+  int view = views[v];
+  view = view < 0 ? 0 : (view > n - 1 ? n - 1 : view);
+  const bool al = bin_map && aligned;
+  if (al) screen_load_bin_map(bin_map + (long)b * n, n, s_map);
+  __syncthreads();
+  if (al && wv == 0) {
+    const int c = screen_bins_in(s_map, n, view, view + 1, s_rows, lane);
+    if (lane == 0) s_cnt = c;
+  }
+  __syncthreads();
+  if (j >= n) return;
+  const float* a = alt + (long)b * map_bs;
+  const long at = ((long)b * V + v) * n + j;
+  delta[at] = a[(long)view * n + j] - ref[(long)view * n + j];
+  if (!al) return;
+  const int c = s_cnt, mj = s_map[j];
+  float out = __int_as_float(0x7fc00000);
+  if (c == 1 && mj >= 0) {
+    out = a[(long)s_rows[0] * n + j] - ref[(long)view * n + mj];
+  } else if (c > 1 && mj >= 0) {
+    double s = 0.0;
+    for (int t = 0; t < c; ++t) s += (double)a[(long)s_rows[t] * n + j];
+    out = (float)(s / (double)c - (double)ref[(long)view * n + mj]);
+  }
+  aligned[at] = out;
+}
+
 // ---- both strands (screen.screen_1m(..., strands="both")): the '-' strand's map is merged into the '+' strand's as genomepredict merges them ------------
 // out[b][i][j] = 0.5 fwd[b][i][j] + 0.5 rev[b][n-1-i][n-1-j] (the expression of strand_merge_kernel: the same bits), and with the two strands' reference maps
 // gap[b] = mean_ij |(fwd - ref_fwd)[i][j] - (rev - ref_rev)[n-1-i][n-1-j]| - how far the strands disagree about the item's effect.  One workgroup per map, one

@@ -831,6 +831,67 @@ def screen_aligned_region_scores(ctx, alt, ref, bin_map_host, rects_host, bin_ma
     return sg, ab
 
 
+# tracks (orca_screen_insulation, orca_screen_viewpoints): 1-D readouts per map; the widths / viewpoints are one more small table, the bin map is optional
+def _track_args(alt, ref, table_host, name, bin_map_host, bin_map):
+    """The arguments the two track entry points share: (alt, ref, batch stride, table [k] int32 on the host, its device copy, bin map host / device or
+    None / None)."""
+    if bin_map_host is None:
+        if bin_map is not None:
+            raise ValueError("bin_map: the device copy of bin_map_host, which is None")
+        (alt, ref, _), m, md = _maps_args(alt, ref), None, None
+    else:
+        alt, ref, m, md = _aligned_args(alt, ref, bin_map_host, bin_map)
+    if alt.shape[0] < 1:
+        raise ValueError("alt: at least one map")
+    t = _host_table(np.asarray(table_host).reshape(-1, 1), np.int32, 1, name)[:, 0]
+    n = ref.shape[0]
+    bs = alt.stride(0) if alt.shape[0] > 1 else max(alt.stride(0), n * n)          # B = 1: torch may report any stride for the one map
+    return alt, ref, bs, t, torch.from_numpy(t).to(alt.device), m, md
+
+
+def screen_insulation(ctx, alt, ref, widths_host, bin_map_host=None, bin_map=None):
+    """Insulation tracks of alt [B, n, n] (any batch stride, rows contiguous) at the W widths ``widths_host`` (1 to 8 ints, each 1 .. 128 bins), against
+    ref [n, n] (orca_screen_insulation): (track [B, W, n], delta [B, W, n], aligned [B, W, n] or None).  The diamond of bin i at width w is rows
+    [i - w, i) x columns (i, i + w]; ins_w(m)[i] is its fp64 mean, NaN where it does not fit (i < w or i >= n - w).  track = ins(alt), delta = ins(alt)[i] -
+    ins(ref)[i], and with ``bin_map_host`` [B, n] int32 (``bin_map``: its device copy, uploaded here when None) aligned = ins(alt)[i] - ins(ref)[map i],
+    NaN where alt bin i stands for no reference bin or the reference diamond does not fit there.  ``ref=None``: the track alone, (track, None, None)."""
+    if ref is None:
+        if bin_map_host is not None or bin_map is not None:
+            raise ValueError("ref=None computes the track alone: no bin map")
+        alt = _f32_cuda(alt, "alt")
+        if alt.dim() != 3:
+            raise ValueError("alt: [B,n,n]")
+        alt, _, bs, w, wd, m, md = _track_args(alt, alt[0], widths_host, "widths", None, None)       # ref only says n here; it is not passed on
+    else:
+        alt, ref, bs, w, wd, m, md = _track_args(alt, ref, widths_host, "widths", bin_map_host, bin_map)
+    B, n, W = alt.shape[0], alt.shape[1], w.shape[0]
+    null = ctypes.c_void_p(0)
+    track, = _f32_outputs(alt.device, (B, W, n))
+    delta = None if ref is None else _f32_outputs(alt.device, (B, W, n))[0]
+    aligned = None if m is None else _f32_outputs(alt.device, (B, W, n))[0]
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_insulation(ctx.handle, _dev_p(alt), bs, null if ref is None else _p(ref), B, n, _dev_p(wd), _np_p(w), W,
+                                             null if m is None else _dev_p(md), null if m is None else _np_p(m), _dev_p(track),
+                                             null if delta is None else _dev_p(delta), null if aligned is None else _dev_p(aligned)), "orca_screen_insulation")
+    return track, delta, aligned
+
+
+def screen_viewpoints(ctx, alt, ref, views_host, bin_map_host=None, bin_map=None):
+    """Viewpoint profiles (virtual 4C) of alt [B, n, n] (any batch stride, rows contiguous) against ref [n, n] at the V viewpoint bins ``views_host`` (1 to
+    64 ints in [0, n)) (orca_screen_viewpoints): (delta [B, V, n], aligned [B, V, n] or None).  delta = alt[view, j] - ref[view, j] in fp32.  With
+    ``bin_map_host`` [B, n] int32 (``bin_map``: its device copy) the viewpoint is a REFERENCE bin: aligned = the mean of the alt rows i with map i == view,
+    at column j, minus ref[view, map j]; NaN where no alt bin stands for the viewpoint or column j stands for nothing."""
+    alt, ref, bs, v, vd, m, md = _track_args(alt, ref, views_host, "viewpoints", bin_map_host, bin_map)
+    B, n, V = alt.shape[0], alt.shape[1], v.shape[0]
+    null = ctypes.c_void_p(0)
+    delta, = _f32_outputs(alt.device, (B, V, n))
+    aligned = None if m is None else _f32_outputs(alt.device, (B, V, n))[0]
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_viewpoints(ctx.handle, _dev_p(alt), bs, _p(ref), B, n, _dev_p(vd), _np_p(v), V, null if m is None else _dev_p(md),
+                                             null if m is None else _np_p(m), _dev_p(delta), null if aligned is None else _dev_p(aligned)), "orca_screen_viewpoints")
+    return delta, aligned
+
+
 # both strands (orca_screen_merge_strands)
 def screen_merge_strands(ctx, fwd, rev, ref_fwd=None, ref_rev=None, out=None):
     """The '+' strand's maps ``fwd`` [B, n, n] and the '-' strand's ``rev`` [B, n, n] (any batch stride, rows contiguous) merged as genomepredict merges

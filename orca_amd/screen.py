@@ -40,6 +40,12 @@ generate the large edits this is for, and ``flank_bp`` reads enough genome behin
 forward coordinates; the front reads the same buffer reverse-complemented, and the '-' strand's plan is the mirror of the '+' strand's
 (`mirror_plan`: '+' row r is '-' row n5 - 1 - r).  One kernel merges a batch's two strands and measures how far they disagree
 (orca_screen_merge_strands, `ScreenResult.strand_gap`); the scores then run unchanged on the merged maps.
+
+The scores above are means and maxima of |alt - ref|: they say that something changed, not what.  ``screen_1m(..., insulation=widths)`` adds
+the insulation track of every alt map - the mean contact across each bin, over a diamond of the given width - and its signed difference to
+the reference's, and ``viewpoints=bins`` the signed row alt - ref of chosen bins (a virtual 4C); with ``aligned=True`` both also come on aligned
+bins, through the same `bin_map` (orca_screen_insulation, orca_screen_viewpoints; `insulation_scores_host`, `viewpoint_scores_host`).  Both are
+1-D tracks per item, so a deletion scan can ask "which deletion fuses the two domains" without ``keep_maps``.
 """
 from dataclasses import dataclass, field, replace
 from typing import Optional
@@ -912,6 +918,101 @@ def aligned_region_scores_host(maps, ref_map, bin_map, regions):
     return sg, ab
 
 
+def check_insulation(widths, n):
+    """``insulation`` as an int32 array of 1 to 8 distinct diamond widths in bins (an int stands for one width), each 1 <= w <= (n - 1) // 2: the
+    widths at which at least one bin of an n-bin map has a diamond."""
+    try:
+        w = _widths(widths)
+    except (TypeError, ValueError):
+        raise ValueError("insulation: a width in bins or a sequence of widths") from None
+    if not 1 <= len(w) <= 8 or len(set(w)) != len(w):
+        raise ValueError("insulation: 1 to 8 distinct widths")
+    for v in w:
+        if not 1 <= v <= (n - 1) // 2:
+            raise ValueError(f"insulation width {v}: 1 .. {(n - 1) // 2} bins on a map of {n} bins (the diamond must fit somewhere)")
+    return np.array(w, dtype=np.int32)
+
+
+def check_viewpoints(views, n):
+    """``viewpoints`` as an int32 array of 1 to 64 bins in [0, n)."""
+    try:
+        v = [int(x) for x in views]
+    except (TypeError, ValueError):
+        raise ValueError("viewpoints: a sequence of bins") from None
+    if not 1 <= len(v) <= 64:
+        raise ValueError("viewpoints: 1 to 64 bins")
+    for x in v:
+        if not 0 <= x < n:
+            raise ValueError(f"viewpoint {x}: inside the map's {n} bins")
+    return np.array(v, dtype=np.int32)
+
+
+def _widths(widths):
+    return [int(widths)] if np.ndim(widths) == 0 else [int(v) for v in widths]
+
+
+def insulation_host(maps, widths):
+    """Insulation tracks of maps [E, n, n] at ``widths`` (bins): fp64 [E, W, n].  The diamond of bin i at width w is rows [i - w, i) x columns
+    (i, i + w] - bin i's own row and column left out, centred on bin i; it fits when w <= i < n - w.  ins_w(m)[i] = the mean of m over the diamond
+    (w^2 terms, fp64), NaN where it does not fit; lower = more insulated.  Every diamond is summed on its own, so a NaN pixel shows in the bins
+    whose diamond holds it and in no other."""
+    m = np.asarray(maps, dtype=np.float64)
+    E, n = m.shape[0], m.shape[1]
+    ws = _widths(widths)
+    out = np.full((E, len(ws), n), np.nan)
+    for k, w in enumerate(ws):
+        for i in range(w, n - w):
+            out[:, k, i] = m[:, i - w: i, i + 1: i + w + 1].sum(axis=(1, 2)) / float(w * w)
+    return out
+
+
+def insulation_scores_host(maps, ref_map, widths, bin_map=None):
+    """The insulation fields of `ScreenResult` from alt maps [E, n, n] and the reference map [n, n] (fp64 host restatement of
+    orca_screen_insulation), with ins = `insulation_host`: (insulation [E, W, n] = ins(alt), delta_insulation [E, W, n] = ins(alt)[i] - ins(ref)[i],
+    aligned_insulation [E, W, n] or None without ``bin_map``).  aligned[e, k, i], with r = bin_map[e, i] ([E, n], or one [n] for all): ins(alt_e)[i] -
+    ins(ref)[r] if r >= 0, the alt diamond fits at i and the reference diamond fits at r, else NaN; indexed by ALT bin; only the centre bin has to
+    be mapped.  Where the bin map is the identity it is delta_insulation."""
+    alt = insulation_host(maps, widths)
+    ref = insulation_host(np.asarray(ref_map)[None], widths)[0]
+    E, n = alt.shape[0], alt.shape[2]
+    if bin_map is None:
+        return alt, alt - ref[None], None
+    bm = _bin_maps(bin_map, E, n)
+    at = np.full(alt.shape, np.nan)
+    for e in range(E):
+        M = np.flatnonzero(bm[e] >= 0)
+        at[e][:, M] = alt[e][:, M] - ref[:, bm[e, M]]
+    return alt, alt - ref[None], at
+
+
+def viewpoint_scores_host(maps, ref_map, views, bin_map=None):
+    """The viewpoint fields of `ScreenResult` from alt maps [E, n, n] and the reference map [n, n] (host restatement of orca_screen_viewpoints):
+    (delta_viewpoint [E, V, n] float32 = alt[view, j] - ref[view, j], the fp32 subtraction; aligned_viewpoint [E, V, n] float32 or None without
+    ``bin_map``).  For the aligned form the viewpoint is a REFERENCE bin: with R = the alt bins i with bin_map[e, i] == view (ascending) and
+    c = |R|, aligned[e, v, j] = fp32((sum_{i in R} alt[i, j]) / c - ref[view, bin_map[e, j]]) in fp64, the rows added in ascending i, where c >= 1
+    and bin_map[e, j] >= 0, else NaN (the viewpoint was deleted, or column j stands for nothing); for c = 1 it is the fp32 subtraction."""
+    alt, ref = np.asarray(maps, dtype=np.float32), np.asarray(ref_map, dtype=np.float32)
+    E, n = alt.shape[0], ref.shape[0]
+    vs = [int(v) for v in views]
+    delta = alt[:, vs, :] - ref[None, vs, :]
+    if bin_map is None:
+        return delta, None
+    bm = _bin_maps(bin_map, E, n)
+    at = np.full((E, len(vs), n), np.nan, dtype=np.float32)
+    for e in range(E):
+        cols = np.flatnonzero(bm[e] >= 0)
+        for k, v in enumerate(vs):
+            R = np.flatnonzero(bm[e] == v)
+            if R.size == 1:
+                at[e, k, cols] = alt[e, R[0], cols] - ref[v, bm[e, cols]]
+            elif R.size > 1:
+                s = np.zeros(cols.size)
+                for i in R:
+                    s = s + alt[e, i, cols].astype(np.float64)
+                at[e, k, cols] = (s / float(R.size) - ref[v, bm[e, cols]].astype(np.float64)).astype(np.float32)
+    return delta, at
+
+
 def merge_strands_host(plus, minus, ref_plus=None, ref_minus=None):
     """The merged maps of ``strands="both"`` (fp64 host restatement of orca_screen_merge_strands): ``plus``, ``minus`` [E, n, n] (or [n, n]) the two
     strands' maps, ``minus`` in the '-' strand's own orientation.  (merged, gap) with merged = 0.5 plus + 0.5 flip(minus), flip reversing both bin
@@ -956,8 +1057,24 @@ class ScreenResult:
       strand_gap         [E]          mean over the map of |(alt+ - ref+) - flip(alt- - ref-)|: how far the two strands disagree about the item's
                                       effect - set it beside ``delta_abs_mean``: an effect well above its gap is one both strands see
       ref_strand_gap     0-dim        mean |ref+ - flip(ref-)|: the model's strand asymmetry on the unedited window
+    With ``insulation=`` (None otherwise; W widths).  The diamond of bin i at width w is rows [i - w, i) x columns (i, i + w] of a map - bin i's own
+    row and column left out; it fits when w <= i < n - w.  ins_w(m)[i] = the mean of m over it (fp64), NaN where it does not fit; lower = more
+    insulated, so a boundary is a dip, and a positive difference at a bin says the boundary there weakened:
+      insulation_widths  [W] int32    the widths, in bins
+      ref_insulation     [W, n]       ins_w(ref_map)
+      insulation         [E, W, n]    ins_w(alt map)
+      delta_insulation   [E, W, n]    ins(alt)[i] - ins(ref)[i] (signed; the difference of the fp64 means, rounded once)
+      aligned_insulation [E, W, n]    with ``aligned=True``: ins(alt)[i] - ins(ref)[map i], indexed by ALT bin; NaN where alt bin i stands for no reference
+                                      bin or a diamond does not fit.  Only the centre bin has to be mapped - the alt diamond may hold inserted bases or
+                                      refill.  Where the bin map is the identity it is ``delta_insulation`` bit for bit
+    With ``viewpoints=`` (None otherwise; V bins) - a virtual 4C, the signed row of a bin:
+      viewpoint_bins     [V] int32    the viewpoint bins
+      delta_viewpoint    [E, V, n]    alt map[view, j] - ref_map[view, j] (fp32)
+      aligned_viewpoint  [E, V, n]    with ``aligned=True``: the viewpoint is a REFERENCE bin.  R = the alt bins that stand for it, c = |R|:
+                                      (sum_{i in R} alt map[i, j]) / c - ref_map[view, map j], indexed by ALT column j; NaN when c = 0 (the viewpoint was
+                                      deleted) or column j stands for nothing
     `scores_host` computes the three map scores from maps on the host, `region_scores_host` the two region scores, `aligned_scores_host` and
-    `aligned_region_scores_host` the aligned ones."""
+    `aligned_region_scores_host` the aligned ones, `insulation_scores_host` and `viewpoint_scores_host` the tracks."""
     ref_map: torch.Tensor
     ref_1d: Optional[torch.Tensor]
     delta_profile: torch.Tensor
@@ -978,6 +1095,14 @@ class ScreenResult:
     aligned_region_abs: Optional[torch.Tensor] = None
     strand_gap: Optional[torch.Tensor] = None
     ref_strand_gap: Optional[torch.Tensor] = None
+    insulation_widths: Optional[torch.Tensor] = None
+    ref_insulation: Optional[torch.Tensor] = None
+    insulation: Optional[torch.Tensor] = None
+    delta_insulation: Optional[torch.Tensor] = None
+    aligned_insulation: Optional[torch.Tensor] = None
+    viewpoint_bins: Optional[torch.Tensor] = None
+    delta_viewpoint: Optional[torch.Tensor] = None
+    aligned_viewpoint: Optional[torch.Tensor] = None
 
 
 # ---- the screen -----------------------------------------------------------------------------------------------------------------------------
@@ -1144,7 +1269,8 @@ class _Screen:
         return self._decode(out), self._decode(self._strand_enc(mirror_plan(p), edits, codes, s5_ref_minus, True))
 
 
-def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regions=None, flank=None, aligned=False, flank_bp=None, strands="+"):
+def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regions=None, flank=None, aligned=False, flank_bp=None, strands="+",
+              insulation=None, viewpoints=None):
     """Score ``edits`` (a list of `Edit` and `EditSet`, one row of every result tensor each) of one window with the 1 Mb model: a `ScreenResult`.
 
     ``model``: an ``H1esc_1M`` / ``Hff_1M`` container or a bare ``orca_modules.Net``.  ``window``: the window's base codes, a [L] uint8 tensor on
@@ -1184,7 +1310,15 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
     pools its '-' rows from the '-' strand's stage-4 cache entries (built with the reference too; ``cache_phases`` counts both strands').  One
     deferred range check covers both strands of a batch (and of the reference).  The screen is decode-bound, so expect about twice the time
     per item.  More ``stats``: ``strands``, ``reverse_two_part_items`` / ``reverse_whole_items`` (items whose '-' strand ran two-part /
-    through the whole-window Encoder: the whole-window route and the range-safe redo)."""
+    through the whole-window Encoder: the whole-window route and the range-safe redo).
+
+    ``insulation``: a diamond width in bins or 1 to 8 distinct widths, each 1 <= w <= (n - 1) // 2, for the insulation tracks
+    `ScreenResult.insulation`, ``ref_insulation``, ``delta_insulation`` and, with ``aligned=True``, ``aligned_insulation`` (orca_screen_insulation):
+    the mean contact across every bin, the readout for "did a boundary weaken or appear".  ``viewpoints``: 1 to 64 bins for
+    `ScreenResult.delta_viewpoint` and, with ``aligned=True``, ``aligned_viewpoint`` (orca_screen_viewpoints): the signed row alt - ref of a bin, a
+    virtual 4C; in the aligned form the viewpoint is a REFERENCE bin, followed to wherever the item moved it.  Both are taken from the batch's
+    maps whichever route made them, with ``strands="both"`` from the merged maps against the merged ``ref_map``.  With both None nothing more is
+    launched and every other field is what it was.  ``stats`` gains ``insulation_widths`` and ``viewpoints``: their numbers (0 when absent)."""
     if strands not in ("+", "both"):
         raise ValueError(f"strands must be '+' or 'both', got {strands!r}")
     both = strands == "both"
@@ -1205,10 +1339,13 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
     if batch <= 0:
         raise ValueError("batch must be positive")
     rects = None if regions is None else check_regions(regions, win.numel() // 4000)
+    widths = None if insulation is None else check_insulation(insulation, win.numel() // 4000)
+    views = None if viewpoints is None else check_viewpoints(viewpoints, win.numel() // 4000)
     st = {"route": None, "two_part_batches": 0, "whole_window_batches": 0, "range_fallback_batches": 0, "range_fallback_reference": False,
           "front_runs": 0, "front_bases": 0, "edits": len(edits), "set_items": sum(isinstance(e, EditSet) for e in edits), "segments": 0,
           "indel_items": sum(changes_length(e) for e in edits), "take_rows": 0, "cache_phases": 0, "aligned_items": 0,
-          "strands": strands, "reverse_two_part_items": 0, "reverse_whole_items": 0}
+          "strands": strands, "reverse_two_part_items": 0, "reverse_whole_items": 0,
+          "insulation_widths": 0 if widths is None else len(widths), "viewpoints": 0 if views is None else len(views)}
     fl = _flank_codes(window, flank, win, flank_bp) if (flank is not None or st["indel_items"]) else None
     sc = _Screen(net, win, st, fl if st["indel_items"] else None)
     E, n, dev = len(edits), sc.n, sc.dev
@@ -1279,6 +1416,18 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
             if rects is not None:
                 res.aligned_region = torch.zeros((E, len(rects)), dtype=torch.float32, device=dev)
                 res.aligned_region_abs = torch.zeros((E, len(rects)), dtype=torch.float32, device=dev)
+        if widths is not None:                           # the reference's own track once, from the final (merged) reference map
+            res.insulation_widths = sc._upload(widths, torch.int32)
+            res.ref_insulation = engine.screen_insulation(sc.ctx, ref_map[None], None, widths)[0][0]
+            res.insulation = torch.zeros((E, len(widths), n), dtype=torch.float32, device=dev)
+            res.delta_insulation = torch.zeros((E, len(widths), n), dtype=torch.float32, device=dev)
+            if aligned:
+                res.aligned_insulation = torch.zeros((E, len(widths), n), dtype=torch.float32, device=dev)
+        if views is not None:
+            res.viewpoint_bins = sc._upload(views, torch.int32)
+            res.delta_viewpoint = torch.zeros((E, len(views), n), dtype=torch.float32, device=dev)
+            if aligned:
+                res.aligned_viewpoint = torch.zeros((E, len(views), n), dtype=torch.float32, device=dev)
         def whole(chunk):                                # a batch on the whole-window route: the '+' strand, or the pair of strands
             if not both:
                 return sc.whole(chunk)
@@ -1324,6 +1473,16 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
                 if rects is not None:
                     res.aligned_region[i0:i1], res.aligned_region_abs[i0:i1] = engine.screen_aligned_region_scores(
                         sc.ctx, maps, ref_map, bmaps[i0:i1], rects, res.bin_map[i0:i1])
+            if widths is not None:
+                tr, dl, al = engine.screen_insulation(sc.ctx, maps, ref_map, widths, bmaps[i0:i1] if aligned else None, res.bin_map[i0:i1] if aligned else None)
+                res.insulation[i0:i1], res.delta_insulation[i0:i1] = tr, dl
+                if aligned:
+                    res.aligned_insulation[i0:i1] = al
+            if views is not None:
+                dl, al = engine.screen_viewpoints(sc.ctx, maps, ref_map, views, bmaps[i0:i1] if aligned else None, res.bin_map[i0:i1] if aligned else None)
+                res.delta_viewpoint[i0:i1] = dl
+                if aligned:
+                    res.aligned_viewpoint[i0:i1] = al
             if h is not None:
                 torch.sub(h, ref_1d[None], out=res.delta_1d[i0:i1])
             if keep_maps:

@@ -26,6 +26,10 @@ Aligned scores, into profiles/screen_1m_aligned.json:
 Both strands, into profiles/screen_1m_strands.json:
   --strands both the 3 250-edit workload at B = 64 through screen_1m with strands="both", and alternated in the same run with strands="+" and the
                  naive both-strand route (the edited windows through Net on both strands, merged by orca_screen_merge_strands, the same scores)
+
+Tracks, into profiles/screen_1m_tracks.json:
+  --tracks       the 3 250-edit workload at B = 64 through screen_1m with insulation=(5, 10, 25), viewpoints=[125] and without, alternated in the same
+                 run; with --aligned also aligned=True with and without the tracks: what the two track kernels add, set beside what aligned=True adds
 """
 import argparse
 import json
@@ -166,6 +170,38 @@ def time_aligned(a, model, win, edits, dev):
     return rep
 
 
+TRACKS = {"insulation": (5, 10, 25), "viewpoints": [125]}
+
+
+def time_tracks(a, model, win, edits, dev):
+    """The --tracks workload: screen_1m on the same edits with and without the insulation tracks and the viewpoint profile, alternated, at B = 64;
+    with --aligned also both with aligned=True.  The overheads are over the plain screen of the same run."""
+    B = 64
+    rep = {"device": torch.cuda.get_device_name(dev), "edits": len(edits), "batch": B, "insulation": list(TRACKS["insulation"]), "viewpoints": TRACKS["viewpoints"]}
+    runs = {"plain": {}, "tracks": dict(TRACKS)}
+    if a.aligned:
+        runs.update({"aligned": {"aligned": True}, "aligned_tracks": dict(TRACKS, aligned=True)})
+    st = {}
+    for kw in runs.values():                                                                     # warm-up
+        S.screen_1m(model, win, edits[:B], batch=B, stats=st, **kw)
+    rep["route"] = st["route"]
+    t = {k: [] for k in runs}
+    for _ in range(a.reps):
+        for k, kw in runs.items():
+            t[k].append(timed(lambda: S.screen_1m(model, win, edits, batch=B, **kw))[0])
+    for k in runs:
+        rep[f"{k}_s"] = [round(x, 3) for x in t[k]]
+        rep[f"{k}_edits_per_s"] = round(len(edits) / min(t[k]), 1)
+    plain = min(t["plain"])
+    rep["tracks_over_plain"] = round(min(t["tracks"]) / plain, 4)
+    if a.aligned:
+        rep["aligned_over_plain"] = round(min(t["aligned"]) / plain, 4)
+        rep["aligned_tracks_over_aligned"] = round(min(t["aligned_tracks"]) / min(t["aligned"]), 4)
+        over = min(t["aligned"]) - plain
+        rep["tracks_overhead_over_aligned_overhead"] = round((min(t["tracks"]) - plain) / over, 2) if over > 0 else None
+    return rep
+
+
 def naive_both(model, win, edits, batch, keep_maps=False):
     """`naive` on both strands: every batch's edited windows through Net's Encoder and Decoder_1m forwards and reverse-complemented, merged."""
     sc = S._Screen(model.net, win, {})
@@ -218,6 +254,7 @@ def main():
     ap.add_argument("--haplotype-span", type=int, default=L)
     ap.add_argument("--indels", type=int, default=0, help="N: time N random 1-50-base indels at B = 64")
     ap.add_argument("--aligned", action="store_true", help="time the 3 250-edit workload with aligned=True against aligned=False")
+    ap.add_argument("--tracks", action="store_true", help="time the 3 250-edit workload at B = 64 with insulation and viewpoint tracks against without")
     ap.add_argument("--strands", default="+", choices=("+", "both"), help="both: time the 3 250-edit workload on both strands at B = 64")
     ap.add_argument("--commit", default="", help="recorded in the report")
     a = ap.parse_args()
@@ -249,6 +286,17 @@ def main():
                 json.dump(rep, f, indent=1)
         return
     edits = S.saturation_edits(c, 499_500, 500_500) + S.tile_edits("mask", 4000, 4000, 0, L)
+    if a.tracks:
+        rep = {"workload": f"H1esc_1M synthetic, 1 Mb window, {len(edits)} edits (saturation SNVs of 1 kb + 250 4 kb mask tiles); screen_1m with "
+                           "insulation=(5, 10, 25), viewpoints=[125] against without, alternated (every call includes its reference)", "commit": a.commit}
+        rep.update(time_tracks(a, model, win, edits, dev))
+        print(json.dumps(rep))
+        out = a.out if a.out != ap.get_default("out") else os.path.join(os.path.dirname(a.out), "screen_1m_tracks.json")
+        if out:
+            os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+            with open(out, "w") as f:
+                json.dump(rep, f, indent=1)
+        return
     if a.aligned:
         rep = {"workload": f"H1esc_1M synthetic, 1 Mb window, {len(edits)} edits (saturation SNVs of 1 kb + 250 4 kb mask tiles); screen_1m with "
                            "aligned=True against aligned=False, alternated (every call includes its reference)", "commit": a.commit}
