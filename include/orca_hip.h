@@ -166,6 +166,10 @@ int orca_net_set_encoder_form(orca_net* net, int form);
  * (conv2d_dblock_run_kernel, bit-identical to the three per-block launches); on by default, 0 = one launch per block.  The other precisions
  * always launch per block.  ORCA_EINVAL on any other net. */
 int orca_net_set_decoder_block_runs(orca_net* net, int on);
+/* ORCA_NET_ENCODER only: orca_encoder_forward_two_strands runs stages 3-7 of both strands as one joint pass (bit-identical to the two per-strand
+ * calls); on by default, 0 = the two calls.  ORCA_EINVAL on any other net. */
+int orca_net_set_encoder_two_strands(orca_net* net, int on);
+int orca_net_get_encoder_two_strands(orca_net* net, int* on);
 /* ORCA_PRECISION_F16X2 only: the kernels raise a device flag when an activation leaves the fp16
  * range (the result of that forward is then invalid).  This call waits for the context's stream,
  * returns the flag in *flag and clears it - the host falls back to ORCA_PRECISION_BF16X3. */
@@ -212,6 +216,12 @@ int orca_encoder_forward_codes_window(orca_ctx* ctx, orca_net* net, const uint8_
  * directly - the one-hot expansion happens in LDS as for the 1-byte codes - so no unpacked copy of the window exists. */
 int orca_encoder_forward_2bit(orca_ctx* ctx, orca_net* net, const uint8_t* two, const uint8_t* nmask, int64_t start, int reverse, int64_t L,
                               int64_t bin_lo, int64_t bin_hi, float* out, int64_t so_c, int64_t chunk_bp);
+/* Both strands of one packed sequence (`codes`: L bytes): the forward strand's bins into out_fwd[c * so_c + bin], the reverse complement's into
+ * out_rev, exactly what orca_encoder_forward_codes with reverse = 0 / 1 writes (bit-identical, the fp16-range flag included).  With
+ * ORCA_PRECISION_F16X2 / _BF16, the default form, L a multiple of 4000 and at most one chunk (32 Mb / $ORCA_ENCODER_CHUNK_BP) stages 1-2 run per
+ * strand and stages 3-7 ONCE for both: the strands share one set of planes with a zero gap between them (stages 3-4) and run as a batch of two
+ * rows (stages 5-7).  That costs a fourth workspace buffer of 6 L bytes x 2 (1.5 GB for 32 Mb).  Any other net state: the two per-strand calls. */
+int orca_encoder_forward_two_strands(orca_ctx* ctx, orca_net* net, const uint8_t* codes, int64_t L, float* out_fwd, float* out_rev, int64_t so_c);
 
 /* ---- the Encoder in two parts: structural-variant screens at arbitrary base positions ----------------------------
  * The reference's drivers place every window at the variant's own phase (orca_predict.py:1613: wpos = coord_clip(mstart) - no rounding to

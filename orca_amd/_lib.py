@@ -50,6 +50,9 @@ SIGNATURES = {
     "orca_net_set_precision": (c_int, [c_void_p, c_int]),
     "orca_net_set_encoder_form": (c_int, [c_void_p, c_int]),
     "orca_net_set_decoder_block_runs": (c_int, [c_void_p, c_int]),
+    "orca_net_set_encoder_two_strands": (c_int, [c_void_p, c_int]),
+    "orca_net_get_encoder_two_strands": (c_int, [c_void_p, POINTER(c_int)]),
+    "orca_encoder_forward_two_strands": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64]),
     "orca_encoder_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_int64,
                                      c_int64, c_void_p, c_int64, c_int64, c_int64]),
     "orca_p16_plane_units": (c_int64, [c_int64]),

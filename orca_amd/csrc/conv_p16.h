@@ -760,12 +760,13 @@ __global__ __launch_bounds__(WM * 64, WM / 4) void conv1d_k9_p16_kernel(ConvP16A
   if (FMT == 0 && OM != 2 && vmax > 65504.f && a.flag) *a.flag = 1u;
 }
 
-// zero the guard / tail units of every plane: [0, P16_GUARD) and [P16_GUARD + n_valid, plen)
-static __global__ void p16_zero_pads_kernel(f32x4* __restrict__ base, long plen, long n_valid) {
+// zero the guard / tail units of every plane: [0, P16_GUARD) and [P16_GUARD + n_valid, plen); and the units of positions [gap0, gap1) between two
+// sequences that share the planes (the two strands of orca_encoder_forward_two_strands; gap0 = gap1: one sequence)
+static __global__ void p16_zero_pads_kernel(f32x4* __restrict__ base, long plen, long n_valid, long gap0, long gap1) {
   f32x4* pl = base + (long)blockIdx.x * plen;
-  const long tail0 = P16_GUARD + n_valid;
-  for (long i = threadIdx.x; i < P16_GUARD + (plen - tail0); i += blockDim.x) {
-    const long u = i < P16_GUARD ? i : tail0 + (i - P16_GUARD);
+  const long tail0 = P16_GUARD + n_valid, ngap = gap1 - gap0;
+  for (long i = threadIdx.x; i < P16_GUARD + ngap + (plen - tail0); i += blockDim.x) {
+    const long u = i < P16_GUARD ? i : i < P16_GUARD + ngap ? gap0 + i : tail0 + (i - P16_GUARD - ngap);
     pl[u] = (f32x4)(0.f);
   }
 }

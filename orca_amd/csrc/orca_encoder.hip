@@ -89,9 +89,9 @@ static int launch_conv1d_b16_ns(orca_ctx* ctx, const ConvLayer& L, const ConvB16
   else if (L.cout == 96) launch_b16_t<96, 1, 3, 8, 1, NS, DT>(s, a, B);
   else if (L.cout == 128) {
     // stages 6-7 of the Encoder (16 000 / 8 000 positions) make 63 / 32 tiles of 256 positions for 256 CUs: 64-position tiles there
-    // (fixed_tile: the 256-position tiles whatever the batch - a batch of edits is many rows)
+    // (fixed_tile 1: the 256-position tiles whatever the batch - a batch of edits is many rows; 2: what one row of the batch would take alone)
     if constexpr (NS <= 2) {
-      if (!fixed_tile && ((a.n + 255) / 256) * B < 200) { launch_b16_t<128, 1, 2, 2, 2, NS, DT>(s, a, B); return ORCA_OK; }
+      if (fixed_tile != 1 && ((a.n + 255) / 256) * (fixed_tile == 2 ? 1 : B) < 200) { launch_b16_t<128, 1, 2, 2, 2, NS, DT>(s, a, B); return ORCA_OK; }
     }
     launch_b16_t<128, 2, 2, 4, 2, NS, DT>(s, a, B);
   }
@@ -131,9 +131,9 @@ int launch_conv1d_b16(orca_ctx* ctx, const ConvLayer& L, int precision, const fl
     return ORCA_OK;
   }
   if (precision == ORCA_PRECISION_BF16X3) rc = launch_conv1d_b16_ns<3, 0>(ctx, L, a, B);
-  else if (precision == ORCA_PRECISION_BF16X2) rc = launch_conv1d_b16_ns<2, 0>(ctx, L, a, B);
+  else if (precision == ORCA_PRECISION_BF16X2) rc = launch_conv1d_b16_ns<2, 0>(ctx, L, a, B, fixed_tile == 2 ? 2 : 0);
   else if (precision == ORCA_PRECISION_F16X2) rc = launch_conv1d_b16_ns<2, 1>(ctx, L, a, B, fixed_tile);
-  else rc = launch_conv1d_b16_ns<1, 0>(ctx, L, a, B);
+  else rc = launch_conv1d_b16_ns<1, 0>(ctx, L, a, B, fixed_tile == 2 ? 2 : 0);
   if (rc != ORCA_OK) return rc;
   LAUNCHCHECK("conv1d_k9_bf16s_kernel");
   ctx->counts[1]++;
@@ -166,9 +166,10 @@ static EdgeFixArgs edge_source(const SeqSource& s) {   // in_mode 1 (bases) or 0
 
 // ---- P16 (planar split fp16) conv1d with LDS-DMA staging (conv_p16.h) -------------------------------------
 // (plane lengths: p16_plen in orca_internal.h)
-int launch_p16_zero_pads(orca_ctx* ctx, float* base, int C, long n_valid, int fmt) {
+int launch_p16_zero_pads(orca_ctx* ctx, float* base, int C, long n_valid, int fmt, long plen, long gap0, long gap1) {
+  if (gap0 < 0 || gap1 < gap0 || gap1 > n_valid || (plen && plen < P16_GUARD + n_valid)) return fail(ORCA_EINVAL, "internal: zero pads outside the planes");
   hipLaunchKernelGGL(p16_zero_pads_kernel, dim3((unsigned)(fmt == 1 ? C / 8 : C / 8 * 2)), dim3(256), 0, ctx->stream, reinterpret_cast<f32x4*>(base),
-                     p16_plen(n_valid), n_valid);
+                     plen ? plen : p16_plen(n_valid), n_valid, gap0, gap1);
   LAUNCHCHECK("p16_zero_pads_kernel");
   return ORCA_OK;
 }
@@ -284,7 +285,7 @@ struct FusedFirst {   // packed bases + first-layer table: the conv's input is p
 
 // fmt 0: P16 activations (fp32-class f16x2 arithmetic); fmt 1: B16 activations (plain bf16, BASELINE config 3)
 int launch_conv1d_p16(orca_ctx* ctx, const ConvLayer& L, const float* x, void* y, const float* r1, long n, int relu,
-                             int out_mode, const FusedFirst* f1, int fmt) {
+                             int out_mode, const FusedFirst* f1, int fmt, const P16Layout* lay) {
   const bool k17 = L.ksize == 17;
   if ((L.ksize != 9 && !k17) || (fmt == 0 ? !L.d_wf16 : !L.d_wb16p)) return fail(ORCA_EINVAL, "layer has no %s pack", fmt == 0 ? "fp16 split" : "bf16");
   if (fmt == 0 && !L.f16_ok) return fail(ORCA_EINVAL, "layer weights exceed the fp16 range: use ORCA_PRECISION_BF16X3");
@@ -293,6 +294,14 @@ int launch_conv1d_p16(orca_ctx* ctx, const ConvLayer& L, const float* x, void* y
   ConvP16Args a;
   a.x = reinterpret_cast<const f32x4*>(x); a.w = reinterpret_cast<const f32x4*>(fmt == 0 ? L.d_wf16 : L.d_wb16p); a.bias = L.d_bias; a.y = y;
   a.r1 = reinterpret_cast<const f32x4*>(r1); a.x_plen = p16_plen(n); a.y_plen = p16_plen(out_mode == 1 ? n / 4 : out_mode == 3 ? n / 5 : n); a.n = n;
+  long n_rec = n;
+  if (lay) {
+    if (f1 || (lay->y_off && out_mode == 2)) return fail(ORCA_EINVAL, "internal: an explicit plane layout on a conv from the bases / an offset into fp32 rows");
+    if (lay->x_plen) a.x_plen = lay->x_plen;
+    if (lay->y_plen) a.y_plen = lay->y_plen;
+    a.y = static_cast<f32x4*>(y) + lay->y_off;
+    if (lay->n_valid) n_rec = lay->n_valid;
+  }
   a.nchunks = (fmt == 0 ? L.cin / 16 : L.cin / 32) * (k17 ? 2 : 1); a.cout = L.cout; a.relu = relu; a.out_mode = out_mode; a.flag = ctx->d_flag;
   a.k17 = k17 ? 1 : 0;
   LaunchTimer timer(ctx, n);
@@ -329,7 +338,7 @@ int launch_conv1d_p16(orca_ctx* ctx, const ConvLayer& L, const float* x, void* y
     return fail(ORCA_EINVAL, "%s conv1d cout %d unsupported", fmt == 1 ? "b16" : "p16", L.cout);
   }
   LAUNCHCHECK("conv1d_k9_p16_kernel");
-  return timer.close(L.cout, L.cin, tile_tag, 1, n, k17 ? 17 : 9);
+  return timer.close(L.cout, L.cin, tile_tag, 1, n_rec, k17 ? 17 : 9);
 }
 
 // one first-layer GEMM launch from the bases / flat [n][4] float rows onto planes (fmt 0 P16, 1 B16): ntap 9 (lconv1.a alone), 17 (lconv1 composed),
@@ -382,9 +391,10 @@ static int launch_stage1_b16(orca_ctx* ctx, const orca_net* net, const ConvLayer
 // the end positions of a stage's composed linear group, recomputed conv by conv (conv_p16.h: lconv_edge_layer_kernel): its first `depth` (2-4) layers
 // Ls[0 ..], ReLU behind the third and the fourth.  The last layer covers `half_last` positions per end, layer l four more per layer behind it; the
 // outermost 4 per end of lout (layer 2) go to `lo`, the outermost 8 of layer 3 to `t`, where given.  fmt 0 / 1: planes, 2: fp32 channel-major with row
-// stride ld_f32, 3: fp32 channel-last.  Scratch: one 40 x 128 float slab per layer in the context.
+// stride ld_f32, 3: fp32 channel-last.  Scratch: one 40 x 128 float slab per layer in the context.  y_plen: plane length of lo / t where it is not
+// p16_plen(n) (a sequence inside longer planes: src.xp, lo, t point at ITS first unit)
 static int launch_edge_chain(orca_ctx* ctx, const ConvLayer* Ls, int depth, int half_last, EdgeFixArgs src, long n, float* lo, float* t, int fmt,
-                             long ld_f32 = 0) {
+                             long ld_f32 = 0, long y_plen = 0) {
   src.n = n;
   if (depth > 4 || 2 * (half_last + 4 * (depth - 1)) > 40) return fail(ORCA_EINVAL, "edge fix: chain too deep");
   for (int l = 0; l < depth; ++l) {
@@ -398,7 +408,7 @@ static int launch_edge_chain(orca_ctx* ctx, const ConvLayer* Ls, int depth, int 
     a.sin = l > 0 ? ctx->d_edge + (l - 1) * ORCA_EDGE_SLAB : nullptr;
     a.sout = ctx->d_edge + l * ORCA_EDGE_SLAB;
     float* const y = l == 1 ? lo : l == 2 ? t : nullptr;
-    a.y = reinterpret_cast<f32x4*>(y); a.y_plen = fmt == 2 ? ld_f32 : p16_plen(n); a.out_fmt = fmt; a.flag = ctx->d_flag;
+    a.y = reinterpret_cast<f32x4*>(y); a.y_plen = fmt == 2 ? ld_f32 : y_plen ? y_plen : p16_plen(n); a.out_fmt = fmt; a.flag = ctx->d_flag;
     a.store_half = !y ? 0 : l == 1 ? 4 : 8;
     hipLaunchKernelGGL(lconv_edge_layer_kernel, dim3((unsigned)(2 * a.half)), dim3(512), 0, ctx->stream, a);
   }
@@ -471,6 +481,13 @@ struct EncRoute {
   // channel-last pipeline: stage 1 composed - from PACKED bases only: the first-layer GEMM splits its X operand into fp16 parts, exact for
   // 0 / 0.25 / 1, while these modes promise fp32 range for arbitrary float rows
   bool compose_nlc = false;
+  // two strands of one sequence (encoder_two_strands).  Their stages 1-2 run per strand and hand over to ONE set of planes: the last stage's pooled
+  // output goes to units [pooled_off, ..) of the planes `pooled_to` of pooled_plen units instead of buf[kS], whose pads are then the caller's.
+  // Stages 3-7 run once on both: `seam` > 0 = the input holds two sequences of *n positions each, the second `seam` positions behind the first
+  // (zeros in between; a multiple of 250, so that every later pool keeps the second on a window boundary)
+  float* pooled_to = nullptr;
+  long pooled_plen = 0, pooled_off = 0;
+  long seam = 0;
   bool compose32 = false;      // exact-fp32 mode: stage 1's linear groups composed as in the 16-bit modes (conv_p16.h: first_taps_f32_kernel reads the source directly)
   bool planar() const { return pipe == PIPE_P16 || pipe == PIPE_B16; }
 };
@@ -594,40 +611,59 @@ static int enc_stage1_planes(orca_ctx* ctx, const orca_net* net, const SeqSource
 static int enc_planar_stages(orca_ctx* ctx, const orca_net* net, const EncRoute& r, float* const buf[3], long* n_io) {
   const int fmt = r.fmt;
   float *S = buf[kS], *T = buf[kT], *LO = buf[kLO];
-  long n = *n_io;
+  long n = *n_io, off = r.seam;      // positions of one sequence; joint tensors: the second sequence's first position
   for (int st = r.first > 1 ? r.first : 1; st < kPlanarStages && st <= r.last; ++st) {
     const ConvLayer* Ls = &net->convs[4 * st];
     const int C = Ls[3].cout;
+    // joint tensors: nt positions, the gap [n, off) among them, in planes with room for a pooled producer's ragged last tile behind ANY position
+    const long nt = off + n;
+    const auto plen = [&](long pos) { return r.seam ? p16_plen(pos + 128) : p16_plen(pos); };
+    const auto conv = [&](const ConvLayer& L, const float* x, void* y, const float* r1, int relu, int out_mode, long n_out) {
+      const P16Layout lay{plen(nt), plen(n_out), 0, 2 * n};
+      return launch_conv1d_p16(ctx, L, x, y, r1, nt, relu, out_mode, nullptr, fmt, r.seam ? &lay : nullptr);
+    };
+    const auto pads = [&](float* base, long n1, long off1) {      // guards, tail and the gap of a tensor of n1 positions per sequence
+      return r.seam ? launch_p16_zero_pads(ctx, base, C, off1 + n1, fmt, plen(off1 + n1), n1, off1) : launch_p16_zero_pads(ctx, base, C, n1, fmt);
+    };
     // the stage's linear pair: (pooled) previous output S -> lout in LO
     if (r.compose && st <= 2 && net->comp[st].d_wf16) {
-      ORCA_TRY(launch_conv1d_p16(ctx, net->comp[st], S, LO, nullptr, n, 0, 0, nullptr, fmt));
-      ORCA_TRY(launch_p16_zero_pads(ctx, LO, C, n, fmt));
-      EdgeFixArgs ef{};
-      ef.in_mode = fmt == 1 ? 3 : 2; ef.xp = reinterpret_cast<const f32x4*>(S); ef.x_plen = p16_plen(n);
-      ORCA_TRY(launch_edge_chain(ctx, Ls, 2, 4, ef, n, LO, nullptr, fmt));
+      ORCA_TRY(conv(net->comp[st], S, LO, nullptr, 0, 0, nt));
+      ORCA_TRY(pads(LO, n, off));
+      for (int seg = 0; seg < (r.seam ? 2 : 1); ++seg) {          // exact ends of every sequence
+        EdgeFixArgs ef{};
+        ef.in_mode = fmt == 1 ? 3 : 2; ef.xp = reinterpret_cast<const f32x4*>(S) + seg * off; ef.x_plen = plen(nt);
+        ORCA_TRY(launch_edge_chain(ctx, Ls, 2, 4, ef, n, LO + 4 * seg * off, nullptr, fmt, 0, plen(nt)));
+      }
     } else {
-      ORCA_TRY(launch_conv1d_p16(ctx, Ls[0], S, T, nullptr, n, 0, 0, nullptr, fmt));
-      ORCA_TRY(launch_p16_zero_pads(ctx, T, C, n, fmt));
-      ORCA_TRY(launch_conv1d_p16(ctx, Ls[1], T, LO, nullptr, n, 0, 0, nullptr, fmt));   // lout
-      ORCA_TRY(launch_p16_zero_pads(ctx, LO, C, n, fmt));
+      ORCA_TRY(conv(Ls[0], S, T, nullptr, 0, 0, nt));
+      ORCA_TRY(pads(T, n, off));
+      ORCA_TRY(conv(Ls[1], T, LO, nullptr, 0, 0, nt));   // lout
+      ORCA_TRY(pads(LO, n, off));
     }
-    ORCA_TRY(launch_conv1d_p16(ctx, Ls[2], LO, T, nullptr, n, 1, 0, nullptr, fmt));
-    ORCA_TRY(launch_p16_zero_pads(ctx, T, C, n, fmt));
+    ORCA_TRY(conv(Ls[2], LO, T, nullptr, 1, 0, nt));
+    ORCA_TRY(pads(T, n, off));
     // the last conv: relu(.) + lout
     if (st + 1 == kPlanarStages) {
-      ORCA_TRY(launch_conv1d_p16(ctx, Ls[3], T, S, LO, n, 1, 2, nullptr, fmt));          // fp32 channel-last hand-over
+      ORCA_TRY(conv(Ls[3], T, S, LO, 1, 2, nt));          // fp32 channel-last hand-over
       break;
     }
     const int pool = kEncPools[st + 1];
     if (pool != 4 && (pool != 5 || C != 128)) return fail(ORCA_EINVAL, "internal: planar stage %d followed by an unexpected pool", st + 1);
+    if (r.seam && (n % pool || off % pool)) return fail(ORCA_EINVAL, "internal: joint stage %d: %ld positions, seam %ld, pool %d", st + 1, n, off, pool);
     if (st == r.last && r.out == OUT_PLANES) {   // stage 3's output as it is, every position: what a stage-3 cache keeps (the pool is the reader's)
-      ORCA_TRY(launch_conv1d_p16(ctx, Ls[3], T, S, LO, n, 1, 0, nullptr, fmt));
-      ORCA_TRY(launch_p16_zero_pads(ctx, S, C, n, fmt));
+      ORCA_TRY(conv(Ls[3], T, S, LO, 1, 0, nt));
+      ORCA_TRY(pads(S, n, off));
       break;
     }
-    ORCA_TRY(launch_conv1d_p16(ctx, Ls[3], T, S, LO, n, 1, pool == 4 ? 1 : 3, nullptr, fmt));   // MaxPool1d(4) / MaxPool1d(5) (conv_p16p5.h)
-    ORCA_TRY(launch_p16_zero_pads(ctx, S, C, n / pool, fmt));
-    n /= pool;
+    if (st == r.last && r.pooled_to) {           // into the joint planes of the two-strand route (their pads: encoder_two_strands)
+      const P16Layout lay{0, r.pooled_plen, r.pooled_off, 0};
+      ORCA_TRY(launch_conv1d_p16(ctx, Ls[3], T, r.pooled_to, LO, n, 1, pool == 4 ? 1 : 3, nullptr, fmt, &lay));
+      n /= pool;
+      break;
+    }
+    ORCA_TRY(conv(Ls[3], T, S, LO, 1, pool == 4 ? 1 : 3, nt / pool));   // MaxPool1d(4) / MaxPool1d(5) (conv_p16p5.h)
+    ORCA_TRY(pads(S, n / pool, off / pool));
+    n /= pool; off /= pool;
   }
   *n_io = n;
   return ORCA_OK;
@@ -666,10 +702,14 @@ static int enc_stage1_groups_nlc(orca_ctx* ctx, const orca_net* net, const SeqSo
 }
 
 // stages `st_from` .. 7 on the channel-last kernels (conv_bf16s.h / conv_small.h): every stage of the channel-last pipeline, stages 5-7 of the planar
-// ones (buf[0] holds stage 4's fp32 rows, or - first stage 5 - the already pooled rows of the caller)
+// ones (buf[0] holds stage 4's fp32 rows, or - first stage 5 - the already pooled rows of the caller).  Two strands (r.seam, stages 5-7): buf[0]
+// holds both, the second r.seam / 5 rows behind the first; stage 5's pool packs them into a batch of two rows that every conv then runs in ONE
+// launch, each row zero-padded by the kernel and computed as it would be alone (tile shape from n: fixed_tile 2).  The result is [2][n][128]
 static int enc_stages_nlc(orca_ctx* ctx, const orca_net* net, const SeqSource& src, const EncRoute& r, int st_from, long n, float* const buf[3], long ld1,
                           float** out, long* out_ld, long* out_n) {
   const int prec = net->precision;
+  const int B = r.seam ? 2 : 1, own_tile = r.seam ? 2 : 0;
+  if (r.seam && st_from != kPlanarStages) return fail(ORCA_EINVAL, "internal: two strands enter the channel-last stages behind stage 4");
   int P = 0;
   // stage 1 uncomposed: the 4-channel first layer stays on the fp32 kernel (K = 36, 1 % of the FLOPs) and writes channel-last
   if (r.pipe == PIPE_NLC && !r.compose_nlc) ORCA_TRY(enc_rows_channel_major(ctx, src, n, buf, ld1));
@@ -680,20 +720,27 @@ static int enc_stages_nlc(orca_ctx* ctx, const orca_net* net, const SeqSource& s
     } else if (kEncPools[st] > 1 && st != r.first) {
       const long n2 = n / kEncPools[st];
       const int Q = (P + 1) % 3;
-      ORCA_TRY(launch_pool_nlc(ctx, buf[P], buf[Q], n2, L[0].cin, kEncPools[st]));
+      if (B > 1 && n % kEncPools[st]) return fail(ORCA_EINVAL, "internal: stage %d: a batch row of %ld positions under MaxPool1d(%d)", st + 1, n, kEncPools[st]);
+      if (B > 1 && st == st_from) {      // from the joint rows: each strand's own windows
+        ORCA_TRY(launch_pool_nlc(ctx, buf[P], buf[Q], n2, L[0].cin, kEncPools[st]));
+        ORCA_TRY(launch_pool_nlc(ctx, buf[P] + (r.seam / 5) * L[0].cin, buf[Q] + n2 * L[0].cin, n2, L[0].cin, kEncPools[st]));
+      } else {
+        ORCA_TRY(launch_pool_nlc(ctx, buf[P], buf[Q], B * n2, L[0].cin, kEncPools[st]));
+      }
       P = Q; n = n2;
     }
     const int T = (P + 1) % 3, LO = (P + 2) % 3;
+    const long bs = B > 1 ? n * 128 : 0;
     if (st == 0 && r.compose_nlc) {
       ORCA_TRY(enc_stage1_groups_nlc(ctx, net, src, n, buf[LO], buf[T]));
     } else {
       if (st == 0) ORCA_TRY(launch_conv1d(ctx, L[0], buf[P], 0, ld1, buf[T], 0, 0, nullptr, nullptr, 1, n, 0, 0, 1));
-      else ORCA_TRY(launch_conv1d_b16(ctx, L[0], prec, buf[P], 0, buf[T], 0, nullptr, 1, n, 0));
-      ORCA_TRY(launch_conv1d_b16(ctx, L[1], prec, buf[T], 0, buf[LO], 0, nullptr, 1, n, 0));
-      ORCA_TRY(launch_conv1d_b16(ctx, L[2], prec, buf[LO], 0, buf[T], 0, nullptr, 1, n, 1));
+      else ORCA_TRY(launch_conv1d_b16(ctx, L[0], prec, buf[P], bs, buf[T], bs, nullptr, B, n, 0, 0, nullptr, own_tile));
+      ORCA_TRY(launch_conv1d_b16(ctx, L[1], prec, buf[T], bs, buf[LO], bs, nullptr, B, n, 0, 0, nullptr, own_tile));
+      ORCA_TRY(launch_conv1d_b16(ctx, L[2], prec, buf[LO], bs, buf[T], bs, nullptr, B, n, 1, 0, nullptr, own_tile));
     }
-    ORCA_TRY(launch_conv1d_b16(ctx, L[3], prec, buf[T], 0, buf[P], 0, st < 6 ? buf[LO] : nullptr, 1, n, 1,
-                               (st < 6 && kEncPools[st + 1] == 4) ? 1 : 0));
+    ORCA_TRY(launch_conv1d_b16(ctx, L[3], prec, buf[T], bs, buf[P], bs, st < 6 ? buf[LO] : nullptr, B, n, 1,
+                               (st < 6 && kEncPools[st + 1] == 4) ? 1 : 0, nullptr, own_tile));
   }
   *out = buf[P]; *out_ld = -128; *out_n = n;   // negative ld: result is channel-last [n][128]
   return ORCA_OK;
@@ -868,6 +915,81 @@ extern "C" int orca_encoder_forward_2bit(orca_ctx* ctx, orca_net* net, const uin
                                          int64_t L, int64_t bin_lo, int64_t bin_hi, float* out, int64_t so_c, int64_t chunk_bp) {
   if (!two || !nmask || start < 0) return fail(ORCA_EINVAL, "orca_encoder_forward_2bit: NULL plane or negative start");
   return encoder_forward_impl(ctx, net, nullptr, 0, 0, 0, two, 0, reverse, 1, L, bin_lo, bin_hi, out, 0, so_c, chunk_bp, 0, -1, nmask, start);
+}
+
+// Both strands of one packed sequence.  Stages 1-2 (n = L and L / 4: hundreds of tile rounds per launch) run per strand; each strand's last
+// stage-2 conv writes its MaxPool1d(4)'d output into ONE set of planes - the forward strand at position 0, the reverse complement at off3 =
+// roundup(n3 + 40, 250), zeros in between - and stages 3-7 (n <= L / 16: launches of a few rounds and latency chains) run ONCE on both.  The
+// kernels see one longer sequence (stages 3-4) or a batch of two rows (stages 5-7); every position reads the inputs and does the arithmetic it
+// would in a call of its own, so the result is bit-identical to two orca_encoder_forward_codes calls.  The joint input is a fourth workspace
+// buffer (96 channels x ~2 L / 16 positions x 4 B: 1.5 GB for 32 Mb), because the second strand's stages 1-2 need all three others.
+static int encoder_two_strands_joint(orca_ctx* ctx, orca_net* net, const unsigned char* codes, long L, float* const out[2], long so_c) {
+  const long n3 = L / 16, off3 = (n3 + 40 + 249) / 250 * 250;
+  const long plen3 = p16_plen(off3 + n3 + 128);                       // enc_planar_stages: plen() of the joint tensors
+  const long ld1 = ru4(L) + 1024;
+  // (a plane unit is 4 floats, a C-channel P16 tensor C / 4 units per position)
+  size_t per = (size_t)64 * ld1;
+  if (per < (size_t)128 * plen3) per = (size_t)128 * plen3;           // stage 3's 128-channel joint tensors
+  size_t perj = (size_t)net->convs[7].cout * plen3;                   // the joint input, then stage 3's pooled output and stage 4's fp32 rows
+  const size_t nt4 = (size_t)(off3 + n3) / 5;
+  if (perj < 128 * (size_t)p16_plen((long)nt4 + 128)) perj = 128 * (size_t)p16_plen((long)nt4 + 128);
+  ORCA_TRY(ws_ensure(ctx, 3 * ru256(per * sizeof(float)) + ru256(perj * sizeof(float))));
+  float* buf[3];
+  for (int i = 0; i < 3; ++i) buf[i] = ws_take(ctx, per);
+  float* const joint = ws_take(ctx, perj);
+  if (!joint) return fail(ORCA_ENOMEM, "internal: workspace arena exhausted");
+  SeqSource src;
+  src.codes = codes; src.codes_L = L; src.codes_off = 0;
+  EncRoute r;
+  ORCA_TRY(enc_route(net, src, ENC_FULL, &r));
+  if (!r.planar()) return fail(ORCA_EINVAL, "internal: the two-strand route needs a planar pipeline");
+  const int C3 = net->convs[7].cout;
+  for (int strand = 0; strand < 2; ++strand) {
+    EncRoute f = r;
+    f.last = 1; f.out = OUT_PLANES_POOLED; f.pooled_to = joint; f.pooled_plen = plen3; f.pooled_off = strand * off3;
+    src.reverse = strand;
+    long n = L;
+    ORCA_TRY(enc_stage1_planes(ctx, net, src, f, buf, &n));
+    ORCA_TRY(enc_planar_stages(ctx, net, f, buf, &n));
+    if (n != n3) return fail(ORCA_EINVAL, "internal: stages 1-2 produced %ld positions for %ld bases", n, L);
+  }
+  ORCA_TRY(launch_p16_zero_pads(ctx, joint, C3, off3 + n3, r.fmt, plen3, n3, off3));
+  r.first = 2; r.seam = off3;
+  float* const jb[3] = {joint, buf[1], buf[2]};
+  long n = n3;
+  ORCA_TRY(enc_planar_stages(ctx, net, r, jb, &n));
+  float* res; long rld, rn;
+  ORCA_TRY(enc_stages_nlc(ctx, net, src, r, kPlanarStages, n, jb, ru4(L), &res, &rld, &rn));
+  if (rn != orca_encoder_num_bins(L)) return fail(ORCA_EINVAL, "internal: the joint stages produced %ld bins, need %ld", rn, (long)orca_encoder_num_bins(L));
+  for (int strand = 0; strand < 2; ++strand) ORCA_TRY(launch_copy2d(ctx, res + strand * rn * 128, 1, 128, out[strand], so_c, 128, rn));
+  return ORCA_OK;
+}
+
+extern "C" int orca_encoder_forward_two_strands(orca_ctx* ctx, orca_net* net, const uint8_t* codes, int64_t L, float* out_fwd, float* out_rev, int64_t so_c) {
+  if (!ctx || !net || !codes || !out_fwd || !out_rev) return fail(ORCA_EINVAL, "orca_encoder_forward_two_strands: NULL argument");
+  if (net->kind != ORCA_NET_ENCODER) return fail(ORCA_EINVAL, "orca_encoder_forward_two_strands: net is not an Encoder");
+  const char* e = getenv("ORCA_ENCODER_CHUNK_BP");
+  const bool planar = net->precision == ORCA_PRECISION_F16X2 || net->precision == ORCA_PRECISION_BF16;
+  // the joint pass: one chunk of whole bins on the default planar route; everything else is the two calls it has always been
+  if (!net->enc_two_strands || !planar || net->enc_form != ORCA_ENCODER_FORM_DEFAULT || L <= 0 || L % kBinBp || L > (e ? atol(e) : 32000000L)) {
+    ORCA_TRY(orca_encoder_forward_codes(ctx, net, codes, 0, 0, 1, L, 0, 0, out_fwd, 0, so_c, 0));
+    return orca_encoder_forward_codes(ctx, net, codes, 0, 1, 1, L, 0, 0, out_rev, 0, so_c, 0);
+  }
+  HIPCHECK(hipSetDevice(ctx->device));
+  float* const out[2] = {out_fwd, out_rev};
+  return encoder_two_strands_joint(ctx, net, codes, L, out, so_c);
+}
+
+extern "C" int orca_net_set_encoder_two_strands(orca_net* net, int on) {
+  if (!net || net->kind != ORCA_NET_ENCODER) return fail(ORCA_EINVAL, "orca_net_set_encoder_two_strands: not an Encoder net");
+  net->enc_two_strands = on ? 1 : 0;
+  return ORCA_OK;
+}
+
+extern "C" int orca_net_get_encoder_two_strands(orca_net* net, int* on) {
+  if (!net || !on || net->kind != ORCA_NET_ENCODER) return fail(ORCA_EINVAL, "orca_net_get_encoder_two_strands: not an Encoder net");
+  *on = net->enc_two_strands;
+  return ORCA_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -98,6 +98,7 @@ struct orca_net {
   int kind = 0;
   int precision = ORCA_PRECISION_F32;
   int dec_block_runs = 1;   // Decoders, f16x2: each run of blocks of dilation 16, 32, 64 is ONE launch (orca_net_set_decoder_block_runs, conv2d_dblock.h)
+  int enc_two_strands = 1;  // Encoder, planar routes: orca_encoder_forward_two_strands runs stages 3-7 of both strands as one joint pass (orca_net_set_encoder_two_strands)
   int enc_form = ORCA_ENCODER_FORM_DEFAULT;   // Encoder: which of the algebraically equal forms of stage 1-3's linear groups runs (orca_net_set_encoder_form)
   float* d_first_w = nullptr;   // Encoder: folded [64][4][9] weights of the first layer, unpacked (conv1d_first_p16_kernel)
   void* d_first_w16 = nullptr;  // same as a K=48 fp16 split pack [2][3][2][64][8] (conv1d_first_mfma_p16_kernel)
@@ -168,15 +169,20 @@ static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) 
 // half reads 9 units past the last tile); the +1 keeps the zero stores of a pooled output's ragged last tile inside the plane for every n
 static inline long p16_plen(long n) { return ((n + 512) / 512) * 512 + 32; }
 struct FusedFirst;
+// a planar conv whose tensors are not laid out as p16_plen(n) says (the joint tensors of the two-strand Encoder): plane lengths of the input (and
+// residual) / the output, the output's first unit, the positions that count in the launch record.  0: as p16_plen(n) / n say
+struct P16Layout { long x_plen = 0, y_plen = 0, y_off = 0, n_valid = 0; };
 // orca_encoder.hip
 int launch_conv1d(orca_ctx* ctx, const ConvLayer& L, const float* x, long x_bs, long ldx, float* y, long y_bs, long ldy, const float* r1, const float* r2,
                   int B, long n, int relu, int tile, int y_nlc = 0);
-// fixed_tile: the tile shape of a long 128-cout layer depends on n alone, not on B (orca_encoder_back5_batch: a row's result never depends on its batch)
+// fixed_tile: the tile shape of a long 128-cout layer depends on n alone, not on B (a row's result never depends on its batch): 1 = the 256-position
+// tiles (orca_encoder_back5_batch), 2 = what a B = 1 call of n positions takes (the two-strand Encoder)
 int launch_conv1d_b16(orca_ctx* ctx, const ConvLayer& L, int precision, const float* x, long x_bs, float* y, long y_bs, const float* r1, int B, long n, int relu,
                       int pool4 = 0, const float* r2 = nullptr, int fixed_tile = 0);
 int launch_conv1d_p16(orca_ctx* ctx, const ConvLayer& L, const float* x, void* y, const float* r1, long n, int relu, int out_mode, const FusedFirst* f1 = nullptr,
-                      int fmt = 0);
-int launch_p16_zero_pads(orca_ctx* ctx, float* base, int C, long n_valid, int fmt = 0);
+                      int fmt = 0, const P16Layout* lay = nullptr);
+// plen 0: p16_plen(n_valid); positions [gap0, gap1) are zeroed too (two sequences in one set of planes)
+int launch_p16_zero_pads(orca_ctx* ctx, float* base, int C, long n_valid, int fmt = 0, long plen = 0, long gap0 = 0, long gap1 = 0);
 int launch_pool(orca_ctx* ctx, const float* x, long ldx, float* y, long ldy, long rows, long n_out, int k);
 // orca_decoder.hip
 int launch_conv2d(orca_ctx* ctx, const ConvLayer& L, const float* x, long x_bs, float* y, long y_bs, const float* r, long r_bs, int B, int n, int relu);

@@ -350,6 +350,16 @@ class Net:
         """Decoder nets, f16x2: run each dilation 16-32-64 block run as one launch (default) or block by block (bit-identical; conv2d_dblock.h)."""
         check(_lib.load().orca_net_set_decoder_block_runs(self.handle, 1 if on else 0), "orca_net_set_decoder_block_runs")
 
+    def set_encoder_two_strands(self, on):
+        """Encoder nets: `encoder_forward_two_strands` runs stages 3-7 of both strands as one joint pass (default) or as the two per-strand calls
+        (bit-identical)."""
+        check(_lib.load().orca_net_set_encoder_two_strands(self.handle, 1 if on else 0), "orca_net_set_encoder_two_strands")
+
+    def encoder_two_strands(self):
+        on = ctypes.c_int(0)
+        check(_lib.load().orca_net_get_encoder_two_strands(self.handle, ctypes.byref(on)), "orca_net_get_encoder_two_strands")
+        return bool(on.value)
+
 
 # ---------------------------------------------------------------------------
 # forward wrappers
@@ -454,6 +464,22 @@ def encoder_forward_codes(net, codes, reverse=False, bin_lo=0, bin_hi=0, chunk_b
         return out
     check(_lib.load().orca_encoder_forward_codes(net.ctx.handle, net.handle, _p(codes), codes.stride(0), 1 if reverse else 0, B, L,
                                                  bin_lo, hi, _p(out), out.stride(0), out.stride(1), chunk_bp), "orca_encoder_forward_codes")
+    return out
+
+
+def encoder_forward_two_strands(net, codes, out):
+    """Forward strand and reverse complement of ONE packed sequence (``codes`` [1,L] uint8) into rows 0 and 1 of ``out`` [2,128,bins]: stages 1-2
+    per strand, stages 3-7 once for both (include/orca_hip.h: orca_encoder_forward_two_strands) - the bits of two `encoder_forward_codes` calls."""
+    if not (isinstance(codes, torch.Tensor) and codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2 and codes.shape[0] == 1):
+        raise ValueError("codes must be a [1,L] uint8 ROCm tensor")
+    if codes.stride(1) != 1:
+        codes = codes.contiguous()
+    L = codes.shape[1]
+    if tuple(out.shape) != (2, 128, encoder_num_bins(L)) or out.stride(2) != 1 or out.dtype != torch.float32:
+        raise ValueError(f"out must be a float32 [2,128,{encoder_num_bins(L)}] view with unit stride along the bins")
+    net.ctx.sync_stream()
+    check(_lib.load().orca_encoder_forward_two_strands(net.ctx.handle, net.handle, _p(codes), L, _p(out[0]), _p(out[1]), out.stride(1)),
+          "orca_encoder_forward_two_strands")
     return out
 
 

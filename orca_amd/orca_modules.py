@@ -207,6 +207,20 @@ class Encoder(_HipModule):
 
     forward_codes.__doc__ += "  (Replaces the float [B,4,L] input of orca_predict.py:334.)"
 
+    def two_strands_ok(self, codes):
+        """Whether `forward_two_strands` may take ``codes``: one packed sequence of whole bins in one chunk, the net on its default planar route,
+        the strands not spread over two streams.  (The library itself keeps the two per-strand calls for whatever else reaches it: the range-safe
+        retry, `set_encoder_two_strands(False)`.)"""
+        return (self.precision in ("f16x2", "bf16") and self.form == "default" and not engine.strand_streams()
+                and isinstance(codes, torch.Tensor) and codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2 and codes.shape[0] == 1
+                and codes.shape[1] % 4000 == 0 and 0 < codes.shape[1] <= int(os.environ.get("ORCA_ENCODER_CHUNK_BP", 32_000_000)))
+
+    def forward_two_strands(self, codes, out):
+        """Forward strand and reverse complement of the packed sequence ``codes`` [1,L] into ``out`` [2,128,bins]: stages 1-2 per strand, stages
+        3-7 as ONE pass over both (engine.encoder_forward_two_strands) - bit-identical to `forward_codes` with reverse = False / True."""
+        net = self._net(codes.device)
+        return self._run_guarded(net, lambda: engine.encoder_forward_two_strands(net, codes, out), "bf16x3")
+
     # ---- the Encoder in two parts (sv.Stage3Cache; include/orca_hip.h: orca_encoder_stage3_planes ...).  f16x2 arithmetic only: the planes are
     # its operand image.  No retry inside: the caller's chain carries the fp16-range check (engine.run_with_overflow_retry, sv.sv_screen) and
     # takes the whole-window route under engine.force_safe_precision() ----

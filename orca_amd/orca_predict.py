@@ -151,7 +151,7 @@ class _StrandInputs:
                 if cache is not None and key in cache:
                     return cache[key][1]
                 enc0 = torch.empty((2 * B, 128, engine.encoder_num_bins(L)), dtype=torch.float32, device=self._codes.device)
-                _encode_two_strands(lambda rev, out: net0.forward_codes(self._codes, reverse=rev, out=out), enc0, B)
+                _encode_two_strands(lambda rev, out: net0.forward_codes(self._codes, reverse=rev, out=out), enc0, B, _joint_encode(net0, self._codes))
                 if cache is not None:
                     cache[key] = (self._codes, enc0)      # (the codes tensor is HELD: its storage - the key - cannot be handed to another sequence meanwhile)
                     # inside a deferred range check (genomepredict_256Mb's forward) this pass is not known to be clean yet: if the check
@@ -162,10 +162,20 @@ class _StrandInputs:
         return torch.cat([net0(self.fwd), net0(self.rev)], dim=0)
 
 
-def _encode_two_strands(encode, enc0, B):
+def _joint_encode(net0, codes):
+    """joint(out) = both strands of the packed sequence ``codes`` in one Encoder call (Encoder.forward_two_strands), or None where the two
+    per-strand calls stay: a batch, a chunked or ragged length, a non-planar precision, a forced form, the two-stream mode, another module."""
+    ok = getattr(net0, "two_strands_ok", None)
+    return (lambda out: net0.forward_two_strands(codes, out)) if ok is not None and ok(codes) else None
+
+
+def _encode_two_strands(encode, enc0, B, joint=None):
     """encode(reverse, out) for the forward strand into enc0[:B] and the reverse complement into enc0[B:]: one after the other on the
-    caller's stream, or (engine.strand_streams(), opt-in) the reverse strand on an auxiliary context beside the forward one."""
-    if engine.strand_streams() and enc0.is_cuda:
+    caller's stream, or (engine.strand_streams(), opt-in) the reverse strand on an auxiliary context beside the forward one.
+    ``joint`` (`_joint_encode`): both strands of one packed sequence in one call instead - stages 3-7 of the Encoder once for both."""
+    if joint is not None and B == 1 and enc0.is_cuda:
+        joint(enc0)
+    elif engine.strand_streams() and enc0.is_cuda:
         pool = engine.context_pool(enc0.device, 1)
         pool.fork()
         pool.run(0, lambda: encode(True, enc0[B:]))
@@ -450,7 +460,7 @@ def cascade_32m(model, xs, mpos, wpos, reverse_flags, distencs=None, merge=False
             # packed strands: each is encoded straight into its rows of one [S*B,128,bins] tensor
             enc0 = torch.empty((len(xs) * B, 128, engine.encoder_num_bins(xs[0].shape[1])), dtype=torch.float32, device=xs[0].device)
             if len(xs) == 2 and xs[0] is xs[1] and list(reverse_flags) == [False, True]:
-                _encode_two_strands(lambda rev, out: encode(xs[0], rev, out), enc0, B)
+                _encode_two_strands(lambda rev, out: encode(xs[0], rev, out), enc0, B, _joint_encode(model.net0, xs[0]))
             else:
                 for k, (x, r) in enumerate(zip(xs, reverse_flags)):
                     encode(x, r, enc0[k * B:(k + 1) * B])
