@@ -372,6 +372,26 @@ int orca_screen_viewpoints(orca_ctx* ctx, const float* alt, int64_t map_bs, cons
 int orca_screen_merge_strands(orca_ctx* ctx, const float* fwd, int64_t fwd_bs, const float* rev, int64_t rev_bs, const float* ref_fwd, const float* ref_rev,
                               int B, int n, float* out, int64_t out_bs, float* gap);
 
+/* Non-additivity of edit sets (screen.epistasis_1m): B set maps alt[b * map_bs + i * n + j] against the sum of their members' effects.  `bank`
+ * (bank[u * bank_bs + i * n + j], U >= 1 maps) holds the map of every single edit applied alone, ref[n][n] the unedited map (B, n >= 1, both batch
+ * strides >= n * n).  The member table: set b has members members[member_off[b] .. member_off[b + 1]) - `member_off` B + 1 int64 from 0 to P, strictly
+ * increasing (no empty set, no cap on a set's members), `members` P int32 bank indices in [0, U); each comes twice like every table (device copy for the
+ * kernel, host copy checked here; the kernels clip all the same, and a clipped member reads as NaN).  Per pixel, every operand converted to fp64 first,
+ * no multiplication:  t = sum_m (bank[member m] - ref), added sequentially for m ascending from 0.0 (the additive expectation);  r = (alt - ref) - t
+ * (the residual; exactly +0.0 for a one-member set whose map holds its bank entry's bits).  Every result is rounded to fp32 once:
+ *   orca_screen_epistasis_scores         profile[b][i] = mean_j |r[i][j]|, mean[b] = mean_ij |r|, amax[b] = max_ij |r|, add_mean[b] = mean_ij |t|.  fp64
+ *                                        sums in an order fixed by n alone (no atomics): a set's bits depend neither on B nor on its place in the batch
+ *   orca_screen_epistasis_region_scores  `rects` as for orca_screen_region_scores: mean_signed[b][k] = mean of r, mean_abs[b][k] = mean of |r| over
+ *                                        rectangle k
+ * A NaN in any map read propagates into the results it enters.  Anything else is ORCA_EINVAL before any launch. */
+int orca_screen_epistasis_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* bank, int64_t bank_bs, int U, const float* ref, int B, int n,
+                                 const int64_t* member_off, const int64_t* member_off_host, const int32_t* members, const int32_t* members_host, int64_t P,
+                                 float* profile, float* mean, float* amax, float* add_mean);
+int orca_screen_epistasis_region_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* bank, int64_t bank_bs, int U, const float* ref, int B,
+                                        int n, const int64_t* member_off, const int64_t* member_off_host, const int32_t* members,
+                                        const int32_t* members_host, int64_t P, const int32_t* rects, const int32_t* rects_host, int K, float* mean_signed,
+                                        float* mean_abs);
+
 /* Number of 4 kb bins Encoder emits for an L-bp input (floor through the
  * 4,4,5,5,5,2 pooling chain). */
 int64_t orca_encoder_num_bins(int64_t L);

@@ -234,6 +234,48 @@ extern "C" int orca_screen_aligned_region_scores(orca_ctx* ctx, const float* alt
                 rects, K, mean_signed, mean_abs);
 }
 
+// ---- non-additivity --------------------------------------------------------------------------------------------------------------------------------------------
+// what the two epistasis entry points share: the maps, the bank and the member table (offsets from 0 to P, strictly increasing - no empty set - and every
+// index inside the bank)
+static int check_epistasis(const char* what, int64_t map_bs, int64_t bank_bs, int B, int n, int U, const int64_t* member_off_host, const int32_t* members_host, int64_t P) {
+  if (B < 1 || n < 1 || U < 1 || P < 1) return fail(ORCA_EINVAL, "%s: %d sets (>= 1) of %d bins (>= 1), a bank of %d maps (>= 1), %ld members (>= 1)", what, B, n, U, (long)P);
+  const int64_t nn = (int64_t)n * n;
+  if (map_bs < nn || bank_bs < nn) return fail(ORCA_EINVAL, "%s: batch strides %ld (alt), %ld (bank) below the map's %ld floats", what, (long)map_bs, (long)bank_bs, (long)nn);
+  if (member_off_host[0] != 0) return fail(ORCA_EINVAL, "%s: member offsets start at %ld, expected 0", what, (long)member_off_host[0]);
+  for (int b = 0; b < B; ++b) {
+    if (member_off_host[b + 1] < member_off_host[b]) return fail(ORCA_EINVAL, "%s: member offsets decrease at set %d", what, b);
+    if (member_off_host[b + 1] > P) return fail(ORCA_EINVAL, "%s: member offsets reach %ld at set %d, the table holds %ld members", what, (long)member_off_host[b + 1], b, (long)P);
+    if (member_off_host[b + 1] == member_off_host[b]) return fail(ORCA_EINVAL, "%s: set %d is empty (a set has at least one member)", what, b);
+  }
+  if (member_off_host[B] != P) return fail(ORCA_EINVAL, "%s: member offsets end at %ld, the table holds %ld members", what, (long)member_off_host[B], (long)P);
+  for (int64_t m = 0; m < P; ++m)
+    if (members_host[m] < 0 || members_host[m] >= U) return fail(ORCA_EINVAL, "%s: member %ld is bank map %d, outside 0 .. %d", what, (long)m, members_host[m], U - 1);
+  return ORCA_OK;
+}
+
+extern "C" int orca_screen_epistasis_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* bank, int64_t bank_bs, int U, const float* ref, int B, int n,
+                                            const int64_t* member_off, const int64_t* member_off_host, const int32_t* members, const int32_t* members_host, int64_t P,
+                                            float* profile, float* mean, float* amax, float* add_mean) {
+  if (!ctx || !alt || !bank || !ref || !member_off || !member_off_host || !members || !members_host || !profile || !mean || !amax || !add_mean)
+    return fail(ORCA_EINVAL, "orca_screen_epistasis_scores: NULL argument");
+  ORCA_TRY(check_epistasis("orca_screen_epistasis_scores", map_bs, bank_bs, B, n, U, member_off_host, members_host, P));
+  return launch(ctx, "screen_epistasis_scores_kernel", screen_epistasis_scores_kernel, dim3((unsigned)B), 512, alt, (long)map_bs, bank, (long)bank_bs, U, ref, n,
+                i64(member_off), members, (long)P, profile, mean, amax, add_mean);
+}
+
+extern "C" int orca_screen_epistasis_region_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* bank, int64_t bank_bs, int U, const float* ref, int B,
+                                                   int n, const int64_t* member_off, const int64_t* member_off_host, const int32_t* members,
+                                                   const int32_t* members_host, int64_t P, const int32_t* rects, const int32_t* rects_host, int K, float* mean_signed,
+                                                   float* mean_abs) {
+  if (!ctx || !alt || !bank || !ref || !member_off || !member_off_host || !members || !members_host || !rects || !rects_host || !mean_signed || !mean_abs)
+    return fail(ORCA_EINVAL, "orca_screen_epistasis_region_scores: NULL argument");
+  ORCA_TRY(check_epistasis("orca_screen_epistasis_region_scores", map_bs, bank_bs, B, n, U, member_off_host, members_host, P));
+  if (K < 1 || K > 64) return fail(ORCA_EINVAL, "orca_screen_epistasis_region_scores: %d rectangles (1..64)", K);
+  ORCA_TRY(check_rects("orca_screen_epistasis_region_scores", rects_host, K, n));
+  return launch(ctx, "screen_epistasis_region_scores_kernel", screen_epistasis_region_scores_kernel, dim3((unsigned)B, (unsigned)K), 256, alt, (long)map_bs, bank,
+                (long)bank_bs, U, ref, n, i64(member_off), members, (long)P, rects, K, mean_signed, mean_abs);
+}
+
 // ---- tracks ----------------------------------------------------------------------------------------------------------------------------------------------------
 // what the two track entry points share: the maps, and the bin map that comes exactly with the aligned output
 static int check_track_maps(const char* what, int64_t map_bs, int B, int n, const int32_t* bin_map, const int32_t* bin_map_host, const float* aligned) {

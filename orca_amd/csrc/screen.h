@@ -576,3 +576,133 @@ static __global__ void __launch_bounds__(512) screen_merge_strands_kernel(const 
     gap[b] = (float)(t / ((double)n * (double)n));
   }
 }
+
+// ---- non-additivity (screen.epistasis_1m): a set's map against the sum of its members' effects ----------------------------------------------------------
+// Set b has members members[member_off[b] .. member_off[b + 1]) (int64 offsets, int32 indices into the bank; include/orca_hip.h:
+// orca_screen_epistasis_scores), S = alt[b] its own map, A_m = bank[members[m]] the map of member m applied alone.  Per pixel, every operand converted to
+// fp64 first and no multiplication anywhere: t = sum_m (A_m - ref), added sequentially for m ascending from 0.0 - the additive expectation - and
+// r = (S - ref) - t, the residual.  For a one-member set whose map holds its bank entry's bits r is exactly +0.0.  The member list is read from global
+// memory (no cap on its length) and is the same for a whole workgroup.  The host entry point checks the table; here the range is clipped to the table
+// all the same, and a member outside the bank reads as NaN.
+struct screen_epi { double r, t; };
+
+static __device__ __forceinline__ screen_epi screen_epistasis_at(const float* __restrict__ a, const float* __restrict__ bank, long bank_bs, int U,
+                                                                 const float* __restrict__ ref, const int* __restrict__ members, long m0, long m1, long at) {
+  const double rf = (double)ref[at];
+  double t = 0.0;
+  for (long m = m0; m < m1; ++m) {
+    const int u = members[m];
+    t += (u >= 0 && u < U) ? (double)bank[(long)u * bank_bs + at] - rf : (double)__int_as_float(0x7fc00000);
+  }
+  screen_epi e;
+  e.r = ((double)a[at] - rf) - t;
+  e.t = t;
+  return e;
+}
+
+// set b's member range, clipped to the P entries of the table
+static __device__ __forceinline__ void screen_member_range(const long long* __restrict__ member_off, long P, int b, long& m0, long& m1) {
+  m0 = (long)member_off[b];
+  m1 = (long)member_off[b + 1];
+  m0 = m0 < 0 ? 0 : m0;
+  m1 = m1 > P ? P : m1;
+}
+
+// screen_scores_kernel on the residual: profile[b][i] = mean_j |r[i][j]|, mean[b] = mean_ij |r|, amax[b] = max_ij |r| (the largest fp64 |r|, rounded
+// once), add_mean[b] = mean_ij |t|.  One workgroup per set, one wave per row at a time: fp64 per lane along its columns, shuffles across the wave, the
+// eight waves' sums serially - an order fixed by n alone, no atomics, so a set's bits depend neither on B nor on its place in the batch.  A NaN in a
+// map propagates through the sums it enters (a NaN r into profile, mean and amax; a NaN t also into add_mean).
+static __global__ void __launch_bounds__(512) screen_epistasis_scores_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ bank,
+                                                                             long bank_bs, int U, const float* __restrict__ ref, int n,
+                                                                             const long long* __restrict__ member_off, const int* __restrict__ members,
+                                                                             long P, float* __restrict__ profile, float* __restrict__ mean,
+                                                                             float* __restrict__ amax, float* __restrict__ add_mean) {
+  __shared__ double s_sum[8], s_add[8], s_max[8];
+  __shared__ int s_nan[8];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float* a = alt + (long)b * map_bs;
+  long m0, m1;
+  screen_member_range(member_off, P, b, m0, m1);
+  double wsum = 0.0, wadd = 0.0, wmax = 0.0;
+  bool wnan = false;
+  for (int i = wv; i < n; i += 8) {
+    double rs = 0.0, ts = 0.0;
+    for (int j = lane; j < n; j += 64) {
+      const screen_epi e = screen_epistasis_at(a, bank, bank_bs, U, ref, members, m0, m1, (long)i * n + j);
+      const double d = fabs(e.r);
+      rs += d;
+      ts += fabs(e.t);
+      wnan |= d != d;
+      wmax = fmax(wmax, d);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      rs += __shfl_xor(rs, o, 64);
+      ts += __shfl_xor(ts, o, 64);
+    }
+    if (lane == 0) profile[(long)b * n + i] = (float)(rs / (double)n);
+    wsum += rs;
+    wadd += ts;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    wmax = fmax(wmax, __shfl_xor(wmax, o, 64));
+    wnan |= __shfl_xor((int)wnan, o, 64) != 0;
+  }
+  if (lane == 0) {
+    s_sum[wv] = wsum;
+    s_add[wv] = wadd;
+    s_max[wv] = wmax;
+    s_nan[wv] = wnan ? 1 : 0;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0, ta = 0.0, m = 0.0;
+    bool nan = false;
+    for (int k = 0; k < 8; ++k) {
+      t += s_sum[k];
+      ta += s_add[k];
+      nan |= s_nan[k] != 0;
+      m = fmax(m, s_max[k]);
+    }
+    const double nn = (double)n * (double)n;
+    const float qnan = __int_as_float(0x7fc00000);
+    mean[b] = (float)(t / nn);
+    amax[b] = nan ? qnan : (float)m;
+    add_mean[b] = (float)(ta / nn);
+  }
+}
+
+// screen_region_scores_kernel on the residual: signed[b][k] = mean of r, absm[b][k] = mean of |r| over rectangle k (int32 (i0, i1, j0, j1), half open,
+// inside [0, n) - the host entry point checks it; clipped here all the same).  One workgroup per (set, rectangle); fp64 sums in a fixed order.
+static __global__ void __launch_bounds__(256) screen_epistasis_region_scores_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ bank,
+                                                                                    long bank_bs, int U, const float* __restrict__ ref, int n,
+                                                                                    const long long* __restrict__ member_off,
+                                                                                    const int* __restrict__ members, long P, const int* __restrict__ rects,
+                                                                                    int K, float* __restrict__ signed_out, float* __restrict__ abs_out) {
+  __shared__ double s_sum[4], s_abs[4];
+  const int b = blockIdx.x, k = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int i0 = rects[4 * k], i1 = rects[4 * k + 1], j0 = rects[4 * k + 2], j1 = rects[4 * k + 3];
+  i0 = i0 < 0 ? 0 : i0; j0 = j0 < 0 ? 0 : j0;
+  i1 = i1 > n ? n : i1; j1 = j1 > n ? n : j1;
+  const int h = i1 > i0 ? i1 - i0 : 0, w = j1 > j0 ? j1 - j0 : 0;
+  const float* a = alt + (long)b * map_bs;
+  long m0, m1;
+  screen_member_range(member_off, P, b, m0, m1);
+  double sum = 0.0, asum = 0.0;
+  for (int e = threadIdx.x; e < h * w; e += 256) {
+    const screen_epi d = screen_epistasis_at(a, bank, bank_bs, U, ref, members, m0, m1, (long)(i0 + e / w) * n + (j0 + e % w));
+    sum += d.r;
+    asum += fabs(d.r);
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    sum += __shfl_xor(sum, o, 64);
+    asum += __shfl_xor(asum, o, 64);
+  }
+  if (lane == 0) { s_sum[wv] = sum; s_abs[wv] = asum; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double cnt = (double)h * (double)w;
+    const double t = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]), ta = (s_abs[0] + s_abs[1]) + (s_abs[2] + s_abs[3]);
+    signed_out[(long)b * K + k] = (float)(t / cnt);
+    abs_out[(long)b * K + k] = (float)(ta / cnt);
+  }
+}

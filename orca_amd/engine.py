@@ -813,6 +813,38 @@ def screen_region_scores(ctx, alt, ref, rects_host):
     return sg, ab
 
 
+# non-additivity (orca_screen_epistasis_scores, orca_screen_epistasis_region_scores): the member table is two more small tables
+def screen_epistasis_scores(ctx, alt, bank, ref, member_off_host, members_host, rects_host=None):
+    """The B set maps alt [B, n, n] against the sum of their members' effects (orca_screen_epistasis_scores): ``bank`` [U, n, n] holds every single
+    edit's map (both any batch stride, rows contiguous), ref [n, n] the unedited map; set b has members ``members_host[member_off_host[b]:
+    member_off_host[b + 1]]`` ([B + 1] int64 from 0, strictly increasing; [P] int32 bank indices in [0, U)).  Per pixel in fp64 t = sum_m (bank[m] - ref),
+    r = (alt - ref) - t: (profile [B, n] = mean_j |r|, mean [B] = mean |r|, max [B] = max |r|, additive mean [B] = mean |t|, region [B, K], region abs
+    [B, K]) - the last two the means of r and of |r| over the K rectangles ``rects_host`` [K, 4] = (i0, i1, j0, j1), half open
+    (orca_screen_epistasis_region_scores), None without them."""
+    alt, ref, n = _maps_args(alt, ref)
+    bank = _f32_cuda(bank, "bank")
+    if bank.dim() != 3 or bank.shape[0] < 1 or tuple(bank.shape[1:]) != (n, n) or bank.stride(2) != 1 or bank.stride(1) != n or bank.device != alt.device:
+        raise ValueError(f"bank: [U,{n},{n}] beside alt with U >= 1 and contiguous maps")
+    o = np.ascontiguousarray(member_off_host, dtype=np.int64)
+    m = np.ascontiguousarray(members_host, dtype=np.int32)
+    B, U = alt.shape[0], bank.shape[0]
+    if o.ndim != 1 or o.size != B + 1 or m.ndim != 1 or B < 1:
+        raise ValueError(f"member table: offsets [{B + 1}] int64 (one set per alt map, at least one), members [P] int32")
+    bs, bank_bs = (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), n * n) for t in (alt, bank))      # one map: torch may report any stride for it
+    od, md = torch.from_numpy(o).to(alt.device), torch.from_numpy(m).to(alt.device)
+    head = (ctx.handle, _dev_p(alt), bs, _dev_p(bank), bank_bs, U, _p(ref), B, n, _dev_p(od), _np_p(o), _dev_p(md), _np_p(m), m.size)
+    profile, mean, amax, add = _f32_outputs(alt.device, (B, n), (B,), (B,), (B,))
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_epistasis_scores(*head, _dev_p(profile), _dev_p(mean), _dev_p(amax), _dev_p(add)), "orca_screen_epistasis_scores")
+    if rects_host is None:
+        return profile, mean, amax, add, None, None
+    r = _host_table(rects_host, np.int32, 4, "rectangles")
+    rd = torch.from_numpy(r).to(alt.device)
+    sg, ab = _f32_outputs(alt.device, (B, r.shape[0]), (B, r.shape[0]))
+    check(_lib.load().orca_screen_epistasis_region_scores(*head, _dev_p(rd), _np_p(r), r.shape[0], _dev_p(sg), _dev_p(ab)), "orca_screen_epistasis_region_scores")
+    return profile, mean, amax, add, sg, ab
+
+
 # aligned scores (orca_screen_aligned_scores, orca_screen_aligned_region_scores): the bin map is one more small table
 SCREEN_ALIGNED_MAX_BINS = 256
 

@@ -46,6 +46,11 @@ the insulation track of every alt map - the mean contact across each bin, over a
 the reference's, and ``viewpoints=bins`` the signed row alt - ref of chosen bins (a virtual 4C); with ``aligned=True`` both also come on aligned
 bins, through the same `bin_map` (orca_screen_insulation, orca_screen_viewpoints; `insulation_scores_host`, `viewpoint_scores_host`).  Both are
 1-D tracks per item, so a deletion scan can ask "which deletion fuses the two domains" without ``keep_maps``.
+
+Every score above compares an item with the unedited window.  `epistasis_1m` asks whether the effect of an `EditSet` is the sum of its members'
+effects: it screens the distinct members and the sets in one pass, keeps the members' maps in a device bank, and scores per set the residual
+r = (alt_set - ref) - sum_m (alt_m - ref), every pixel in fp64 (orca_screen_epistasis_scores, orca_screen_epistasis_region_scores;
+`epistasis_items`, `epistasis_scores_host`) - the readout of a `pair_edits` screen, and of "is this haplotype more than its SNVs".
 """
 from dataclasses import dataclass, field, replace
 from typing import Optional
@@ -1025,6 +1030,88 @@ def merge_strands_host(plus, minus, ref_plus=None, ref_minus=None):
     return merged, np.abs(d).mean(axis=(-1, -2))
 
 
+def epistasis_items(sets):
+    """What `epistasis_1m` screens for a list of `EditSet`s (a bare `Edit` counts as a one-member set): ``(singles, member_off, members)``.
+    ``singles``: the distinct members of all sets as `Edit`s, in order of first appearance - two `Edit`s are the same when kind, pos, length and
+    the bytes of seq agree.  Set e has members ``singles[members[m]]`` for m in [member_off[e], member_off[e + 1]), in the set's own sorted
+    order: ``member_off`` np.int64 [E + 1], ``members`` np.int32 [P] - the member table of orca_screen_epistasis_scores.  A ``del`` or ``ins``
+    member is a ValueError: behind a displacement "bin with bin" additivity is not defined."""
+    singles, index, off, members = [], {}, [0], []
+    for item in sets:
+        for e in members_of(item):
+            if e.kind in LEN_KINDS:
+                raise ValueError(f"epistasis: {e!r} changes the length; the sum of the members' effects is defined for length-preserving members only")
+            key = (e.kind, e.pos, e.length, None if e.seq is None else e.seq.tobytes())
+            if key not in index:
+                index[key] = len(singles)
+                singles.append(e)
+            members.append(index[key])
+        off.append(len(members))
+    return singles, np.array(off, dtype=np.int64), np.array(members, dtype=np.int32)
+
+
+def _member_table(member_off, members, E, U):
+    off, mem = np.asarray(member_off, dtype=np.int64), np.asarray(members, dtype=np.int64)
+    if off.shape != (E + 1,) or mem.ndim != 1 or off[0] != 0 or off[-1] != mem.size or np.any(np.diff(off) < 1) or (mem.size and (mem.min() < 0 or mem.max() >= U)):
+        raise ValueError(f"member table: offsets [{E + 1}] from 0 to P, strictly increasing, and [P] indices in [0, {U})")
+    return off, mem
+
+
+def epistasis_scores_host(maps, bank, ref, member_off, members, regions=None):
+    """The scores of `EpistasisResult` from the sets' maps [E, n, n], the singles' maps ``bank`` [U, n, n], the reference map [n, n] and the member
+    table of `epistasis_items` (fp64 host restatement of orca_screen_epistasis_scores and orca_screen_epistasis_region_scores, in their order:
+    every pixel converted to fp64 first, no multiplication).  Per set, t = sum_m (bank[member m] - ref) added sequentially for m ascending
+    from 0.0, r = (maps[e] - ref) - t: (epi_profile [E, n] = mean_j |r|, epi_abs_mean [E] = mean |r|, epi_abs_max [E] = max |r|,
+    additive_abs_mean [E] = mean |t|, epi_region [E, K], epi_region_abs [E, K]) - the last two the means of r and of |r| over the rectangles
+    of ``regions``, None without them."""
+    alt, bk, rf = np.asarray(maps, dtype=np.float64), np.asarray(bank, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    E, n = alt.shape[0], rf.shape[0]
+    off, mem = _member_table(member_off, members, E, bk.shape[0])
+    r, t = np.empty((E, n, n)), np.empty((E, n, n))
+    for e in range(E):
+        s = np.zeros((n, n))
+        for m in mem[off[e]: off[e + 1]]:
+            s = s + (bk[m] - rf)
+        r[e], t[e] = (alt[e] - rf) - s, s
+    with np.errstate(invalid="ignore"):
+        a = np.abs(r)
+        out = (a.mean(axis=2), a.mean(axis=(1, 2)), a.max(axis=(1, 2)), np.abs(t).mean(axis=(1, 2)))
+        if regions is None:
+            return out + (None, None)
+        rects = check_regions(regions, n)
+        sg = np.stack([r[:, i0:i1, j0:j1].mean(axis=(1, 2)) for i0, i1, j0, j1 in rects], axis=1)
+        ab = np.stack([a[:, i0:i1, j0:j1].mean(axis=(1, 2)) for i0, i1, j0, j1 in rects], axis=1)
+    return out + (sg, ab)
+
+
+@dataclass
+class EpistasisResult:
+    """Result of `epistasis_1m` (device tensors unless said otherwise).  U singles, E sets; S_e the map of set e, A_m the map of its member m applied
+    alone (both from ``screen``, so with ``strands="both"`` the merged maps), ref = ``screen.ref_map``.  Per pixel, every operand converted to fp64
+    first: t = sum_m (A_m - ref), the additive expectation; r = (S_e - ref) - t, the residual.  Every field is rounded to fp32 once:
+      screen            the `ScreenResult` of ``singles + sets`` (items [0, U) the singles, item U + e set e)
+      singles           list of `Edit`, n_singles = U; member_off [E + 1] int64 and members [P] int32 (numpy): `epistasis_items`' table
+      epi_profile       [E, n]  mean_j |r[i, j]|
+      epi_abs_mean      [E]     mean_ij |r|
+      epi_abs_max       [E]     max_ij |r|
+      additive_abs_mean [E]     mean_ij |t|: the scale to set ``epi_abs_mean`` against
+      epi_region        [E, K]  with ``regions``: the mean of r over rectangle k (signed; positive = more contact than the members' effects add up to)
+      epi_region_abs    [E, K]  the mean of |r| over rectangle k
+    A one-member set scores exactly 0 wherever its map holds its single's bits (on the two-part route it does).  `epistasis_scores_host` computes
+    the same from maps on the host."""
+    screen: "ScreenResult"
+    singles: list
+    n_singles: int
+    member_off: np.ndarray
+    members: np.ndarray
+    epi_profile: torch.Tensor
+    epi_abs_mean: torch.Tensor
+    epi_abs_max: torch.Tensor
+    additive_abs_mean: torch.Tensor
+    epi_region: Optional[torch.Tensor] = None
+    epi_region_abs: Optional[torch.Tensor] = None
+
+
 @dataclass
 class ScreenResult:
     """Result of `screen_1m` (device tensors).  Maps are the model's output, the log observed / expected map of ``_Orca1M.forward`` (the
@@ -1319,6 +1406,14 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
     virtual 4C; in the aligned form the viewpoint is a REFERENCE bin, followed to wherever the item moved it.  Both are taken from the batch's
     maps whichever route made them, with ``strands="both"`` from the merged maps against the merged ``ref_map``.  With both None nothing more is
     launched and every other field is what it was.  ``stats`` gains ``insulation_widths`` and ``viewpoints``: their numbers (0 when absent)."""
+    return _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, aligned, flank_bp, strands, insulation, viewpoints)
+
+
+def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, aligned, flank_bp, strands, insulation, viewpoints, hook=None):
+    """The body of `screen_1m` (its arguments, its result).  ``hook``: called as ``hook(res, i0, i1, maps)`` at the end of every batch, on every
+    route, with the `ScreenResult` under construction (``res.ref_map`` is final) and the FINAL maps [i1 - i0, n, n] of items [i0, i1) - after the
+    strand merge and after any range fallback; the buffer is the batch's own, so the hook reads it before it returns.  Without a hook nothing
+    is launched that `screen_1m` did not launch."""
     if strands not in ("+", "both"):
         raise ValueError(f"strands must be '+' or 'both', got {strands!r}")
     both = strands == "both"
@@ -1487,6 +1582,66 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
                 torch.sub(h, ref_1d[None], out=res.delta_1d[i0:i1])
             if keep_maps:
                 res.maps[i0:i1] = maps
+            if hook is not None:
+                hook(res, i0, i1, maps)
     if stats is not None:
         stats.update(st)
     return res
+
+
+def epistasis_1m(model, window, sets, batch=64, regions=None, strands="+", keep_maps=False, stats=None, bank_bytes=4 << 30):
+    """Non-additivity scores of ``sets`` (a list of `EditSet`; a bare `Edit` counts as a one-member set) on one window with the 1 Mb model: is the
+    effect of a set the sum of its members' effects?  An `EpistasisResult`.
+
+    ``singles, member_off, members = epistasis_items(sets)``, and ``singles + sets`` go through ONE screen (`screen_1m`'s arguments ``model``,
+    ``window``, ``batch``, ``regions``, ``strands``, ``keep_maps``, ``stats`` mean what they mean there): one reference, one plan.  The singles'
+    final maps - after the strand merge and after any range fallback, whichever route made them - are kept in a device bank [U, n, n], and in
+    the same batch loop every set's map is scored against the bank (orca_screen_epistasis_scores, orca_screen_epistasis_region_scores): per
+    pixel in fp64, t = sum_m (A_m - ref) and r = (S - ref) - t, `EpistasisResult` has the fields.  The singles come first, so every member is
+    banked before a set needs it; a batch may hold the last singles and the first sets.  No set's map is kept unless ``keep_maps``.
+
+    r is a small difference of four nearly equal maps.  An fp32 pixel is exact in fp64, so here every difference is exact up to fp64
+    rounding whatever the maps hold, the sums keep their accuracy under cancellation, and only the final results are rounded to fp32
+    (DESIGN 3e says what that did and did not change on the workload measured).
+
+    ``del`` / ``ins`` members are a ValueError (`epistasis_items`).  ``bank_bytes``: the most the bank may take (U n^2 4 bytes; 4 GiB by
+    default) - a larger one is a ValueError: split the set list.  ``stats`` gains ``epistasis_sets``, ``epistasis_singles`` and ``bank_bytes``
+    (the bank's size)."""
+    sets = list(sets)
+    for s in sets:
+        if not isinstance(s, (Edit, EditSet)):
+            raise TypeError("sets: a list of screen.EditSet (and screen.Edit)")
+    if not sets:
+        raise ValueError("epistasis_1m: at least one set")
+    singles, member_off, members = epistasis_items(sets)
+    win = _window_codes(window)
+    U, E, n, dev = len(singles), len(sets), win.numel() // 4000, win.device
+    need = U * n * n * 4
+    if need > bank_bytes:
+        raise ValueError(f"epistasis_1m: the bank of {U} single-edit maps takes {need} bytes, above bank_bytes = {bank_bytes}: split the set list")
+    rects = None if regions is None else check_regions(regions, n)
+    ctx = engine.get_context(dev)
+    bank = torch.empty((U, n, n), dtype=torch.float32, device=dev)
+    out = EpistasisResult(None, singles, U, member_off, members, torch.zeros((E, n), dtype=torch.float32, device=dev),
+                          *(torch.zeros(E, dtype=torch.float32, device=dev) for _ in range(3)))
+    if rects is not None:
+        out.epi_region, out.epi_region_abs = (torch.zeros((E, len(rects)), dtype=torch.float32, device=dev) for _ in range(2))
+
+    def score(res, i0, i1, maps):
+        if i0 < U:                                       # the batch's singles into the bank, before its sets are scored
+            bank[i0: min(i1, U)] = maps[: min(i1, U) - i0]
+        if i1 <= U:
+            return
+        s0 = max(i0, U)
+        e0, e1 = s0 - U, i1 - U
+        off = member_off[e0: e1 + 1] - member_off[e0]
+        got = engine.screen_epistasis_scores(ctx, maps[s0 - i0:], bank, res.ref_map, off, members[member_off[e0]: member_off[e1]], rects)
+        out.epi_profile[e0:e1], out.epi_abs_mean[e0:e1], out.epi_abs_max[e0:e1], out.additive_abs_mean[e0:e1] = got[:4]
+        if rects is not None:
+            out.epi_region[e0:e1], out.epi_region_abs[e0:e1] = got[4:]
+    st = {}
+    out.screen = _run_screen(model, win, singles + sets, batch, keep_maps, st, rects, None, False, None, strands, None, None, hook=score)
+    st.update(epistasis_sets=E, epistasis_singles=U, bank_bytes=need)
+    if stats is not None:
+        stats.update(st)
+    return out

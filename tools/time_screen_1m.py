@@ -30,6 +30,11 @@ Both strands, into profiles/screen_1m_strands.json:
 Tracks, into profiles/screen_1m_tracks.json:
   --tracks       the 3 250-edit workload at B = 64 through screen_1m with insulation=(5, 10, 25), viewpoints=[125] and without, alternated in the same
                  run; with --aligned also aligned=True with and without the tracks: what the two track kernels add, set beside what aligned=True adds
+
+Non-additivity, into profiles/screen_1m_epistasis.json:
+  --epistasis NA NB  the NA x NB pairs of 4 kb mask tiles (NA from base 100 000, NB from base 600 000) at B = 64 through screen.epistasis_1m, and
+                 through today's route - screen_1m on the singles and on the pairs with keep_maps=True, then the residual in torch, in fp32 -
+                 alternated in the same run, best of three; also the largest |fp32-route residual - fp64 residual| seen on the same maps
 """
 import argparse
 import json
@@ -242,6 +247,55 @@ def time_strands(a, model, win, edits, dev):
     return rep
 
 
+def fp32_residuals(model, win, ta, tb, pairs, index, batch):
+    """Today's route to the non-additivity residual: the singles and the pairs through screen_1m with keep_maps=True, then
+    r = (alt_AB - ref) - (alt_A - ref) - (alt_B - ref) in torch, in fp32.  (mean |r| per pair, the two results)."""
+    one = S.screen_1m(model, win, ta + tb, batch=batch, keep_maps=True)
+    two = S.screen_1m(model, win, pairs, batch=batch, keep_maps=True)
+    ia = torch.tensor([i for i, _ in index], device=win.device)
+    ib = torch.tensor([len(ta) + j for _, j in index], device=win.device)
+    out = torch.empty(len(pairs), dtype=torch.float32, device=win.device)
+    for k0 in range(0, len(pairs), 256):                                                  # chunks: the difference maps are temporaries
+        k1 = min(k0 + 256, len(pairs))
+        r = (two.maps[k0:k1] - two.ref_map) - (one.maps[ia[k0:k1]] - one.ref_map) - (one.maps[ib[k0:k1]] - one.ref_map)
+        out[k0:k1] = r.abs().mean(dim=(1, 2))
+    return out, one, two
+
+
+def time_epistasis(a, model, win, dev):
+    """The --epistasis NA NB workload: the NA x NB pairs of two lists of 4 kb mask tiles through epistasis_1m, and through two screen_1m calls with
+    keep_maps=True plus the fp32 arithmetic in torch, alternated, best of three, at B = 64.  Outside the timing, the largest difference between the
+    fp32 route's residual and the fp64 residual of the same maps, per pixel and in the per-pair mean."""
+    na, nb = a.epistasis
+    B = 64
+    ta = S.tile_edits("mask", 4000, 4000, 100_000, 100_000 + 4000 * na)
+    tb = S.tile_edits("mask", 4000, 4000, 600_000, 600_000 + 4000 * nb)
+    pairs, index = S.pair_edits(ta, tb)
+    rep = {"device": torch.cuda.get_device_name(dev), "pairs": len(pairs), "singles": na + nb, "batch": B}
+    st = {}
+    res = S.epistasis_1m(model, win, pairs, batch=B, stats=st)                              # warm-up and cross-check
+    m32, one, two = fp32_residuals(model, win, ta, tb, pairs, index, B)
+    rep.update({"route": st["route"], "bank_bytes": st["bank_bytes"], "kept_map_bytes_fp32_route": int(one.maps.numel() + two.maps.numel()) * 4})
+    ref = two.ref_map.double()
+    pix = torch.zeros((), dtype=torch.float64, device=dev)
+    for k, (i, j) in enumerate(index):                                                    # the same maps, the kernel's arithmetic in torch fp64
+        t = (one.maps[i].double() - ref) + (one.maps[na + j].double() - ref)
+        r64 = (two.maps[k].double() - ref) - t
+        r32 = (two.maps[k] - two.ref_map) - (one.maps[i] - one.ref_map) - (one.maps[na + j] - one.ref_map)
+        pix = torch.maximum(pix, (r32.double() - r64).abs().max())
+    rep.update({"max_abs_fp32_residual_minus_fp64_residual": float(pix), "max_abs_mean_fp32_route_minus_epistasis_1m": float((m32 - res.epi_abs_mean).abs().max()),
+                "epi_abs_mean_median": float(res.epi_abs_mean.median()), "additive_abs_mean_median": float(res.additive_abs_mean.median()),
+                "map_abs_max": float(two.ref_map.abs().max())})
+    del one, two, m32, res
+    te, tf = [], []
+    for _ in range(3):
+        te.append(timed(lambda: S.epistasis_1m(model, win, pairs, batch=B))[0])
+        tf.append(timed(lambda: fp32_residuals(model, win, ta, tb, pairs, index, B)[0])[0])
+    rep.update({"epistasis_1m_s": [round(t, 3) for t in te], "fp32_route_s": [round(t, 3) for t in tf], "epistasis_1m_pairs_per_s": round(len(pairs) / min(te), 1),
+                "fp32_route_pairs_per_s": round(len(pairs) / min(tf), 1), "fp32_route_over_epistasis_1m": round(min(tf) / min(te), 3)})
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="16,64")
@@ -256,12 +310,26 @@ def main():
     ap.add_argument("--aligned", action="store_true", help="time the 3 250-edit workload with aligned=True against aligned=False")
     ap.add_argument("--tracks", action="store_true", help="time the 3 250-edit workload at B = 64 with insulation and viewpoint tracks against without")
     ap.add_argument("--strands", default="+", choices=("+", "both"), help="both: time the 3 250-edit workload on both strands at B = 64")
+    ap.add_argument("--epistasis", type=int, nargs=2, metavar=("NA", "NB"), help="time the NA x NB mask-tile pairs through epistasis_1m against two screen_1m "
+                    "calls with keep_maps=True plus fp32 arithmetic in torch")
     ap.add_argument("--commit", default="", help="recorded in the report")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     model = M.H1esc_1M(synthetic_seed=0).to(dev)
     c = window()
     win = torch.from_numpy(c).to(dev)
+    if a.epistasis:
+        rep = {"workload": f"H1esc_1M synthetic, 1 Mb window, the {a.epistasis[0]} x {a.epistasis[1]} pairs of 4 kb mask tiles; epistasis_1m against "
+                           "screen_1m(singles, keep_maps=True) + screen_1m(pairs, keep_maps=True) + the residual in torch fp32, alternated, best of "
+                           "three (every call includes its references)", "commit": a.commit}
+        rep.update(time_epistasis(a, model, win, dev))
+        print(json.dumps(rep))
+        out = a.out if a.out != ap.get_default("out") else os.path.join(os.path.dirname(a.out), "screen_1m_epistasis.json")
+        if out:
+            os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+            with open(out, "w") as f:
+                json.dump(rep, f, indent=1)
+        return
     if a.indels:
         rep = {"workload": "H1esc_1M synthetic, 1 Mb window, random insertions and deletions; naive = the same alt windows through model.net; "
                            "snv_screen = SNVs at the same positions through the screen (every call includes its reference and, for indels, "
