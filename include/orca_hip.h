@@ -525,10 +525,17 @@ int orca_pointwise1d_forward(orca_ctx* ctx, const float* w_dev, const float* bia
 int orca_conv1d_forward(orca_ctx* ctx, const orca_conv_desc* conv, const float* x, int64_t x_bs, int64_t ldx,
                         float* y, int64_t y_bs, int64_t ldy, const float* r1, const float* r2, int B, int64_t n,
                         int relu, int tile);
-/* Channel-last variant on the bf16 matrix cores with split operands (precision = ORCA_PRECISION_BF16 /
- * _BF16X2 / _BF16X3): x [B][n][cin], y and r1 [B][n][cout], all contiguous; cin % 16 == 0. */
+/* Channel-last variant on the 16-bit matrix cores with split operands (precision = ORCA_PRECISION_BF16 /
+ * _BF16X2 / _BF16X3 / _F16X2): x [B][n][cin], y and r1 [B][n][cout], all contiguous; cin % 16 == 0. */
 int orca_conv1d_nlc_forward(orca_ctx* ctx, const orca_conv_desc* conv, int precision, const float* x, float* y,
                             const float* r1, int B, int64_t n, int relu);
+/* The same launcher with every argument the nets give it: r2 = a second residual [B][n][cout] (the U-net encoders' skip
+ * connection; may be y itself - each element is read by the lane that then stores it), pool4 = 1 fuses MaxPool1d(4) into
+ * the epilogue (y is [B][n/4][cout], a ragged last window is dropped, r1 stays [B][n][cout]; no r2 then),
+ * fixed_tile = 0 / 1 / 2: the position tile of a long 128-cout layer by n and B / 256 positions whatever B is / what a
+ * B = 1 call of n positions takes.  Batch strides are the contiguous ones.  ORCA_EINVAL, before any launch, on anything else. */
+int orca_conv1d_nlc_forward_full(orca_ctx* ctx, const orca_conv_desc* conv, int precision, const float* x, float* y,
+                                 const float* r1, const float* r2, int B, int64_t n, int relu, int pool4, int fixed_tile);
 /* The P16 / LDS-DMA conv1d of the Encoder's stages 1-3 (conv_p16.h), wrapped for tests: channel-last fp32
  * in/out (x [n][cin], r1 [n][cout], y [n][cout] or, with out_mode 1 = fused MaxPool1d(4), [n/4][cout], with out_mode 3 = fused
  * MaxPool1d(5) (128 couts: conv_p16p5.h), [n/5][cout]);

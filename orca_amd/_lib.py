@@ -119,6 +119,8 @@ SIGNATURES = {
     "orca_conv1d_forward": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                     c_void_p, c_void_p, c_int, c_int64, c_int, c_int]),
     "orca_conv1d_nlc_forward": (c_int, [c_void_p, POINTER(ConvDesc), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int]),
+    "orca_conv1d_nlc_forward_full": (c_int, [c_void_p, POINTER(ConvDesc), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
+                                             c_int, c_int]),
     "orca_conv1d_p16_forward": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int]),
     "orca_conv1d_b16_forward": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int]),
     "orca_conv2d_forward": (c_int, [c_void_p, POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]),

@@ -120,6 +120,14 @@ static __global__ void copy2d_kernel(const float* __restrict__ src, long lds_, l
   dst[r * ldd + c] = src[r * lds_ + c * scol];
 }
 
+// the same copy for ANY number of rows (they are not a grid dimension): one thread per element, row-major over [rows][cols]
+static __global__ void copy2d_flat_kernel(const float* __restrict__ src, long lds_, long scol, float* __restrict__ dst, long ldd, long rows, long cols) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows * cols) return;
+  const long r = idx / cols, c = idx - r * cols;
+  dst[r * ldd + c] = src[r * lds_ + c * scol];
+}
+
 // Decoder input (orca_modules.py:462-463): mat[c][i][j] = x[c][i] + x[c][j] (c<128),
 // channel 128 = distenc[i][j] (if given), remaining pad channels = 0.
 // out layout [cpad][n][256]; one thread writes a float4 of columns.

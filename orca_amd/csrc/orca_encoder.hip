@@ -439,6 +439,14 @@ static int launch_copy2d(orca_ctx* ctx, const float* src, long lds_, long scol, 
   return ORCA_OK;
 }
 
+// the same with the rows out of gridDim.y (<= 65 535): a position-strided input of any length
+static int launch_copy2d_flat(orca_ctx* ctx, const float* src, long lds_, long scol, float* dst, long ldd, long rows, long cols) {
+  if (rows <= 0 || cols <= 0) return ORCA_OK;
+  hipLaunchKernelGGL(copy2d_flat_kernel, dim3((unsigned)((rows * cols + 255) / 256)), dim3(256), 0, ctx->stream, src, lds_, scol, dst, ldd, rows, cols);
+  LAUNCHCHECK("copy2d_flat_kernel");
+  return ORCA_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Encoder (orca_modules.py:929-980)
 // ---------------------------------------------------------------------------
@@ -1231,7 +1239,7 @@ static int unet_forward_nlc(orca_ctx* ctx, orca_net* net, const float* x, int64_
   // the (possibly strided) channel-major input -> [B][n][128]
   if (sx_l == 1) ORCA_TRY(launch_transpose(ctx, x, sx_c, sx_b, encs[0], 128, (long)n * 128, 128, n, B));
   else
-    for (int b = 0; b < B; ++b) ORCA_TRY(launch_copy2d(ctx, x + (long)b * sx_b, sx_l, sx_c, encs[0] + (size_t)b * n * 128, 128, n, 128));
+    for (int b = 0; b < B; ++b) ORCA_TRY(launch_copy2d_flat(ctx, x + (long)b * sx_b, sx_l, sx_c, encs[0] + (size_t)b * n * 128, 128, n, 128));
   const ConvLayer* L = net->convs.data();
   for (int i = 0; i < nlev; ++i) {      // contracting path
     const long no = n >> (i + 1), bs = 128 * no;

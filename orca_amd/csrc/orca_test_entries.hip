@@ -35,6 +35,26 @@ extern "C" int orca_conv1d_nlc_forward(orca_ctx* ctx, const orca_conv_desc* conv
   return rc;
 }
 
+// the launcher as the nets call it: second residual (may be y), fused MaxPool1d(4), the tile rule of the long 128-cout layers
+extern "C" int orca_conv1d_nlc_forward_full(orca_ctx* ctx, const orca_conv_desc* conv, int precision, const float* x, float* y,
+                                            const float* r1, const float* r2, int B, int64_t n, int relu, int pool4, int fixed_tile) {
+  if (!ctx || !conv || !x || !y) return fail(ORCA_EINVAL, "orca_conv1d_nlc_forward_full: NULL argument");
+  if (precision < ORCA_PRECISION_BF16 || precision > ORCA_PRECISION_F16X2) return fail(ORCA_EINVAL, "precision %d unsupported here", precision);
+  if (B <= 0 || B > 65535 || n < 0) return fail(ORCA_EINVAL, "orca_conv1d_nlc_forward_full: batch %d / length %ld unsupported", B, (long)n);
+  if (pool4 < 0 || pool4 > 1 || fixed_tile < 0 || fixed_tile > 2) return fail(ORCA_EINVAL, "orca_conv1d_nlc_forward_full: pool4 %d (0, 1) / fixed_tile %d (0..2)", pool4, fixed_tile);
+  if (pool4 && r2) return fail(ORCA_EINVAL, "orca_conv1d_nlc_forward_full: the pooled epilogue takes no second residual");
+  if (conv->ksize != 9 || conv->cin % 16 || (conv->cout != 64 && conv->cout != 96 && conv->cout != 128))
+    return fail(ORCA_EINVAL, "orca_conv1d_nlc_forward_full: %d taps, %d -> %d channels unsupported", conv->ksize, conv->cin, conv->cout);
+  HIPCHECK(hipSetDevice(ctx->device));
+  ConvLayer L;
+  ORCA_TRY(make_layer(*conv, &L));
+  const long nout = pool4 ? n / 4 : n;
+  int rc = launch_conv1d_b16(ctx, L, precision, x, (long)n * conv->cin, y, nout * conv->cout, r1, B, n, relu, pool4, r2, fixed_tile);
+  (void)hipStreamSynchronize(ctx->stream);
+  free_layer(L);
+  return rc;
+}
+
 static int conv1d_planar_test(orca_ctx* ctx, const orca_conv_desc* conv, const float* x, float* y, const float* r1, int64_t n, int relu,
                               int out_mode, int fmt) {
   if (!ctx || !conv || !x || !y) return fail(ORCA_EINVAL, "orca_conv1d_p16/b16_forward: NULL argument");

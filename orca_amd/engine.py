@@ -1198,19 +1198,38 @@ def conv1d(x, w, b, relu=False, r1=None, r2=None, tile=0):
     return y
 
 
-def conv1d_nlc(x, w, b, precision="bf16x3", relu=False, r1=None):
-    """channel-last split-bf16 conv: x [B,n,cin] -> [B,n,cout]."""
+def conv1d_nlc(x, w, b, precision="bf16x3", relu=False, r1=None, r2=None, inplace=False, pool4=False, fixed_tile=0):
+    """channel-last split-operand conv: x [B,n,cin] -> [B,n,cout] (pool4: MaxPool1d(4) fused, [B,n//4,cout]).  r2: a second residual
+    [B,n,cout]; inplace: it is copied into the output buffer and that buffer is passed as both (the U-net encoders' skip connection).
+    fixed_tile: the tile rule of the long 128-cout layers (include/orca_hip.h).  Any of the last four: the full test entry."""
     x = _f32_cuda(x, "x").contiguous()
     B, n, cin = x.shape
     w = np.ascontiguousarray(w, dtype=np.float32)
     b = np.ascontiguousarray(b, dtype=np.float32)
     cout = w.shape[0]
     d = make_descs([{"w": w, "b": b, "cout": cout, "cin": cin, "k": 9, "dil": 1}])
-    y = torch.empty((B, n, cout), dtype=torch.float32, device=x.device)
+    if inplace and r2 is None:
+        raise ValueError("conv1d_nlc: inplace needs r2")
+    y = torch.empty((B, n // 4 if pool4 else n, cout), dtype=torch.float32, device=x.device)
+    if y.numel() == 0:
+        return y
     ctx = get_context(x.device)
     r1 = r1.contiguous() if r1 is not None else None
-    check(_lib.load().orca_conv1d_nlc_forward(ctx.handle, d, _lib.PRECISIONS[precision], _p(x), _p(y),
-                                              _p(r1) if r1 is not None else None, B, n, 1 if relu else 0), "orca_conv1d_nlc_forward")
+    if r2 is None and not pool4 and not fixed_tile:
+        check(_lib.load().orca_conv1d_nlc_forward(ctx.handle, d, _lib.PRECISIONS[precision], _p(x), _p(y),
+                                                  _p(r1) if r1 is not None else None, B, n, 1 if relu else 0), "orca_conv1d_nlc_forward")
+        return y
+    if r2 is not None:
+        if tuple(r2.shape) != tuple(y.shape):
+            raise ValueError(f"conv1d_nlc: r2 must be {tuple(y.shape)}, got {tuple(r2.shape)}")
+        r2 = _f32_cuda(r2, "r2").contiguous()
+        if inplace:
+            y.copy_(r2)
+            r2 = y
+    ctx.sync_stream()       # the copy above was enqueued on torch's stream
+    check(_lib.load().orca_conv1d_nlc_forward_full(ctx.handle, d, _lib.PRECISIONS[precision], _p(x), _p(y), _p(r1) if r1 is not None else None,
+                                                   _p(r2) if r2 is not None else None, B, n, 1 if relu else 0, 1 if pool4 else 0,
+                                                   int(fixed_tile)), "orca_conv1d_nlc_forward_full")
     return y
 
 
