@@ -463,6 +463,20 @@ int orca_decoder_probe(orca_ctx* ctx, orca_net* net, const float* x, int64_t sx_
                        int64_t sy_b, int64_t sy_c, int64_t sy_h, int64_t sy_w, int B, int n, int stage, int channels,
                        float* map_out);
 
+/* For tests (export 76), the Encoder's counterpart of orca_decoder_probe: one chunk of ONE whole sequence of L bases (no halo, no bin range) through
+ * stages 1..`stage` (1..7) of the route that orca_encoder_forward / _forward_codes take for this net - its precision and encoder form decide it, the
+ * probe chooses no kernel: the same launches with the same arguments, fused pools and edge chains included, with an early return - and what that route
+ * leaves behind the stage, copied to out as fp32 channel-last [*n_out][*channels] (64, 96, 128 channels for stages 1, 2, 3..7).  The input is either
+ * packed codes (with `reverse`) or float rows x[c * sx_c + l * sx_l]; the other pointer is NULL.  *pool: the MaxPool1d the route has already applied
+ * to that tensor (tails dropped), 1 = none:
+ *   ORCA_PRECISION_F32               every stage unpooled (every pool is a launch of its own)
+ *   ORCA_PRECISION_BF16X3 / _BF16X2  stages 1, 2 MaxPool1d(4)'d (fused into the last conv's epilogue), stages 3..7 unpooled
+ *   ORCA_PRECISION_F16X2 / _BF16     stages 1, 2, 3 pooled by 4, 4, 5 (planes, decoded), stage 4 the fp32 rows of the hand-over and stages 5..7 unpooled
+ * ORCA_EINVAL, before any launch: both or neither input, a stage whose input or whose returned tensor has no position left (stage 5 of 80 bases),
+ * out_floats < *n_out x *channels (L x 64 floats always suffice).  The two-strand joint route is not probed. */
+int orca_encoder_probe(orca_ctx* ctx, orca_net* net, const uint8_t* codes, int reverse, const float* x, int64_t sx_c, int64_t sx_l, int64_t L,
+                       int stage, float* out, int64_t out_floats, int64_t* n_out, int* channels, int* pool);
+
 /* Replaces: the strand merge `0.5*fwd + 0.5*rev[::-1, ::-1]`
  * (orca_predict.py:514-523) for contiguous [n,n] maps. */
 int orca_strand_merge(orca_ctx* ctx, const float* fwd, const float* rev, float* out, int n);

@@ -108,6 +108,8 @@ SIGNATURES = {
     "orca_decoder1m_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int]),
     "orca_decoder_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p,
                                    c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+    "orca_encoder_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64,
+                                   POINTER(c_int64), POINTER(c_int), POINTER(c_int)]),
     "orca_strand_merge": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "orca_block_mean_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int]),
     "orca_adaptive_coarsegrain": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, ctypes.c_float, c_int, c_int, c_void_p, c_int64]),

@@ -721,7 +721,7 @@ static int enc_stages_nlc(orca_ctx* ctx, const orca_net* net, const SeqSource& s
   int P = 0;
   // stage 1 uncomposed: the 4-channel first layer stays on the fp32 kernel (K = 36, 1 % of the FLOPs) and writes channel-last
   if (r.pipe == PIPE_NLC && !r.compose_nlc) ORCA_TRY(enc_rows_channel_major(ctx, src, n, buf, ld1));
-  for (int st = st_from; st < 7; ++st) {
+  for (int st = st_from; st < 7 && st <= r.last; ++st) {
     const ConvLayer* L = &net->convs[4 * st];
     if (kEncPools[st] == 4) {
       n = n / 4;  // MaxPool1d(4) was fused into the epilogue of the previous stage's last conv
@@ -750,7 +750,8 @@ static int enc_stages_nlc(orca_ctx* ctx, const orca_net* net, const SeqSource& s
     ORCA_TRY(launch_conv1d_b16(ctx, L[3], prec, buf[T], bs, buf[P], bs, st < 6 ? buf[LO] : nullptr, B, n, 1,
                                (st < 6 && kEncPools[st + 1] == 4) ? 1 : 0, nullptr, own_tile));
   }
-  *out = buf[P]; *out_ld = -128; *out_n = n;   // negative ld: result is channel-last [n][128]
+  if (r.last < 6 && kEncPools[r.last + 1] == 4) n = n / 4;   // stopped behind stage 1 / 2 (orca_encoder_probe): their last conv pooled
+  *out = buf[P]; *out_ld = -128; *out_n = n;   // negative ld: result is channel-last [n][C]
   return ORCA_OK;
 }
 
@@ -760,7 +761,7 @@ static int enc_stages_f32(orca_ctx* ctx, const orca_net* net, const SeqSource& s
   hipStream_t s = ctx->stream;
   int P = 0, cprev = 4;
   if (!r.compose32) ORCA_TRY(enc_rows_channel_major(ctx, src, n, buf, ld));
-  for (int st = 0; st < 7; ++st) {
+  for (int st = 0; st < 7 && st <= r.last; ++st) {
     const ConvLayer* L = &net->convs[4 * st];
     if (kEncPools[st] > 1) {
       const long n2 = n / kEncPools[st], ld2 = ru4(n2);
@@ -796,10 +797,8 @@ static int enc_stages_f32(orca_ctx* ctx, const orca_net* net, const SeqSource& s
 
 // One chunk: src (n1 positions; a part that starts behind stage 1: its input in buf[0]) -> the route's output in one of the three buffers.
 // *out_ld: row stride of a channel-major result [128][ld]; negative: fp32 channel-last [n][128]; 0: planes
-static int encoder_chunk(orca_ctx* ctx, orca_net* net, const SeqSource& src, long n1, float* const buf[3],
-                         long ld1, float** out, long* out_ld, long* out_n, int part = ENC_FULL) {
-  EncRoute r;
-  ORCA_TRY(enc_route(net, src, part, &r));
+static int enc_run_route(orca_ctx* ctx, orca_net* net, const SeqSource& src, const EncRoute& r, long n1, float* const buf[3],
+                         long ld1, float** out, long* out_ld, long* out_n) {
   if (r.pipe == PIPE_F32) return enc_stages_f32(ctx, net, src, r, n1, buf, ld1, out, out_ld, out_n);
   long n = n1;
   int st = r.first;
@@ -812,6 +811,12 @@ static int encoder_chunk(orca_ctx* ctx, orca_net* net, const SeqSource& src, lon
   return enc_stages_nlc(ctx, net, src, r, st, n, buf, ld1, out, out_ld, out_n);
 }
 
+static int encoder_chunk(orca_ctx* ctx, orca_net* net, const SeqSource& src, long n1, float* const buf[3],
+                         long ld1, float** out, long* out_ld, long* out_n, int part = ENC_FULL) {
+  EncRoute r;
+  ORCA_TRY(enc_route(net, src, part, &r));
+  return enc_run_route(ctx, net, src, r, n1, buf, ld1, out, out_ld, out_n);
+}
 
 static int encoder_forward_impl(orca_ctx* ctx, orca_net* net, const float* x, int64_t sx_b, int64_t sx_c, int64_t sx_l,
                                 const unsigned char* codes, int64_t sc_b, int reverse,
@@ -997,6 +1002,52 @@ extern "C" int orca_net_set_encoder_two_strands(orca_net* net, int on) {
 extern "C" int orca_net_get_encoder_two_strands(orca_net* net, int* on) {
   if (!net || !on || net->kind != ORCA_NET_ENCODER) return fail(ORCA_EINVAL, "orca_net_get_encoder_two_strands: not an Encoder net");
   *on = net->enc_two_strands;
+  return ORCA_OK;
+}
+
+// orca_encoder_probe: the ENC_FULL route of the net's own arithmetic and form, stopped behind stage `stage` (EncRoute::last), and what that route
+// leaves there copied out as fp32 channel-last rows.  The route comes from enc_route like every other; only `last` and the hand-over format of a
+// planar stage are the probe's, so that the part exports keep their refusals
+extern "C" int orca_encoder_probe(orca_ctx* ctx, orca_net* net, const uint8_t* codes, int reverse, const float* x, int64_t sx_c, int64_t sx_l, int64_t L,
+                                  int stage, float* out, int64_t out_floats, int64_t* n_out, int* channels, int* pool) {
+  if (!ctx || !net || !out || !n_out || !channels || !pool) return fail(ORCA_EINVAL, "orca_encoder_probe: NULL argument");
+  if ((codes == nullptr) == (x == nullptr)) return fail(ORCA_EINVAL, "orca_encoder_probe: exactly one of codes and x");
+  if (net->kind != ORCA_NET_ENCODER) return fail(ORCA_EINVAL, "orca_encoder_probe: net is not an Encoder");
+  if (stage < 1 || stage > 7 || L <= 0) return fail(ORCA_EINVAL, "orca_encoder_probe: stage %d (1..7) of %ld bases", stage, (long)L);
+  SeqSource src;
+  if (codes) { src.codes = codes; src.codes_L = L; src.codes_off = 0; src.reverse = reverse ? 1 : 0; }
+  else { src.x = x; src.sx_c = sx_c; src.sx_l = sx_l; }
+  EncRoute r;
+  ORCA_TRY(enc_route(net, src, ENC_FULL, &r));
+  r.last = stage - 1;
+  long n = L;                                              // positions the stage reads
+  for (int st = 1; st < stage; ++st) n /= kEncPools[st];
+  int pl = 1;                                              // the pool the route has already applied to what it leaves behind the stage
+  if (r.pipe == PIPE_NLC && stage <= 2) pl = 4;            // fused into the last conv's epilogue (conv_bf16s.h)
+  if (r.planar() && stage < kPlanarStages) { pl = kEncPools[stage]; r.out = OUT_PLANES_POOLED; }
+  if (r.planar() && stage == kPlanarStages) r.out = OUT_ROWS;
+  const int C = net->convs[4 * (stage - 1) + 3].cout;
+  const long nout = n / pl;
+  if (n <= 0 || nout <= 0) return fail(ORCA_EINVAL, "orca_encoder_probe: %ld bases leave stage %d no position", (long)L, stage);
+  if (nout * C > out_floats) return fail(ORCA_EINVAL, "orca_encoder_probe: out holds %ld floats, stage %d needs %ld x %d", (long)out_floats, stage, nout, C);
+  HIPCHECK(hipSetDevice(ctx->device));
+  const long ld1 = ru4(L) + 1024;
+  float* buf[3];
+  ORCA_TRY(ws_three(ctx, (size_t)64 * ld1, buf));
+  float* res; long rld, rn;
+  ORCA_TRY(enc_run_route(ctx, net, src, r, L, buf, ru4(L), &res, &rld, &rn));
+  if (rn != nout) return fail(ORCA_EINVAL, "internal: the probe of stage %d produced %ld positions, expected %ld", stage, rn, nout);
+  if (rld > 0) {                                           // channel-major [C][ld]
+    ORCA_TRY(launch_copy2d_flat(ctx, res, 1, rld, out, C, nout, C));
+  } else if (rld < 0) {                                    // fp32 rows [n][C]
+    HIPCHECK(hipMemcpyAsync(out, res, (size_t)nout * C * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+  } else {
+    const dim3 grid((unsigned)((nout * (C / 4) + 255) / 256));
+    if (r.fmt == 1) hipLaunchKernelGGL(b16_to_nlc_kernel, grid, dim3(256), 0, ctx->stream, reinterpret_cast<const f32x4*>(res), out, nout, C, p16_plen(nout));
+    else hipLaunchKernelGGL(p16_to_nlc_kernel, grid, dim3(256), 0, ctx->stream, reinterpret_cast<const f32x4*>(res), out, nout, C, p16_plen(nout));
+    LAUNCHCHECK("p16_to_nlc_kernel");
+  }
+  *n_out = nout; *channels = C; *pool = pl;
   return ORCA_OK;
 }
 

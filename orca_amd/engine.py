@@ -1152,6 +1152,31 @@ def decoder_probe(net, x, distenc, y, stage):
     return out
 
 
+def encoder_probe(net, codes=None, x=None, reverse=False, stage=7):
+    """Test entry (orca_encoder_probe): stages 1..``stage`` of the route `encoder_forward` / `encoder_forward_codes` take for ``net`` (its
+    precision and form decide it) on ONE whole sequence - ``codes`` [L] uint8 (``reverse``: its reverse complement) or float rows ``x`` [4, L]
+    (any strides) - and what the route leaves behind that stage: (fp32 [n_out, C], pool), pool = the MaxPool1d already applied to it (1, 4, 5)."""
+    if (codes is None) == (x is None):
+        raise ValueError("encoder_probe: exactly one of codes and x")
+    if codes is not None:
+        codes = _codes1d(codes)
+        L, dev, cp, xp, sx = codes.numel(), codes.device, _p(codes), ctypes.c_void_p(0), (0, 0)
+    else:
+        x = _f32_cuda(x, "x")
+        if x.dim() != 2 or x.shape[0] != 4:
+            raise ValueError(f"encoder_probe: float rows must be [4,L], got {tuple(x.shape)}")
+        L, dev, cp, xp, sx = x.shape[1], x.device, ctypes.c_void_p(0), _p(x), (x.stride(0), x.stride(1))
+    n = L
+    for pool in (4, 4, 5, 5, 5, 2)[: max(0, int(stage) - 1)]:
+        n //= pool
+    buf = torch.empty(max(1, n * 128), dtype=torch.float32, device=dev)
+    n_out, C, pl = ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0)
+    net.ctx.sync_stream()
+    check(_lib.load().orca_encoder_probe(net.ctx.handle, net.handle, cp, 1 if reverse else 0, xp, *sx, L, int(stage), _p(buf), buf.numel(),
+                                         ctypes.byref(n_out), ctypes.byref(C), ctypes.byref(pl)), "orca_encoder_probe")
+    return buf[: n_out.value * C.value].view(n_out.value, C.value), int(pl.value)
+
+
 def strand_merge(fwd, rev):
     """0.5*fwd + 0.5*rev[::-1, ::-1] for contiguous [n,n] maps (orca_predict.py:514-523)."""
     fwd, rev = _f32_cuda(fwd, "fwd").contiguous(), _f32_cuda(rev, "rev").contiguous()
