@@ -392,6 +392,38 @@ int orca_screen_epistasis_region_scores(orca_ctx* ctx, const float* alt, int64_t
                                         const int32_t* members_host, int64_t P, const int32_t* rects, const int32_t* rects_host, int K, float* mean_signed,
                                         float* mean_abs);
 
+/* Distance strata (screen.screen_1m(..., strata=)): how similar B maps alt[b * map_bs + i * n + j] (B >= 1, 1 <= n <= 256, map_bs >= n * n) are to
+ * ref[n][n], stratified by genomic distance.  Stratum d (0 <= d < n) is the set of pairs (i, i + d): only the upper triangle, diagonal included, is ever
+ * read (the screen's maps are symmetric).  For a pair, x = the alt pixel and y = the reference pixel, both converted to fp64 first.
+ *   bin with bin (bin_map NULL)   P_d = all n - d pairs of stratum d, c_d = n - d, y = ref[i][i + d]
+ *   aligned (`bin_map` as above: device copy and checked host copy, values outside -1 .. n - 1 refused)
+ *                                 P_d = the pairs with map i >= 0 and map (i + d) >= 0, c_d = |P_d|, y = ref[map i][map (i + d)]: the stratum is the ALT
+ *                                 distance, every result is indexed by alt bins, an unmapped pair is never read
+ * Per stratum, two passes, each for i ascending from 0.0: (1) the means mx_d, my_d - the sequential sums, then one division by c_d; (2) the centred sums
+ * X_d = sum (x - mx_d)^2, Y_d = sum (y - my_d)^2, C_d = sum (x - mx_d)(y - my_d) and, with dl = x - y, sum dl, sum |dl|, sum dl^2.
+ * Per-stratum outputs [B][n]:
+ *   dist_delta = sum dl / c_d,  dist_abs = sum |dl| / c_d,  dist_rms = sqrt(sum dl^2 / c_d)       fp32, rounded once
+ *   dist_corr  = C_d / sqrt(X_d Y_d)                                                              fp64 (1 - r of a small edit has to survive); NaN when
+ *                c_d < 2, X_d == 0.0 or Y_d == 0.0 - for a constant stratum the centred sums are exactly 0.0 (a sum of at most 256 equal fp32 values is
+ *                exact in fp64, and so is its mean)
+ *   dist_count = c_d (int32)                                                                      aligned only: non-NULL exactly when `bin_map` is
+ *   every floating-point value of a stratum is NaN where c_d = 0
+ * Per-map outputs [B], over the strata d_lo <= d < d_hi (0 <= d_lo < d_hi <= n) combined serially for d ascending, empty strata skipped, c = sum c_d:
+ *   mse  = sum_d sum dl^2 / c                                                                     fp32
+ *   scc  = sum_d C_d / sum_d sqrt(X_d Y_d)                                                        fp64; HiCRep's stratum-adjusted correlation: its
+ *          weighting c_d sqrt(var_x var_y) of the per-stratum correlations, on raw values (no smoothing, no rank transform); NaN when the denominator is 0.0
+ *   corr = C / sqrt(X Y)                                                                          fp64; the Pearson correlation over all pairs of those
+ *          strata from the pooled centred sums: mx = (sum_d c_d mx_d) / c, X = sum_d [X_d + c_d (mx_d - mx)^2], C = sum_d [C_d + c_d (mx_d - mx)(my_d - my)],
+ *          my and Y likewise; NaN when X or Y is 0.0 or c < 2
+ *   all three are NaN when c = 0
+ * A NaN pixel at a pair of P_d makes every output of stratum d NaN and, if d_lo <= d < d_hi, the three per-map scores; it affects nothing else, and one
+ * below the diagonal or at an unmapped pair never shows.  Each stratum is summed by one thread in an order fixed by (n, the bin map) alone (no atomics):
+ * a map's results are bit for bit the same whatever B and its place in the batch, and where the bin map is the identity they are the bin-with-bin bits.
+ * `bin_map` and `bin_map_host` are NULL together.  Anything else is ORCA_EINVAL before any launch. */
+int orca_screen_strata_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* bin_map,
+                              const int32_t* bin_map_host, int d_lo, int d_hi, float* dist_delta, float* dist_abs, float* dist_rms, double* dist_corr,
+                              int32_t* dist_count, float* mse, double* corr, double* scc);
+
 /* Number of 4 kb bins Encoder emits for an L-bp input (floor through the
  * 4,4,5,5,5,2 pooling chain). */
 int64_t orca_encoder_num_bins(int64_t L);

@@ -311,6 +311,22 @@ extern "C" int orca_screen_viewpoints(orca_ctx* ctx, const float* alt, int64_t m
   return launch(ctx, "screen_viewpoints_kernel", screen_viewpoints_kernel, dim3((unsigned)B, (unsigned)V), 256, alt, (long)map_bs, ref, n, views, V, bin_map, delta, aligned);
 }
 
+// ---- distance strata --------------------------------------------------------------------------------------------------------------------------------------------
+extern "C" int orca_screen_strata_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, const float* ref, int B, int n, const int32_t* bin_map,
+                                         const int32_t* bin_map_host, int d_lo, int d_hi, float* dist_delta, float* dist_abs, float* dist_rms, double* dist_corr,
+                                         int32_t* dist_count, float* mse, double* corr, double* scc) {
+  if (!ctx || !alt || !ref || !dist_delta || !dist_abs || !dist_rms || !dist_corr || !mse || !corr || !scc)
+    return fail(ORCA_EINVAL, "orca_screen_strata_scores: NULL argument");
+  if (B < 1 || n < 1 || n > SCREEN_ALIGNED_MAX_BINS || map_bs < (int64_t)n * n)
+    return fail(ORCA_EINVAL, "orca_screen_strata_scores: %d maps (>= 1) of %d bins (1..%d), batch stride %ld (>= n * n)", B, n, SCREEN_ALIGNED_MAX_BINS, (long)map_bs);
+  if (d_lo < 0 || d_lo >= d_hi || d_hi > n) return fail(ORCA_EINVAL, "orca_screen_strata_scores: strata [%d, %d) of a map of %d bins (0 <= d_lo < d_hi <= n)", d_lo, d_hi, n);
+  if ((bin_map != nullptr) != (bin_map_host != nullptr)) return fail(ORCA_EINVAL, "orca_screen_strata_scores: the bin map and its host copy come together or not at all");
+  if ((dist_count != nullptr) != (bin_map != nullptr)) return fail(ORCA_EINVAL, "orca_screen_strata_scores: dist_count and the bin map come together or not at all");
+  if (bin_map) ORCA_TRY(check_bin_map("orca_screen_strata_scores", bin_map_host, B, n));
+  return launch(ctx, "screen_strata_scores_kernel", screen_strata_scores_kernel, dim3((unsigned)B), 256, alt, (long)map_bs, ref, n, bin_map, d_lo, d_hi, dist_delta,
+                dist_abs, dist_rms, dist_corr, dist_count, mse, corr, scc);
+}
+
 // ---- both strands --------------------------------------------------------------------------------------------------------------------------------------------
 extern "C" int orca_screen_merge_strands(orca_ctx* ctx, const float* fwd, int64_t fwd_bs, const float* rev, int64_t rev_bs, const float* ref_fwd, const float* ref_rev,
                                          int B, int n, float* out, int64_t out_bs, float* gap) {

@@ -512,6 +512,114 @@ static __global__ void __launch_bounds__(256) screen_viewpoints_kernel(const flo
   aligned[at] = out;
 }
 
+// ---- distance strata (screen.screen_1m(..., strata=)): similarity of an alt map to the reference, stratified by genomic distance ------------------------
+// Stratum d of an [n, n] map is the pairs (i, i + d), 0 <= i < n - d: the upper triangle, diagonal included, is all that is read.  For a pair x = the
+// alt pixel and y = ref[i][i + d] or, with the bin map, ref[map i][map (i + d)] for the pairs whose two bins are mapped (the stratum is the ALT
+// distance); both converted to fp64 first, c_d = the number of pairs.  Two passes per stratum, each for i ascending from 0.0: the means mx_d, my_d (one
+// division by c_d), then the centred sums X_d = sum (x - mx_d)^2, Y_d = sum (y - my_d)^2, C_d = sum (x - mx_d)(y - my_d) and, with dl = x - y, sum dl,
+// sum |dl|, sum dl^2.  include/orca_hip.h (orca_screen_strata_scores) says what is made of them.  One workgroup of 256 threads per map, thread t owns
+// stratum d = t and walks its own diagonal (address stride n + 1): at a fixed i the lanes of a wave read consecutive addresses a[i n + i + d], so the
+// loads stay coalesced while every stratum is summed by one thread, sequentially, in an order fixed by (n, the bin map) alone - no shuffles, no
+// atomics, and a map's bits depend neither on B nor on its place in the batch.  The per-stratum sums go to LDS and thread 0 combines the strata
+// [d_lo, d_hi) serially for d ascending (empty strata skipped).  The aligned branch differs in the indices of y alone, so where the bin map is the
+// identity it evaluates the bin-with-bin expressions: the same bits.  A NaN pixel at a pair of stratum d enters that stratum's sums and, through
+// them, the per-map scores if d_lo <= d < d_hi; unmapped pairs and the lower triangle are never read.
+static __global__ void __launch_bounds__(256) screen_strata_scores_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, int n,
+                                                                          const int* __restrict__ bin_map, int d_lo, int d_hi,
+                                                                          float* __restrict__ dist_delta, float* __restrict__ dist_abs,
+                                                                          float* __restrict__ dist_rms, double* __restrict__ dist_corr,
+                                                                          int* __restrict__ dist_count, float* __restrict__ mse,
+                                                                          double* __restrict__ corr, double* __restrict__ scc) {
+  __shared__ int s_map[SCREEN_ALIGNED_MAX_BINS], s_c[SCREEN_ALIGNED_MAX_BINS];
+  __shared__ double s_mx[SCREEN_ALIGNED_MAX_BINS], s_my[SCREEN_ALIGNED_MAX_BINS], s_X[SCREEN_ALIGNED_MAX_BINS], s_Y[SCREEN_ALIGNED_MAX_BINS],
+      s_C[SCREEN_ALIGNED_MAX_BINS], s_Q[SCREEN_ALIGNED_MAX_BINS];
+  const int b = blockIdx.x, d = threadIdx.x;
+  n = n > SCREEN_ALIGNED_MAX_BINS ? SCREEN_ALIGNED_MAX_BINS : n;
+  d_lo = d_lo < 0 ? 0 : d_lo;
+  d_hi = d_hi > n ? n : d_hi;
+  const bool al = bin_map != nullptr;
+  if (al) screen_load_bin_map(bin_map + (long)b * n, n, s_map);
+  __syncthreads();
+  const float* a = alt + (long)b * map_bs;
+  const float qnan = __int_as_float(0x7fc00000);
+  const double dnan = (double)qnan;
+  if (d < n) {
+    int c = 0;
+    double sx = 0.0, sy = 0.0;
+    for (int i = 0; i + d < n; ++i) {
+      int ri = i, rj = i + d;
+      if (al) {
+        ri = s_map[i];
+        rj = s_map[i + d];
+        if (ri < 0 || rj < 0) continue;
+      }
+      sx += (double)a[(long)i * n + i + d];
+      sy += (double)ref[(long)ri * n + rj];
+      ++c;
+    }
+    const double cd = (double)c;
+    const double mx = sx / cd, my = sy / cd;             // c = 0: never used
+    double X = 0.0, Y = 0.0, C = 0.0, sd = 0.0, sa = 0.0, sq = 0.0;
+    for (int i = 0; i + d < n; ++i) {
+      int ri = i, rj = i + d;
+      if (al) {
+        ri = s_map[i];
+        rj = s_map[i + d];
+        if (ri < 0 || rj < 0) continue;
+      }
+      const double x = (double)a[(long)i * n + i + d], y = (double)ref[(long)ri * n + rj];
+      const double ex = x - mx, ey = y - my, dl = x - y;
+      X += ex * ex;
+      Y += ey * ey;
+      C += ex * ey;
+      sd += dl;
+      sa += fabs(dl);
+      sq += dl * dl;
+    }
+    s_c[d] = c;
+    s_mx[d] = mx; s_my[d] = my;
+    s_X[d] = X; s_Y[d] = Y; s_C[d] = C; s_Q[d] = sq;
+    const long at = (long)b * n + d;
+    dist_delta[at] = c > 0 ? (float)(sd / cd) : qnan;
+    dist_abs[at] = c > 0 ? (float)(sa / cd) : qnan;
+    dist_rms[at] = c > 0 ? (float)sqrt(sq / cd) : qnan;
+    dist_corr[at] = (c < 2 || X == 0.0 || Y == 0.0) ? dnan : C / sqrt(X * Y);
+    if (dist_count) dist_count[at] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  long c = 0;
+  double q = 0.0, num = 0.0, den = 0.0, wx = 0.0, wy = 0.0;
+  for (int k = d_lo; k < d_hi; ++k) {
+    if (s_c[k] == 0) continue;
+    const double ck = (double)s_c[k];
+    c += s_c[k];
+    q += s_Q[k];
+    num += s_C[k];
+    den += sqrt(s_X[k] * s_Y[k]);
+    wx += ck * s_mx[k];
+    wy += ck * s_my[k];
+  }
+  if (c == 0) {
+    mse[b] = qnan;
+    corr[b] = dnan;
+    scc[b] = dnan;
+    return;
+  }
+  const double cc = (double)c, mx = wx / cc, my = wy / cc;
+  double X = 0.0, Y = 0.0, C = 0.0;
+  for (int k = d_lo; k < d_hi; ++k) {
+    if (s_c[k] == 0) continue;
+    const double ck = (double)s_c[k], ex = s_mx[k] - mx, ey = s_my[k] - my;
+    X += s_X[k] + ck * (ex * ex);
+    Y += s_Y[k] + ck * (ey * ey);
+    C += s_C[k] + ck * (ex * ey);
+  }
+  mse[b] = (float)(q / cc);
+  scc[b] = den == 0.0 ? dnan : num / den;
+  corr[b] = (c < 2 || X == 0.0 || Y == 0.0) ? dnan : C / sqrt(X * Y);
+}
+
 // ---- both strands (screen.screen_1m(..., strands="both")): the '-' strand's map is merged into the '+' strand's as genomepredict merges them ------------
 // out[b][i][j] = 0.5 fwd[b][i][j] + 0.5 rev[b][n-1-i][n-1-j] (the expression of strand_merge_kernel: the same bits), and with the two strands' reference maps
 // gap[b] = mean_ij |(fwd - ref_fwd)[i][j] - (rev - ref_rev)[n-1-i][n-1-j]| - how far the strands disagree about the item's effect.  One workgroup per map, one

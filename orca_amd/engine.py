@@ -950,6 +950,43 @@ def screen_viewpoints(ctx, alt, ref, views_host, bin_map_host=None, bin_map=None
     return delta, aligned
 
 
+# distance strata (orca_screen_strata_scores): similarity scores per genomic distance and per map; the bin map is optional
+def screen_strata_scores(ctx, alt, ref, bin_map=None, d_range=None, bin_map_dev=None):
+    """Distance-stratified similarity of alt [B, n, n] (any batch stride, rows contiguous) to ref [n, n] (orca_screen_strata_scores; include/orca_hip.h
+    has the definitions): a dict of ``dist_delta``, ``dist_abs``, ``dist_rms`` [B, n] float32 (the mean of alt - ref, of its absolute value and its root
+    mean square over stratum d, the pairs (i, i + d)), ``dist_corr`` [B, n] float64 (the Pearson correlation within stratum d), ``mse`` [B] float32,
+    ``corr`` and ``scc`` [B] float64 (mean squared difference, Pearson and stratum-adjusted correlation over the strata ``d_range`` = (d_lo, d_hi),
+    0 <= d_lo < d_hi <= n; all of them by default) and ``dist_count`` [B, n] int32, the pairs per stratum, or None without a bin map.  ``bin_map``
+    [B, n] int32 numpy on the host (``bin_map_dev``: its device copy, uploaded here when None): the aligned form, alt pair (i, i + d) against
+    reference pair (map i, map (i + d)) where both are mapped."""
+    if bin_map is None:
+        if bin_map_dev is not None:
+            raise ValueError("bin_map_dev: the device copy of bin_map, which is None")
+        (alt, ref, n), m, md = _maps_args(alt, ref), None, None
+    else:
+        alt, ref, m, md = _aligned_args(alt, ref, bin_map, bin_map_dev)
+        n = ref.shape[0]
+    B = alt.shape[0]
+    if B < 1:
+        raise ValueError("alt: at least one map")
+    try:
+        d_lo, d_hi = (0, n) if d_range is None else (int(v) for v in d_range)
+    except (TypeError, ValueError):
+        raise ValueError("d_range: (d_lo, d_hi)") from None
+    bs = alt.stride(0) if B > 1 else max(alt.stride(0), n * n)                     # B = 1: torch may report any stride for the one map
+    dev, null = alt.device, ctypes.c_void_p(0)
+    out = dict(zip(("dist_delta", "dist_abs", "dist_rms", "mse"), _f32_outputs(dev, (B, n), (B, n), (B, n), (B,))))
+    out["dist_corr"] = torch.empty((B, n), dtype=torch.float64, device=dev)
+    out["corr"], out["scc"] = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(2))
+    out["dist_count"] = None if m is None else torch.empty((B, n), dtype=torch.int32, device=dev)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_strata_scores(ctx.handle, _dev_p(alt), bs, _p(ref), B, n, null if m is None else _dev_p(md), null if m is None else _np_p(m),
+                                                d_lo, d_hi, _dev_p(out["dist_delta"]), _dev_p(out["dist_abs"]), _dev_p(out["dist_rms"]), _dev_p(out["dist_corr"]),
+                                                null if m is None else _dev_p(out["dist_count"]), _dev_p(out["mse"]), _dev_p(out["corr"]), _dev_p(out["scc"])),
+          "orca_screen_strata_scores")
+    return out
+
+
 # both strands (orca_screen_merge_strands)
 def screen_merge_strands(ctx, fwd, rev, ref_fwd=None, ref_rev=None, out=None):
     """The '+' strand's maps ``fwd`` [B, n, n] and the '-' strand's ``rev`` [B, n, n] (any batch stride, rows contiguous) merged as genomepredict merges

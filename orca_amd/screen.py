@@ -47,6 +47,12 @@ the reference's, and ``viewpoints=bins`` the signed row alt - ref of chosen bins
 bins, through the same `bin_map` (orca_screen_insulation, orca_screen_viewpoints; `insulation_scores_host`, `viewpoint_scores_host`).  Both are
 1-D tracks per item, so a deletion scan can ask "which deletion fuses the two domains" without ``keep_maps``.
 
+``screen_1m(..., strata=True)`` adds how similar every alt map is to the reference map, by genomic distance: per stratum d - the pairs
+(i, i + d) - the mean, mean absolute and root-mean-square difference and the fp64 correlation, and per map the mean squared difference, the
+Pearson correlation and HiCRep's stratum-adjusted correlation, bin with bin and, with ``aligned=True``, through `bin_map`
+(orca_screen_strata_scores; `strata_scores_host`).  A uniform shift of a distance band and a re-patterning inside it, which a mean of
+|alt - ref| cannot tell apart, separate there.
+
 Every score above compares an item with the unedited window.  `epistasis_1m` asks whether the effect of an `EditSet` is the sum of its members'
 effects: it screens the distinct members and the sets in one pass, keeps the members' maps in a device bank, and scores per set the residual
 r = (alt_set - ref) - sum_m (alt_m - ref), every pixel in fp64 (orca_screen_epistasis_scores, orca_screen_epistasis_region_scores;
@@ -1018,6 +1024,90 @@ def viewpoint_scores_host(maps, ref_map, views, bin_map=None):
     return delta, at
 
 
+STRATA_FIELDS = ("dist_delta", "dist_abs", "dist_rms", "dist_corr", "mse", "corr", "scc")
+
+
+def check_strata(strata, n):
+    """``strata`` as the stratum range (d_lo, d_hi) of the per-map scores on a map of n bins: True stands for every stratum, (0, n); a pair of
+    ints must satisfy 0 <= d_lo < d_hi <= n.  Anything else is a ValueError."""
+    if strata is True:
+        return 0, n
+    try:
+        lo, hi = strata
+        if isinstance(lo, (bool, np.bool_)) or isinstance(hi, (bool, np.bool_)) or int(lo) != lo or int(hi) != hi:
+            raise ValueError
+        lo, hi = int(lo), int(hi)
+    except (TypeError, ValueError):
+        raise ValueError("strata: True (every stratum) or a pair (d_lo, d_hi) of ints") from None
+    if not 0 <= lo < hi <= n:
+        raise ValueError(f"strata ({lo}, {hi}): 0 <= d_lo < d_hi <= {n} on a map of {n} bins")
+    return lo, hi
+
+
+def strata_scores_host(maps, ref_map, bin_map=None, d_range=None):
+    """The distance-stratified scores of `ScreenResult` from alt maps [E, n, n] and the reference map [n, n] (fp64 host restatement of
+    orca_screen_strata_scores): a dict of fp64 arrays ``dist_delta``, ``dist_abs``, ``dist_rms``, ``dist_corr`` [E, n], ``mse``, ``corr``, ``scc``
+    [E], and ``dist_count`` [E, n] int32 (also without ``bin_map``: n - d then).  Stratum d is the pairs (i, i + d); x = the alt pixel, y =
+    ref[i, i + d] or, with ``bin_map`` ([E, n], or one [n] for all), ref[map i, map (i + d)] over the pairs whose two bins are mapped - the stratum
+    is the ALT distance, an unmapped pair is never read.  The same two passes as the kernel, each for i ascending from 0.0: the means mx_d, my_d
+    (one division by c_d), then X_d = sum (x - mx_d)^2, Y_d = sum (y - my_d)^2, C_d = sum (x - mx_d)(y - my_d) and sum dl, sum |dl|, sum dl^2 of
+    dl = x - y.  dist_delta / dist_abs / dist_rms = the mean of dl, of |dl|, and the root of the mean of dl^2; dist_corr = C_d / sqrt(X_d Y_d), NaN
+    when c_d < 2, X_d == 0 or Y_d == 0; all NaN where c_d = 0.  Over the strata ``d_range`` = (d_lo, d_hi) (all by default), serially for d
+    ascending, c = sum c_d: mse = sum sum dl^2 / c; scc = sum C_d / sum sqrt(X_d Y_d) (HiCRep's stratum-adjusted correlation on raw values), NaN
+    when the denominator is 0; corr = the Pearson correlation of all those pairs from the pooled sums, mx = (sum c_d mx_d) / c,
+    X = sum [X_d + c_d (mx_d - mx)^2], C = sum [C_d + c_d (mx_d - mx)(my_d - my)], NaN when X or Y is 0 or c < 2; all three NaN when c = 0."""
+    a, r = np.asarray(maps, dtype=np.float64), np.asarray(ref_map, dtype=np.float64)
+    E, n = a.shape[0], r.shape[0]
+    if a.shape != (E, n, n) or r.shape != (n, n):
+        raise ValueError("maps [E, n, n], ref_map [n, n]")
+    lo, hi = check_strata(True if d_range is None else d_range, n)
+    bm = None if bin_map is None else _bin_maps(bin_map, E, n)
+
+    def pairs(i):                                        # row i's pairs (i, i + d), d = 0 .. n - 1 - i: x [E, w], y [E, w], whether the pair counts
+        x = a[:, i, i:]
+        if bm is None:
+            return x, np.broadcast_to(r[i, i:], x.shape), np.ones(x.shape, dtype=bool)
+        mi, mj = bm[:, i: i + 1], bm[:, i:]
+        ok = (mi >= 0) & (mj >= 0)
+        return x, r[np.where(ok, mi, 0), np.where(ok, mj, 0)], ok
+    cnt = np.zeros((E, n), dtype=np.int64)
+    sx, sy = np.zeros((E, n)), np.zeros((E, n))
+    for i in range(n):                                   # adding 0.0 for a pair that does not count leaves a sum as it is
+        x, y, ok = pairs(i)
+        sx[:, : n - i] += np.where(ok, x, 0.0)
+        sy[:, : n - i] += np.where(ok, y, 0.0)
+        cnt[:, : n - i] += ok
+    X, Y, C, sd, sa, sq = (np.zeros((E, n)) for _ in range(6))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        c = cnt.astype(np.float64)
+        mx, my = sx / c, sy / c
+        for i in range(n):
+            x, y, ok = pairs(i)
+            ex, ey, dl = x - mx[:, : n - i], y - my[:, : n - i], x - y
+            for acc, v in ((X, ex * ex), (Y, ey * ey), (C, ex * ey), (sd, dl), (sa, np.abs(dl)), (sq, dl * dl)):
+                acc[:, : n - i] += np.where(ok, v, 0.0)
+        out = {"dist_delta": sd / c, "dist_abs": sa / c, "dist_rms": np.sqrt(sq / c), "dist_count": cnt.astype(np.int32)}
+        out["dist_corr"] = np.where((cnt < 2) | (X == 0.0) | (Y == 0.0), np.nan, C / np.sqrt(X * Y))
+        some = cnt > 0                                   # empty strata are skipped
+        tot = np.zeros(E, dtype=np.int64)
+        q, num, den, wx, wy = (np.zeros(E) for _ in range(5))
+        for d in range(lo, hi):
+            tot += cnt[:, d]
+            for acc, v in ((q, sq[:, d]), (num, C[:, d]), (den, np.sqrt(X[:, d] * Y[:, d])), (wx, c[:, d] * mx[:, d]), (wy, c[:, d] * my[:, d])):
+                acc += np.where(some[:, d], v, 0.0)
+        t = tot.astype(np.float64)
+        pmx, pmy = wx / t, wy / t
+        PX, PY, PC = (np.zeros(E) for _ in range(3))
+        for d in range(lo, hi):
+            ex, ey = mx[:, d] - pmx, my[:, d] - pmy
+            for acc, v in ((PX, X[:, d] + c[:, d] * (ex * ex)), (PY, Y[:, d] + c[:, d] * (ey * ey)), (PC, C[:, d] + c[:, d] * (ex * ey))):
+                acc += np.where(some[:, d], v, 0.0)
+        out["mse"] = q / t
+        out["scc"] = np.where((tot == 0) | (den == 0.0), np.nan, num / den)
+        out["corr"] = np.where((tot < 2) | (PX == 0.0) | (PY == 0.0), np.nan, PC / np.sqrt(PX * PY))
+    return out
+
+
 def merge_strands_host(plus, minus, ref_plus=None, ref_minus=None):
     """The merged maps of ``strands="both"`` (fp64 host restatement of orca_screen_merge_strands): ``plus``, ``minus`` [E, n, n] (or [n, n]) the two
     strands' maps, ``minus`` in the '-' strand's own orientation.  (merged, gap) with merged = 0.5 plus + 0.5 flip(minus), flip reversing both bin
@@ -1160,8 +1250,27 @@ class ScreenResult:
       aligned_viewpoint  [E, V, n]    with ``aligned=True``: the viewpoint is a REFERENCE bin.  R = the alt bins that stand for it, c = |R|:
                                       (sum_{i in R} alt map[i, j]) / c - ref_map[view, map j], indexed by ALT column j; NaN when c = 0 (the viewpoint was
                                       deleted) or column j stands for nothing
+    With ``strata=`` (None otherwise) - how similar the alt map is to ``ref_map``, by genomic distance.  Stratum d is the pairs (i, i + d) of the upper
+    triangle, x = the alt pixel, y = the reference pixel, dl = x - y, all in fp64; mx_d, my_d the stratum's means, X_d, Y_d, C_d its centred sums
+    of squares and of products (two passes), c_d = n - d its pairs:
+      strata_range       (d_lo, d_hi) the strata the three per-map scores run over
+      dist_delta         [E, n]       the mean of dl over stratum d: the change of the distance-decay curve (a deletion lifts whole bands)
+      dist_abs           [E, n]       the mean of |dl|
+      dist_rms           [E, n]       sqrt(mean of dl^2)
+      dist_corr          [E, n] f64   C_d / sqrt(X_d Y_d), the Pearson correlation within the stratum: a uniform shift of the band leaves it at 1, a
+                                      re-patterning lowers it.  NaN when c_d < 2 or either side is constant there.  fp64: 1 - r of a small edit survives
+      mse                [E]          sum_d sum dl^2 / c over d_lo <= d < d_hi, c = sum_d c_d
+      corr               [E] f64      the Pearson correlation over all pairs of those strata (from the pooled centred sums)
+      scc                [E] f64      sum_d C_d / sum_d sqrt(X_d Y_d): HiCRep's stratum-adjusted correlation (its weights c_d sqrt(var_x var_y)) on raw
+                                      values - no smoothing, no rank transform; read an effect as 1 - scc
+    and with ``aligned=True`` the same over the pairs whose two alt bins stand for reference bins, y = ref_map[map i, map (i + d)] (the stratum is
+    the ALT distance; where the bin map is the identity they are the fields above bit for bit):
+      aligned_dist_delta, aligned_dist_abs, aligned_dist_rms, aligned_dist_corr [E, n];  aligned_mse, aligned_corr, aligned_scc [E]
+      aligned_dist_count [E, n] int32 c_d, the mapped pairs of stratum d; every per-stratum value is NaN where it is 0
+    A NaN pixel at a pair of stratum d makes that stratum's values NaN and, if d_lo <= d < d_hi, the three per-map scores; nothing else.
     `scores_host` computes the three map scores from maps on the host, `region_scores_host` the two region scores, `aligned_scores_host` and
-    `aligned_region_scores_host` the aligned ones, `insulation_scores_host` and `viewpoint_scores_host` the tracks."""
+    `aligned_region_scores_host` the aligned ones, `insulation_scores_host` and `viewpoint_scores_host` the tracks, `strata_scores_host` the
+    distance-stratified scores."""
     ref_map: torch.Tensor
     ref_1d: Optional[torch.Tensor]
     delta_profile: torch.Tensor
@@ -1190,6 +1299,22 @@ class ScreenResult:
     viewpoint_bins: Optional[torch.Tensor] = None
     delta_viewpoint: Optional[torch.Tensor] = None
     aligned_viewpoint: Optional[torch.Tensor] = None
+    strata_range: Optional[tuple] = None
+    dist_delta: Optional[torch.Tensor] = None
+    dist_abs: Optional[torch.Tensor] = None
+    dist_rms: Optional[torch.Tensor] = None
+    dist_corr: Optional[torch.Tensor] = None
+    mse: Optional[torch.Tensor] = None
+    corr: Optional[torch.Tensor] = None
+    scc: Optional[torch.Tensor] = None
+    aligned_dist_delta: Optional[torch.Tensor] = None
+    aligned_dist_abs: Optional[torch.Tensor] = None
+    aligned_dist_rms: Optional[torch.Tensor] = None
+    aligned_dist_corr: Optional[torch.Tensor] = None
+    aligned_dist_count: Optional[torch.Tensor] = None
+    aligned_mse: Optional[torch.Tensor] = None
+    aligned_corr: Optional[torch.Tensor] = None
+    aligned_scc: Optional[torch.Tensor] = None
 
 
 # ---- the screen -----------------------------------------------------------------------------------------------------------------------------
@@ -1357,7 +1482,7 @@ class _Screen:
 
 
 def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regions=None, flank=None, aligned=False, flank_bp=None, strands="+",
-              insulation=None, viewpoints=None):
+              insulation=None, viewpoints=None, strata=None):
     """Score ``edits`` (a list of `Edit` and `EditSet`, one row of every result tensor each) of one window with the 1 Mb model: a `ScreenResult`.
 
     ``model``: an ``H1esc_1M`` / ``Hff_1M`` container or a bare ``orca_modules.Net``.  ``window``: the window's base codes, a [L] uint8 tensor on
@@ -1405,11 +1530,21 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
     `ScreenResult.delta_viewpoint` and, with ``aligned=True``, ``aligned_viewpoint`` (orca_screen_viewpoints): the signed row alt - ref of a bin, a
     virtual 4C; in the aligned form the viewpoint is a REFERENCE bin, followed to wherever the item moved it.  Both are taken from the batch's
     maps whichever route made them, with ``strands="both"`` from the merged maps against the merged ``ref_map``.  With both None nothing more is
-    launched and every other field is what it was.  ``stats`` gains ``insulation_widths`` and ``viewpoints``: their numbers (0 when absent)."""
-    return _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, aligned, flank_bp, strands, insulation, viewpoints)
+    launched and every other field is what it was.  ``stats`` gains ``insulation_widths`` and ``viewpoints``: their numbers (0 when absent).
+
+    ``strata``: True, or a pair (d_lo, d_hi) with 0 <= d_lo < d_hi <= n (`check_strata`), for the similarity of every alt map to ``ref_map`` by
+    genomic distance (orca_screen_strata_scores): per stratum d - the pairs (i, i + d) - `ScreenResult.dist_delta`, ``dist_abs``, ``dist_rms`` and the
+    fp64 correlation ``dist_corr``; per map, over the strata d_lo <= d < d_hi (all of them with True), ``mse``, the Pearson ``corr`` and the
+    stratum-adjusted correlation ``scc`` (HiCRep's), both fp64, so that 1 - scc of a small edit is not lost; with ``aligned=True`` also the
+    ``aligned_dist_*`` fields, ``aligned_mse``, ``aligned_corr`` and ``aligned_scc`` through `bin_map` (a second call).  The means of |alt - ref| above
+    cannot tell a uniform shift of a distance band (``dist_delta`` moves, ``dist_corr`` stays 1) from a re-patterning inside it (``dist_corr`` drops).
+    Taken from the batch's final maps whichever route made them, with ``strands="both"`` from the merged maps against the merged ``ref_map``.  With
+    None (or False) nothing more is launched and every other field is what it was.  ``stats`` gains ``strata``: the number of strata the per-map
+    scores run over (0 when absent)."""
+    return _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, aligned, flank_bp, strands, insulation, viewpoints, strata=strata)
 
 
-def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, aligned, flank_bp, strands, insulation, viewpoints, hook=None):
+def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, aligned, flank_bp, strands, insulation, viewpoints, hook=None, strata=None):
     """The body of `screen_1m` (its arguments, its result).  ``hook``: called as ``hook(res, i0, i1, maps)`` at the end of every batch, on every
     route, with the `ScreenResult` under construction (``res.ref_map`` is final) and the FINAL maps [i1 - i0, n, n] of items [i0, i1) - after the
     strand merge and after any range fallback; the buffer is the batch's own, so the hook reads it before it returns.  Without a hook nothing
@@ -1436,11 +1571,13 @@ def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, a
     rects = None if regions is None else check_regions(regions, win.numel() // 4000)
     widths = None if insulation is None else check_insulation(insulation, win.numel() // 4000)
     views = None if viewpoints is None else check_viewpoints(viewpoints, win.numel() // 4000)
+    drange = None if strata is None or strata is False else check_strata(strata, win.numel() // 4000)
     st = {"route": None, "two_part_batches": 0, "whole_window_batches": 0, "range_fallback_batches": 0, "range_fallback_reference": False,
           "front_runs": 0, "front_bases": 0, "edits": len(edits), "set_items": sum(isinstance(e, EditSet) for e in edits), "segments": 0,
           "indel_items": sum(changes_length(e) for e in edits), "take_rows": 0, "cache_phases": 0, "aligned_items": 0,
           "strands": strands, "reverse_two_part_items": 0, "reverse_whole_items": 0,
-          "insulation_widths": 0 if widths is None else len(widths), "viewpoints": 0 if views is None else len(views)}
+          "insulation_widths": 0 if widths is None else len(widths), "viewpoints": 0 if views is None else len(views),
+          "strata": 0 if drange is None else drange[1] - drange[0]}
     fl = _flank_codes(window, flank, win, flank_bp) if (flank is not None or st["indel_items"]) else None
     sc = _Screen(net, win, st, fl if st["indel_items"] else None)
     E, n, dev = len(edits), sc.n, sc.dev
@@ -1523,6 +1660,14 @@ def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, a
             res.delta_viewpoint = torch.zeros((E, len(views), n), dtype=torch.float32, device=dev)
             if aligned:
                 res.aligned_viewpoint = torch.zeros((E, len(views), n), dtype=torch.float32, device=dev)
+        if drange is not None:
+            res.strata_range = drange
+            for pre in ("", "aligned_") if aligned else ("",):
+                for name in STRATA_FIELDS:
+                    setattr(res, pre + name, torch.zeros((E, n) if name.startswith("dist_") else (E,), device=dev,
+                                                         dtype=torch.float64 if name in ("dist_corr", "corr", "scc") else torch.float32))
+            if aligned:
+                res.aligned_dist_count = torch.zeros((E, n), dtype=torch.int32, device=dev)
         def whole(chunk):                                # a batch on the whole-window route: the '+' strand, or the pair of strands
             if not both:
                 return sc.whole(chunk)
@@ -1578,6 +1723,14 @@ def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, a
                 res.delta_viewpoint[i0:i1] = dl
                 if aligned:
                     res.aligned_viewpoint[i0:i1] = al
+            if drange is not None:
+                got = engine.screen_strata_scores(sc.ctx, maps, ref_map, None, drange)
+                for name in STRATA_FIELDS:
+                    getattr(res, name)[i0:i1] = got[name]
+                if aligned:
+                    got = engine.screen_strata_scores(sc.ctx, maps, ref_map, bmaps[i0:i1], drange, res.bin_map[i0:i1])
+                    for name in STRATA_FIELDS + ("dist_count",):
+                        getattr(res, "aligned_" + name)[i0:i1] = got[name]
             if h is not None:
                 torch.sub(h, ref_1d[None], out=res.delta_1d[i0:i1])
             if keep_maps:

@@ -31,6 +31,10 @@ Tracks, into profiles/screen_1m_tracks.json:
   --tracks       the 3 250-edit workload at B = 64 through screen_1m with insulation=(5, 10, 25), viewpoints=[125] and without, alternated in the same
                  run; with --aligned also aligned=True with and without the tracks: what the two track kernels add, set beside what aligned=True adds
 
+Distance strata, into profiles/screen_1m_strata.json:
+  --strata       the 3 250-edit workload at B = 64 through screen_1m with strata=True and without, and both again with aligned=True, alternated in
+                 the same run, best of three: what orca_screen_strata_scores adds, set beside what aligned=True adds
+
 Non-additivity, into profiles/screen_1m_epistasis.json:
   --epistasis NA NB  the NA x NB pairs of 4 kb mask tiles (NA from base 100 000, NB from base 600 000) at B = 64 through screen.epistasis_1m, and
                  through today's route - screen_1m on the singles and on the pairs with keep_maps=True, then the residual in torch, in fp32 -
@@ -207,6 +211,31 @@ def time_tracks(a, model, win, edits, dev):
     return rep
 
 
+def time_strata(a, model, win, edits, dev):
+    """The --strata workload: screen_1m on the same edits with and without strata=True, plain and with aligned=True, alternated, at B = 64, best of
+    max(--reps, 3).  The overheads are over the plain screen of the same run."""
+    B, reps = 64, max(a.reps, 3)
+    rep = {"device": torch.cuda.get_device_name(dev), "edits": len(edits), "batch": B, "reps": reps}
+    runs = {"plain": {}, "strata": {"strata": True}, "aligned": {"aligned": True}, "aligned_strata": {"aligned": True, "strata": True}}
+    st = {}
+    for kw in runs.values():                                                                     # warm-up
+        S.screen_1m(model, win, edits[:B], batch=B, stats=st, **kw)
+    rep["route"] = st["route"]
+    t = {k: [] for k in runs}
+    for _ in range(reps):
+        for k, kw in runs.items():
+            t[k].append(timed(lambda: S.screen_1m(model, win, edits, batch=B, **kw))[0])
+    for k in runs:
+        rep[f"{k}_s"] = [round(x, 3) for x in t[k]]
+        rep[f"{k}_edits_per_s"] = round(len(edits) / min(t[k]), 1)
+    plain = min(t["plain"])
+    rep["strata_over_plain"] = round(min(t["strata"]) / plain, 4)
+    rep["aligned_over_plain"] = round(min(t["aligned"]) / plain, 4)
+    rep["aligned_strata_over_aligned"] = round(min(t["aligned_strata"]) / min(t["aligned"]), 4)
+    rep["plain_spread"] = round(max(t["plain"]) / plain, 4)
+    return rep
+
+
 def naive_both(model, win, edits, batch, keep_maps=False):
     """`naive` on both strands: every batch's edited windows through Net's Encoder and Decoder_1m forwards and reverse-complemented, merged."""
     sc = S._Screen(model.net, win, {})
@@ -309,6 +338,7 @@ def main():
     ap.add_argument("--indels", type=int, default=0, help="N: time N random 1-50-base indels at B = 64")
     ap.add_argument("--aligned", action="store_true", help="time the 3 250-edit workload with aligned=True against aligned=False")
     ap.add_argument("--tracks", action="store_true", help="time the 3 250-edit workload at B = 64 with insulation and viewpoint tracks against without")
+    ap.add_argument("--strata", action="store_true", help="time the 3 250-edit workload at B = 64 with strata=True against without, plain and with aligned=True")
     ap.add_argument("--strands", default="+", choices=("+", "both"), help="both: time the 3 250-edit workload on both strands at B = 64")
     ap.add_argument("--epistasis", type=int, nargs=2, metavar=("NA", "NB"), help="time the NA x NB mask-tile pairs through epistasis_1m against two screen_1m "
                     "calls with keep_maps=True plus fp32 arithmetic in torch")
@@ -354,6 +384,17 @@ def main():
                 json.dump(rep, f, indent=1)
         return
     edits = S.saturation_edits(c, 499_500, 500_500) + S.tile_edits("mask", 4000, 4000, 0, L)
+    if a.strata:
+        rep = {"workload": f"H1esc_1M synthetic, 1 Mb window, {len(edits)} edits (saturation SNVs of 1 kb + 250 4 kb mask tiles); screen_1m with "
+                           "strata=True against without, each also with aligned=True, alternated (every call includes its reference)", "commit": a.commit}
+        rep.update(time_strata(a, model, win, edits, dev))
+        print(json.dumps(rep))
+        out = a.out if a.out != ap.get_default("out") else os.path.join(os.path.dirname(a.out), "screen_1m_strata.json")
+        if out:
+            os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+            with open(out, "w") as f:
+                json.dump(rep, f, indent=1)
+        return
     if a.tracks:
         rep = {"workload": f"H1esc_1M synthetic, 1 Mb window, {len(edits)} edits (saturation SNVs of 1 kb + 250 4 kb mask tiles); screen_1m with "
                            "insulation=(5, 10, 25), viewpoints=[125] against without, alternated (every call includes its reference)", "commit": a.commit}
