@@ -424,6 +424,35 @@ int orca_screen_strata_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, c
                               const int32_t* bin_map_host, int d_lo, int d_hi, float* dist_delta, float* dist_abs, float* dist_rms, double* dist_corr,
                               int32_t* dist_count, float* mse, double* corr, double* scc);
 
+/* Loops (screen.screen_1m(..., loops=)): dot calls on B maps m = maps[b * map_bs + i * n + j] (B >= 1, 1 <= n <= 256, map_bs >= n * n) of log observed /
+ * expected, where a focal peak's enrichment over its local background is a difference of means.  Integers 0 <= p < w <= 16, 1 <= r <= 16,
+ * d_min >= 2 w + 1, 1 <= K <= 4096 and an fp32 threshold T (not NaN).
+ *   eligible      pixel (i, j) with w <= i, j <= n - 1 - w and j - i >= d_min: every set below then lies inside the map and strictly above the diagonal;
+ *                 the smallest map with an eligible pixel has n = 4 w + 2
+ *   the sets      (HiCCUPS', Rao et al. 2014) of offsets (a, b) from (i, j), a along rows:
+ *                 P  (peak)        |a| <= p and |b| <= p
+ *                 D  (donut)       |a| <= w and |b| <= w, not in P, a != 0 and b != 0
+ *                 LL (lower left)  1 <= a <= w and -w <= b <= -1, not in P: towards the diagonal
+ *                 H                |a| <= 1 and p < |b| <= w
+ *                 V                |b| <= 1 and p < |a| <= w
+ *   enrichment    e(i, j) = mean P - max(mean D, mean LL, mean H, mean V).  Each set is summed on its own in fp64 (row by row over the window; no running
+ *                 sums from pixel to pixel), one division by its count, no multiplication anywhere, the fp64 result rounded to fp32 once.  The sets cover
+ *                 the window, so a NaN anywhere in the (2 w + 1)^2 window makes e NaN; e is NaN at every ineligible pixel; nothing on or below the
+ *                 diagonal is read
+ *   dot           (i, j) with e not NaN, e >= T, and for every pixel (i', j') within Chebyshev distance r whose e' is not NaN: e > e' where (i', j')
+ *                 precedes (i, j) in row-major order, e >= e' where it follows.  fp32 comparisons; a NaN neighbour neither wins nor loses.  A constant
+ *                 map with T = 0 has exactly one dot, (w, w + d_min)
+ * orca_screen_dot_calls writes e_map[B][n][n] (caller-owned: the enrichment map, NaN where ineligible - the second launch reads it), count[B] (int32, ALL
+ * dots of the map), and the first K dots in row-major order as ij[B][K][2] (int32, (i, j)) and enrich[B][K] (their e); the slots behind min(count, K) hold
+ * -1 / NaN.  orca_screen_dot_enrichment writes out[B][Q] = e at the listed pixels[B][Q][2] (int32, 1 <= Q <= 4096; a device copy and a host copy,
+ * coordinates outside -1 .. n - 1 refused): NaN for (-1, -1) and any other ineligible pixel, and otherwise the bits of e_map - one device function
+ * computes both.  No atomics: a map's outputs are bit for bit the same whatever B, its place in the batch and the batch stride.  Anything else is
+ * ORCA_EINVAL before any launch. */
+int orca_screen_dot_calls(orca_ctx* ctx, const float* maps, int64_t map_bs, int B, int n, int p, int w, int d_min, int r, float T, int K, float* e_map,
+                          int32_t* count, int32_t* ij, float* enrich);
+int orca_screen_dot_enrichment(orca_ctx* ctx, const float* maps, int64_t map_bs, int B, int n, int p, int w, int d_min, const int32_t* pixels,
+                               const int32_t* pixels_host, int Q, float* out);
+
 /* Number of 4 kb bins Encoder emits for an L-bp input (floor through the
  * 4,4,5,5,5,2 pooling chain). */
 int64_t orca_encoder_num_bins(int64_t L);

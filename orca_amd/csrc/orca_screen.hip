@@ -327,6 +327,38 @@ extern "C" int orca_screen_strata_scores(orca_ctx* ctx, const float* alt, int64_
                 dist_abs, dist_rms, dist_corr, dist_count, mse, corr, scc);
 }
 
+// ---- loops: dot calls and the enrichment at listed pixels ---------------------------------------------------------------------------------------------------------
+static int check_dot_params(const char* what, int B, int n, int64_t map_bs, int p, int w, int d_min) {
+  if (B < 1 || n < 1 || n > SCREEN_ALIGNED_MAX_BINS || map_bs < (int64_t)n * n)
+    return fail(ORCA_EINVAL, "%s: %d maps (>= 1) of %d bins (1..%d), batch stride %ld (>= n * n)", what, B, n, SCREEN_ALIGNED_MAX_BINS, (long)map_bs);
+  if (p < 0 || p >= w || w > SCREEN_DOT_MAX_W) return fail(ORCA_EINVAL, "%s: peak half-width p = %d, window half-width w = %d (0 <= p < w <= %d)", what, p, w, SCREEN_DOT_MAX_W);
+  if (d_min < 2 * w + 1) return fail(ORCA_EINVAL, "%s: d_min = %d (>= 2 w + 1 = %d: the windows stay above the diagonal)", what, d_min, 2 * w + 1);
+  return ORCA_OK;
+}
+
+extern "C" int orca_screen_dot_calls(orca_ctx* ctx, const float* maps, int64_t map_bs, int B, int n, int p, int w, int d_min, int r, float T, int K, float* e_map,
+                                     int32_t* count, int32_t* ij, float* enrich) {
+  if (!ctx || !maps || !e_map || !count || !ij || !enrich) return fail(ORCA_EINVAL, "orca_screen_dot_calls: NULL argument");
+  ORCA_TRY(check_dot_params("orca_screen_dot_calls", B, n, map_bs, p, w, d_min));
+  if (r < 1 || r > SCREEN_DOT_MAX_R) return fail(ORCA_EINVAL, "orca_screen_dot_calls: local-maximum radius r = %d (1..%d)", r, SCREEN_DOT_MAX_R);
+  if (K < 1 || K > SCREEN_DOT_MAX_CALLS) return fail(ORCA_EINVAL, "orca_screen_dot_calls: K = %d listed calls per map (1..%d)", K, SCREEN_DOT_MAX_CALLS);
+  if (T != T) return fail(ORCA_EINVAL, "orca_screen_dot_calls: the threshold T is NaN");
+  ORCA_TRY(launch(ctx, "screen_dot_enrich_map_kernel", screen_dot_enrich_map_kernel, dim3((unsigned)B, (unsigned)n), 256, maps, (long)map_bs, n, p, w, d_min, e_map));
+  return launch(ctx, "screen_dot_calls_kernel", screen_dot_calls_kernel, dim3((unsigned)B), 256, (const float*)e_map, n, w, d_min, r, T, K, count, ij, enrich);
+}
+
+extern "C" int orca_screen_dot_enrichment(orca_ctx* ctx, const float* maps, int64_t map_bs, int B, int n, int p, int w, int d_min, const int32_t* pixels,
+                                          const int32_t* pixels_host, int Q, float* out) {
+  if (!ctx || !maps || !pixels || !pixels_host || !out) return fail(ORCA_EINVAL, "orca_screen_dot_enrichment: NULL argument");
+  ORCA_TRY(check_dot_params("orca_screen_dot_enrichment", B, n, map_bs, p, w, d_min));
+  if (Q < 1 || Q > SCREEN_DOT_MAX_CALLS) return fail(ORCA_EINVAL, "orca_screen_dot_enrichment: Q = %d pixels per map (1..%d)", Q, SCREEN_DOT_MAX_CALLS);
+  for (size_t k = 0; k < (size_t)B * Q * 2; ++k)
+    if (pixels_host[k] < -1 || pixels_host[k] >= n)
+      return fail(ORCA_EINVAL, "orca_screen_dot_enrichment: pixel %ld of map %ld has coordinate %d, outside -1 .. %d", (long)(k / 2 % Q), (long)(k / 2 / Q), pixels_host[k], n - 1);
+  return launch(ctx, "screen_dot_enrichment_kernel", screen_dot_enrichment_kernel, dim3((unsigned)B, (unsigned)((Q + 255) / 256)), 256, maps, (long)map_bs, n, p, w, d_min,
+                pixels, Q, out);
+}
+
 // ---- both strands --------------------------------------------------------------------------------------------------------------------------------------------
 extern "C" int orca_screen_merge_strands(orca_ctx* ctx, const float* fwd, int64_t fwd_bs, const float* rev, int64_t rev_bs, const float* ref_fwd, const float* ref_rev,
                                          int B, int n, float* out, int64_t out_bs, float* gap) {

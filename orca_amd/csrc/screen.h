@@ -620,6 +620,150 @@ static __global__ void __launch_bounds__(256) screen_strata_scores_kernel(const 
   corr[b] = (c < 2 || X == 0.0 || Y == 0.0) ? dnan : C / sqrt(X * Y);
 }
 
+// ---- loops (screen.screen_1m(..., loops=)): dot calls per map, HiCCUPS' neighbourhoods on the model's log observed / expected ---------------------------
+// include/orca_hip.h (orca_screen_dot_calls) has the definitions: the eligible pixels, the five sets P, D, LL, H, V of offsets (a, b) with |a|, |b| <= w,
+// the enrichment e = mean P - max(mean D, mean LL, mean H, mean V) and what makes a pixel a dot.  screen_dot_enrich is the one place e is computed: `m`
+// points at the pixel, `ld` is the row stride of the image it sits in (the map itself, or a row band of it in LDS).  Each set has its own fp64 sum, taken
+// over the window row by row (a ascending, then b ascending), then one division by the set's count; no product anywhere, so nothing for the compiler to
+// contract, and the bits do not depend on where the image lies.  The five sets cover the whole window, so a NaN anywhere in it makes e NaN.
+#define SCREEN_DOT_MAX_W 16
+#define SCREEN_DOT_MAX_R 16
+#define SCREEN_DOT_MAX_CALLS 4096
+
+static __device__ __forceinline__ bool screen_dot_eligible(int i, int j, int n, int w, int d_min) { return i >= w && j <= n - 1 - w && j - i >= d_min; }
+
+static __device__ __forceinline__ float screen_dot_enrich(const float* m, int ld, int p, int w) {
+  double sP = 0.0, sD = 0.0, sL = 0.0, sH = 0.0, sV = 0.0;
+  int cP = 0, cD = 0, cL = 0, cH = 0, cV = 0;
+  for (int a = -w; a <= w; ++a) {
+    const int aa = a < 0 ? -a : a;
+    const float* row = m + a * ld;
+    for (int b = -w; b <= w; ++b) {
+      const int ab = b < 0 ? -b : b;
+      const double x = (double)row[b];
+      if (aa <= p && ab <= p) {
+        sP += x; ++cP;
+      } else {
+        if (a != 0 && b != 0) { sD += x; ++cD; }
+        if (a >= 1 && b <= -1) { sL += x; ++cL; }
+      }
+      if (aa <= 1 && ab > p) { sH += x; ++cH; }
+      if (ab <= 1 && aa > p) { sV += x; ++cV; }
+    }
+  }
+  const double mP = sP / (double)cP, mD = sD / (double)cD, mL = sL / (double)cL, mH = sH / (double)cH, mV = sV / (double)cV;
+  double bg = mD;
+  if (mL > bg) bg = mL;
+  if (mH > bg) bg = mH;
+  if (mV > bg) bg = mV;
+  const double e = mP - bg;
+  return (mP != mP || mD != mD || mL != mL || mH != mH || mV != mV) ? __int_as_float(0x7fc00000) : (float)e;
+}
+
+// The enrichment map e[b][i][j] of B maps: NaN at every ineligible pixel.  One workgroup of 256 threads per (map, row i), thread t owns column j = t.
+// The eligible pixels of row i are columns i + d_min .. n - 1 - w and their windows lie in rows i - w .. i + w, columns c0 = i + d_min - w .. n - 1:
+// strictly above the diagonal (d_min >= 2 w + 1) and all that is read.  That band goes to LDS once - (2 w + 1) rows of 256 floats, row r, column c at
+// s_band[r][c - c0], filled with consecutive lanes on consecutive addresses - and every window is summed from there: at a fixed (a, b) the lanes read
+// consecutive LDS words, no bank conflict.  A row without an eligible pixel stages nothing.
+static __global__ void __launch_bounds__(256) screen_dot_enrich_map_kernel(const float* __restrict__ maps, long map_bs, int n, int p, int w, int d_min,
+                                                                           float* __restrict__ e_map) {
+  __shared__ float s_band[2 * SCREEN_DOT_MAX_W + 1][SCREEN_ALIGNED_MAX_BINS];
+  const int b = blockIdx.x, i = blockIdx.y, j = threadIdx.x;
+  n = n > SCREEN_ALIGNED_MAX_BINS ? SCREEN_ALIGNED_MAX_BINS : n;
+  w = w > SCREEN_DOT_MAX_W ? SCREEN_DOT_MAX_W : (w < 1 ? 1 : w);
+  p = p >= w ? w - 1 : (p < 0 ? 0 : p);
+  d_min = d_min < 2 * w + 1 ? 2 * w + 1 : d_min;
+  if (i >= n) return;
+  const float qnan = __int_as_float(0x7fc00000);
+  float* out = e_map + ((long)b * n + i) * n;
+  const bool row_ok = i >= w && i <= n - 1 - w - d_min;          // wave-uniform: some column of row i is eligible
+  if (!row_ok) {
+    if (j < n) out[j] = qnan;
+    return;
+  }
+  const int c0 = i + d_min - w, nc = n - c0, rows = 2 * w + 1;   // c0 >= w + 1 + i > i + w; 2 w + 1 <= nc <= 256
+  const float* src = maps + (long)b * map_bs + (long)(i - w) * n + c0;
+  for (int r = 0; r < rows; ++r)
+    for (int c = j; c < nc; c += 256) s_band[r][c] = src[(long)r * n + c];
+  __syncthreads();
+  if (j >= n) return;
+  out[j] = screen_dot_eligible(i, j, n, w, d_min) ? screen_dot_enrich(&s_band[w][j - c0], SCREEN_ALIGNED_MAX_BINS, p, w) : qnan;
+}
+
+// e at Q listed pixels (i, j) of each map, NaN for (-1, -1) and every other ineligible pixel: one thread per pixel, the windows read from the map itself
+// with the device function of the kernel above - the same sums in the same order, the same bits.
+static __global__ void __launch_bounds__(256) screen_dot_enrichment_kernel(const float* __restrict__ maps, long map_bs, int n, int p, int w, int d_min,
+                                                                           const int* __restrict__ pixels, int Q, float* __restrict__ out) {
+  const int b = blockIdx.x, q = blockIdx.y * 256 + threadIdx.x;
+  n = n > SCREEN_ALIGNED_MAX_BINS ? SCREEN_ALIGNED_MAX_BINS : n;
+  w = w > SCREEN_DOT_MAX_W ? SCREEN_DOT_MAX_W : (w < 1 ? 1 : w);
+  p = p >= w ? w - 1 : (p < 0 ? 0 : p);
+  d_min = d_min < 2 * w + 1 ? 2 * w + 1 : d_min;
+  if (q >= Q) return;
+  const long at = (long)b * Q + q;
+  const int i = pixels[2 * at], j = pixels[2 * at + 1];
+  const bool ok = i >= 0 && j >= 0 && j < n && screen_dot_eligible(i, j, n, w, d_min);
+  out[at] = ok ? screen_dot_enrich(maps + (long)b * map_bs + (long)i * n + j, n, p, w) : __int_as_float(0x7fc00000);
+}
+
+// The dots of each map from its enrichment map (written by screen_dot_enrich_map_kernel, an earlier launch on the same stream), listed in row-major
+// order.  One workgroup of 256 threads per map walks the rows that hold eligible pixels, thread t at column j = t.  Pixel (i, j) is a dot when e is not
+// NaN, e >= T and, for every pixel within Chebyshev distance r whose e is not NaN (ineligible pixels hold NaN), e > e' where (i', j') precedes (i, j)
+// in row-major order and e >= e' where it follows: comparisons of fp32 values, so of two equal neighbours exactly the first is a dot.  The order comes
+// from a ballot per wave, the four waves' counts through LDS (two buffers, one barrier per row) and a running base that every thread keeps: no atomics,
+// and a map's list depends on the map alone.  count = the number of dots; the first K are written, the rest of the K slots get -1 / NaN.
+static __global__ void __launch_bounds__(256) screen_dot_calls_kernel(const float* __restrict__ e_map, int n, int w, int d_min, int r, float T, int K,
+                                                                      int* __restrict__ count, int* __restrict__ ij, float* __restrict__ enrich) {
+  __shared__ int s_wave[2][4];
+  const int b = blockIdx.x, j = threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  n = n > SCREEN_ALIGNED_MAX_BINS ? SCREEN_ALIGNED_MAX_BINS : n;
+  w = w > SCREEN_DOT_MAX_W ? SCREEN_DOT_MAX_W : (w < 1 ? 1 : w);
+  d_min = d_min < 2 * w + 1 ? 2 * w + 1 : d_min;
+  r = r > SCREEN_DOT_MAX_R ? SCREEN_DOT_MAX_R : (r < 1 ? 1 : r);
+  K = K < 0 ? 0 : K;
+  const float* e = e_map + (long)b * n * n;
+  int* my_ij = ij + (long)b * K * 2;
+  float* my_en = enrich + (long)b * K;
+  int base = 0;
+  for (int i = w; i <= n - 1 - w - d_min; ++i) {
+    bool dot = false;
+    float v = 0.f;
+    if (j < n && screen_dot_eligible(i, j, n, w, d_min)) {
+      v = e[(long)i * n + j];
+      dot = v == v && v >= T;
+      const int i0 = i - r < 0 ? 0 : i - r, i1 = i + r > n - 1 ? n - 1 : i + r, j0 = j - r < 0 ? 0 : j - r, j1 = j + r > n - 1 ? n - 1 : j + r;
+      for (int ii = i0; dot && ii <= i1; ++ii)
+        for (int jj = j0; jj <= j1; ++jj) {
+          if (ii == i && jj == j) continue;
+          const float f = e[(long)ii * n + jj];
+          if (f != f) continue;
+          const bool before = ii < i || (ii == i && jj < j);
+          if (before ? !(v > f) : !(v >= f)) dot = false;
+        }
+    }
+    const unsigned long long mask = __ballot(dot);
+    if (lane == 0) s_wave[i & 1][wave] = __popcll(mask);
+    __syncthreads();
+    int at = base + __popcll(mask & ((1ull << lane) - 1ull));
+    for (int k = 0; k < 4; ++k) {
+      const int c = s_wave[i & 1][k];
+      if (k < wave) at += c;
+      base += c;
+    }
+    if (dot && at < K) {
+      my_ij[2 * at] = i;
+      my_ij[2 * at + 1] = j;
+      my_en[at] = v;
+    }
+  }
+  if (threadIdx.x == 0) count[b] = base;
+  for (int k = (base < K ? base : K) + threadIdx.x; k < K; k += 256) {
+    my_ij[2 * k] = -1;
+    my_ij[2 * k + 1] = -1;
+    my_en[k] = __int_as_float(0x7fc00000);
+  }
+}
+
 // ---- both strands (screen.screen_1m(..., strands="both")): the '-' strand's map is merged into the '+' strand's as genomepredict merges them ------------
 // out[b][i][j] = 0.5 fwd[b][i][j] + 0.5 rev[b][n-1-i][n-1-j] (the expression of strand_merge_kernel: the same bits), and with the two strands' reference maps
 // gap[b] = mean_ij |(fwd - ref_fwd)[i][j] - (rev - ref_rev)[n-1-i][n-1-j]| - how far the strands disagree about the item's effect.  One workgroup per map, one

@@ -987,6 +987,49 @@ def screen_strata_scores(ctx, alt, ref, bin_map=None, d_range=None, bin_map_dev=
     return out
 
 
+# loops (orca_screen_dot_calls, orca_screen_dot_enrichment): dot calls per map and the enrichment at listed pixels
+def _dot_args(maps, p, w, d_min):
+    maps = _f32_cuda(maps, "maps")
+    if maps.dim() != 3 or maps.shape[1] != maps.shape[2] or maps.stride(2) != 1 or maps.stride(1) != maps.shape[1]:
+        raise ValueError("maps: [B,n,n] with contiguous maps")
+    B, n = maps.shape[0], maps.shape[1]
+    if B < 1:
+        raise ValueError("maps: at least one map")
+    bs = maps.stride(0) if B > 1 else max(maps.stride(0), n * n)                   # B = 1: torch may report any stride for the one map
+    return maps, B, n, bs, int(p), int(w), 2 * int(w) + 1 if d_min is None else int(d_min)
+
+
+def screen_dot_calls(ctx, maps, p, w, r, threshold, max_calls, d_min=None):
+    """Dot (loop) calls on maps [B, n, n] (any batch stride, rows contiguous) of log observed / expected (orca_screen_dot_calls; include/orca_hip.h has the
+    definitions): a dict of ``count`` [B] int32 (all dots of the map), ``ij`` [B, K, 2] int32 and ``enrich`` [B, K] float32 (the first K = ``max_calls``
+    dots in row-major order, -1 / NaN behind them) and ``e_map`` [B, n, n] float32, the enrichment at every pixel (NaN where ineligible).  0 <= p < w <= 16,
+    1 <= r <= 16, ``d_min`` >= 2 w + 1 (its default), 1 <= K <= 4096."""
+    maps, B, n, bs, p, w, d_min = _dot_args(maps, p, w, d_min)
+    K, dev = int(max_calls), maps.device
+    e_map, enrich = _f32_outputs(dev, (B, n, n), (B, max(K, 0)))
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    ij = torch.empty((B, max(K, 0), 2), dtype=torch.int32, device=dev)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_dot_calls(ctx.handle, _dev_p(maps), bs, B, n, p, w, d_min, int(r), float(threshold), K, _dev_p(e_map), _dev_p(count), _dev_p(ij),
+                                            _dev_p(enrich)), "orca_screen_dot_calls")
+    return {"count": count, "ij": ij, "enrich": enrich, "e_map": e_map}
+
+
+def screen_dot_enrichment(ctx, maps, pixels_host, p, w, d_min=None):
+    """The enrichment e of maps [B, n, n] at the listed pixels ``pixels_host`` [B, Q, 2] int32 numpy, (i, j) per pixel, 1 <= Q <= 4096
+    (orca_screen_dot_enrichment): [B, Q] float32, NaN for (-1, -1) and every other ineligible pixel, otherwise the bits of `screen_dot_calls`' ``e_map``."""
+    maps, B, n, bs, p, w, d_min = _dot_args(maps, p, w, d_min)
+    px = np.ascontiguousarray(pixels_host, dtype=np.int32)
+    if px.ndim != 3 or px.shape[0] != B or px.shape[2] != 2:
+        raise ValueError(f"pixels: [{B},Q,2] int32, one list per map")
+    Q = px.shape[1]
+    out, = _f32_outputs(maps.device, (B, Q))
+    pd = torch.from_numpy(px).to(maps.device)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_dot_enrichment(ctx.handle, _dev_p(maps), bs, B, n, p, w, d_min, _dev_p(pd), _np_p(px), Q, _dev_p(out)), "orca_screen_dot_enrichment")
+    return out
+
+
 # both strands (orca_screen_merge_strands)
 def screen_merge_strands(ctx, fwd, rev, ref_fwd=None, ref_rev=None, out=None):
     """The '+' strand's maps ``fwd`` [B, n, n] and the '-' strand's ``rev`` [B, n, n] (any batch stride, rows contiguous) merged as genomepredict merges

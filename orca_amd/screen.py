@@ -53,6 +53,12 @@ Pearson correlation and HiCRep's stratum-adjusted correlation, bin with bin and,
 (orca_screen_strata_scores; `strata_scores_host`).  A uniform shift of a distance band and a re-patterning inside it, which a mean of
 |alt - ref| cannot tell apart, separate there.
 
+``screen_1m(..., loops=True)`` (or a `LoopParams`) calls loops - the focal peaks between two anchors - on every alt map and on the reference
+map: the enrichment of a pixel's peak over HiCCUPS' donut, lower-left, horizontal and vertical backgrounds as a difference of fp64 means of
+log observed / expected, thresholded and reduced to local maxima on the device (orca_screen_dot_calls, orca_screen_dot_enrichment), then the
+change of the enrichment at every reference dot and which dots were gained or lost, bin with bin and, with ``aligned=True``, through `bin_map`
+(`loop_scores_host` restates it all).  "Which CTCF-site knock-out removes this loop" needs no ``keep_maps``.
+
 Every score above compares an item with the unedited window.  `epistasis_1m` asks whether the effect of an `EditSet` is the sum of its members'
 effects: it screens the distinct members and the sets in one pass, keeps the members' maps in a device bank, and scores per set the residual
 r = (alt_set - ref) - sum_m (alt_m - ref), every pixel in fp64 (orca_screen_epistasis_scores, orca_screen_epistasis_region_scores;
@@ -1108,6 +1114,266 @@ def strata_scores_host(maps, ref_map, bin_map=None, d_range=None):
     return out
 
 
+# ---- loops: dot calls (orca_screen_dot_calls, orca_screen_dot_enrichment) ---------------------------------------------------------------------
+LOOP_MAX_W, LOOP_MAX_R, LOOP_MAX_CALLS = 16, 16, 4096
+LOOP_FIELDS = ("loop_delta", "loops_gained", "loops_lost", "loop_is_gained", "ref_loop_is_lost")
+
+
+@dataclass(frozen=True)
+class LoopParams:
+    """The parameters of the dot (loop) calls of ``screen_1m(..., loops=)``; include/orca_hip.h (orca_screen_dot_calls) defines what they mean.
+      p          peak half-width: the peak set P is the (2 p + 1)^2 pixels around (i, j)
+      w          window half-width of the HiCCUPS sets D, LL, H, V; 0 <= p < w <= 16
+      r          a dot is the local maximum of the enrichment within Chebyshev distance r; 1 <= r <= 16
+      threshold  a dot has enrichment e >= threshold (compared in fp32).  The maps are log observed / expected, so e is a log fold enrichment
+                 of the peak over its strongest local background.  The default, 0.25, is NOT calibrated on the published checkpoints - nobody
+                 on this project has them; choose it from ``ref_loop_enrichment`` and known loops of the cell type
+      d_min      the smallest distance j - i of a pixel that can be called; None = 2 w + 1, the smallest at which every set lies strictly
+                 above the diagonal
+      max_calls  K, the dots listed per map (row-major order; ``loop_count`` still counts all); 1 <= K <= 4096
+      tol        an alt dot matches a reference dot when their Chebyshev distance is <= tol bins (``loops_gained`` / ``loops_lost``)"""
+    p: int = 1
+    w: int = 4
+    r: int = 2
+    threshold: float = 0.25
+    d_min: Optional[int] = None
+    max_calls: int = 64
+    tol: int = 1
+
+
+def _loop_params(params):
+    """``params`` (a `LoopParams`) validated, with ``d_min`` resolved and ``threshold`` as the fp32 the kernel compares with."""
+    if not isinstance(params, LoopParams):
+        raise ValueError("loops: True (the defaults) or a screen.LoopParams")
+    vals = {}
+    for k in ("p", "w", "r", "d_min", "max_calls", "tol"):
+        v = getattr(params, k)
+        if k == "d_min" and v is None:
+            continue
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"loops: {k} = {v!r} must be an int")
+        vals[k] = int(v)
+    p, w = vals["p"], vals["w"]
+    if not 0 <= p < w <= LOOP_MAX_W:
+        raise ValueError(f"loops: p = {p}, w = {w}: 0 <= p < w <= {LOOP_MAX_W}")
+    if not 1 <= vals["r"] <= LOOP_MAX_R:
+        raise ValueError(f"loops: r = {vals['r']}: 1 .. {LOOP_MAX_R}")
+    d_min = vals.get("d_min", 2 * w + 1)
+    if d_min < 2 * w + 1:
+        raise ValueError(f"loops: d_min = {d_min} below 2 w + 1 = {2 * w + 1} (the sets must stay above the diagonal)")
+    if not 1 <= vals["max_calls"] <= LOOP_MAX_CALLS:
+        raise ValueError(f"loops: max_calls = {vals['max_calls']}: 1 .. {LOOP_MAX_CALLS}")
+    if vals["tol"] < 0:
+        raise ValueError(f"loops: tol = {vals['tol']} must not be negative")
+    try:
+        t = float(np.float32(params.threshold))
+    except (TypeError, ValueError):
+        raise ValueError("loops: threshold must be a number") from None
+    if isinstance(params.threshold, (bool, np.bool_)) or t != t:
+        raise ValueError("loops: threshold must be a number, not NaN")
+    return LoopParams(p, w, vals["r"], t, d_min, vals["max_calls"], vals["tol"])
+
+
+def check_loops(loops, n):
+    """``loops`` as a validated `LoopParams` for a map of n bins: True stands for the defaults, ``d_min=None`` becomes 2 w + 1.  A ValueError
+    for anything that is not True or a `LoopParams`, for values outside their ranges (0 <= p < w <= 16, 1 <= r <= 16, d_min >= 2 w + 1,
+    1 <= max_calls <= 4096, tol >= 0, threshold not NaN) and when no pixel of an n-bin map is eligible (n < 2 w + 1 + d_min)."""
+    q = _loop_params(LoopParams() if loops is True else loops)
+    if n < 2 * q.w + 1 + q.d_min:
+        raise ValueError(f"loops: a map of {n} bins has no eligible pixel at w = {q.w}, d_min = {q.d_min} (n >= 2 w + 1 + d_min = {2 * q.w + 1 + q.d_min})")
+    return q
+
+
+def dot_enrichment_host(maps, params):
+    """The enrichment e of maps [E, n, n] at every pixel (host restatement of the device function behind orca_screen_dot_calls): float32
+    [E, n, n], NaN at the ineligible pixels.  Pixel (i, j) is eligible when w <= i, j <= n - 1 - w and j - i >= d_min.  Over the offsets (a, b),
+    |a|, |b| <= w: P = |a| <= p and |b| <= p; D = not P, a != 0 and b != 0; LL = 1 <= a, b <= -1, not P; H = |a| <= 1 and |b| > p; V = |b| <= 1
+    and |a| > p.  e = mean P - max(mean D, mean LL, mean H, mean V), every set summed on its own in fp64 (a ascending, then b ascending), one
+    division by its count, rounded to fp32 once; NaN when any set holds a NaN.  Nothing on or below the diagonal enters an eligible pixel."""
+    q = _loop_params(params)
+    m = np.asarray(maps, dtype=np.float32)
+    if m.ndim != 3 or m.shape[1] != m.shape[2]:
+        raise ValueError("maps: [E, n, n]")
+    E, n = m.shape[0], m.shape[1]
+    p, w, d_min = q.p, q.w, q.d_min
+    out = np.full((E, n, n), np.nan, dtype=np.float32)
+    c = n - 2 * w                                        # the pixels whose window is inside the map: rows and columns w .. n - 1 - w
+    if c <= 0 or n < 2 * w + 1 + d_min:
+        return out
+    m64 = m.astype(np.float64)
+    sums = {k: np.zeros((E, c, c)) for k in "PDLHV"}
+    cnt = dict.fromkeys("PDLHV", 0)
+    for a in range(-w, w + 1):
+        for b in range(-w, w + 1):
+            x = m64[:, w + a: w + a + c, w + b: w + b + c]
+            sets = []
+            if abs(a) <= p and abs(b) <= p:
+                sets.append("P")
+            else:
+                if a != 0 and b != 0:
+                    sets.append("D")
+                if a >= 1 and b <= -1:
+                    sets.append("L")
+            if abs(a) <= 1 and abs(b) > p:
+                sets.append("H")
+            if abs(b) <= 1 and abs(a) > p:
+                sets.append("V")
+            for k in sets:
+                sums[k] = sums[k] + x
+                cnt[k] += 1
+    mean = {k: sums[k] / float(cnt[k]) for k in "PDLHV"}
+    nan = np.zeros((E, c, c), dtype=bool)
+    for k in "PDLHV":
+        nan |= np.isnan(mean[k])
+    with np.errstate(invalid="ignore"):
+        bg = mean["D"]
+        for k in "LHV":
+            bg = np.where(mean[k] > bg, mean[k], bg)
+        e = np.where(nan, np.nan, mean["P"] - bg).astype(np.float32)
+    i = np.arange(w, n - w)
+    e[:, ~(i[None, :] - i[:, None] >= d_min)] = np.nan
+    out[:, w: n - w, w: n - w] = e
+    return out
+
+
+def dot_calls_host(maps, params):
+    """The dot calls of maps [E, n, n] (host restatement of orca_screen_dot_calls): a dict of ``count`` [E] int32 (all dots), ``ij`` [E, K, 2] int32
+    and ``enrich`` [E, K] float32 (the first K = max_calls dots in row-major order, -1 / NaN behind them) and ``e_map`` = `dot_enrichment_host`.
+    (i, j) is a dot when e is not NaN, e >= threshold and, for every pixel within Chebyshev distance r whose e' is not NaN,
+    e > e' where that pixel precedes (i, j) in row-major order and e >= e' where it follows; all in fp32."""
+    q = _loop_params(params)
+    e = dot_enrichment_host(maps, q)
+    E, n = e.shape[0], e.shape[1]
+    r, K, T = q.r, q.max_calls, np.float32(q.threshold)
+    pad = np.full((E, n + 2 * r, n + 2 * r), np.nan, dtype=np.float32)
+    pad[:, r: r + n, r: r + n] = e
+    with np.errstate(invalid="ignore"):
+        dot = ~np.isnan(e) & (e >= T)
+        for di in range(-r, r + 1):
+            for dj in range(-r, r + 1):
+                if di == 0 and dj == 0:
+                    continue
+                f = pad[:, r + di: r + di + n, r + dj: r + dj + n]
+                wins = (e > f) if (di < 0 or (di == 0 and dj < 0)) else (e >= f)
+                dot &= np.isnan(f) | wins
+    count = dot.reshape(E, -1).sum(axis=1).astype(np.int32)
+    ij = np.full((E, K, 2), -1, dtype=np.int32)
+    enrich = np.full((E, K), np.nan, dtype=np.float32)
+    for k in range(E):
+        at = np.argwhere(dot[k])[:K]                     # row-major
+        ij[k, : len(at)] = at
+        enrich[k, : len(at)] = e[k, at[:, 0], at[:, 1]]
+    return {"count": count, "ij": ij, "enrich": enrich, "e_map": e}
+
+
+def follow_loop(bin_map_row, i, j, params):
+    """Where the reference pixel (i, j) went in an alt map with bin map ``bin_map_row`` [n]: (a, b) with a the LOWEST alt bin that stands for
+    reference bin i and b the HIGHEST that stands for j - the anchors' outer edges, should an insertion have left two alt bins on one reference
+    bin.  (-1, -1) when either reference bin is behind no alt bin (the anchor was deleted or pushed out) or (a, b) is not an eligible pixel."""
+    q = _loop_params(params)
+    bm = np.asarray(bin_map_row)
+    n = bm.shape[0]
+    ia, jb = np.flatnonzero(bm == i), np.flatnonzero(bm == j)
+    if i < 0 or j < 0 or not ia.size or not jb.size:
+        return -1, -1
+    a, b = int(ia[0]), int(jb[-1])
+    if not (a >= q.w and b <= n - 1 - q.w and b - a >= q.d_min):
+        return -1, -1
+    return a, b
+
+
+def _follow_loops(bin_maps, ref_ij, q):
+    """`follow_loop` of every reference dot ``ref_ij`` [R, 2] under every row of ``bin_maps`` [E, n]: int32 [E, R, 2]."""
+    bm = np.asarray(bin_maps)
+    E, n = bm.shape
+    out = np.full((E, ref_ij.shape[0], 2), -1, dtype=np.int32)
+    if not ref_ij.shape[0]:
+        return out
+    ident = (bm == np.arange(n)[None]).all(axis=1)       # most items of a screen keep their length: every dot stays where it is
+    ri, rj = ref_ij[:, 0].astype(np.int64), ref_ij[:, 1].astype(np.int64)
+    out[ident] = np.where(((ri >= q.w) & (rj <= n - 1 - q.w) & (rj - ri >= q.d_min))[:, None], ref_ij, -1)[None]
+    for e in np.flatnonzero(~ident):
+        idx = np.flatnonzero(bm[e] >= 0)
+        first, last = np.full(n, -1), np.full(n, -1)
+        first[bm[e, idx[::-1]]] = idx[::-1]              # written in descending order: the lowest alt bin stays
+        last[bm[e, idx]] = idx
+        a, b = first[ref_ij[:, 0]], last[ref_ij[:, 1]]
+        ok = (a >= q.w) & (b >= 0) & (b <= n - 1 - q.w) & (b - a >= q.d_min)
+        out[e, ok, 0], out[e, ok, 1] = a[ok], b[ok]
+    return out
+
+
+def match_loops_host(alt_ij, ref_ij, tol, bin_map_row=None):
+    """Match the listed dots of an alt map, ``alt_ij`` [K, 2] (-1 rows are padding), to the reference's, ``ref_ij`` [R, 2]: (is_gained [K] bool,
+    is_lost [R] bool).  An alt dot matches a reference dot when their Chebyshev distance is <= ``tol``; gained = a listed alt dot that matches
+    none, lost = a reference dot that no alt dot matches.  With ``bin_map_row`` [n] an alt dot (a, b) stands for (map a, map b) before it is
+    compared; if either bin is unmapped it is gained and matches nothing."""
+    alt, ref = np.asarray(alt_ij, dtype=np.int64).reshape(-1, 2), np.asarray(ref_ij, dtype=np.int64).reshape(-1, 2)
+    listed = alt[:, 0] >= 0
+    ok = listed.copy()
+    if bin_map_row is not None:
+        bm = np.asarray(bin_map_row, dtype=np.int64)
+        alt = np.where(listed[:, None], bm[np.where(listed[:, None], alt, 0)], -1)
+        ok = listed & (alt >= 0).all(axis=1)
+    near = (np.abs(alt[:, None, :] - ref[None, :, :]).max(axis=2) <= int(tol)) & ok[:, None]       # [K, R]
+    return listed & ~near.any(axis=1), ~near.any(axis=0)
+
+
+def _match_loops(alt_ij, ref_ij, tol, bin_maps=None):
+    """`match_loops_host` of every item at once: ``alt_ij`` [E, K, 2], ``ref_ij`` [R, 2], ``bin_maps`` [E, n] or None -> (is_gained [E, K], is_lost [E, R])."""
+    alt, ref = np.asarray(alt_ij, dtype=np.int32), np.asarray(ref_ij, dtype=np.int32).reshape(-1, 2)
+    E, K, R = alt.shape[0], alt.shape[1], ref.shape[0]
+    listed = alt[:, :, 0] >= 0
+    ok = listed
+    if bin_maps is not None:
+        bm = np.asarray(bin_maps, dtype=np.int32)
+        alt = np.where(listed[:, :, None], np.take_along_axis(bm, np.where(listed[:, :, None], alt, 0).reshape(E, 2 * K), axis=1).reshape(E, K, 2), -1)
+        ok = listed & (alt >= 0).all(axis=2)
+    if not R or not E:
+        return listed.copy(), np.zeros((E, R), dtype=bool) if not R else np.ones((E, R), dtype=bool)
+    gained, lost = np.zeros((E, K), dtype=bool), np.zeros((E, R), dtype=bool)
+    step = max(1, (1 << 22) // (K * R))                  # items per pass: [step, K, R] temporaries of a few MB
+    for e0 in range(0, E, step):
+        a = alt[e0: e0 + step]
+        near = ok[e0: e0 + step, :, None]
+        for c in range(2):                               # Chebyshev distance <= tol, coordinate by coordinate
+            near = near & (np.abs(a[:, :, c, None] - ref[None, None, :, c]) <= int(tol))
+        gained[e0: e0 + step], lost[e0: e0 + step] = listed[e0: e0 + step] & ~near.any(axis=2), ~near.any(axis=1)
+    return gained, lost
+
+
+def loop_scores_host(maps, ref_map, params, bin_map=None):
+    """Every loop field of `ScreenResult` from alt maps [E, n, n] and the reference map [n, n] (host restatement of ``screen_1m(..., loops=)``): a
+    dict of ``ref_loop_count`` (int, all dots of the reference), ``ref_loops`` [R, 2] int32 and ``ref_loop_enrichment`` [R] float32 (the listed
+    ones, R = min(count, K)), ``loops`` [E, K, 2] int32, ``loop_enrichment`` [E, K] float32, ``loop_count`` [E] int32, ``loop_delta`` [E, R] float32
+    (e of the alt map at the reference dot's pixel minus the reference's e there, an fp32 subtraction; NaN where the alt e is), ``loops_gained``,
+    ``loops_lost`` [E] int32 and the masks ``loop_is_gained`` [E, K], ``ref_loop_is_lost`` [E, R] (`match_loops_host`); with ``bin_map`` ([E, n],
+    or one [n] for all) also their ``aligned_`` forms: the reference dot followed to its alt pixel (`follow_loop`; NaN when it has none) and the
+    alt dots matched through the bin map."""
+    q = _loop_params(params)
+    alt = np.asarray(maps, dtype=np.float32)
+    E, n = alt.shape[0], alt.shape[1]
+    rc = dot_calls_host(np.asarray(ref_map, dtype=np.float32)[None], q)
+    R = min(int(rc["count"][0]), q.max_calls)
+    ref_ij, ref_e = rc["ij"][0, :R], rc["enrich"][0, :R]
+    ac = dot_calls_host(alt, q)
+    out = {"ref_loop_count": int(rc["count"][0]), "ref_loops": ref_ij, "ref_loop_enrichment": ref_e, "loops": ac["ij"], "loop_enrichment": ac["enrich"],
+           "loop_count": ac["count"]}
+    bms = None if bin_map is None else _bin_maps(bin_map, E, n)
+    for pre in ("", "aligned_") if bms is not None else ("",):
+        delta = np.full((E, R), np.nan, dtype=np.float32)
+        gained, lost = np.zeros((E, q.max_calls), dtype=bool), np.zeros((E, R), dtype=bool)
+        for e in range(E):
+            for k in range(R):
+                a, b = (int(ref_ij[k, 0]), int(ref_ij[k, 1])) if not pre else follow_loop(bms[e], int(ref_ij[k, 0]), int(ref_ij[k, 1]), q)
+                if a >= 0:
+                    delta[e, k] = ac["e_map"][e, a, b] - ref_e[k]
+            gained[e], lost[e] = match_loops_host(ac["ij"][e], ref_ij, q.tol, bms[e] if pre else None)
+        out[pre + "loop_delta"], out[pre + "loop_is_gained"], out[pre + "ref_loop_is_lost"] = delta, gained, lost
+        out[pre + "loops_gained"], out[pre + "loops_lost"] = gained.sum(axis=1).astype(np.int32), lost.sum(axis=1).astype(np.int32)
+    return out
+
+
 def merge_strands_host(plus, minus, ref_plus=None, ref_minus=None):
     """The merged maps of ``strands="both"`` (fp64 host restatement of orca_screen_merge_strands): ``plus``, ``minus`` [E, n, n] (or [n, n]) the two
     strands' maps, ``minus`` in the '-' strand's own orientation.  (merged, gap) with merged = 0.5 plus + 0.5 flip(minus), flip reversing both bin
@@ -1268,9 +1534,23 @@ class ScreenResult:
       aligned_dist_delta, aligned_dist_abs, aligned_dist_rms, aligned_dist_corr [E, n];  aligned_mse, aligned_corr, aligned_scc [E]
       aligned_dist_count [E, n] int32 c_d, the mapped pairs of stratum d; every per-stratum value is NaN where it is 0
     A NaN pixel at a pair of stratum d makes that stratum's values NaN and, if d_lo <= d < d_hi, the three per-map scores; nothing else.
+    With ``loops=`` (None otherwise) - dot calls (`LoopParams`; include/orca_hip.h, orca_screen_dot_calls, defines eligible pixels, the
+    enrichment e and a dot).  K = max_calls, R = min(ref_loop_count, K):
+      loop_params        LoopParams   the validated parameters (d_min resolved)
+      ref_loops          [R, 2] int32 the reference map's dots (i, j), row-major;  ref_loop_enrichment [R] their e;  ref_loop_count (int) all of them
+      loops              [E, K, 2] int32  the first K dots of every alt map, row-major, -1 behind them;  loop_enrichment [E, K] their e, NaN behind
+      loop_count         [E] int32    all dots of the alt map (above K the list is truncated)
+      loop_delta         [E, R]       e of the alt map at reference dot k's pixel minus the reference's e there: "this loop weakened by x";
+                                      NaN where the alt e is (a NaN pixel in the window)
+      loop_is_gained     [E, K] bool  a listed alt dot with no reference dot within Chebyshev distance tol;  loops_gained [E] int32 their number
+      ref_loop_is_lost   [E, R] bool  a reference dot with no listed alt dot within tol;  loops_lost [E] int32 their number
+    and with ``aligned=True`` aligned_loop_delta, aligned_loop_is_gained, aligned_loops_gained, aligned_ref_loop_is_lost, aligned_loops_lost:
+    reference dot (i, j) is followed to alt pixel (lowest a with map a = i, highest b with map b = j) - NaN when either bin does not exist or
+    the pixel is ineligible - and an alt dot (a, b) stands for (map a, map b), gained if either bin is unmapped; where the bin map is the
+    identity they hold the plain fields' bits.
     `scores_host` computes the three map scores from maps on the host, `region_scores_host` the two region scores, `aligned_scores_host` and
     `aligned_region_scores_host` the aligned ones, `insulation_scores_host` and `viewpoint_scores_host` the tracks, `strata_scores_host` the
-    distance-stratified scores."""
+    distance-stratified scores, `loop_scores_host` the loop fields."""
     ref_map: torch.Tensor
     ref_1d: Optional[torch.Tensor]
     delta_profile: torch.Tensor
@@ -1315,6 +1595,23 @@ class ScreenResult:
     aligned_mse: Optional[torch.Tensor] = None
     aligned_corr: Optional[torch.Tensor] = None
     aligned_scc: Optional[torch.Tensor] = None
+    loop_params: Optional[LoopParams] = None
+    ref_loops: Optional[torch.Tensor] = None
+    ref_loop_enrichment: Optional[torch.Tensor] = None
+    ref_loop_count: Optional[int] = None
+    loops: Optional[torch.Tensor] = None
+    loop_enrichment: Optional[torch.Tensor] = None
+    loop_count: Optional[torch.Tensor] = None
+    loop_delta: Optional[torch.Tensor] = None
+    loops_gained: Optional[torch.Tensor] = None
+    loops_lost: Optional[torch.Tensor] = None
+    loop_is_gained: Optional[torch.Tensor] = None
+    ref_loop_is_lost: Optional[torch.Tensor] = None
+    aligned_loop_delta: Optional[torch.Tensor] = None
+    aligned_loops_gained: Optional[torch.Tensor] = None
+    aligned_loops_lost: Optional[torch.Tensor] = None
+    aligned_loop_is_gained: Optional[torch.Tensor] = None
+    aligned_ref_loop_is_lost: Optional[torch.Tensor] = None
 
 
 # ---- the screen -----------------------------------------------------------------------------------------------------------------------------
@@ -1482,7 +1779,7 @@ class _Screen:
 
 
 def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regions=None, flank=None, aligned=False, flank_bp=None, strands="+",
-              insulation=None, viewpoints=None, strata=None):
+              insulation=None, viewpoints=None, strata=None, loops=None):
     """Score ``edits`` (a list of `Edit` and `EditSet`, one row of every result tensor each) of one window with the 1 Mb model: a `ScreenResult`.
 
     ``model``: an ``H1esc_1M`` / ``Hff_1M`` container or a bare ``orca_modules.Net``.  ``window``: the window's base codes, a [L] uint8 tensor on
@@ -1540,11 +1837,21 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
     cannot tell a uniform shift of a distance band (``dist_delta`` moves, ``dist_corr`` stays 1) from a re-patterning inside it (``dist_corr`` drops).
     Taken from the batch's final maps whichever route made them, with ``strands="both"`` from the merged maps against the merged ``ref_map``.  With
     None (or False) nothing more is launched and every other field is what it was.  ``stats`` gains ``strata``: the number of strata the per-map
-    scores run over (0 when absent)."""
-    return _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, aligned, flank_bp, strands, insulation, viewpoints, strata=strata)
+    scores run over (0 when absent).
+
+    ``loops``: True (the defaults) or a `LoopParams` (`check_loops`), for dot calls on every alt map and on ``ref_map`` (orca_screen_dot_calls):
+    `ScreenResult.ref_loops`, ``ref_loop_enrichment``, ``ref_loop_count``, ``loops``, ``loop_enrichment``, ``loop_count``, the change of the enrichment
+    at every reference dot ``loop_delta``, and ``loops_gained`` / ``loops_lost`` with their masks; with ``aligned=True`` also the ``aligned_`` forms
+    of the last five, through `bin_map` (the followed pixels go through orca_screen_dot_enrichment).  The default threshold is NOT calibrated on the
+    published checkpoints.  Taken from the batch's final maps whichever route made them, with ``strands="both"`` from the merged maps; the
+    reference's dots are called once from the final ``ref_map``; the lists are matched on the host after the last batch.  With None (or False)
+    nothing more is launched and every other field is what it was.  ``stats`` gains ``loops`` (K, 0 when absent) and ``loop_truncated_items``
+    (items with more than K dots)."""
+    return _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, aligned, flank_bp, strands, insulation, viewpoints, strata=strata, loops=loops)
 
 
-def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, aligned, flank_bp, strands, insulation, viewpoints, hook=None, strata=None):
+def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, aligned, flank_bp, strands, insulation, viewpoints, hook=None, strata=None,
+                loops=None):
     """The body of `screen_1m` (its arguments, its result).  ``hook``: called as ``hook(res, i0, i1, maps)`` at the end of every batch, on every
     route, with the `ScreenResult` under construction (``res.ref_map`` is final) and the FINAL maps [i1 - i0, n, n] of items [i0, i1) - after the
     strand merge and after any range fallback; the buffer is the batch's own, so the hook reads it before it returns.  Without a hook nothing
@@ -1572,12 +1879,13 @@ def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, a
     widths = None if insulation is None else check_insulation(insulation, win.numel() // 4000)
     views = None if viewpoints is None else check_viewpoints(viewpoints, win.numel() // 4000)
     drange = None if strata is None or strata is False else check_strata(strata, win.numel() // 4000)
+    lp = None if loops is None or loops is False else check_loops(loops, win.numel() // 4000)
     st = {"route": None, "two_part_batches": 0, "whole_window_batches": 0, "range_fallback_batches": 0, "range_fallback_reference": False,
           "front_runs": 0, "front_bases": 0, "edits": len(edits), "set_items": sum(isinstance(e, EditSet) for e in edits), "segments": 0,
           "indel_items": sum(changes_length(e) for e in edits), "take_rows": 0, "cache_phases": 0, "aligned_items": 0,
           "strands": strands, "reverse_two_part_items": 0, "reverse_whole_items": 0,
           "insulation_widths": 0 if widths is None else len(widths), "viewpoints": 0 if views is None else len(views),
-          "strata": 0 if drange is None else drange[1] - drange[0]}
+          "strata": 0 if drange is None else drange[1] - drange[0], "loops": 0 if lp is None else lp.max_calls, "loop_truncated_items": 0}
     fl = _flank_codes(window, flank, win, flank_bp) if (flank is not None or st["indel_items"]) else None
     sc = _Screen(net, win, st, fl if st["indel_items"] else None)
     E, n, dev = len(edits), sc.n, sc.dev
@@ -1668,6 +1976,21 @@ def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, a
                                                          dtype=torch.float64 if name in ("dist_corr", "corr", "scc") else torch.float32))
             if aligned:
                 res.aligned_dist_count = torch.zeros((E, n), dtype=torch.int32, device=dev)
+        ref_ij = ref_pix = followed = None
+        if lp is not None:                               # the reference's dots once, from the final (merged) reference map
+            got = engine.screen_dot_calls(sc.ctx, ref_map[None], lp.p, lp.w, lp.r, lp.threshold, lp.max_calls, lp.d_min)
+            res.loop_params, res.ref_loop_count = lp, int(got["count"][0])
+            R, K = min(res.ref_loop_count, lp.max_calls), lp.max_calls
+            res.ref_loops, res.ref_loop_enrichment = got["ij"][0, :R].contiguous(), got["enrich"][0, :R].contiguous()
+            ref_ij = res.ref_loops.cpu().numpy()
+            ref_pix = res.ref_loops.long()
+            res.loops = torch.full((E, K, 2), -1, dtype=torch.int32, device=dev)
+            res.loop_enrichment = torch.full((E, K), float("nan"), dtype=torch.float32, device=dev)
+            res.loop_count = torch.zeros(E, dtype=torch.int32, device=dev)
+            res.loop_delta = torch.zeros((E, R), dtype=torch.float32, device=dev)
+            if aligned:                                  # every reference dot followed to its alt pixel, per item: (-1, -1) where it has none
+                res.aligned_loop_delta = torch.full((E, R), float("nan"), dtype=torch.float32, device=dev)
+                followed = _follow_loops(bmaps, ref_ij, lp)
         def whole(chunk):                                # a batch on the whole-window route: the '+' strand, or the pair of strands
             if not both:
                 return sc.whole(chunk)
@@ -1731,12 +2054,33 @@ def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, a
                     got = engine.screen_strata_scores(sc.ctx, maps, ref_map, bmaps[i0:i1], drange, res.bin_map[i0:i1])
                     for name in STRATA_FIELDS + ("dist_count",):
                         getattr(res, "aligned_" + name)[i0:i1] = got[name]
+            if lp is not None:
+                got = engine.screen_dot_calls(sc.ctx, maps, lp.p, lp.w, lp.r, lp.threshold, lp.max_calls, lp.d_min)
+                res.loops[i0:i1], res.loop_enrichment[i0:i1], res.loop_count[i0:i1] = got["ij"], got["enrich"], got["count"]
+                if ref_pix.shape[0]:
+                    res.loop_delta[i0:i1] = got["e_map"][:, ref_pix[:, 0], ref_pix[:, 1]] - res.ref_loop_enrichment[None]
+                    if aligned:
+                        res.aligned_loop_delta[i0:i1] = engine.screen_dot_enrichment(sc.ctx, maps, followed[i0:i1], lp.p, lp.w, lp.d_min) - res.ref_loop_enrichment[None]
             if h is not None:
                 torch.sub(h, ref_1d[None], out=res.delta_1d[i0:i1])
             if keep_maps:
                 res.maps[i0:i1] = maps
             if hook is not None:
                 hook(res, i0, i1, maps)
+        if lp is not None:                               # the lists are tiny: one copy to the host, the matching in numpy
+            alt_ij = res.loops.cpu().numpy()
+            st["loop_truncated_items"] = int((res.loop_count > lp.max_calls).sum())
+            for pre in ("", "aligned_") if aligned else ("",):
+                if not pre:
+                    gained, lost = _match_loops(alt_ij, ref_ij, lp.tol)
+                else:                                    # an identity bin map changes nothing: only the other items are matched again
+                    moved = np.flatnonzero((bmaps != np.arange(n, dtype=np.int32)[None]).any(axis=1))
+                    gained, lost = gained.copy(), lost.copy()
+                    gained[moved], lost[moved] = _match_loops(alt_ij[moved], ref_ij, lp.tol, bmaps[moved])
+                setattr(res, pre + "loop_is_gained", sc._upload(gained, torch.bool))
+                setattr(res, pre + "ref_loop_is_lost", sc._upload(lost, torch.bool))
+                setattr(res, pre + "loops_gained", sc._upload(gained.sum(axis=1), torch.int32))
+                setattr(res, pre + "loops_lost", sc._upload(lost.sum(axis=1), torch.int32))
     if stats is not None:
         stats.update(st)
     return res

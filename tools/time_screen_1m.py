@@ -35,6 +35,10 @@ Distance strata, into profiles/screen_1m_strata.json:
   --strata       the 3 250-edit workload at B = 64 through screen_1m with strata=True and without, and both again with aligned=True, alternated in
                  the same run, best of three: what orca_screen_strata_scores adds, set beside what aligned=True adds
 
+Loops, into profiles/screen_1m_loops.json:
+  --loops        the 3 250-edit workload at B = 64 through screen_1m with loops=True, with the lists filled (threshold 0.0) and without, and both again with aligned=True, alternated in
+                 the same run, best of three: what the dot-call kernels and the host matching add, set beside what aligned=True adds
+
 Non-additivity, into profiles/screen_1m_epistasis.json:
   --epistasis NA NB  the NA x NB pairs of 4 kb mask tiles (NA from base 100 000, NB from base 600 000) at B = 64 through screen.epistasis_1m, and
                  through today's route - screen_1m on the singles and on the pairs with keep_maps=True, then the residual in torch, in fp32 -
@@ -236,6 +240,40 @@ def time_strata(a, model, win, edits, dev):
     return rep
 
 
+def time_loops(a, model, win, edits, dev):
+    """The --loops workload: screen_1m on the same edits with and without loops=True, plain and with aligned=True, alternated, at B = 64, best of
+    max(--reps, 3).  The overheads are over the plain screen of the same run.  The default threshold, 0.25, is not calibrated, and on these synthetic
+    weights (enrichments near 0.03) it calls nothing: the kernels run in full but the lists stay empty and the host matching idles.  So the same is
+    timed once more with the default parameters at threshold 0.0 (``*_full``), which fills every list; ``ref_loop_count_*`` and the largest
+    ``loop_count`` of the first batch say how many dots there were."""
+    B, reps = 64, max(a.reps, 3)
+    rep = {"device": torch.cuda.get_device_name(dev), "edits": len(edits), "batch": B, "reps": reps, "full_threshold": 0.0}
+    full = S.LoopParams(threshold=0.0)
+    runs = {"plain": {}, "loops": {"loops": True}, "loops_full": {"loops": full}, "aligned": {"aligned": True},
+            "aligned_loops": {"aligned": True, "loops": True}, "aligned_loops_full": {"aligned": True, "loops": full}}
+    st = {}
+    for k, kw in runs.items():                                                                   # warm-up
+        res = S.screen_1m(model, win, edits[:B], batch=B, stats=st, **kw)
+        if k in ("loops", "loops_full"):
+            rep[f"ref_loop_count_{k}"], rep[f"max_loop_count_first_batch_{k}"] = res.ref_loop_count, int(res.loop_count.max())
+    rep["route"] = st["route"]
+    t = {k: [] for k in runs}
+    for _ in range(reps):
+        for k, kw in runs.items():
+            t[k].append(timed(lambda: S.screen_1m(model, win, edits, batch=B, **kw))[0])
+    for k in runs:
+        rep[f"{k}_s"] = [round(x, 3) for x in t[k]]
+        rep[f"{k}_edits_per_s"] = round(len(edits) / min(t[k]), 1)
+    plain = min(t["plain"])
+    rep["loops_over_plain"] = round(min(t["loops"]) / plain, 4)
+    rep["loops_full_over_plain"] = round(min(t["loops_full"]) / plain, 4)
+    rep["aligned_over_plain"] = round(min(t["aligned"]) / plain, 4)
+    rep["aligned_loops_over_aligned"] = round(min(t["aligned_loops"]) / min(t["aligned"]), 4)
+    rep["aligned_loops_full_over_aligned"] = round(min(t["aligned_loops_full"]) / min(t["aligned"]), 4)
+    rep["plain_spread"] = round(max(t["plain"]) / plain, 4)
+    return rep
+
+
 def naive_both(model, win, edits, batch, keep_maps=False):
     """`naive` on both strands: every batch's edited windows through Net's Encoder and Decoder_1m forwards and reverse-complemented, merged."""
     sc = S._Screen(model.net, win, {})
@@ -339,6 +377,7 @@ def main():
     ap.add_argument("--aligned", action="store_true", help="time the 3 250-edit workload with aligned=True against aligned=False")
     ap.add_argument("--tracks", action="store_true", help="time the 3 250-edit workload at B = 64 with insulation and viewpoint tracks against without")
     ap.add_argument("--strata", action="store_true", help="time the 3 250-edit workload at B = 64 with strata=True against without, plain and with aligned=True")
+    ap.add_argument("--loops", action="store_true", help="time the 3 250-edit workload at B = 64 with loops=True against without, plain and with aligned=True")
     ap.add_argument("--strands", default="+", choices=("+", "both"), help="both: time the 3 250-edit workload on both strands at B = 64")
     ap.add_argument("--epistasis", type=int, nargs=2, metavar=("NA", "NB"), help="time the NA x NB mask-tile pairs through epistasis_1m against two screen_1m "
                     "calls with keep_maps=True plus fp32 arithmetic in torch")
@@ -390,6 +429,17 @@ def main():
         rep.update(time_strata(a, model, win, edits, dev))
         print(json.dumps(rep))
         out = a.out if a.out != ap.get_default("out") else os.path.join(os.path.dirname(a.out), "screen_1m_strata.json")
+        if out:
+            os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+            with open(out, "w") as f:
+                json.dump(rep, f, indent=1)
+        return
+    if a.loops:
+        rep = {"workload": f"H1esc_1M synthetic, 1 Mb window, {len(edits)} edits (saturation SNVs of 1 kb + 250 4 kb mask tiles); screen_1m with "
+                           "loops=True and with loops=LoopParams(threshold=0.0) (full lists) against without, each also with aligned=True, alternated (every call includes its reference)", "commit": a.commit}
+        rep.update(time_loops(a, model, win, edits, dev))
+        print(json.dumps(rep))
+        out = a.out if a.out != ap.get_default("out") else os.path.join(os.path.dirname(a.out), "screen_1m_loops.json")
         if out:
             os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
             with open(out, "w") as f:
