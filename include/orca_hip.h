@@ -424,6 +424,24 @@ int orca_screen_strata_scores(orca_ctx* ctx, const float* alt, int64_t map_bs, c
                               const int32_t* bin_map_host, int d_lo, int d_hi, float* dist_delta, float* dist_abs, float* dist_rms, double* dist_corr,
                               int32_t* dist_count, float* mse, double* corr, double* scc);
 
+/* Paired aligned scores (sv.sv_screen(..., scores=), sv.sv_scores): B pairs of maps, alt[b * alt_bs + i * n + j] against a reference map OF ITS OWN
+ * ref[b * ref_bs + ..] (B >= 1, 1 <= n <= 256, both batch strides >= n * n) through `bin_map` (B x n int32 as above: device copy for the kernel, checked
+ * host copy; bin_map[b][i] = the reference bin alt bin i of pair b stands for, -1 for none, anything outside -1 .. n - 1 refused).  The map may ascend
+ * with a jump (a deletion), repeat reference bins (a duplication's second copy) or descend (inside an inversion); every result is indexed by ALT bin.
+ * With M = {i : map i >= 0}, c = |M|, and over the c^2 pairs (i, j) of M x M: x = alt[i][j], y = ref[map i][map j], dl = x - y, all in fp64:
+ *   profile[b][i] = sum_j |dl| / c  (fp32; NaN for i outside M)        abs_mean[b]   = sum |dl| / c^2        abs_max[b] = max |dl|
+ *   delta_mean[b] = sum dl / c^2                                       rms[b]        = sqrt(sum dl^2 / c^2)                          (fp32, rounded once)
+ *   corr[b]       = C / sqrt(X Y)  (fp64: 1 - r of a small variant has to survive), the Pearson correlation over the c^2 pairs from two-pass centred
+ *                   sums: the means mx = sum x / c^2, my = sum y / c^2 first, then X = sum (x - mx)^2, Y = sum (y - my)^2, C = sum (x - mx)(y - my);
+ *                   NaN when c^2 < 2 or X or Y is exactly 0.0 (orca_screen_strata_scores' rule)
+ *   count[b]      = c (int32)
+ * Every floating-point output is NaN when c = 0.  A NaN pixel at a mapped pair makes that pair's scalar outputs and its row of `profile` NaN; one at an
+ * unmapped pair is never read.  Sums in an order fixed by (n, the bin map) alone, no atomics: a pair's results are bit for bit the same whatever B, its
+ * place in the batch and the strides.  Anything else is ORCA_EINVAL before any launch. */
+int orca_screen_paired_aligned_scores(orca_ctx* ctx, const float* alt, int64_t alt_bs, const float* ref, int64_t ref_bs, int B, int n, const int32_t* bin_map,
+                                      const int32_t* bin_map_host, float* profile, float* abs_mean, float* abs_max, float* delta_mean, float* rms, double* corr,
+                                      int32_t* count);
+
 /* Loops (screen.screen_1m(..., loops=)): dot calls on B maps m = maps[b * map_bs + i * n + j] (B >= 1, 1 <= n <= 256, map_bs >= n * n) of log observed /
  * expected, where a focal peak's enrichment over its local background is a difference of means.  Integers 0 <= p < w <= 16, 1 <= r <= 16,
  * d_min >= 2 w + 1, 1 <= K <= 4096 and an fp32 threshold T (not NaN).

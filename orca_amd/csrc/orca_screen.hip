@@ -327,6 +327,20 @@ extern "C" int orca_screen_strata_scores(orca_ctx* ctx, const float* alt, int64_
                 dist_abs, dist_rms, dist_corr, dist_count, mse, corr, scc);
 }
 
+// ---- paired aligned scores: every alt map against a reference map of its own (the SV screen) ------------------------------------------------------------------
+extern "C" int orca_screen_paired_aligned_scores(orca_ctx* ctx, const float* alt, int64_t alt_bs, const float* ref, int64_t ref_bs, int B, int n,
+                                                 const int32_t* bin_map, const int32_t* bin_map_host, float* profile, float* abs_mean, float* abs_max,
+                                                 float* delta_mean, float* rms, double* corr, int32_t* count) {
+  if (!ctx || !alt || !ref || !bin_map || !bin_map_host || !profile || !abs_mean || !abs_max || !delta_mean || !rms || !corr || !count)
+    return fail(ORCA_EINVAL, "orca_screen_paired_aligned_scores: NULL argument");
+  if (B < 1 || n < 1 || n > SCREEN_ALIGNED_MAX_BINS || alt_bs < (int64_t)n * n || ref_bs < (int64_t)n * n)
+    return fail(ORCA_EINVAL, "orca_screen_paired_aligned_scores: %d pairs (>= 1) of maps of %d bins (1..%d), batch strides %ld (alt), %ld (ref) (>= n * n)", B, n,
+                SCREEN_ALIGNED_MAX_BINS, (long)alt_bs, (long)ref_bs);
+  ORCA_TRY(check_bin_map("orca_screen_paired_aligned_scores", bin_map_host, B, n));
+  return launch(ctx, "screen_paired_aligned_scores_kernel", screen_paired_aligned_scores_kernel, dim3((unsigned)B), 512, alt, (long)alt_bs, ref, (long)ref_bs, n,
+                bin_map, profile, abs_mean, abs_max, delta_mean, rms, corr, count);
+}
+
 // ---- loops: dot calls and the enrichment at listed pixels ---------------------------------------------------------------------------------------------------------
 static int check_dot_params(const char* what, int B, int n, int64_t map_bs, int p, int w, int d_min) {
   if (B < 1 || n < 1 || n > SCREEN_ALIGNED_MAX_BINS || map_bs < (int64_t)n * n)

@@ -620,6 +620,116 @@ static __global__ void __launch_bounds__(256) screen_strata_scores_kernel(const 
   corr[b] = (c < 2 || X == 0.0 || Y == 0.0) ? dnan : C / sqrt(X * Y);
 }
 
+// ---- paired aligned scores (sv.sv_screen(..., scores=)): B alt maps, each against a reference map OF ITS OWN through its bin map --------------------------
+// include/orca_hip.h (orca_screen_paired_aligned_scores) has the definitions.  Pair b is alt + b * alt_bs against ref + b * ref_bs; M = {i : map i >= 0},
+// c = |M|, and over the c^2 pairs (i, j) of M x M: x = alt[i][j], y = ref[map i][map j], dl = x - y, all fp64.  One workgroup of 8 waves per pair with the
+// bin map in LDS, in the mould of screen_aligned_scores_kernel: wave w takes the alt rows w, w + 8, .., lane l the columns l, l + 64, .. - the alt row is
+// read along its columns, the reference row `map i` at columns `map j` (runs of consecutive addresses, ascending or, inside an inversion, descending).
+// Two passes over the maps: (1) sum x, sum y, sum dl, sum |dl| (also per row: the profile), sum dl^2, max |dl|; thread 0 makes the means mx, my of them;
+// (2) the centred sums X, Y, C.  The second pass re-reads what the first just touched (2 x 250 KB: it sits in L2); nothing is staged.  Every thread adds
+// its terms in the order it meets them, a sum crosses the lanes by xor shuffles (every lane ends with the same bits) and the 8 waves' sums are combined
+// serially by thread 0, wave 0 first: no atomics, and the order of every sum is fixed by (n, the bin map) alone - a pair's bits depend neither on B nor on
+// its place in the batch nor on the strides.  Only mapped pairs are read.  A NaN at one makes sum |dl| NaN, and with it every scalar (the maximum by an
+// explicit test: fmax drops a NaN) and the row's profile.
+static __device__ __forceinline__ double screen_wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+static __global__ void __launch_bounds__(512) screen_paired_aligned_scores_kernel(const float* __restrict__ alt, long alt_bs, const float* __restrict__ ref,
+                                                                                  long ref_bs, int n, const int* __restrict__ bin_map,
+                                                                                  float* __restrict__ profile, float* __restrict__ abs_mean,
+                                                                                  float* __restrict__ abs_max, float* __restrict__ delta_mean,
+                                                                                  float* __restrict__ rms, double* __restrict__ corr, int* __restrict__ count) {
+  __shared__ int s_map[SCREEN_ALIGNED_MAX_BINS];
+  __shared__ double s_red[8][6], s_mean[2];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  n = n > SCREEN_ALIGNED_MAX_BINS ? SCREEN_ALIGNED_MAX_BINS : n;
+  const int mine = screen_load_bin_map(bin_map + (long)b * n, n, s_map);
+  const int c = __syncthreads_count(mine >= 0);
+  const float* a = alt + (long)b * alt_bs;
+  const float* r = ref + (long)b * ref_bs;
+  const float qnan = __int_as_float(0x7fc00000);
+  const double dnan = (double)qnan, cc = (double)c * (double)c;
+  double sx = 0.0, sy = 0.0, sd = 0.0, sq = 0.0, sa = 0.0, mx_abs = 0.0;
+  for (int i = wv; i < n; i += 8) {
+    const int mi = s_map[i];                         // wave-uniform
+    if (mi < 0) {
+      if (lane == 0) profile[(long)b * n + i] = qnan;
+      continue;
+    }
+    double rs = 0.0;
+    for (int j = lane; j < n; j += 64) {
+      const int mj = s_map[j];
+      if (mj < 0) continue;
+      const double x = (double)a[(long)i * n + j], y = (double)r[(long)mi * n + mj];
+      const double dl = x - y, ad = fabs(dl);
+      sx += x;
+      sy += y;
+      sd += dl;
+      sq += dl * dl;
+      rs += ad;
+      mx_abs = fmax(mx_abs, ad);
+    }
+    rs = screen_wave_sum(rs);
+    if (lane == 0) profile[(long)b * n + i] = (float)(rs / (double)c);
+    sa += rs;                                        // the same in every lane
+  }
+  sx = screen_wave_sum(sx);
+  sy = screen_wave_sum(sy);
+  sd = screen_wave_sum(sd);
+  sq = screen_wave_sum(sq);
+  for (int o = 32; o > 0; o >>= 1) mx_abs = fmax(mx_abs, __shfl_xor(mx_abs, o, 64));
+  if (lane == 0) {
+    s_red[wv][0] = sx; s_red[wv][1] = sy; s_red[wv][2] = sd; s_red[wv][3] = sq; s_red[wv][4] = sa; s_red[wv][5] = mx_abs;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tx = 0.0, ty = 0.0, td = 0.0, tq = 0.0, ta = 0.0, tm = 0.0;
+    for (int k = 0; k < 8; ++k) {
+      tx += s_red[k][0]; ty += s_red[k][1]; td += s_red[k][2]; tq += s_red[k][3]; ta += s_red[k][4];
+      tm = fmax(tm, s_red[k][5]);
+    }
+    s_mean[0] = tx / cc;                             // c = 0: never used
+    s_mean[1] = ty / cc;
+    const bool none = c == 0;
+    abs_mean[b] = none ? qnan : (float)(ta / cc);
+    abs_max[b] = (none || ta != ta) ? qnan : (float)tm;
+    delta_mean[b] = none ? qnan : (float)(td / cc);
+    rms[b] = none ? qnan : (float)sqrt(tq / cc);
+    count[b] = c;
+  }
+  __syncthreads();                                   // the means are there, and s_red has been read
+  const double mx = s_mean[0], my = s_mean[1];
+  double X = 0.0, Y = 0.0, C = 0.0;
+  for (int i = wv; i < n; i += 8) {
+    const int mi = s_map[i];
+    if (mi < 0) continue;
+    for (int j = lane; j < n; j += 64) {
+      const int mj = s_map[j];
+      if (mj < 0) continue;
+      const double ex = (double)a[(long)i * n + j] - mx, ey = (double)r[(long)mi * n + mj] - my;
+      X = fma(ex, ex, X);                            // spelled out: where alt and ref hold the same bits, X, Y and C do too
+      Y = fma(ey, ey, Y);
+      C = fma(ex, ey, C);
+    }
+  }
+  X = screen_wave_sum(X);
+  Y = screen_wave_sum(Y);
+  C = screen_wave_sum(C);
+  if (lane == 0) {
+    s_red[wv][0] = X; s_red[wv][1] = Y; s_red[wv][2] = C;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tX = 0.0, tY = 0.0, tC = 0.0;
+    for (int k = 0; k < 8; ++k) {
+      tX += s_red[k][0]; tY += s_red[k][1]; tC += s_red[k][2];
+    }
+    corr[b] = (c < 2 || tX == 0.0 || tY == 0.0) ? dnan : tC / sqrt(tX * tY);
+  }
+}
+
 // ---- loops (screen.screen_1m(..., loops=)): dot calls per map, HiCCUPS' neighbourhoods on the model's log observed / expected ---------------------------
 // include/orca_hip.h (orca_screen_dot_calls) has the definitions: the eligible pixels, the five sets P, D, LL, H, V of offsets (a, b) with |a|, |b| <= w,
 // the enrichment e = mean P - max(mean D, mean LL, mean H, mean V) and what makes a pixel a dot.  screen_dot_enrich is the one place e is computed: `m`

@@ -987,6 +987,37 @@ def screen_strata_scores(ctx, alt, ref, bin_map=None, d_range=None, bin_map_dev=
     return out
 
 
+# paired aligned scores (orca_screen_paired_aligned_scores): every alt map against a reference map of its own - the readout of the SV screen
+PAIRED_SCORE_FIELDS = ("profile", "abs_mean", "abs_max", "delta_mean", "rms", "corr", "count")
+
+
+def screen_paired_aligned_scores(ctx, alt, ref, bin_map_host):
+    """B pairs of maps, alt [B, n, n] against ref [B, n, n] (both any batch stride, rows contiguous), pair b through row b of ``bin_map_host`` [B, n]
+    int32 numpy: the reference bin alt bin i stands for, or -1 (orca_screen_paired_aligned_scores; include/orca_hip.h has the definitions).  A dict of
+    device tensors: ``profile`` [B, n], ``abs_mean``, ``abs_max``, ``delta_mean``, ``rms`` [B] float32, ``corr`` [B] float64 and ``count`` [B] int32,
+    the mapped bins; every float is NaN for a pair with none."""
+    alt, ref = _f32_cuda(alt, "alt"), _f32_cuda(ref, "ref")
+    if alt.dim() != 3 or alt.shape[0] < 1 or alt.shape[1] != alt.shape[2] or ref.shape != alt.shape or ref.device != alt.device:
+        raise ValueError(f"alt, ref: [B,n,n] with B >= 1 on one device, got {tuple(alt.shape)} and {tuple(ref.shape)}")
+    B, n = alt.shape[0], alt.shape[1]
+    for t, name in ((alt, "alt"), (ref, "ref")):
+        if t.stride(2) != 1 or t.stride(1) != n:
+            raise ValueError(f"{name}: [{B},{n},{n}] with contiguous maps")
+    m = _host_table(bin_map_host, np.int32, n, "bin map")
+    if m.shape[0] != B:
+        raise ValueError(f"bin map: [{B},{n}] int32, one row per pair")
+    alt_bs, ref_bs = (t.stride(0) if B > 1 else max(t.stride(0), n * n) for t in (alt, ref))       # B = 1: torch may report any stride for the one map
+    dev = alt.device
+    md = torch.from_numpy(m).to(dev)
+    out = dict(zip(PAIRED_SCORE_FIELDS[:5], _f32_outputs(dev, (B, n), (B,), (B,), (B,), (B,))))
+    out["corr"] = torch.empty(B, dtype=torch.float64, device=dev)
+    out["count"] = torch.empty(B, dtype=torch.int32, device=dev)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_paired_aligned_scores(ctx.handle, _dev_p(alt), alt_bs, _dev_p(ref), ref_bs, B, n, _dev_p(md), _np_p(m),
+                                                        *(_dev_p(out[k]) for k in PAIRED_SCORE_FIELDS)), "orca_screen_paired_aligned_scores")
+    return out
+
+
 # loops (orca_screen_dot_calls, orca_screen_dot_enrichment): dot calls per map and the enrichment at listed pixels
 def _dot_args(maps, p, w, d_min):
     maps = _f32_cuda(maps, "maps")

@@ -115,6 +115,132 @@ def assemble_codes(genome_codes, pieces):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# Impact scores on aligned bins.  The two windows of a variant are centred on different coordinates (`sv_windows`), every level zooms to a
+# start of its own, behind a deletion or a duplication every locus sits elsewhere and inside an inversion the loci run backwards: an alt map
+# cannot be compared with its reference map bin with bin.  The BIN MAP of a level says which reference bin an alt bin stands for; it comes
+# from the same piece list that assembles the allele, and orca_screen_paired_aligned_scores scores alt against its own reference through it.
+# ---------------------------------------------------------------------------------------------------------------------------------
+LEVELS = 6
+LEVEL_BINS = 250
+SCORE_FIELDS = ("abs_mean", "abs_max", "delta_mean", "rms", "corr", "profile")
+
+
+def allele_bin_map(pieces, alt_start, ref_start, binsize, n=250):
+    """int32 [n]: the reference bin each of the ``n`` alt bins of ``binsize`` bases from ``alt_start`` (alt-allele coordinates) stands for, in a
+    reference window of the same geometry from ``ref_start`` - or -1.  ``pieces``: the allele over the whole chromosome (`allele_pieces`).  Alt
+    bin i is placed by its midpoint base x = alt_start + i * binsize + binsize // 2 (the rule of `screen.bin_map`): the piece (src, ln, strand)
+    that holds x, at offset off, gives the reference base y = src + off ('+') or src + ln - 1 - off ('-'), and the bin is (y - ref_start) //
+    binsize if that lies in 0 .. n - 1.  -1 also where x is outside the allele.  No special cases: the map ascends with a jump across a
+    deletion, repeats reference bins in a duplication's second copy (results are indexed by ALT bin) and descends inside an inversion."""
+    binsize, n = int(binsize), int(n)
+    out = np.full(n, -1, dtype=np.int32)
+    pieces = [p for p in pieces if p[1] > 0]
+    if not pieces or n < 1:
+        return out
+    src = np.array([p[0] for p in pieces], dtype=np.int64)
+    ln = np.array([p[1] for p in pieces], dtype=np.int64)
+    minus = np.array([p[2] == "-" for p in pieces])
+    ends = np.cumsum(ln)
+    x = int(alt_start) + np.arange(n, dtype=np.int64) * binsize + binsize // 2
+    k = np.minimum(np.searchsorted(ends, x, side="right"), len(pieces) - 1)         # the piece with ends[k] - ln[k] <= x < ends[k]
+    off = x - (ends[k] - ln[k])
+    y = np.where(minus[k], src[k] + ln[k] - 1 - off, src[k] + off)
+    m = (y - int(ref_start)) // binsize
+    ok = (x >= 0) & (x < ends[-1]) & (m >= 0) & (m < n)
+    out[ok] = m[ok]
+    return out
+
+
+def level_bin_maps(sv, chrlen, ref_out, alt_out):
+    """int32 [6, 250]: the bin map of every level of a variant's two windows, from the ``start_coords`` of its two output dicts (`genomepredict`'s,
+    `sv_screen`'s): level k has bins of 128000 >> k bases.  The starts depend on the windows' coordinates only, so the map is the same for every
+    model of a call.  Registration is exact to half a bin of the level."""
+    pieces = allele_pieces(sv, chrlen)
+    return np.stack([allele_bin_map(pieces, alt_out["start_coords"][k], ref_out["start_coords"][k], 128000 >> k, LEVEL_BINS) for k in range(LEVELS)])
+
+
+def junction_bins(sv, chrlen, alt_out):
+    """int32 [6, J]: per level, the alt bin that holds each of the J junctions between the pieces of the allele (the first base behind the
+    junction; J = 1 for a deletion, 2 for a duplication or an inversion), -1 where the level's window does not hold it.  ``profile`` at these
+    bins is the change at the breakpoints."""
+    at = np.cumsum([p[1] for p in allele_pieces(sv, chrlen)], dtype=np.int64)[:-1]
+    out = np.full((LEVELS, len(at)), -1, dtype=np.int32)
+    for k in range(LEVELS):
+        b = (at - int(alt_out["start_coords"][k])) // (128000 >> k)
+        ok = (b >= 0) & (b < LEVEL_BINS)
+        out[k, ok] = b[ok]
+    return out
+
+
+def paired_aligned_scores_host(alt, ref, bin_map):
+    """fp64 numpy restatement of orca_screen_paired_aligned_scores: alt [B, n, n] against ref [B, n, n], pair b through ``bin_map`` [B, n] (or one
+    [n] for all).  With M = the alt bins whose map is >= 0, c = |M|, and over M x M: x = alt[i, j], y = ref[map i, map j], dl = x - y.  A dict of
+    ``profile`` [B, n] = sum_j |dl| / c (NaN outside M), ``abs_mean`` = sum |dl| / c^2, ``abs_max`` = max |dl|, ``delta_mean`` = sum dl / c^2,
+    ``rms`` = sqrt(sum dl^2 / c^2), ``corr`` = the Pearson correlation over the c^2 pairs from two-pass centred sums (the means first, then X, Y,
+    C; NaN when c^2 < 2 or X or Y is exactly 0) - all float64 [B] - and ``count`` [B] int32 = c.  Every float is NaN for a pair with c = 0."""
+    a, r = np.asarray(alt, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    if a.ndim != 3 or a.shape[1] != a.shape[2] or r.shape != a.shape:
+        raise ValueError("alt, ref: [B, n, n]")
+    B, n = a.shape[0], a.shape[1]
+    bm = np.asarray(bin_map, dtype=np.int64)
+    bm = np.broadcast_to(bm, (B, n)) if bm.ndim == 1 else bm
+    if bm.shape != (B, n) or bm.min(initial=0) < -1 or bm.max(initial=0) >= n:
+        raise ValueError(f"bin map: [{B}, {n}] (or [{n}]) with values -1 .. {n - 1}")
+    out = {k: np.full(B, np.nan) for k in ("abs_mean", "abs_max", "delta_mean", "rms", "corr")}
+    out["profile"], out["count"] = np.full((B, n), np.nan), np.zeros(B, dtype=np.int32)
+    with np.errstate(invalid="ignore"):
+        for b in range(B):
+            M = np.flatnonzero(bm[b] >= 0)
+            c = out["count"][b] = M.size
+            if c == 0:
+                continue
+            x, y = a[b][np.ix_(M, M)], r[b][np.ix_(bm[b, M], bm[b, M])]
+            dl = x - y
+            out["profile"][b, M] = np.abs(dl).sum(axis=1) / c
+            out["abs_mean"][b], out["abs_max"][b] = np.abs(dl).sum() / c ** 2, np.abs(dl).max()
+            out["delta_mean"][b], out["rms"][b] = dl.sum() / c ** 2, np.sqrt((dl * dl).sum() / c ** 2)
+            ex, ey = x - x.sum() / c ** 2, y - y.sum() / c ** 2
+            X, Y, C = (ex * ex).sum(), (ey * ey).sum(), (ex * ey).sum()
+            if c >= 2 and X != 0.0 and Y != 0.0:
+                out["corr"][b] = C / np.sqrt(X * Y)
+    return out
+
+
+def _scores_entry(sv, chrlen, ref_out, alt_out):
+    """The model-independent part of an entry's ``scores``."""
+    bm = level_bin_maps(sv, chrlen, ref_out, alt_out)
+    return {"bin_map": bm, "count": (bm >= 0).sum(axis=1).astype(np.int32), "junction_bins": junction_bins(sv, chrlen, alt_out), "models": []}
+
+
+def _model_scores(ctx, ref_maps, alt_maps, bin_map):
+    """One model's scores of one variant: ``ref_maps``, ``alt_maps`` [6, C, n, n] contiguous on the device, ``bin_map`` [6, n] (repeated per
+    target channel here) - one launch of 6 C pairs on the current stream; a dict of numpy arrays [6, C] (``profile`` [6, C, n])."""
+    lv, C, n = alt_maps.shape[0], alt_maps.shape[1], alt_maps.shape[2]
+    got = engine.screen_paired_aligned_scores(ctx, alt_maps.reshape(lv * C, n, n), ref_maps.reshape(lv * C, n, n), np.repeat(bin_map, C, axis=0))
+    return {k: got[k].cpu().numpy().reshape((lv, C, n) if k == "profile" else (lv, C)) for k in SCORE_FIELDS}
+
+
+def _dict_maps(out, m, device):
+    """Model m's six maps of a `genomepredict` output dict as one [6, C, n, n] float32 tensor on ``device``."""
+    maps = np.stack([np.asarray(p, dtype=np.float32).reshape((-1,) + np.shape(p)[-2:]) for p in out["predictions"][m]])
+    return torch.from_numpy(np.ascontiguousarray(maps)).to(device)
+
+
+def sv_scores(sv, ref_out, alt_out, chrlen, device=None):
+    """The ``scores`` of `sv_screen(..., scores=True)` from ANY pair of `genomepredict` output dicts of a variant's reference and alternative
+    allele (the `process_*` drivers', `sv_screen(..., incremental=False)`'s): the maps are uploaded to ``device`` (default: the current MI355X)
+    and scored by the same kernel through `level_bin_maps` - the same dict."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if ref_out["predictions"] is None or alt_out["predictions"] is None:
+        raise ValueError("sv_scores: the output dicts hold no maps (keep_maps=False)")
+    entry = _scores_entry(sv, chrlen, ref_out, alt_out)
+    ctx = engine.get_context(dev)
+    for m in range(len(alt_out["predictions"])):
+        entry["models"].append(_model_scores(ctx, _dict_maps(ref_out, m, dev), _dict_maps(alt_out, m, dev), entry["bin_map"]))
+    return entry
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # Incremental encoding (round 4).  The reference pushes every allele window through the whole Encoder (orca_predict.py:1510-1817 build
 # ref / alt windows, :231 encodes each): a screen of 1 024 variants on one chromosome encodes the same bases ~2 000 times - 74 % of
 # the screen's time.  The Encoder is a translation-covariant stack on a 4 kb grid: Encoder bin j of a sequence depends on the bases
@@ -793,22 +919,22 @@ def _cascade_windows(model, enc0, params):
     return torch.stack(merged), starts
 
 
-def _window_outputs(model, merged, starts, params, mchr):
-    """`genomepredict`'s output dict (one model) per window."""
+def _window_outputs(model, merged, starts, params, mchr, keep_maps=True):
+    """`genomepredict`'s output dict (one model) per window; ``keep_maps=False``: without the maps (no copy to the host, "predictions": None)."""
     levels = [32, 16, 8, 4, 2, 1]
-    host = merged.cpu().numpy()
+    host = merged.cpu().numpy() if keep_maps else None
     outs = []
     for w, (mpos, wpos) in enumerate(params):
         sc = [wpos - 16000000 + s * 4000 for s in starts[2 * w]]
         # [250,250] per level for single-target models, [C,250,250] otherwise (orca_predict.py:510-523)
-        outs.append({"predictions": [[host[w, j, 0] if host.shape[2] == 1 else host[w, j] for j in range(6)]], "experiments": None, "start_coords": sc,
+        outs.append({"predictions": None if host is None else [[host[w, j, 0] if host.shape[2] == 1 else host[w, j] for j in range(6)]], "experiments": None, "start_coords": sc,
                      "end_coords": [int(sc[ii] + 32000000 / 2 ** ii) for ii in range(6)], "chr": mchr, "annos": None,
                      "normmats": [[model.normmats[ii] for ii in levels]]})
     return outs
 
 
 def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, incremental=True, min_uses=3, stats=None, on_result=None,
-              streams=None, group=2, stage3="auto"):
+              streams=None, group=2, stage3="auto", scores=False, keep_maps=True):
     """Predict reference and alternative allele (6 maps each, per model) for this rank's share of ``svs``
     (independent windows: replicas, no collective).  genome_codes: [chrlen] uint8 tensor on the MI355X.
     Returns {sv_index: {"sv": SV, "ref": output_dict, "alt": output_dict}} with genomepredict's output dicts.
@@ -832,9 +958,21 @@ def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, i
     ``stage3``: the stage-3 cache (`Stage3Cache`: windows at arbitrary base positions take stages 1-3 of the Encoder from the chromosome's
     cached planes - 1 KB of HBM per base of the chromosome and model).  "auto" (default): built when the screen has at least 32 window
     strands per 32 Mb of chromosome whose 4 kb phase is not shared, the Encoders run the default arithmetic and the planes fit beside 40 GB of
-    workspace; True / False force / forbid it."""
+    workspace; True / False force / forbid it.
+    ``scores``: every entry gains ``entry["scores"]`` - how far the alt maps are from the variant's OWN reference maps, level by level, on aligned
+    bins (`level_bin_maps`; orca_screen_paired_aligned_scores, include/orca_hip.h has the definitions), computed on the device from the maps as
+    they leave the decoders (after the range-safe retry, if there was one):
+        {"bin_map": int32 [6, 250], "count": int32 [6] (the mapped bins per level), "junction_bins": int32 [6, J] (`junction_bins`),
+         "models": [{"abs_mean", "abs_max", "delta_mean", "rms": float32 [6, C], "corr": float64 [6, C], "profile": float32 [6, C, 250]} per model]}
+    indexed by level (32 Mb first) and target channel, ``profile`` also by ALT bin.  A level whose two windows share no locus has count 0 and
+    NaN scores - the finest levels of a deletion larger than their window, since `sv_windows` centres the reference window on the deleted span.
+    With ``incremental=False`` the scores come from the returned host maps (`sv_scores`).
+    ``keep_maps=False`` (needs ``scores=True``): the maps are not copied to the host - the output dicts keep ``start_coords``, ``end_coords``,
+    ``chr`` and ``normmats`` and have "predictions": None.  A screen then returns a few KB per variant instead of 3 MB."""
     import time
     from . import dist, orca_predict
+    if not keep_maps and not scores:
+        raise ValueError("sv_screen: keep_maps=False returns nothing without scores=True")
     res = {}
     mine = list(dist.shard_indices(len(svs), rank, world))
     if not incremental:
@@ -844,6 +982,10 @@ def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, i
             ref = orca_predict.genomepredict(assemble_codes(genome_codes, rp)[None], mchr, rm, rw, models=models)
             alt = orca_predict.genomepredict(assemble_codes(genome_codes, ap)[None], mchr, am, aw, models=models)
             entry = {"sv": sv, "ref": ref, "alt": alt}
+            if scores:
+                entry["scores"] = sv_scores(sv, ref, alt, chrlen, genome_codes.device)
+                if not keep_maps:
+                    ref["predictions"] = alt["predictions"] = None
             if on_result is not None:
                 on_result(i, entry)
             else:
@@ -952,15 +1094,20 @@ def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, i
                         merged, starts = _cascade_windows(model, enc0, pl["params"])
                     ctx.take_overflow()
                 encoded += slot["n"]
-                outs = _window_outputs(model, merged, starts, pl["params"], mchr)
+                outs = _window_outputs(model, merged, starts, pl["params"], mchr, keep_maps)
                 for v, i in enumerate(ch):
                     r, a = outs[2 * v], outs[2 * v + 1]
                     if mi == 0:
                         entries[i] = {"sv": svs[i], "ref": r, "alt": a}
+                        if scores:
+                            entries[i]["scores"] = _scores_entry(svs[i], chrlen, r, a)
                     else:
                         for o, n in ((entries[i]["ref"], r), (entries[i]["alt"], a)):
-                            o["predictions"] += n["predictions"]
+                            if keep_maps:
+                                o["predictions"] += n["predictions"]
                             o["normmats"] += n["normmats"]
+                    if scores:      # the final maps of this (variant, model), still on the device, on the stream the decoders ran on
+                        entries[i]["scores"]["models"].append(_model_scores(ctx, merged[2 * v], merged[2 * v + 1], entries[i]["scores"]["bin_map"]))
                 if pool is None and k + 1 < len(units):
                     prep(k + 1)
                 if mi == len(models) - 1:

@@ -1,6 +1,10 @@
-"""SV screen timing (BASELINE configs[4]) on one GPU: python tools/time_sv_screen.py [n_svs] [incremental 0|1] [streams: auxiliary contexts of the local encodes, 0 = none, -1 = default] [align: 1 = unaligned (default), 4000 = the 4 kb grid]"""
+"""SV screen timing (BASELINE configs[4]) on one GPU: python tools/time_sv_screen.py [n_svs] [incremental 0|1] [streams: auxiliary contexts of the local encodes, 0 = none, -1 = default] [align: 1 = unaligned (default), 4000 = the 4 kb grid]
+--scores: what the on-device impact scores cost - the same variants through (a) the plain screen, (b) scores=True, (c) scores=True, keep_maps=False,
+alternated in one run, best of three each; writes profiles/sv_screen_scores.json"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+SCORES = "--scores" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--scores"]
 import torch
 from orca_amd import orca_models, sv
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 32
@@ -14,6 +18,31 @@ genome = torch.randint(0, 4, (40_000_000,), device=dev, generator=g, dtype=torch
 svs = sv.synth_svs(n + 2, 40_000_000, align=align)
 sv.sv_screen([h1], genome, svs[:2], 40_000_000, incremental=inc, min_uses=1, streams=streams)
 torch.cuda.synchronize()
+if SCORES:
+    import json
+    modes = {"plain": {}, "scores": {"scores": True}, "scores_no_maps": {"scores": True, "keep_maps": False}}
+    runs = {k: [] for k in modes}
+    for rep in range(3):
+        for k, kw in modes.items():
+            st = {}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sv.sv_screen([h1], genome, svs[2:], 40_000_000, incremental=inc, stats=st, streams=streams, on_result=lambda i, e: None, **kw)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            build = (st.get("stage3_cache") or {}).get("build_s", 0.0)      # the stage cache is rebuilt by every call: its time is not the screen's
+            runs[k].append({"total_s": round(dt, 4), "stage_cache_build_s": build, "ms_per_sv": round((dt - build) / n * 1e3, 3)})
+            print(k, runs[k][-1])
+    best = {k: min(r["ms_per_sv"] for r in v) for k, v in runs.items()}
+    spread = max(r["ms_per_sv"] for r in runs["plain"]) - best["plain"]
+    out = {"tool": "tools/time_sv_screen.py --scores", "n_svs": n, "incremental": inc, "streams": streams, "align": align, "runs": runs,
+           "best_ms_per_sv": best, "plain_spread_ms_per_sv": round(spread, 3),
+           "scores_cost_ms_per_sv": round(best["scores"] - best["plain"], 3), "scores_within_plain_spread": bool(best["scores"] <= best["plain"] + spread),
+           "no_maps_saving_ms_per_sv": round(best["plain"] - best["scores_no_maps"], 3)}
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sv_screen_scores.json")
+    json.dump(out, open(path, "w"), indent=1)
+    print(json.dumps({k: v for k, v in out.items() if k != "runs"}))
+    sys.exit(0)
 t0 = time.perf_counter()
 st = {}
 sv.sv_screen([h1], genome, svs[2:], 40_000_000, incremental=inc, stats=st, streams=streams)
