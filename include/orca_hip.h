@@ -530,13 +530,15 @@ int orca_decoder1m_forward(orca_ctx* ctx, orca_net* net, const float* x, int64_t
                            int64_t sx_l, int B, int n, float* out, int accumulate);
 
 /* For tests: a Decoder / Decoder_1m forward (arguments of orca_decoder_forward_mt; a Decoder_1m takes distenc = y = NULL) that stops behind
- * the launches that complete `stage` and writes that feature map, decoded from its 16-bit planes, to map_out [B,channels,n,n] (contiguous).
- * It is the forward's own launch sequence with an early return.  Stages:
+ * the launches that complete `stage` and writes that feature map - decoded from its 16-bit planes, or copied from the fp32 planes of an
+ * ORCA_PRECISION_F32 net - to map_out [B,channels,n,n] (contiguous).  It is the forward's own launch sequence with an early return.  Stages:
  *   0      IN: the Decoder's distenc chunk (T channels, then zeros; 16) / the Decoder_1m's x_i + x_j (128)
  *   1      after lcombinerD's first conv (Decoder; 64)
  *   2      A (Decoder): combinerD(.) + . in channels 0..63; with y 80 channels - the up-sampled y in 64..64+T-1, zeros to 79
  *   3 + i  the residual stream after block i (64): i < 28 (Decoder; block 0 = lcombiner / combiner with y) or i < 19 (Decoder_1m)
- * ORCA_EINVAL: a stage the net kind does not have, `channels` other than the stage's, an ORCA_PRECISION_F32 net (no 16-bit planes). */
+ * An ORCA_PRECISION_F32 net hands out what its fp32 maps hold: stage 0 of a Decoder is the WHOLE input map, 136 channels (x_i + x_j in
+ * 0..127, distenc in 128..128+T-1, zeros to 135), and A with y has 72 (the up-sampled y in 64..64+T-1, zeros to 71); the rest as above.
+ * ORCA_EINVAL: a stage the net kind does not have, `channels` other than the stage's. */
 int orca_decoder_probe(orca_ctx* ctx, orca_net* net, const float* x, int64_t sx_b, int64_t sx_c, int64_t sx_l,
                        const float* distenc, int64_t sd_b, int64_t sd_c, int64_t sd_h, int64_t sd_w, const float* y,
                        int64_t sy_b, int64_t sy_c, int64_t sy_h, int64_t sy_w, int B, int n, int stage, int channels,

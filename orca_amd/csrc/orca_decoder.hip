@@ -142,7 +142,8 @@ static FinalArgs final_args(const orca_net* net, const float* cur, long cur_bs, 
   return a;
 }
 
-// orca_decoder_probe: the forward stops behind the launches that complete `stage` and hands out that map as fp32 [B][channels][n][n].
+// orca_decoder_probe: the forward stops behind the launches that complete `stage` and hands out that map as fp32 [B][channels][n][n] - in
+// either arithmetic: decoder_m16 decodes its M16 units, the exact-fp32 branch of decoder_common copies its planes.
 // Stages (oracle/orca_oracle.py `decoder_stages`): 0 = IN, 1 = after lcombinerD.a (Decoder), 2 = A (Decoder), 3 + i = the residual stream after block i.
 struct DecoderProbe {
   int stage, channels;
@@ -306,7 +307,6 @@ static int decoder_common(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx
     return decoder_m16<1, 0>(ctx, net, x, sx_c, sx_l, de, sd_c, sd_h, sd_w, y, sy_c, sy_h, sy_w, B, n, out, accumulate, probe);
   if (net->precision == ORCA_PRECISION_F16)
     return decoder_m16<1, 1>(ctx, net, x, sx_c, sx_l, de, sd_c, sd_h, sd_w, y, sy_c, sy_h, sy_w, B, n, out, accumulate, probe);
-  if (probe) return fail(ORCA_EINVAL, "orca_decoder_probe: an f32 net has no M16 stages (its convs are conv2d_3x3_kernel)");
   // exact fp32: maps as planes [channels][n][256], conv2d_3x3_kernel layer by layer
   typedef DecMaps<float> M;
   const bool is1m = net->kind == ORCA_NET_DECODER_1M;
@@ -318,26 +318,48 @@ static int decoder_common(orca_ctx* ctx, orca_net* net, const RowSrc& x, long sx
   auto take = [&](size_t floats) { return M{ws_take(ctx, B * floats), (long)floats, 0}; };
   const M IN = take(szIN), A = take(szA), Bf = take(sz64), Cf = take(sz64), Df = take(sz64), T = take(sz32);
   hipStream_t s = ctx->stream;
+  // probe: the first probe->channels planes of map `m` are what stage k leaves - copy them out of their padded rows and stop
+  auto emit = [&](const M& m) -> int {
+    for (int b = 0; b < B; ++b)
+      hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)(probe->channels * n)), dim3(ORCA_LDW), 0, s, m.p + b * m.bs,
+                         probe->out + (size_t)b * probe->channels * n * n, n, 0);
+    LAUNCHCHECK("pad_rows_kernel");
+    return DEC_STOP;
+  };
+#define PROBE(k, m) \
+  if (probe && probe->stage == (k)) return emit(m)
   for (int b = 0; b < B; ++b) {
     hipLaunchKernelGGL(outer_sum_kernel, dim3((unsigned)n, (unsigned)cin0), dim3(64), 0, s, x.at(b), sx_c, sx_l,
                        de.at(b), sd_c, sd_h, sd_w, nt2, IN.p + b * szIN, n, cin0);
     LAUNCHCHECK("outer_sum_kernel");
   }
+  const auto stop = [](int rc) { return rc == DEC_STOP ? ORCA_OK : rc; };
+  if (probe && probe->stage == 0) return stop(emit(IN));
   const ConvLayer* L = net->convs.data();
+  const ConvLayer* pairs = is1m ? L : L + 8;
+  const int npairs = is1m ? 19 : 28;
   auto conv = [&](const ConvLayer& l, const M& src, const M& dst, const M* res, int relu) -> int {
     ORCA_TRY(launch_conv2d(ctx, l, src.p, src.bs, dst.p, dst.bs, res ? res->p : nullptr, res ? res->bs : 0, B, n, relu));
-    if (is1m || !y || &l != L + 3) return ORCA_OK;
-    for (int b = 0; b < B; ++b) {   // behind combinerD: the upsampled coarse prediction into channels 64.. of A
-      hipLaunchKernelGGL(upsample2d_x2_kernel, dim3((unsigned)n, 8), dim3(ORCA_LDW), 0, s, y.at(b), sy_c, sy_h, sy_w, nt2,
-                         A.p + b * szA + 64 * plane, n, net->upsample_mode == ORCA_UPSAMPLE_BILINEAR ? 1 : 0, 8);
-      LAUNCHCHECK("upsample2d_x2_kernel");
-    }
+    if (!is1m && &l == L) PROBE(1, dst);
+    if (is1m || &l != L + 3) return ORCA_OK;
+    if (y)
+      for (int b = 0; b < B; ++b) {   // behind combinerD: the upsampled coarse prediction into channels 64.. of A
+        hipLaunchKernelGGL(upsample2d_x2_kernel, dim3((unsigned)n, 8), dim3(ORCA_LDW), 0, s, y.at(b), sy_c, sy_h, sy_w, nt2,
+                           A.p + b * szA + 64 * plane, n, net->upsample_mode == ORCA_UPSAMPLE_BILINEAR ? 1 : 0, 8);
+        LAUNCHCHECK("upsample2d_x2_kernel");
+      }
+    PROBE(2, dst);                  // A: 64 channels, with y 72
     return ORCA_OK;
   };
-  const ConvLayer* pairs = is1m ? L : L + 8;
-  auto block = [&](int i, const M& cur, const M& oth) -> int { return residual_block(conv, pairs + 4 * i, cur, oth, T); };
+  auto block = [&](int i, const M& cur, const M& oth) -> int {
+    PROBE(3 + i - 1, cur);
+    return residual_block(conv, pairs + 4 * i, cur, oth, T);
+  };
   M cur;
-  ORCA_TRY(decoder_chain(net, (bool)y, IN, A, Bf, Cf, Df, T, conv, block, &cur));
+  int rc = decoder_chain(net, (bool)y, IN, A, Bf, Cf, Df, T, conv, block, &cur);
+  if (rc == ORCA_OK && probe && probe->stage == 3 + npairs - 1) rc = emit(cur);
+#undef PROBE
+  if (rc != ORCA_OK) return stop(rc);
   const FinalArgs fa = final_args(net, cur.p, cur.bs, out, n, accumulate);
   hipLaunchKernelGGL(final_sym_kernel, dim3((unsigned)n, (unsigned)B), dim3(256), 0, s, fa);
   LAUNCHCHECK("final_sym_kernel");
@@ -409,7 +431,10 @@ extern "C" int orca_decoder_probe(orca_ctx* ctx, orca_net* net, const float* x, 
   const int last = 3 + (is1m ? 19 : 28) - 1;
   if (stage < 0 || stage > last || (is1m && (stage == 1 || stage == 2)))
     return fail(ORCA_EINVAL, "orca_decoder_probe: this net has no stage %d", stage);
-  const int want = stage == 0 ? (is1m ? 128 : 16) : (stage == 2 && y ? 80 : 64);
+  // an f32 net hands out what its fp32 planes hold: the whole 136-channel input map of a Decoder (128 outer-sum, T distenc, zeros), A with the
+  // 8 planes upsample2d_x2_kernel writes
+  const bool f32 = net->precision == ORCA_PRECISION_F32;
+  const int want = stage == 0 ? (is1m ? 128 : (f32 ? 136 : 16)) : (stage == 2 && y ? (f32 ? 72 : 80) : 64);
   if (channels != want) return fail(ORCA_EINVAL, "orca_decoder_probe: stage %d has %d channels, got %d", stage, want, channels);
   const DecoderProbe probe{stage, channels, map_out};
   RowSrc xs, ds, ys;

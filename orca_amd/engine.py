@@ -322,6 +322,7 @@ class Net:
     def __init__(self, ctx, kind, convs, upsample_mode=_lib.ORCA_UPSAMPLE_BILINEAR):
         lib = _lib.load()
         self.ctx, self.kind = ctx, kind
+        self.precision = "f32"          # what orca_net_create leaves; `set_precision` keeps it current
         self.handle = ctypes.c_void_p()
         descs = make_descs(convs)  # `convs` keeps the numpy arrays alive during the call
         check(lib.orca_net_create(ctx.handle, kind, descs, len(convs), upsample_mode, ctypes.byref(self.handle)), "orca_net_create")
@@ -339,6 +340,7 @@ class Net:
         if name not in _lib.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}, got {name!r}")
         check(_lib.load().orca_net_set_precision(self.handle, _lib.PRECISIONS[name]), "orca_net_set_precision")
+        self.precision = name
 
     def set_encoder_form(self, name):
         """Encoder nets: force a less composed form of stage 1-3's linear groups (include/orca_hip.h: ORCA_ENCODER_FORM_*; the parity suite's handle)."""
@@ -1237,7 +1239,8 @@ def decoder1m_forward(net, x, out=None, accumulate=False):
 def decoder_probe(net, x, distenc, y, stage):
     """Test entry (orca_decoder_probe): the Decoder / Decoder_1m forward of ``net`` stopped behind the launches that complete ``stage``;
     returns that feature map as fp32 [B,C,n,n].  Stages: 0 = IN (16 channels; Decoder_1m 128), 1 = after lcombinerD's first conv, 2 = A
-    (80 channels with y, else 64), 3 + i = the residual stream after block i.  A Decoder_1m takes distenc = y = None."""
+    (80 channels with y, else 64), 3 + i = the residual stream after block i.  A Decoder_1m takes distenc = y = None.  An exact-fp32 net hands
+    out what its fp32 maps hold: stage 0 of a Decoder is the whole 136-channel input map (x_i + x_j, distenc, zeros), A with y has 72."""
     x = _f32_cuda(x, "x")
     B, C, n = x.shape
     if C != 128:
@@ -1255,7 +1258,8 @@ def decoder_probe(net, x, distenc, y, stage):
         if tuple(y.shape) != (B, T, n // 2, n // 2):
             raise ValueError(f"coarse prediction must be [{B},{T},{n // 2},{n // 2}], got {tuple(y.shape)}")
         yp, sy = _p(y), (y.stride(0), y.stride(1), y.stride(2), y.stride(3))
-    channels = (128 if is1m else 16) if stage == 0 else (80 if stage == 2 and y is not None else 64)
+    f32 = net.precision == "f32"
+    channels = (128 if is1m else 136 if f32 else 16) if stage == 0 else ((72 if f32 else 80) if stage == 2 and y is not None else 64)
     out = torch.empty((B, channels, n, n), dtype=torch.float32, device=x.device)
     net.ctx.sync_stream()
     check(_lib.load().orca_decoder_probe(net.ctx.handle, net.handle, _p(x), x.stride(0), x.stride(1), x.stride(2), dp, *sd, yp, *sy, B, n,

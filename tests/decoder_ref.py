@@ -1,5 +1,6 @@
 """fp64 references for the Decoders stage by stage (oracle `decoder_stages` and its pieces, as numpy), the residual block of dilation
-16 / 32 / 64 on its own, and the inputs the GPU tests share.  The counterpart of tests/encoder_ref.py."""
+16 / 32 / 64 on its own, what the exact-fp32 nets' maps add (the 136-channel stage 0, the 72-channel A, the torch-fp32 yardstick, an exactly
+summable conv case), and the inputs the GPU tests share.  The counterpart of tests/encoder_ref.py."""
 import functools
 
 import numpy as np
@@ -68,22 +69,72 @@ def first(sd, x, in0):
     return _np(O.decoder_first(sd, x, in0, F64))
 
 
-def mat(sd, s1):
+def mat(sd, s1, dtype=F64):
     """Channels 0..63 of stage 2 from stage 1."""
-    return _np(O.decoder_mat(sd, s1, None, F64))
+    return _np(O.decoder_mat(sd, s1, None, dtype))
 
 
-def block(sd, kind, i, cur):
-    return _np(O.decoder_block(sd, kind, i, cur, F64))
+def block(sd, kind, i, cur, dtype=F64):
+    return _np(O.decoder_block(sd, kind, i, cur, dtype))
 
 
-def final(sd, cur):
-    return _np(O.final_sym(sd, cur, F64))
+def final(sd, cur, dtype=F64):
+    return _np(O.final_sym(sd, cur, dtype))
 
 
 def stages(sd, kind, x, distenc=None, y=None, upsample_mode="bilinear", dtype=F64):
     st = O.decoder_1m_stages(sd, x, dtype) if kind == "Decoder_1m" else O.decoder_stages(sd, x, distenc, y, upsample_mode, dtype)
     return {k: _np(v) for k, v in st.items()}
+
+
+# ---- the exact-fp32 nets (tests/test_gpu_decoder_f32_stages.py) ------------------------------------------------------------------------------
+# Their probe hands out what the fp32 planes hold: stage 0 of a Decoder is the WHOLE 136-channel input map (x_i + x_j in 0..127, distenc in
+# 128..128+T-1, zeros), A with y has 72 channels (64 + the 8 planes of the up-sampled coarse prediction).
+F32_IN_CHANNELS, F32_A_CHANNELS = 136, 72
+# A convolution stage's bound is YARD_FACTOR x its YARDSTICK: the rel_err of the same stage on the same input in torch fp32 on the CPU against
+# the fp64 reference.  5.5 (a plain sequential K-term fp32 chain - what the kernel's fmaf chain is - has 1.2 .. 5.5 x the error of torch's
+# blocked sum: 1.47e-6 against 2.67e-7 at cin 136, d 1) x 3 (order, fmaf, the extreme-value spread between shapes).
+# test_decoder_stages_cpu.py proves that such a chain stays within it and that fp16-rounded operands do not.
+YARD_FACTOR = 16
+
+
+def head_f32(x, distenc, y=None, upsample_mode="bilinear"):
+    """(stage 0 [B,136,n,n], channels 64..71 of stage 2 [B,8,n,n] or None) of an exact-fp32 Decoder."""
+    in0, up = head(x, distenc, y, upsample_mode)
+    return np.concatenate([outer_sum(x), in0[:, : F32_IN_CHANNELS - 128]], axis=1), None if up is None else up[:, : F32_A_CHANNELS - 64]
+
+
+def first_map(sd, in_map, dtype=F64):
+    """Stage 1 from the 136-channel stage 0 of an exact-fp32 Decoder: lcombinerD's conv 0 + BN on its first 128 + T channels."""
+    sd = O._as_sd(sd, dtype)
+    T = sd["lcombinerD.0.weight"].shape[1] - 128
+    with torch.no_grad():
+        return _np(O._bn(sd, "lcombinerD.1", O._conv(sd, "lcombinerD.0", O._t(in_map, dtype)[:, : 128 + T])))
+
+
+def yardstick(stage, *args):
+    """(fp64 reference, YARDSTICK) of a convolution stage: ``stage(*args, dtype)`` is one of `first_map`, `mat`, `block`, `final`."""
+    ref = stage(*args, F64)
+    return ref, rel_err(stage(*args, torch.float32), ref)
+
+
+def exact_conv_case(cin, cout, n, B, seed=0):
+    """One 3x3 conv that fp32 computes EXACTLY in any order: x integers in [-8, 8], w = k / 8 with integer |k| <= 8, bias k / 8, residual
+    integers - every partial sum is a multiple of 1/8 below 2^17 such units (9 * 136 * 64 + 8 + 64 = 78 408).  (x, w, b, r), float32."""
+    rs = np.random.RandomState(1000 * cin + 10 * n + B + seed)
+    x = rs.randint(-8, 9, (B, cin, n, n)).astype(np.float32)
+    w = (rs.randint(-8, 9, (cout, cin, 3, 3)) / 8.0).astype(np.float32)
+    b = (rs.randint(-8, 9, cout) / 8.0).astype(np.float32)
+    r = rs.randint(-8, 9, (B, cout, n, n)).astype(np.float32)
+    return torch.from_numpy(x), w, b, torch.from_numpy(r)
+
+
+def conv_ref(x, w, b, d, relu=False, r=None, dtype=F64):
+    """act(conv3x3(x; w, b), dilation = padding = d) + r in ``dtype``."""
+    with torch.no_grad():
+        out = F.conv2d(O._t(x, dtype), O._t(w, dtype), O._t(b, dtype), padding=d, dilation=d)
+        out = F.relu(out) if relu else out
+        return _np(out if r is None else out + O._t(r, dtype))
 
 
 # ---- one residual block of dilation 16 / 32 / 64 on its own ---------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """CPU: the oracle's Decoder stages (oracle/orca_oracle.py `decoder_stages`, `decoder_1m_stages`, `decoder_block`) that
 tests/test_gpu_decoder_stages.py holds the HIP kernels to - they compose to the forward the golden fixtures pin, fp32 and fp64 agree, the exact
-case of the block kernel is exact in every storage format, and a per-stage comparison sees a defect that the end-to-end tolerance hides."""
+case of the block kernel is exact in every storage format, and a per-stage comparison sees a defect that the end-to-end tolerance hides.
+For the exact-fp32 nets (tests/test_gpu_decoder_f32_stages.py): the yardstick bound holds a sequential fp32 chain and fails fp16-rounded
+operands, the 136- / 72-channel stage references are the pieces above, and the integer conv case is exact in fp32."""
 import functools
 
 import numpy as np
@@ -124,3 +126,98 @@ def test_one_dropped_lo_weight_plane_shows_per_stage_but_not_end_to_end(i):
         print(f"block {i} (d = {O.DECODER_DILATIONS[i]}), {name} without its lo plane: stage rel_err {err:.3g} "
               f"(per-block bound {R.BLOCK_BOUND:.1g}); final output max-abs {end:.3g} (end-to-end tolerance 1e-4)")
         assert err >= 3 * R.BLOCK_BOUND, (name, err)
+
+
+# ---- the yardstick of tests/test_gpu_decoder_f32_stages.py ------------------------------------------------------------------------------------
+def _seq_conv(x, w, b, d, relu=False, r=None):
+    """A 3x3 conv as a plain sequential float32 chain, one term at a time (numpy float32: the product and the sum each round): channel-major,
+    the nine taps inside, bias last - the order of conv2d_3x3_kernel's chunks.  x [B,cin,n,n], w [cout,cin,3,3] (BN folded), b [cout]."""
+    x, w = np.asarray(x, np.float32), np.asarray(w, np.float32)
+    n = x.shape[-1]
+    xp = np.pad(x, ((0, 0), (0, 0), (d, d), (d, d)))
+    acc = np.zeros((x.shape[0], w.shape[0], n, n), np.float32)
+    for ci in range(x.shape[1]):
+        for ky in range(3):
+            for kx in range(3):
+                acc += w[None, :, ci, ky, kx, None, None] * xp[:, ci, None, ky * d: ky * d + n, kx * d: kx * d + n]
+    acc += np.asarray(b, np.float32)[None, :, None, None]
+    if relu:
+        acc = np.maximum(acc, np.float32(0))
+    return acc if r is None else acc + r
+
+
+def _folded(sd, pairs):
+    from orca_amd import engine
+    return [engine.fold_conv(sd, c, bn) for c, bn in pairs]
+
+
+def _seq_stage(sd, i, x, half=False):
+    """The first conv (i = None, x = the 136-channel stage 0) or residual block i >= 1 (x = the stream in front of it) of the seed's Decoder
+    as `_seq_conv` chains on the library's BN-folded fp32 weights; ``half``: x and every w rounded to fp16 first."""
+    def h(v):
+        return np.asarray(v, np.float32).astype(np.float16).astype(np.float32) if half else np.asarray(v, np.float32)
+    if i is None:
+        (c,) = _folded(sd, [("lcombinerD.0", "lcombinerD.1")])
+        return _seq_conv(h(x)[:, : c["cin"]], h(c["w"]), c["b"], 1)
+    d = O.DECODER_DILATIONS[i]
+    la, lb, ma, mb = _folded(sd, [(f"lconvtwos.{i}.0", f"lconvtwos.{i}.1"), (f"lconvtwos.{i}.2", f"lconvtwos.{i}.3"),
+                                  (f"convtwos.{i}.0", f"convtwos.{i}.1"), (f"convtwos.{i}.3", f"convtwos.{i}.4")])
+    x = h(x)
+    o = _seq_conv(_seq_conv(x, h(la["w"]), la["b"], d), h(lb["w"]), lb["b"], d, r=x)
+    return _seq_conv(_seq_conv(o, h(ma["w"]), ma["b"], d, relu=True), h(mb["w"]), mb["b"], d, relu=True, r=o)
+
+
+@functools.lru_cache(maxsize=1)
+def _f32_stage_inputs():
+    """fp32 stages of the seed-0 Decoder at n = 30, B = 2, with stage 0 as an exact-fp32 net holds it (136 channels)."""
+    sd = R.decoder_sd("Decoder", 0)
+    x, de, y = _inputs()
+    st = R.stages(sd, "Decoder", x, de, y, dtype=torch.float32)
+    st[0] = R.head_f32(x, de, y)[0].astype(np.float32)
+    return sd, st
+
+
+@pytest.mark.parametrize("i", [None, 7, 4, 6])
+def test_fp32_yardstick_holds_a_sequential_chain_and_sees_fp16_operands(i):
+    """What lets test_gpu_decoder_f32_stages.py hold conv2d_3x3_kernel to YARD_FACTOR x the yardstick (torch fp32 against fp64 on the same
+    input, in `rel_err`), at n = 30: the first conv (K = 9 x 136) and one block per dilation 1, 16 and 64 (i = 7, 4, 6) as a plain sequential
+    float32 chain - the worst order a correct fp32 kernel can sum in - stay within the bound, and the same stage with x and w rounded to fp16
+    (an 11-bit operand path) exceeds it."""
+    sd, st = _f32_stage_inputs()
+    if i is None:
+        ref, yard = R.yardstick(R.first_map, sd, st[0])
+        src = st[0]
+    else:
+        ref, yard = R.yardstick(R.block, sd, "Decoder", i, st[2 + i])
+        src = st[2 + i]
+    seq, half = rel_err(_seq_stage(sd, i, src), ref), rel_err(_seq_stage(sd, i, src, half=True), ref)
+    print(f"stage {'first conv' if i is None else f'block {i}'}: yardstick {yard:.3g}; sequential fp32 chain {seq:.3g} ({seq / yard:.2f} x), "
+          f"fp16 operands {half:.3g} ({half / yard:.0f} x); bound {R.YARD_FACTOR} x")
+    assert yard > 0 and seq <= R.YARD_FACTOR * yard < half
+    assert ref.shape == (2, 64, N, N)
+
+
+def test_head_f32_is_the_whole_input_map_and_the_72_channel_A():
+    """`head_f32`: x_i + x_j in channels 0..127, distenc behind them, zeros to 135; the up-sampled y in 8 planes - the pieces the 16-bit
+    file's `head` and `outer_sum` give, and what `first_map` reads is `decoder_first`'s input."""
+    sd = R.decoder_sd("Decoder", 0)
+    x, de, y = _inputs()
+    in0, up = R.head_f32(x, de, y)
+    h0, hup = R.head(x, de, y)
+    assert in0.shape == (2, 136, N, N) and up.shape == (2, 8, N, N)
+    assert np.array_equal(in0[:, :128], R.outer_sum(x)) and np.array_equal(in0[:, 128:], h0[:, :8]) and np.array_equal(up, hup[:, :8])
+    assert not in0[:, 129:].any() and not up[:, 1:].any()
+    assert np.array_equal(R.first_map(sd, in0), R.first(sd, x, h0))
+    assert R.head_f32(x, de, None)[1] is None
+
+
+@pytest.mark.parametrize("cin,cout,d,n,B", [(136, 64, 1, 30, 1), (65, 64, 1, 17, 2), (64, 32, 16, 2, 2), (32, 64, 8, 1, 1)])
+def test_exact_conv_case_is_exact_in_fp32(cin, cout, d, n, B):
+    """What lets the GPU test ask conv2d_3x3_kernel for EQUALITY: on `exact_conv_case` data torch fp32 equals fp64 (with and without ReLU and
+    residual), every value is a multiple of 1/8 below 2^17 such units, and the result is no trivial map."""
+    x, w, b, r = R.exact_conv_case(cin, cout, n, B)
+    for relu, res in ((False, None), (True, r)):
+        ref = R.conv_ref(x, w, b, d, relu, res)
+        assert np.array_equal(R.conv_ref(x, w, b, d, relu, res, torch.float32).astype(np.float64), ref)
+        assert np.array_equal(np.round(ref * 8), ref * 8) and np.abs(ref * 8).max() < 2 ** 17
+        assert len(np.unique(ref)) > min(16, ref.size // 4)

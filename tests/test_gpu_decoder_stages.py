@@ -251,9 +251,16 @@ def test_probe_and_block_entry_refuse_what_they_cannot_run(cuda):
     for stage, ch in ((1, 64), (2, 64), (22, 64), (0, 16)):
         assert raw(net1, None, None, stage, ch) == -1, (stage, ch)
     assert raw(net1, de.data_ptr(), None, 3, 64) == -1                                     # a Decoder_1m takes no distenc
-    mf = _module(cuda, "Decoder", 0, precision="f32")
-    with pytest.raises(OrcaHipError, match="f32"):
-        engine.decoder_probe(_net(mf, cuda), x, de, y, 3)
+    # an exact-fp32 net hands out its fp32 planes: the whole 136-channel input map, A with the 8 planes of the up-sampled y
+    netf, netf1 = _net(_module(cuda, "Decoder", 0, precision="f32"), cuda), _net(_module(cuda, "Decoder_1m", 0, precision="f32"), cuda)
+    assert [tuple(engine.decoder_probe(netf, x, de, yy, k).shape[1:]) for k, yy in ((0, y), (1, y), (2, y), (2, None), (3, y), (30, y))] == \
+        [(136, 30, 30), (64, 30, 30), (72, 30, 30), (64, 30, 30), (64, 30, 30), (64, 30, 30)]
+    assert [tuple(engine.decoder_probe(netf1, x, None, None, k).shape) for k in (0, 3, 21)] == [(1, 128, 30, 30), (1, 64, 30, 30), (1, 64, 30, 30)]
+    for stage, ch in ((31, 64), (-1, 64), (0, 16), (0, 128), (1, 72), (2, 80), (2, 64), (5, 32)):   # no such stage / a channel mismatch
+        assert raw(netf, de.data_ptr(), y.data_ptr(), stage, ch) == -1, (stage, ch)
+    assert raw(netf, de.data_ptr(), None, 2, 72) == -1
+    for stage, ch in ((1, 64), (2, 64), (22, 64), (0, 136)):
+        assert raw(netf1, None, None, stage, ch) == -1, (stage, ch)
     # the block entry
     convs = R.dense_block(1)
     xb = torch.zeros((1, 64, 30, 30), device=cuda)

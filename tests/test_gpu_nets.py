@@ -439,7 +439,8 @@ def test_encoder_length_sweep_split_fp16_vs_exact_fp32(cuda, nbins):
 @pytest.mark.parametrize("n", [2, 4, 18, 62, 126, 250, 256])
 def test_decoder_size_sweep_split_fp16_vs_exact_fp32(cuda, n):
     """Decoder / Decoder_1m on map sizes from 2 to the 256-pixel pitch: split-fp16 kernels (XCD-banded rows, LDS-transposed
-    epilogue, border tap skipping with dilations up to 64 > n) against the exact-fp32 kernels of the same library."""
+    epilogue, border tap skipping with dilations up to 64 > n) against the exact-fp32 kernels of the same library.  That reference is
+    itself pinned kernel by kernel against fp64 by tests/test_gpu_decoder_f32_stages.py."""
     rs = np.random.RandomState(n)
     x = torch.from_numpy(rs.randn(2, 128, n).astype(np.float32) * 0.5).to(cuda)
     de = torch.from_numpy(rs.randn(2, 1, n, n).astype(np.float32)).to(cuda)
