@@ -442,7 +442,38 @@ int orca_screen_paired_aligned_scores(orca_ctx* ctx, const float* alt, int64_t a
                                       const int32_t* bin_map_host, float* profile, float* abs_mean, float* abs_max, float* delta_mean, float* rms, double* corr,
                                       int32_t* count);
 
-/* Loops (screen.screen_1m(..., loops=)): dot calls on B maps m = maps[b * map_bs + i * n + j] (B >= 1, 1 <= n <= 256, map_bs >= n * n) of log observed /
+/* Paired tracks and strata (sv.sv_screen(..., scores=True, insulation=, viewpoints=, strata=)): the three readouts above for B pairs of maps with the
+ * conventions of orca_screen_paired_aligned_scores - pair b is alt + b * alt_bs against a reference map OF ITS OWN ref + b * ref_bs (B >= 1,
+ * 1 <= n <= 256, both strides >= n * n) through row b of `bin_map` (B x n int32, -1 .. n - 1, required; it may ascend with jumps, repeat or descend).
+ * Every small table comes twice (device copy, checked host copy), no pointer may be NULL, every result is indexed by ALT bin.
+ *   orca_screen_paired_insulation     `widths` as for orca_screen_insulation (1 <= W <= 8, each 1..128; one that fits nowhere is legal).  [B][W][n]:
+ *                                     track = ins_wk(alt b)[i];  ref_track = ins_wk(ref b)[i] at the reference's OWN bin i;  aligned = ins(alt b)[i] -
+ *                                     ins(ref b)[map_b i] where map_b i >= 0 and both diamonds fit, else NaN (fp64 difference, rounded once).  The diamond
+ *                                     and the order of its sum are orca_screen_insulation's: `track` of a map and `aligned` of an (alt, ref, map) hold the
+ *                                     bits that entry point gives for them
+ *   orca_screen_paired_viewpoints     `views` is B x V int32 (1 <= V <= 64), one list per pair, of REFERENCE bins -1 .. n - 1; -1 = "not in this pair's
+ *                                     window".  R = the alt bins i with map_b i == view (ascending): count[b][v] = |R| (int32; 0 for view -1), and
+ *                                     aligned[b][v][j] is orca_screen_viewpoints' aligned expression with the pair's own reference - the fp32 subtraction
+ *                                     for c = 1, the fp64 mean over R minus ref_b[view][map_b j] for c > 1, NaN where c = 0 or map_b j < 0: the same bits
+ *                                     as that entry point on the same inputs
+ *   orca_screen_paired_strata_scores  the definitions, the two passes, the NaN rules and the serial combination over [d_lo, d_hi) (0 <= d_lo < d_hi <= n)
+ *                                     of orca_screen_strata_scores' aligned form, with one difference: the reference pixel of alt pair (i, i + d) is
+ *                                     ref_b[min(mi, mj)][max(mi, mj)], mi = map_b i, mj = map_b (i + d).  Inside an inversion the bin map descends and
+ *                                     (mi, mj) lies below the reference's diagonal; a contact map is symmetric, so the mirrored pixel is the same contact,
+ *                                     and nothing on the lower side of the diagonal of either map is ever read, whichever way the bin map runs.  Where
+ *                                     the bin map is non-decreasing the results are orca_screen_strata_scores' bits
+ * No atomics; every sum runs in an order fixed by (n, the table, the bin map) alone, so a pair's results are bit for bit the same whatever B, its place in
+ * the batch and the strides.  Anything else is ORCA_EINVAL before any launch. */
+int orca_screen_paired_insulation(orca_ctx* ctx, const float* alt, int64_t alt_bs, const float* ref, int64_t ref_bs, int B, int n, const int32_t* widths,
+                                  const int32_t* widths_host, int W, const int32_t* bin_map, const int32_t* bin_map_host, float* track, float* ref_track,
+                                  float* aligned);
+int orca_screen_paired_viewpoints(orca_ctx* ctx, const float* alt, int64_t alt_bs, const float* ref, int64_t ref_bs, int B, int n, const int32_t* views,
+                                  const int32_t* views_host, int V, const int32_t* bin_map, const int32_t* bin_map_host, float* aligned, int32_t* count);
+int orca_screen_paired_strata_scores(orca_ctx* ctx, const float* alt, int64_t alt_bs, const float* ref, int64_t ref_bs, int B, int n, const int32_t* bin_map,
+                                     const int32_t* bin_map_host, int d_lo, int d_hi, float* dist_delta, float* dist_abs, float* dist_rms, double* dist_corr,
+                                     int32_t* dist_count, float* mse, double* corr, double* scc);
+
+/* Loops(screen.screen_1m(..., loops=)): dot calls on B maps m = maps[b * map_bs + i * n + j] (B >= 1, 1 <= n <= 256, map_bs >= n * n) of log observed /
  * expected, where a focal peak's enrichment over its local background is a difference of means.  Integers 0 <= p < w <= 16, 1 <= r <= 16,
  * d_min >= 2 w + 1, 1 <= K <= 4096 and an fp32 threshold T (not NaN).
  *   eligible      pixel (i, j) with w <= i, j <= n - 1 - w and j - i >= d_min: every set below then lies inside the map and strictly above the diagonal;

@@ -341,6 +341,57 @@ extern "C" int orca_screen_paired_aligned_scores(orca_ctx* ctx, const float* alt
                 bin_map, profile, abs_mean, abs_max, delta_mean, rms, corr, count);
 }
 
+// ---- paired tracks and strata: the readouts above, every alt map against a reference map of its own (sv.sv_screen(..., insulation=, viewpoints=, strata=)) ---
+// what the three share: the pairs, their strides and the bin map, which is required
+static int check_pairs(const char* what, int64_t alt_bs, int64_t ref_bs, int B, int n, const int32_t* bin_map_host) {
+  if (B < 1 || n < 1 || n > SCREEN_ALIGNED_MAX_BINS || alt_bs < (int64_t)n * n || ref_bs < (int64_t)n * n)
+    return fail(ORCA_EINVAL, "%s: %d pairs (>= 1) of maps of %d bins (1..%d), batch strides %ld (alt), %ld (ref) (>= n * n)", what, B, n, SCREEN_ALIGNED_MAX_BINS,
+                (long)alt_bs, (long)ref_bs);
+  return check_bin_map(what, bin_map_host, B, n);
+}
+
+extern "C" int orca_screen_paired_insulation(orca_ctx* ctx, const float* alt, int64_t alt_bs, const float* ref, int64_t ref_bs, int B, int n, const int32_t* widths,
+                                             const int32_t* widths_host, int W, const int32_t* bin_map, const int32_t* bin_map_host, float* track,
+                                             float* ref_track, float* aligned) {
+  if (!ctx || !alt || !ref || !widths || !widths_host || !bin_map || !bin_map_host || !track || !ref_track || !aligned)
+    return fail(ORCA_EINVAL, "orca_screen_paired_insulation: NULL argument");
+  ORCA_TRY(check_pairs("orca_screen_paired_insulation", alt_bs, ref_bs, B, n, bin_map_host));
+  if (W < 1 || W > SCREEN_INSULATION_MAX_WIDTHS) return fail(ORCA_EINVAL, "orca_screen_paired_insulation: %d widths (1..%d)", W, SCREEN_INSULATION_MAX_WIDTHS);
+  for (int k = 0; k < W; ++k)
+    if (widths_host[k] < 1 || widths_host[k] > SCREEN_INSULATION_MAX_WIDTH)
+      return fail(ORCA_EINVAL, "orca_screen_paired_insulation: width %d is %d bins, outside 1 .. %d", k, widths_host[k], SCREEN_INSULATION_MAX_WIDTH);
+  const unsigned chunks = (unsigned)((n + SCREEN_INSULATION_BINS - 1) / SCREEN_INSULATION_BINS);
+  return launch(ctx, "screen_paired_insulation_kernel", screen_paired_insulation_kernel, dim3((unsigned)B, (unsigned)W, chunks), 256, alt, (long)alt_bs, ref,
+                (long)ref_bs, n, widths, W, bin_map, track, ref_track, aligned);
+}
+
+extern "C" int orca_screen_paired_viewpoints(orca_ctx* ctx, const float* alt, int64_t alt_bs, const float* ref, int64_t ref_bs, int B, int n, const int32_t* views,
+                                             const int32_t* views_host, int V, const int32_t* bin_map, const int32_t* bin_map_host, float* aligned, int32_t* count) {
+  if (!ctx || !alt || !ref || !views || !views_host || !bin_map || !bin_map_host || !aligned || !count)
+    return fail(ORCA_EINVAL, "orca_screen_paired_viewpoints: NULL argument");
+  ORCA_TRY(check_pairs("orca_screen_paired_viewpoints", alt_bs, ref_bs, B, n, bin_map_host));
+  if (V < 1 || V > SCREEN_VIEWPOINTS_MAX) return fail(ORCA_EINVAL, "orca_screen_paired_viewpoints: %d viewpoints (1..%d)", V, SCREEN_VIEWPOINTS_MAX);
+  for (int b = 0; b < B; ++b)
+    for (int v = 0; v < V; ++v) {
+      const int32_t x = views_host[(size_t)b * V + v];
+      if (x < -1 || x >= n) return fail(ORCA_EINVAL, "orca_screen_paired_viewpoints: viewpoint %d of pair %d is reference bin %d, outside -1 .. %d", v, b, x, n - 1);
+    }
+  return launch(ctx, "screen_paired_viewpoints_kernel", screen_paired_viewpoints_kernel, dim3((unsigned)B, (unsigned)V), 256, alt, (long)alt_bs, ref, (long)ref_bs, n,
+                views, V, bin_map, aligned, count);
+}
+
+extern "C" int orca_screen_paired_strata_scores(orca_ctx* ctx, const float* alt, int64_t alt_bs, const float* ref, int64_t ref_bs, int B, int n,
+                                                const int32_t* bin_map, const int32_t* bin_map_host, int d_lo, int d_hi, float* dist_delta, float* dist_abs,
+                                                float* dist_rms, double* dist_corr, int32_t* dist_count, float* mse, double* corr, double* scc) {
+  if (!ctx || !alt || !ref || !bin_map || !bin_map_host || !dist_delta || !dist_abs || !dist_rms || !dist_corr || !dist_count || !mse || !corr || !scc)
+    return fail(ORCA_EINVAL, "orca_screen_paired_strata_scores: NULL argument");
+  ORCA_TRY(check_pairs("orca_screen_paired_strata_scores", alt_bs, ref_bs, B, n, bin_map_host));
+  if (d_lo < 0 || d_lo >= d_hi || d_hi > n)
+    return fail(ORCA_EINVAL, "orca_screen_paired_strata_scores: strata [%d, %d) of a map of %d bins (0 <= d_lo < d_hi <= n)", d_lo, d_hi, n);
+  return launch(ctx, "screen_paired_strata_scores_kernel", screen_paired_strata_scores_kernel, dim3((unsigned)B), 256, alt, (long)alt_bs, ref, (long)ref_bs, n,
+                bin_map, d_lo, d_hi, dist_delta, dist_abs, dist_rms, dist_corr, dist_count, mse, corr, scc);
+}
+
 // ---- loops: dot calls and the enrichment at listed pixels ---------------------------------------------------------------------------------------------------------
 static int check_dot_params(const char* what, int B, int n, int64_t map_bs, int p, int w, int d_min) {
   if (B < 1 || n < 1 || n > SCREEN_ALIGNED_MAX_BINS || map_bs < (int64_t)n * n)

@@ -439,14 +439,18 @@ static __device__ __forceinline__ double screen_diamond_sum(const float* __restr
 // reference diamond fits at map i, else NaN - only the centre bin has to be mapped.  ref, delta, aligned and bin_map may each be NULL (the host entry
 // point says which combinations).  One workgroup per (map, width, SCREEN_INSULATION_BINS bins), one wave per bin at a time; the pixels come from global
 // memory (a map does not fit LDS; neighbouring diamonds overlap, so the re-reads hit L2).  Where map i == i the aligned value is the delta's expression.
-static __global__ void __launch_bounds__(256) screen_insulation_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, int n,
-                                                                       const int* __restrict__ widths, int W, const int* __restrict__ bin_map,
-                                                                       float* __restrict__ track, float* __restrict__ delta, float* __restrict__ aligned) {
+// PAIRED (orca_screen_paired_insulation): map b has a reference of its own, ref + b * ref_bs, and the `delta` slot takes ref_track[b][k][i] = ins_wk(ref b)[i]
+// at the reference's own bin i instead of the difference; track and aligned are the expressions above, so the same bits for the same (alt, ref, map).
+template <bool PAIRED>
+static __device__ __forceinline__ void screen_insulation_body(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, long ref_bs, int n,
+                                                              const int* __restrict__ widths, int W, const int* __restrict__ bin_map,
+                                                              float* __restrict__ track, float* __restrict__ delta, float* __restrict__ aligned) {
   __shared__ int s_map[SCREEN_ALIGNED_MAX_BINS];
   const int b = blockIdx.x, k = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   n = n > SCREEN_ALIGNED_MAX_BINS ? SCREEN_ALIGNED_MAX_BINS : n;
   if (bin_map) screen_load_bin_map(bin_map + (long)b * n, n, s_map);
   __syncthreads();
+  if (PAIRED) ref += (long)b * ref_bs;
   int w = widths[k];
   w = (w >= 1 && w <= SCREEN_INSULATION_MAX_WIDTH) ? w : n;          // n fits nowhere
   const double ww = (double)w * (double)w;
@@ -466,10 +470,23 @@ static __global__ void __launch_bounds__(256) screen_insulation_kernel(const flo
     }
     if (lane == 0) {
       track[at] = fits ? (float)ia : qnan;
-      if (delta) delta[at] = (fits && ref) ? (float)(ia - ir) : qnan;
+      if (delta) delta[at] = (fits && ref) ? (PAIRED ? (float)ir : (float)(ia - ir)) : qnan;
       if (aligned) aligned[at] = al;
     }
   }
+}
+
+static __global__ void __launch_bounds__(256) screen_insulation_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, int n,
+                                                                       const int* __restrict__ widths, int W, const int* __restrict__ bin_map,
+                                                                       float* __restrict__ track, float* __restrict__ delta, float* __restrict__ aligned) {
+  screen_insulation_body<false>(alt, map_bs, ref, 0, n, widths, W, bin_map, track, delta, aligned);
+}
+
+static __global__ void __launch_bounds__(256) screen_paired_insulation_kernel(const float* __restrict__ alt, long alt_bs, const float* __restrict__ ref, long ref_bs,
+                                                                              int n, const int* __restrict__ widths, int W, const int* __restrict__ bin_map,
+                                                                              float* __restrict__ track, float* __restrict__ ref_track,
+                                                                              float* __restrict__ aligned) {
+  screen_insulation_body<true>(alt, alt_bs, ref, ref_bs, n, widths, W, bin_map, track, ref_track, aligned);
 }
 
 // viewpoint profiles (virtual 4C) of B alt maps [B][n][n] (batch stride map_bs) against ref [n][n] at V viewpoint bins (int32, 0 .. n - 1 - the host
@@ -478,27 +495,35 @@ static __global__ void __launch_bounds__(256) screen_insulation_kernel(const flo
 // ref[view][map j] in fp64 where c >= 1 and map j >= 0 (for c = 1 the fp32 subtraction itself), else NaN - the viewpoint was deleted, or column j stands
 // for nothing.  One workgroup per (map, viewpoint), one thread per column: wave 0 lists R in LDS, then every thread walks R down its own column
 // (coalesced along the row) and gathers the reference row through the LDS bin map.  bin_map and aligned are NULL together.
-static __global__ void __launch_bounds__(256) screen_viewpoints_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, int n,
-                                                                       const int* __restrict__ views, int V, const int* __restrict__ bin_map,
-                                                                       float* __restrict__ delta, float* __restrict__ aligned) {
+// PAIRED (orca_screen_paired_viewpoints): map b has a reference of its own, ref + b * ref_bs, and a view list of its own, views + b * V, whose entries may
+// be -1 ("not in this pair's window": c = 0, nothing is read); count[b][v] = c goes out, delta is not written (a pair's two maps share no bin grid).
+template <bool PAIRED>
+static __device__ __forceinline__ void screen_viewpoints_body(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, long ref_bs, int n,
+                                                              const int* __restrict__ views, int V, const int* __restrict__ bin_map,
+                                                              float* __restrict__ delta, float* __restrict__ aligned, int* __restrict__ count) {
   __shared__ int s_map[SCREEN_ALIGNED_MAX_BINS], s_rows[SCREEN_ALIGNED_MAX_BINS];
   __shared__ int s_cnt;
   const int b = blockIdx.x, v = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = threadIdx.x;
   n = n > SCREEN_ALIGNED_MAX_BINS ? SCREEN_ALIGNED_MAX_BINS : n;
-  int view = views[v];
+  int view = views[PAIRED ? b * V + v : v];
+  const bool absent = PAIRED && (view < 0 || view > n - 1);
   view = view < 0 ? 0 : (view > n - 1 ? n - 1 : view);
   const bool al = bin_map && aligned;
   if (al) screen_load_bin_map(bin_map + (long)b * n, n, s_map);
   __syncthreads();
   if (al && wv == 0) {
-    const int c = screen_bins_in(s_map, n, view, view + 1, s_rows, lane);
-    if (lane == 0) s_cnt = c;
+    const int c = absent ? 0 : screen_bins_in(s_map, n, view, view + 1, s_rows, lane);
+    if (lane == 0) {
+      s_cnt = c;
+      if (PAIRED) count[(long)b * V + v] = c;
+    }
   }
   __syncthreads();
   if (j >= n) return;
   const float* a = alt + (long)b * map_bs;
   const long at = ((long)b * V + v) * n + j;
-  delta[at] = a[(long)view * n + j] - ref[(long)view * n + j];
+  if (PAIRED) ref += (long)b * ref_bs;
+  else delta[at] = a[(long)view * n + j] - ref[(long)view * n + j];
   if (!al) return;
   const int c = s_cnt, mj = s_map[j];
   float out = __int_as_float(0x7fc00000);
@@ -510,6 +535,18 @@ static __global__ void __launch_bounds__(256) screen_viewpoints_kernel(const flo
     out = (float)(s / (double)c - (double)ref[(long)view * n + mj]);
   }
   aligned[at] = out;
+}
+
+static __global__ void __launch_bounds__(256) screen_viewpoints_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, int n,
+                                                                       const int* __restrict__ views, int V, const int* __restrict__ bin_map,
+                                                                       float* __restrict__ delta, float* __restrict__ aligned) {
+  screen_viewpoints_body<false>(alt, map_bs, ref, 0, n, views, V, bin_map, delta, aligned, nullptr);
+}
+
+static __global__ void __launch_bounds__(256) screen_paired_viewpoints_kernel(const float* __restrict__ alt, long alt_bs, const float* __restrict__ ref, long ref_bs,
+                                                                              int n, const int* __restrict__ views, int V, const int* __restrict__ bin_map,
+                                                                              float* __restrict__ aligned, int* __restrict__ count) {
+  screen_viewpoints_body<true>(alt, alt_bs, ref, ref_bs, n, views, V, bin_map, nullptr, aligned, count);
 }
 
 // ---- distance strata (screen.screen_1m(..., strata=)): similarity of an alt map to the reference, stratified by genomic distance ------------------------
@@ -524,12 +561,17 @@ static __global__ void __launch_bounds__(256) screen_viewpoints_kernel(const flo
 // [d_lo, d_hi) serially for d ascending (empty strata skipped).  The aligned branch differs in the indices of y alone, so where the bin map is the
 // identity it evaluates the bin-with-bin expressions: the same bits.  A NaN pixel at a pair of stratum d enters that stratum's sums and, through
 // them, the per-map scores if d_lo <= d < d_hi; unmapped pairs and the lower triangle are never read.
-static __global__ void __launch_bounds__(256) screen_strata_scores_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, int n,
-                                                                          const int* __restrict__ bin_map, int d_lo, int d_hi,
-                                                                          float* __restrict__ dist_delta, float* __restrict__ dist_abs,
-                                                                          float* __restrict__ dist_rms, double* __restrict__ dist_corr,
-                                                                          int* __restrict__ dist_count, float* __restrict__ mse,
-                                                                          double* __restrict__ corr, double* __restrict__ scc) {
+// PAIRED (orca_screen_paired_strata_scores): map b has a reference of its own, ref + b * ref_bs, and y = ref_b[min(mi, mj)][max(mi, mj)] with mi = map i,
+// mj = map (i + d): inside an inversion the bin map descends and (mi, mj) would lie below the reference's diagonal, which holds the same contact but is
+// outside this kernel's contract - the mirrored pixel is read instead, so the lower side of neither map is ever touched.  Where the bin map does not
+// descend nothing is swapped: the unpaired expressions, the same bits.
+template <bool PAIRED>
+static __device__ __forceinline__ void screen_strata_scores_body(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, long ref_bs, int n,
+                                                                 const int* __restrict__ bin_map, int d_lo, int d_hi,
+                                                                 float* __restrict__ dist_delta, float* __restrict__ dist_abs,
+                                                                 float* __restrict__ dist_rms, double* __restrict__ dist_corr,
+                                                                 int* __restrict__ dist_count, float* __restrict__ mse,
+                                                                 double* __restrict__ corr, double* __restrict__ scc) {
   __shared__ int s_map[SCREEN_ALIGNED_MAX_BINS], s_c[SCREEN_ALIGNED_MAX_BINS];
   __shared__ double s_mx[SCREEN_ALIGNED_MAX_BINS], s_my[SCREEN_ALIGNED_MAX_BINS], s_X[SCREEN_ALIGNED_MAX_BINS], s_Y[SCREEN_ALIGNED_MAX_BINS],
       s_C[SCREEN_ALIGNED_MAX_BINS], s_Q[SCREEN_ALIGNED_MAX_BINS];
@@ -541,6 +583,7 @@ static __global__ void __launch_bounds__(256) screen_strata_scores_kernel(const 
   if (al) screen_load_bin_map(bin_map + (long)b * n, n, s_map);
   __syncthreads();
   const float* a = alt + (long)b * map_bs;
+  if (PAIRED) ref += (long)b * ref_bs;
   const float qnan = __int_as_float(0x7fc00000);
   const double dnan = (double)qnan;
   if (d < n) {
@@ -552,6 +595,7 @@ static __global__ void __launch_bounds__(256) screen_strata_scores_kernel(const 
         ri = s_map[i];
         rj = s_map[i + d];
         if (ri < 0 || rj < 0) continue;
+        if (PAIRED && ri > rj) { const int t = ri; ri = rj; rj = t; }
       }
       sx += (double)a[(long)i * n + i + d];
       sy += (double)ref[(long)ri * n + rj];
@@ -566,6 +610,7 @@ static __global__ void __launch_bounds__(256) screen_strata_scores_kernel(const 
         ri = s_map[i];
         rj = s_map[i + d];
         if (ri < 0 || rj < 0) continue;
+        if (PAIRED && ri > rj) { const int t = ri; ri = rj; rj = t; }
       }
       const double x = (double)a[(long)i * n + i + d], y = (double)ref[(long)ri * n + rj];
       const double ex = x - mx, ey = y - my, dl = x - y;
@@ -618,6 +663,24 @@ static __global__ void __launch_bounds__(256) screen_strata_scores_kernel(const 
   mse[b] = (float)(q / cc);
   scc[b] = den == 0.0 ? dnan : num / den;
   corr[b] = (c < 2 || X == 0.0 || Y == 0.0) ? dnan : C / sqrt(X * Y);
+}
+
+static __global__ void __launch_bounds__(256) screen_strata_scores_kernel(const float* __restrict__ alt, long map_bs, const float* __restrict__ ref, int n,
+                                                                          const int* __restrict__ bin_map, int d_lo, int d_hi,
+                                                                          float* __restrict__ dist_delta, float* __restrict__ dist_abs,
+                                                                          float* __restrict__ dist_rms, double* __restrict__ dist_corr,
+                                                                          int* __restrict__ dist_count, float* __restrict__ mse,
+                                                                          double* __restrict__ corr, double* __restrict__ scc) {
+  screen_strata_scores_body<false>(alt, map_bs, ref, 0, n, bin_map, d_lo, d_hi, dist_delta, dist_abs, dist_rms, dist_corr, dist_count, mse, corr, scc);
+}
+
+static __global__ void __launch_bounds__(256) screen_paired_strata_scores_kernel(const float* __restrict__ alt, long alt_bs, const float* __restrict__ ref,
+                                                                                 long ref_bs, int n, const int* __restrict__ bin_map, int d_lo, int d_hi,
+                                                                                 float* __restrict__ dist_delta, float* __restrict__ dist_abs,
+                                                                                 float* __restrict__ dist_rms, double* __restrict__ dist_corr,
+                                                                                 int* __restrict__ dist_count, float* __restrict__ mse,
+                                                                                 double* __restrict__ corr, double* __restrict__ scc) {
+  screen_strata_scores_body<true>(alt, alt_bs, ref, ref_bs, n, bin_map, d_lo, d_hi, dist_delta, dist_abs, dist_rms, dist_corr, dist_count, mse, corr, scc);
 }
 
 // ---- paired aligned scores (sv.sv_screen(..., scores=)): B alt maps, each against a reference map OF ITS OWN through its bin map --------------------------

@@ -1020,6 +1020,90 @@ def screen_paired_aligned_scores(ctx, alt, ref, bin_map_host):
     return out
 
 
+# paired tracks and strata (orca_screen_paired_insulation / _viewpoints / _strata_scores): the 1 Mb screen's readouts, every alt map against a reference
+# map of its own through its bin map
+def _pair_args(alt, ref, bin_map_host):
+    """What the paired entry points share: (alt, alt batch stride, ref, ref batch stride, bin map [B, n] int32 on the host, its device copy)."""
+    alt, ref = _f32_cuda(alt, "alt"), _f32_cuda(ref, "ref")
+    if alt.dim() != 3 or alt.shape[0] < 1 or alt.shape[1] != alt.shape[2] or ref.shape != alt.shape or ref.device != alt.device:
+        raise ValueError(f"alt, ref: [B,n,n] with B >= 1 on one device, got {tuple(alt.shape)} and {tuple(ref.shape)}")
+    B, n = alt.shape[0], alt.shape[1]
+    for t, name in ((alt, "alt"), (ref, "ref")):
+        if t.stride(2) != 1 or t.stride(1) != n:
+            raise ValueError(f"{name}: [{B},{n},{n}] with contiguous maps")
+    m = _host_table(bin_map_host, np.int32, n, "bin map")
+    if m.shape[0] != B:
+        raise ValueError(f"bin map: [{B},{n}] int32, one row per pair")
+    alt_bs, ref_bs = (t.stride(0) if B > 1 else max(t.stride(0), n * n) for t in (alt, ref))       # B = 1: torch may report any stride for the one map
+    return alt, alt_bs, ref, ref_bs, m, torch.from_numpy(m).to(alt.device)
+
+
+def screen_paired_insulation(ctx, alt, ref, widths_host, bin_map_host):
+    """Insulation tracks of B pairs of maps, alt [B, n, n] against ref [B, n, n] (both any batch stride, rows contiguous) at the W widths ``widths_host``
+    (1 to 8 ints, each 1 .. 128 bins) through ``bin_map_host`` [B, n] int32 numpy (orca_screen_paired_insulation): (track, ref_track, aligned), each
+    [B, W, n] float32.  track = ins(alt b)[i], ref_track = ins(ref b)[i] at the reference's own bin i, aligned = ins(alt b)[i] - ins(ref b)[map i],
+    NaN where alt bin i stands for no reference bin or either diamond does not fit."""
+    alt, alt_bs, ref, ref_bs, m, md = _pair_args(alt, ref, bin_map_host)
+    B, n = m.shape
+    w = _host_table(np.asarray(widths_host).reshape(-1, 1), np.int32, 1, "widths")[:, 0]
+    W = w.shape[0]
+    wd = torch.from_numpy(w).to(alt.device)
+    track, ref_track, aligned = _f32_outputs(alt.device, (B, W, n), (B, W, n), (B, W, n))
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_paired_insulation(ctx.handle, _dev_p(alt), alt_bs, _dev_p(ref), ref_bs, B, n, _dev_p(wd), _np_p(w), W, _dev_p(md), _np_p(m),
+                                                    _dev_p(track), _dev_p(ref_track), _dev_p(aligned)), "orca_screen_paired_insulation")
+    return track, ref_track, aligned
+
+
+def screen_paired_viewpoints(ctx, alt, ref, views_host, bin_map_host):
+    """Viewpoint profiles (virtual 4C) of B pairs of maps, alt [B, n, n] against ref [B, n, n], at ``views_host`` [B, V] int32 numpy (or one [V] list for
+    every pair): REFERENCE bins in -1 .. n - 1, 1 <= V <= 64, -1 = not in that pair's window (orca_screen_paired_viewpoints): (aligned [B, V, n] float32,
+    count [B, V] int32).  count = the alt bins that stand for the viewpoint; aligned[b, v, j] = their mean alt row at column j minus
+    ref[b][view, map j], NaN where count is 0 or column j stands for nothing."""
+    alt, alt_bs, ref, ref_bs, m, md = _pair_args(alt, ref, bin_map_host)
+    B, n = m.shape
+    v = np.asarray(views_host)
+    if v.ndim == 1:
+        v = np.broadcast_to(v, (B, v.shape[0]))
+    if v.ndim != 2 or v.shape[0] != B:
+        raise ValueError(f"viewpoints: [{B},V] int32, one row per pair (or one [V] list for all)")
+    v = np.ascontiguousarray(v, dtype=np.int32)
+    V = v.shape[1]
+    vd = torch.from_numpy(v).to(alt.device)
+    aligned, = _f32_outputs(alt.device, (B, V, n))
+    count = torch.empty((B, V), dtype=torch.int32, device=alt.device)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_paired_viewpoints(ctx.handle, _dev_p(alt), alt_bs, _dev_p(ref), ref_bs, B, n, _dev_p(vd), _np_p(v), V, _dev_p(md), _np_p(m),
+                                                    _dev_p(aligned), _dev_p(count)), "orca_screen_paired_viewpoints")
+    return aligned, count
+
+
+PAIRED_STRATA_FIELDS = ("dist_delta", "dist_abs", "dist_rms", "dist_corr", "dist_count", "mse", "corr", "scc")
+
+
+def screen_paired_strata_scores(ctx, alt, ref, bin_map_host, d_range=None):
+    """Distance-stratified similarity of B pairs of maps, alt [B, n, n] against ref [B, n, n] through ``bin_map_host`` [B, n] int32 numpy
+    (orca_screen_paired_strata_scores): `screen_strata_scores`' dict in its aligned form - ``dist_delta``, ``dist_abs``, ``dist_rms`` [B, n] float32,
+    ``dist_corr`` [B, n] float64, ``dist_count`` [B, n] int32, ``mse`` [B] float32, ``corr``, ``scc`` [B] float64 over the strata ``d_range`` =
+    (d_lo, d_hi), all by default.  The reference pixel of alt pair (i, i + d) is ref[b][min(mi, mj), max(mi, mj)], mi = map i, mj = map (i + d): the
+    lower side of the diagonal of neither map is read, whichever way the bin map runs."""
+    alt, alt_bs, ref, ref_bs, m, md = _pair_args(alt, ref, bin_map_host)
+    B, n = m.shape
+    try:
+        d_lo, d_hi = (0, n) if d_range is None else (int(v) for v in d_range)
+    except (TypeError, ValueError):
+        raise ValueError("d_range: (d_lo, d_hi)") from None
+    dev = alt.device
+    out = dict(zip(("dist_delta", "dist_abs", "dist_rms", "mse"), _f32_outputs(dev, (B, n), (B, n), (B, n), (B,))))
+    out["dist_corr"] = torch.empty((B, n), dtype=torch.float64, device=dev)
+    out["corr"], out["scc"] = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(2))
+    out["dist_count"] = torch.empty((B, n), dtype=torch.int32, device=dev)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_paired_strata_scores(ctx.handle, _dev_p(alt), alt_bs, _dev_p(ref), ref_bs, B, n, _dev_p(md), _np_p(m), d_lo, d_hi,
+                                                       *(_dev_p(out[k]) for k in PAIRED_STRATA_FIELDS)), "orca_screen_paired_strata_scores")
+    return out
+
+
 # loops (orca_screen_dot_calls, orca_screen_dot_enrichment): dot calls per map and the enrichment at listed pixels
 def _dot_args(maps, p, w, d_min):
     maps = _f32_cuda(maps, "maps")

@@ -206,18 +206,219 @@ def paired_aligned_scores_host(alt, ref, bin_map):
     return out
 
 
-def _scores_entry(sv, chrlen, ref_out, alt_out):
-    """The model-independent part of an entry's ``scores``."""
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Readouts per level: what changed, not only how much.  The 1 Mb screen's insulation tracks, viewpoint profiles (virtual 4C) and distance
+# strata (orca_amd/screen.py), in their paired forms: every (level, target) alt map against the variant's own reference map through the
+# level's bin map.  A genomic position is a different bin at every level, or none; inside an inversion the bin map descends, and the strata
+# read the reference pixel mirrored into the upper triangle (the min/max rule).
+# ---------------------------------------------------------------------------------------------------------------------------------
+STRATA_FIELDS = ("dist_delta", "dist_abs", "dist_rms", "dist_corr", "mse", "corr", "scc")     # the strata kernel's ``corr`` is ``strata_corr`` in an entry
+
+
+def viewpoint_bins(positions, ref_out):
+    """int32 [6, V]: the REFERENCE bin that holds each of the V base positions (on the original chromosome) at every level of the reference
+    window of ``ref_out`` (a `genomepredict` / `sv_screen` output dict): (pos - start_coords[k]) // (128000 >> k) if that lies in 0 .. 249,
+    else -1 - the position is outside that level's window."""
+    pos = np.asarray([int(p) for p in positions], dtype=np.int64)
+    out = np.full((LEVELS, pos.size), -1, dtype=np.int32)
+    for k in range(LEVELS):
+        b = (pos - int(ref_out["start_coords"][k])) // (128000 >> k)
+        ok = (b >= 0) & (b < LEVEL_BINS)
+        out[k, ok] = b[ok]
+    return out
+
+
+def _pairs_host(alt, ref, bin_map, dtype):
+    a, r = np.asarray(alt, dtype=dtype), np.asarray(ref, dtype=dtype)
+    if a.ndim != 3 or a.shape[1] != a.shape[2] or r.shape != a.shape:
+        raise ValueError("alt, ref: [B, n, n]")
+    B, n = a.shape[0], a.shape[1]
+    bm = np.asarray(bin_map, dtype=np.int64)
+    bm = np.broadcast_to(bm, (B, n)) if bm.ndim == 1 else bm
+    if bm.shape != (B, n) or bm.min(initial=0) < -1 or bm.max(initial=0) >= n:
+        raise ValueError(f"bin map: [{B}, {n}] (or [{n}]) with values -1 .. {n - 1}")
+    return a, r, bm, B, n
+
+
+def paired_insulation_host(alt, ref, widths, bin_map):
+    """fp64 numpy restatement of orca_screen_paired_insulation: alt [B, n, n] against ref [B, n, n], pair b through ``bin_map`` [B, n] (or one
+    [n] for all), at ``widths`` (bins).  ins_w(m)[i] = the mean of m over rows [i - w, i) x columns (i, i + w], NaN unless w <= i < n - w
+    (`screen.insulation_host`).  (track, ref_track, aligned), each fp64 [B, W, n]: track = ins(alt b)[i], ref_track = ins(ref b)[i] at the
+    reference's own bin i, aligned = ins(alt b)[i] - ins(ref b)[map i] where map i >= 0 and both diamonds fit, else NaN."""
+    from . import screen
+    a, r, bm, B, n = _pairs_host(alt, ref, bin_map, np.float64)
+    track, ref_track = screen.insulation_host(a, widths), screen.insulation_host(r, widths)
+    aligned = np.full(track.shape, np.nan)
+    for b in range(B):
+        M = np.flatnonzero(bm[b] >= 0)
+        aligned[b][:, M] = track[b][:, M] - ref_track[b][:, bm[b, M]]
+    return track, ref_track, aligned
+
+
+def paired_viewpoints_host(alt, ref, views, bin_map):
+    """Numpy restatement of orca_screen_paired_viewpoints: alt [B, n, n] against ref [B, n, n] (float32), pair b through ``bin_map`` [B, n] (or
+    one [n]) at its own viewpoints ``views`` [B, V] (or one [V] for all): REFERENCE bins, -1 = none.  With R = the alt bins i with map i ==
+    view (ascending), c = |R|: (aligned float32 [B, V, n], count int32 [B, V] = c; 0 for view -1).  aligned[b, v, j] = fp32((sum_{i in R}
+    alt[i, j]) / c - ref_b[view, map j]) in fp64, the rows added in ascending i, where c >= 1 and map j >= 0, else NaN; for c = 1 it is the fp32
+    subtraction alt[R0, j] - ref_b[view, map j]."""
+    a, r, bm, B, n = _pairs_host(alt, ref, bin_map, np.float32)
+    vs = np.asarray(views, dtype=np.int64)
+    vs = np.broadcast_to(vs, (B, vs.shape[0])) if vs.ndim == 1 else vs
+    if vs.ndim != 2 or vs.shape[0] != B or vs.min(initial=0) < -1 or vs.max(initial=0) >= n:
+        raise ValueError(f"views: [{B}, V] (or [V]) with values -1 .. {n - 1}")
+    V = vs.shape[1]
+    aligned, count = np.full((B, V, n), np.nan, dtype=np.float32), np.zeros((B, V), dtype=np.int32)
+    for b in range(B):
+        cols = np.flatnonzero(bm[b] >= 0)
+        for k in range(V):
+            v = int(vs[b, k])
+            if v < 0:
+                continue
+            R = np.flatnonzero(bm[b] == v)
+            count[b, k] = R.size
+            if R.size == 1:
+                aligned[b, k, cols] = a[b, R[0], cols] - r[b, v, bm[b, cols]]
+            elif R.size > 1:
+                s = np.zeros(cols.size)
+                for i in R:
+                    s = s + a[b, i, cols].astype(np.float64)
+                aligned[b, k, cols] = (s / float(R.size) - r[b, v, bm[b, cols]].astype(np.float64)).astype(np.float32)
+    return aligned, count
+
+
+def _seq(v):
+    """the sum of v added sequentially from 0.0, in order"""
+    return float(np.cumsum(v)[-1]) if v.size else 0.0
+
+
+def paired_strata_host(alt, ref, bin_map, d_range=None):
+    """fp64 numpy restatement of orca_screen_paired_strata_scores: alt [B, n, n] against ref [B, n, n], pair b through ``bin_map`` [B, n] (or
+    one [n] for all).  Stratum d is the alt pairs (i, i + d) with mi = map i >= 0 and mj = map (i + d) >= 0, c_d of them; x = alt[i, i + d],
+    y = ref_b[min(mi, mj), max(mi, mj)] - the reference pixel mirrored into the upper triangle where the bin map descends, so that nothing below
+    the diagonal of either map is read.  Per stratum, two passes, each for i ascending from 0.0: the means mx_d, my_d, then X_d = sum (x - mx_d)^2,
+    Y_d, C_d = sum (x - mx_d)(y - my_d) and sum dl, sum |dl|, sum dl^2 of dl = x - y.  A dict of ``dist_delta``, ``dist_abs``, ``dist_rms``,
+    ``dist_corr`` [B, n] (the mean of dl, of |dl|, the root of the mean of dl^2, C_d / sqrt(X_d Y_d); NaN where c_d = 0, dist_corr also where
+    c_d < 2 or X_d or Y_d is 0), ``dist_count`` [B, n] int32, and over the strata ``d_range`` = (d_lo, d_hi) (all by default), serially for d
+    ascending, empty strata skipped, c = sum c_d: ``mse`` = sum sum dl^2 / c, ``scc`` = sum C_d / sum sqrt(X_d Y_d) (NaN when the denominator
+    is 0), ``corr`` = the Pearson correlation from the pooled sums, mx = (sum c_d mx_d) / c, X = sum [X_d + c_d (mx_d - mx)^2], C = sum [C_d +
+    c_d (mx_d - mx)(my_d - my)] (NaN when X or Y is 0 or c < 2); all three NaN when c = 0."""
+    from . import screen
+    a, r, bm, B, n = _pairs_host(alt, ref, bin_map, np.float64)
+    lo, hi = screen.check_strata(True if d_range is None else d_range, n)
+    out = {k: np.full((B, n), np.nan) for k in ("dist_delta", "dist_abs", "dist_rms", "dist_corr")}
+    out.update({k: np.full(B, np.nan) for k in ("mse", "corr", "scc")})
+    out["dist_count"] = np.zeros((B, n), dtype=np.int32)
+    with np.errstate(invalid="ignore"):
+        for b in range(B):
+            cnt = np.zeros(n, dtype=np.int64)
+            mx, my, X, Y, C, Q = (np.zeros(n) for _ in range(6))
+            for d in range(n):
+                i = np.arange(n - d)
+                mi, mj = bm[b, i], bm[b, i + d]
+                ok = (mi >= 0) & (mj >= 0)
+                i, mi, mj = i[ok], mi[ok], mj[ok]
+                c = cnt[d] = i.size
+                if c == 0:
+                    continue
+                x, y = a[b, i, i + d], r[b, np.minimum(mi, mj), np.maximum(mi, mj)]
+                mx[d], my[d] = _seq(x) / c, _seq(y) / c
+                ex, ey, dl = x - mx[d], y - my[d], x - y
+                X[d], Y[d], C[d], Q[d] = _seq(ex * ex), _seq(ey * ey), _seq(ex * ey), _seq(dl * dl)
+                out["dist_delta"][b, d], out["dist_abs"][b, d], out["dist_rms"][b, d] = _seq(dl) / c, _seq(np.abs(dl)) / c, np.sqrt(Q[d] / c)
+                if c >= 2 and X[d] != 0.0 and Y[d] != 0.0:
+                    out["dist_corr"][b, d] = C[d] / np.sqrt(X[d] * Y[d])
+            out["dist_count"][b] = cnt
+            ds = [d for d in range(lo, hi) if cnt[d] > 0]
+            tot = int(sum(cnt[d] for d in ds))
+            if tot == 0:
+                continue
+            q = num = den = wx = wy = 0.0
+            for d in ds:
+                q, num, den = q + Q[d], num + C[d], den + np.sqrt(X[d] * Y[d])
+                wx, wy = wx + cnt[d] * mx[d], wy + cnt[d] * my[d]
+            pmx, pmy = wx / tot, wy / tot
+            PX = PY = PC = 0.0
+            for d in ds:
+                ex, ey = mx[d] - pmx, my[d] - pmy
+                PX, PY, PC = PX + (X[d] + cnt[d] * (ex * ex)), PY + (Y[d] + cnt[d] * (ey * ey)), PC + (C[d] + cnt[d] * (ex * ey))
+            out["mse"][b] = q / tot
+            if den != 0.0 and not np.isnan(den):
+                out["scc"][b] = num / den
+            if tot >= 2 and PX != 0.0 and PY != 0.0:
+                out["corr"][b] = PC / np.sqrt(PX * PY)
+    return out
+
+
+def check_tracks(insulation=None, viewpoints=None, strata=None):
+    """The three readout arguments of `sv_screen` / `sv_scores`, checked: None when all are unset, else {"insulation": int32 widths or None,
+    "viewpoints": [positions] or None, "strata": (d_lo, d_hi) or None}.  ``insulation`` as `screen.check_insulation` takes it, ``strata`` as
+    `screen.check_strata`, on the levels' 250 bins; ``viewpoints``: 1 to 64 base positions on the original chromosome."""
+    from . import screen
+    if insulation is None and viewpoints is None and strata is None:
+        return None
+    spec = {"insulation": None, "viewpoints": None, "strata": None}
+    if insulation is not None:
+        spec["insulation"] = screen.check_insulation(insulation, LEVEL_BINS)
+    if viewpoints is not None:
+        try:
+            pos = [int(p) for p in viewpoints]
+        except (TypeError, ValueError):
+            raise ValueError("viewpoints: a sequence of base positions") from None
+        if not 1 <= len(pos) <= 64 or min(pos) < 0:
+            raise ValueError("viewpoints: 1 to 64 base positions >= 0")
+        spec["viewpoints"] = pos
+    if strata is not None:
+        spec["strata"] = screen.check_strata(strata, LEVEL_BINS)
+    return spec
+
+
+def _strata_counts(bm):
+    """int32 [n]: the alt pairs (i, i + d) of a bin map [n] whose two bins are mapped, per d."""
+    ok = (bm >= 0).astype(np.int64)
+    return np.correlate(ok, ok, "full")[ok.size - 1:].astype(np.int32)
+
+
+def _scores_entry(sv, chrlen, ref_out, alt_out, tracks=None):
+    """The model-independent part of an entry's ``scores`` (``tracks``: `check_tracks`' dict or None)."""
     bm = level_bin_maps(sv, chrlen, ref_out, alt_out)
-    return {"bin_map": bm, "count": (bm >= 0).sum(axis=1).astype(np.int32), "junction_bins": junction_bins(sv, chrlen, alt_out), "models": []}
+    entry = {"bin_map": bm, "count": (bm >= 0).sum(axis=1).astype(np.int32), "junction_bins": junction_bins(sv, chrlen, alt_out), "models": []}
+    if tracks is None:
+        return entry
+    if tracks["insulation"] is not None:
+        entry["insulation_widths"] = tracks["insulation"].copy()
+    if tracks["viewpoints"] is not None:
+        vb = entry["viewpoint_bins"] = viewpoint_bins(tracks["viewpoints"], ref_out)
+        entry["viewpoint_count"] = np.where(vb >= 0, (bm[:, None, :] == vb[:, :, None]).sum(axis=2), 0).astype(np.int32)
+    if tracks["strata"] is not None:
+        entry["strata_range"] = tuple(tracks["strata"])
+        entry["dist_count"] = np.stack([_strata_counts(bm[k]) for k in range(LEVELS)])
+    return entry
 
 
-def _model_scores(ctx, ref_maps, alt_maps, bin_map):
+def _model_scores(ctx, ref_maps, alt_maps, bin_map, entry=None):
     """One model's scores of one variant: ``ref_maps``, ``alt_maps`` [6, C, n, n] contiguous on the device, ``bin_map`` [6, n] (repeated per
-    target channel here) - one launch of 6 C pairs on the current stream; a dict of numpy arrays [6, C] (``profile`` [6, C, n])."""
+    target channel here) - one launch of 6 C pairs on the current stream; a dict of numpy arrays [6, C] (``profile`` [6, C, n]).  ``entry``
+    (`_scores_entry`'s dict): one more launch per readout it names, over the same pairs."""
     lv, C, n = alt_maps.shape[0], alt_maps.shape[1], alt_maps.shape[2]
-    got = engine.screen_paired_aligned_scores(ctx, alt_maps.reshape(lv * C, n, n), ref_maps.reshape(lv * C, n, n), np.repeat(bin_map, C, axis=0))
-    return {k: got[k].cpu().numpy().reshape((lv, C, n) if k == "profile" else (lv, C)) for k in SCORE_FIELDS}
+    alt, ref, bmc = alt_maps.reshape(lv * C, n, n), ref_maps.reshape(lv * C, n, n), np.repeat(bin_map, C, axis=0)
+    got = engine.screen_paired_aligned_scores(ctx, alt, ref, bmc)
+    out = {k: got[k].cpu().numpy().reshape((lv, C, n) if k == "profile" else (lv, C)) for k in SCORE_FIELDS}
+    if entry is None:
+        return out
+    if "insulation_widths" in entry:
+        W = len(entry["insulation_widths"])
+        tracks = engine.screen_paired_insulation(ctx, alt, ref, entry["insulation_widths"], bmc)
+        for k, t in zip(("insulation", "ref_insulation", "insulation_delta"), tracks):
+            out[k] = t.cpu().numpy().reshape(lv, C, W, n)
+    if "viewpoint_bins" in entry:
+        vb = entry["viewpoint_bins"]
+        aligned, _ = engine.screen_paired_viewpoints(ctx, alt, ref, np.repeat(vb, C, axis=0), bmc)
+        out["viewpoint_delta"] = aligned.cpu().numpy().reshape(lv, C, vb.shape[1], n)
+    if "strata_range" in entry:
+        st = engine.screen_paired_strata_scores(ctx, alt, ref, bmc, entry["strata_range"])
+        for k in STRATA_FIELDS:
+            out["strata_corr" if k == "corr" else k] = st[k].cpu().numpy().reshape((lv, C, n) if k.startswith("dist_") else (lv, C))
+    return out
 
 
 def _dict_maps(out, m, device):
@@ -226,17 +427,19 @@ def _dict_maps(out, m, device):
     return torch.from_numpy(np.ascontiguousarray(maps)).to(device)
 
 
-def sv_scores(sv, ref_out, alt_out, chrlen, device=None):
+def sv_scores(sv, ref_out, alt_out, chrlen, device=None, insulation=None, viewpoints=None, strata=None):
     """The ``scores`` of `sv_screen(..., scores=True)` from ANY pair of `genomepredict` output dicts of a variant's reference and alternative
     allele (the `process_*` drivers', `sv_screen(..., incremental=False)`'s): the maps are uploaded to ``device`` (default: the current MI355X)
-    and scored by the same kernel through `level_bin_maps` - the same dict."""
+    and scored by the same kernel through `level_bin_maps` - the same dict.  ``insulation``, ``viewpoints``, ``strata``: the readouts of
+    `sv_screen`, the same keys."""
+    tracks = check_tracks(insulation, viewpoints, strata)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if ref_out["predictions"] is None or alt_out["predictions"] is None:
         raise ValueError("sv_scores: the output dicts hold no maps (keep_maps=False)")
-    entry = _scores_entry(sv, chrlen, ref_out, alt_out)
+    entry = _scores_entry(sv, chrlen, ref_out, alt_out, tracks)
     ctx = engine.get_context(dev)
     for m in range(len(alt_out["predictions"])):
-        entry["models"].append(_model_scores(ctx, _dict_maps(ref_out, m, dev), _dict_maps(alt_out, m, dev), entry["bin_map"]))
+        entry["models"].append(_model_scores(ctx, _dict_maps(ref_out, m, dev), _dict_maps(alt_out, m, dev), entry["bin_map"], entry))
     return entry
 
 
@@ -934,7 +1137,7 @@ def _window_outputs(model, merged, starts, params, mchr, keep_maps=True):
 
 
 def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, incremental=True, min_uses=3, stats=None, on_result=None,
-              streams=None, group=2, stage3="auto", scores=False, keep_maps=True):
+              streams=None, group=2, stage3="auto", scores=False, keep_maps=True, insulation=None, viewpoints=None, strata=None):
     """Predict reference and alternative allele (6 maps each, per model) for this rank's share of ``svs``
     (independent windows: replicas, no collective).  genome_codes: [chrlen] uint8 tensor on the MI355X.
     Returns {sv_index: {"sv": SV, "ref": output_dict, "alt": output_dict}} with genomepredict's output dicts.
@@ -967,12 +1170,31 @@ def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, i
     indexed by level (32 Mb first) and target channel, ``profile`` also by ALT bin.  A level whose two windows share no locus has count 0 and
     NaN scores - the finest levels of a deletion larger than their window, since `sv_windows` centres the reference window on the deleted span.
     With ``incremental=False`` the scores come from the returned host maps (`sv_scores`).
+    ``insulation``, ``viewpoints``, ``strata`` (each needs ``scores=True``, else ValueError): readouts of WHAT changed, per level, from the same
+    final maps through the same bin maps - one more launch per readout and (variant, model) over the 6 C pairs, on the decoders' stream
+    (orca_screen_paired_insulation / _viewpoints / _strata_scores; `paired_insulation_host`, `paired_viewpoints_host`, `paired_strata_host`
+    restate them in numpy).  Unset, ``entry["scores"]`` has exactly the keys and bits above.
+      ``insulation=(5, 10, 25)``: diamond widths in bins, the same at every level (`screen.check_insulation` on 250 bins).  Adds
+        ``insulation_widths`` and per model ``insulation``, ``ref_insulation``, ``insulation_delta`` float32 [6, C, W, 250]: ins(alt)[i],
+        ins(ref)[i] at the reference's own bin, and ins(alt)[i] - ins(ref)[map i] by alt bin (NaN where bin i is unmapped or a diamond does
+        not fit); ``insulation_delta[k, c, w, junction_bins[k]]`` is the change at the breakpoint - a lost boundary reads positive.
+      ``viewpoints=[pos, ...]``: 1 to 64 base positions on the ORIGINAL chromosome (`viewpoint_bins`: a reference bin per level, -1 outside
+        the level's window).  Adds ``viewpoint_bins``, ``viewpoint_count`` int32 [6, V] (the alt bins that stand for the viewpoint: 0 deleted
+        or outside, 2 duplicated) and per model ``viewpoint_delta`` float32 [6, C, V, 250] by alt bin: the mean alt row of those bins minus the
+        reference's row of the viewpoint, column j against reference column map j.
+      ``strata=True`` or ``(d_lo, d_hi)`` (`screen.check_strata` on 250 bins).  Adds ``strata_range``, ``dist_count`` int32 [6, 250] and per
+        model ``dist_delta``, ``dist_abs``, ``dist_rms`` float32 [6, C, 250], ``dist_corr`` float64 [6, C, 250], ``mse`` float32 [6, C],
+        ``strata_corr``, ``scc`` float64 [6, C] (the strata kernel's pooled Pearson and HiCRep's stratum-adjusted correlation over the range;
+        ``corr`` keeps its meaning).  Inside an inversion the reference pixel is read mirrored into the upper triangle.
     ``keep_maps=False`` (needs ``scores=True``): the maps are not copied to the host - the output dicts keep ``start_coords``, ``end_coords``,
     ``chr`` and ``normmats`` and have "predictions": None.  A screen then returns a few KB per variant instead of 3 MB."""
     import time
     from . import dist, orca_predict
     if not keep_maps and not scores:
         raise ValueError("sv_screen: keep_maps=False returns nothing without scores=True")
+    tracks = check_tracks(insulation, viewpoints, strata)
+    if tracks is not None and not scores:
+        raise ValueError("sv_screen: insulation, viewpoints and strata are part of the scores (scores=True)")
     res = {}
     mine = list(dist.shard_indices(len(svs), rank, world))
     if not incremental:
@@ -983,7 +1205,7 @@ def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, i
             alt = orca_predict.genomepredict(assemble_codes(genome_codes, ap)[None], mchr, am, aw, models=models)
             entry = {"sv": sv, "ref": ref, "alt": alt}
             if scores:
-                entry["scores"] = sv_scores(sv, ref, alt, chrlen, genome_codes.device)
+                entry["scores"] = sv_scores(sv, ref, alt, chrlen, genome_codes.device, insulation, viewpoints, strata)
                 if not keep_maps:
                     ref["predictions"] = alt["predictions"] = None
             if on_result is not None:
@@ -1100,14 +1322,14 @@ def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, i
                     if mi == 0:
                         entries[i] = {"sv": svs[i], "ref": r, "alt": a}
                         if scores:
-                            entries[i]["scores"] = _scores_entry(svs[i], chrlen, r, a)
+                            entries[i]["scores"] = _scores_entry(svs[i], chrlen, r, a, tracks)
                     else:
                         for o, n in ((entries[i]["ref"], r), (entries[i]["alt"], a)):
                             if keep_maps:
                                 o["predictions"] += n["predictions"]
                             o["normmats"] += n["normmats"]
                     if scores:      # the final maps of this (variant, model), still on the device, on the stream the decoders ran on
-                        entries[i]["scores"]["models"].append(_model_scores(ctx, merged[2 * v], merged[2 * v + 1], entries[i]["scores"]["bin_map"]))
+                        entries[i]["scores"]["models"].append(_model_scores(ctx, merged[2 * v], merged[2 * v + 1], entries[i]["scores"]["bin_map"], entries[i]["scores"]))
                 if pool is None and k + 1 < len(units):
                     prep(k + 1)
                 if mi == len(models) - 1:

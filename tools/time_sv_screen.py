@@ -1,10 +1,14 @@
 """SV screen timing (BASELINE configs[4]) on one GPU: python tools/time_sv_screen.py [n_svs] [incremental 0|1] [streams: auxiliary contexts of the local encodes, 0 = none, -1 = default] [align: 1 = unaligned (default), 4000 = the 4 kb grid]
 --scores: what the on-device impact scores cost - the same variants through (a) the plain screen, (b) scores=True, (c) scores=True, keep_maps=False,
-alternated in one run, best of three each; writes profiles/sv_screen_scores.json"""
+alternated in one run, best of three each; writes profiles/sv_screen_scores.json
+--tracks: what the readouts per level cost - the same variants with (a) scores=True, (b) scores=True, insulation=(5, 10, 25), viewpoints=[one position],
+strata=True, alternated in one run, best of three each; the added ms per variant is reported against the scores=True repetition beside it, with the
+spread of the baseline's three repetitions; writes profiles/sv_screen_tracks.json"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SCORES = "--scores" in sys.argv
-sys.argv = [a for a in sys.argv if a != "--scores"]
+TRACKS = "--tracks" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--scores", "--tracks")]
 import torch
 from orca_amd import orca_models, sv
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 32
@@ -40,6 +44,35 @@ if SCORES:
            "scores_cost_ms_per_sv": round(best["scores"] - best["plain"], 3), "scores_within_plain_spread": bool(best["scores"] <= best["plain"] + spread),
            "no_maps_saving_ms_per_sv": round(best["plain"] - best["scores_no_maps"], 3)}
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sv_screen_scores.json")
+    json.dump(out, open(path, "w"), indent=1)
+    print(json.dumps({k: v for k, v in out.items() if k != "runs"}))
+    sys.exit(0)
+if TRACKS:
+    import json
+    modes = {"scores": {"scores": True},
+             "tracks": {"scores": True, "insulation": (5, 10, 25), "viewpoints": [20_000_000], "strata": True}}
+    sv.sv_screen([h1], genome, svs[:2], 40_000_000, incremental=inc, min_uses=1, streams=streams, **modes["tracks"])     # the new kernels' first launch
+    torch.cuda.synchronize()
+    runs = {k: [] for k in modes}
+    for rep in range(3):
+        for k, kw in modes.items():
+            st = {}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sv.sv_screen([h1], genome, svs[2:], 40_000_000, incremental=inc, stats=st, streams=streams, on_result=lambda i, e: None, **kw)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            build = (st.get("stage3_cache") or {}).get("build_s", 0.0)      # the stage cache is rebuilt by every call: its time is not the screen's
+            runs[k].append({"total_s": round(dt, 4), "stage_cache_build_s": build, "ms_per_sv": round((dt - build) / n * 1e3, 3)})
+            print(k, runs[k][-1])
+    best = {k: min(r["ms_per_sv"] for r in v) for k, v in runs.items()}
+    beside = [round(t["ms_per_sv"] - s["ms_per_sv"], 3) for s, t in zip(runs["scores"], runs["tracks"])]      # each against the baseline repetition beside it
+    spread = max(r["ms_per_sv"] for r in runs["scores"]) - best["scores"]
+    out = {"tool": "tools/time_sv_screen.py --tracks", "n_svs": n, "incremental": inc, "streams": streams, "align": align, "modes": {k: {a: list(b) if isinstance(b, tuple) else b for a, b in kw.items()} for k, kw in modes.items()},
+           "runs": runs, "best_ms_per_sv": best, "scores_spread_ms_per_sv": round(spread, 3), "tracks_added_ms_per_sv_per_repetition": beside,
+           "tracks_added_ms_per_sv_best_of_three": round(best["tracks"] - best["scores"], 3),
+           "tracks_within_scores_spread": bool(best["tracks"] <= best["scores"] + spread)}
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sv_screen_tracks.json")
     json.dump(out, open(path, "w"), indent=1)
     print(json.dumps({k: v for k, v in out.items() if k != "runs"}))
     sys.exit(0)
