@@ -502,6 +502,31 @@ int orca_screen_dot_calls(orca_ctx* ctx, const float* maps, int64_t map_bs, int 
 int orca_screen_dot_enrichment(orca_ctx* ctx, const float* maps, int64_t map_bs, int B, int n, int p, int w, int d_min, const int32_t* pixels,
                                const int32_t* pixels_host, int Q, float* out);
 
+/* Loops per level of the SV screen (sv.sv_screen(..., scores=True, loops=)): the reference dots of B pairs followed through each pair's bin map into the
+ * alt map.  Everything about e - the sets, eligibility, what makes a pixel a dot, the list order and the truncation to K - is orca_screen_dot_calls': the
+ * caller runs it on the reference maps and on the alt maps, and this entry point only gathers.
+ *   alt_e        [B][n][n] at alt_e + b * e_bs (e_bs >= n * n): the enrichment map orca_screen_dot_calls wrote for the alt maps (NaN where ineligible)
+ *   ref_ij       [B][R][2] int32 and ref_enrich [B][R]: the lists orca_screen_dot_calls wrote for the reference maps, ON THE DEVICE ONLY (1 <= R <= 4096).
+ *                A slot that holds no dot - the -1 padding, or anything that does not satisfy 0 <= ri < rj <= n - 1 - is an EMPTY slot: it has no
+ *                candidate and is never used as an index
+ *   bin_map      B x n int32, -1 .. n - 1 (device copy and checked host copy), as in the other paired entry points; w, d_min: the calls' (1 <= w <= 16,
+ *                d_min >= 2 w + 1)
+ * For reference dot k = (ri, rj) of pair b: A = the alt bins a with map_b a = ri, C = the alt bins c with map_b c = rj (disjoint, ri != rj).  The
+ * CANDIDATES are the pixels (min(a, c), max(a, c)) over A x C that are eligible in the alt map (w <= i, j <= n - 1 - w, j - i >= d_min).  The min/max is
+ * the mirror rule of orca_screen_paired_strata_scores: inside an inversion the bin map descends, a contact map is symmetric, and nothing on or below a
+ * diagonal is ever read.  The candidates are distinct pixels.  The chosen one is the best under one total order: a non-NaN e beats a NaN e, a larger e
+ * beats a smaller one (fp32 comparison), and of two equals the earlier in row-major order wins - "does this loop survive anywhere in the allele".
+ *   candidates[b][k] = their number (int32): 0 = an anchor is deleted, outside the alt window, or too near the diagonal or the edge; 1 = the ordinary
+ *                      case; 2 to 4 under a tandem duplication
+ *   at[b][k][2]      = the chosen pixel (i, j) (int32);  enrich[b][k] = alt_e there (its bits);  delta[b][k] = enrich[b][k] - ref_enrich[b][k], one fp32
+ *                      subtraction (NaN propagates)
+ * With no candidate, and in every empty slot: 0, (-1, -1), NaN, NaN.  Comparisons and one subtraction only, no atomics: a pair's outputs are bit for bit
+ * the same whatever B, its place in the batch and the strides.  Anything else - a NULL pointer, a bin-map value outside -1 .. n - 1 - is ORCA_EINVAL
+ * before any launch. */
+int orca_screen_paired_dot_follow(orca_ctx* ctx, const float* alt_e, int64_t e_bs, int B, int n, int w, int d_min, const int32_t* ref_ij,
+                                  const float* ref_enrich, int R, const int32_t* bin_map, const int32_t* bin_map_host, int32_t* candidates, int32_t* at,
+                                  float* enrich, float* delta);
+
 /* Number of 4 kb bins Encoder emits for an L-bp input (floor through the
  * 4,4,5,5,5,2 pooling chain). */
 int64_t orca_encoder_num_bins(int64_t L);

@@ -424,6 +424,25 @@ extern "C" int orca_screen_dot_enrichment(orca_ctx* ctx, const float* maps, int6
                 pixels, Q, out);
 }
 
+// the reference dots of B pairs followed into the alt maps' enrichment map; the lists are on the device only (the kernel treats every slot that holds no
+// dot as empty), the bin map comes twice
+extern "C" int orca_screen_paired_dot_follow(orca_ctx* ctx, const float* alt_e, int64_t e_bs, int B, int n, int w, int d_min, const int32_t* ref_ij,
+                                             const float* ref_enrich, int R, const int32_t* bin_map, const int32_t* bin_map_host, int32_t* candidates,
+                                             int32_t* at, float* enrich, float* delta) {
+  if (!ctx || !alt_e || !ref_ij || !ref_enrich || !bin_map || !bin_map_host || !candidates || !at || !enrich || !delta)
+    return fail(ORCA_EINVAL, "orca_screen_paired_dot_follow: NULL argument");
+  if (B < 1 || n < 1 || n > SCREEN_ALIGNED_MAX_BINS || e_bs < (int64_t)n * n)
+    return fail(ORCA_EINVAL, "orca_screen_paired_dot_follow: %d pairs (>= 1) of enrichment maps of %d bins (1..%d), batch stride %ld (>= n * n)", B, n,
+                SCREEN_ALIGNED_MAX_BINS, (long)e_bs);
+  if (w < 1 || w > SCREEN_DOT_MAX_W) return fail(ORCA_EINVAL, "orca_screen_paired_dot_follow: window half-width w = %d (1..%d)", w, SCREEN_DOT_MAX_W);
+  if (d_min < 2 * w + 1) return fail(ORCA_EINVAL, "orca_screen_paired_dot_follow: d_min = %d (>= 2 w + 1 = %d)", d_min, 2 * w + 1);
+  if (R < 1 || R > SCREEN_DOT_MAX_CALLS) return fail(ORCA_EINVAL, "orca_screen_paired_dot_follow: R = %d listed reference dots per pair (1..%d)", R, SCREEN_DOT_MAX_CALLS);
+  ORCA_TRY(check_bin_map("orca_screen_paired_dot_follow", bin_map_host, B, n));
+  return launch(ctx, "screen_paired_dot_follow_kernel", screen_paired_dot_follow_kernel,
+                dim3((unsigned)B, (unsigned)((R + SCREEN_FOLLOW_DOTS - 1) / SCREEN_FOLLOW_DOTS)), 64 * SCREEN_FOLLOW_DOTS, alt_e, (long)e_bs, n, w, d_min, ref_ij,
+                ref_enrich, R, bin_map, candidates, at, enrich, delta);
+}
+
 // ---- both strands --------------------------------------------------------------------------------------------------------------------------------------------
 extern "C" int orca_screen_merge_strands(orca_ctx* ctx, const float* fwd, int64_t fwd_bs, const float* rev, int64_t rev_bs, const float* ref_fwd, const float* ref_rev,
                                          int B, int n, float* out, int64_t out_bs, float* gap) {

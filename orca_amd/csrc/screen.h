@@ -937,6 +937,86 @@ static __global__ void __launch_bounds__(256) screen_dot_calls_kernel(const floa
   }
 }
 
+// ---- loops per level of the SV screen (sv.sv_screen(..., scores=True, loops=)): a reference dot followed through the pair's bin map ---------------------
+// include/orca_hip.h (orca_screen_paired_dot_follow) has the rule.  Reference dot k = (ri, rj) of pair b, A = the alt bins a with map a = ri, C = those
+// with map c = rj: the candidates are the pixels (min(a, c), max(a, c)) over A x C that are eligible in the alt map - the min/max mirrors a pixel of a
+// descending bin map into the upper triangle - and the best of them goes out under ONE total order: a non-NaN e beats a NaN e, a larger e a smaller one
+// (fp32 comparison), and of two equals the earlier pixel in row-major order.  A x C holds distinct pixels (ri != rj: A and C are disjoint), so the order
+// is total and the result does not depend on which lane met which candidate.  e is gathered from the alt maps' enrichment map, written by an earlier
+// launch on the same stream (screen_dot_enrich_map_kernel): nothing is computed here but comparisons and one fp32 subtraction.
+// One workgroup of 4 waves per (pair, 4 list slots), one wave per slot: the bin map goes to LDS once, the wave lists A and C there (ascending), walks
+// the |A| |C| pairs with a stride of 64 (a degenerate map has up to (n / 2)^2 of them) and reduces by shuffles.  A slot that holds no dot - anything but
+// 0 <= ri < rj <= n - 1; the lists are on the device only - has no candidate and is never used as an index.  No candidate: 0, (-1, -1), NaN, NaN.
+#define SCREEN_FOLLOW_DOTS 4               // list slots per workgroup: one wave each
+
+// is candidate (e, at) better than (f, other)?  at, other: row-major pixel indices, -1 = none yet
+static __device__ __forceinline__ bool screen_follow_better(float e, int at, float f, int other) {
+  if (at < 0) return false;
+  if (other < 0) return true;
+  const bool en = e != e, fn = f != f;
+  if (en != fn) return fn;
+  if (!en && e != f) return e > f;
+  return at < other;
+}
+
+static __global__ void __launch_bounds__(64 * SCREEN_FOLLOW_DOTS) screen_paired_dot_follow_kernel(const float* __restrict__ alt_e, long e_bs, int n, int w,
+                                                                                                  int d_min, const int* __restrict__ ref_ij,
+                                                                                                  const float* __restrict__ ref_enrich, int R,
+                                                                                                  const int* __restrict__ bin_map, int* __restrict__ candidates,
+                                                                                                  int* __restrict__ at_out, float* __restrict__ enrich,
+                                                                                                  float* __restrict__ delta) {
+  __shared__ int s_map[SCREEN_ALIGNED_MAX_BINS];
+  __shared__ int s_a[SCREEN_FOLLOW_DOTS][SCREEN_ALIGNED_MAX_BINS], s_c[SCREEN_FOLLOW_DOTS][SCREEN_ALIGNED_MAX_BINS];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, k = blockIdx.y * SCREEN_FOLLOW_DOTS + wv;
+  n = n > SCREEN_ALIGNED_MAX_BINS ? SCREEN_ALIGNED_MAX_BINS : n;
+  w = w > SCREEN_DOT_MAX_W ? SCREEN_DOT_MAX_W : (w < 1 ? 1 : w);
+  d_min = d_min < 2 * w + 1 ? 2 * w + 1 : d_min;
+  screen_load_bin_map(bin_map + (long)b * n, n, s_map);
+  __syncthreads();
+  int ri = -1, rj = -1;
+  if (k < R) {
+    ri = ref_ij[2 * ((long)b * R + k)];
+    rj = ref_ij[2 * ((long)b * R + k) + 1];
+  }
+  const bool dot = ri >= 0 && ri < rj && rj <= n - 1;              // wave-uniform
+  const int na = dot ? screen_bins_in(s_map, n, ri, ri + 1, s_a[wv], lane) : 0;
+  const int nc = dot ? screen_bins_in(s_map, n, rj, rj + 1, s_c[wv], lane) : 0;
+  __syncthreads();                                                 // the lists are read by other lanes than wrote them
+  if (k >= R) return;
+  const float* e = alt_e + (long)b * e_bs;
+  const float qnan = __int_as_float(0x7fc00000);
+  int cnt = 0, best = -1;
+  float best_e = qnan;
+  for (int t = lane; t < na * nc; t += 64) {
+    const int a = s_a[wv][t / nc], c = s_c[wv][t % nc];
+    const int i = a < c ? a : c, j = a < c ? c : a;
+    if (!screen_dot_eligible(i, j, n, w, d_min)) continue;
+    const int at = i * n + j;
+    const float v = e[at];
+    ++cnt;
+    if (screen_follow_better(v, at, best_e, best)) {
+      best = at;
+      best_e = v;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    cnt += __shfl_xor(cnt, o, 64);
+    const int other = __shfl_xor(best, o, 64);
+    const float f = __shfl_xor(best_e, o, 64);
+    if (screen_follow_better(f, other, best_e, best)) {
+      best = other;
+      best_e = f;
+    }
+  }
+  if (lane != 0) return;
+  const long out = (long)b * R + k;
+  candidates[out] = cnt;
+  at_out[2 * out] = best < 0 ? -1 : best / n;
+  at_out[2 * out + 1] = best < 0 ? -1 : best % n;
+  enrich[out] = best < 0 ? qnan : best_e;
+  delta[out] = best < 0 ? qnan : best_e - ref_enrich[out];
+}
+
 // ---- both strands (screen.screen_1m(..., strands="both")): the '-' strand's map is merged into the '+' strand's as genomepredict merges them ------------
 // out[b][i][j] = 0.5 fwd[b][i][j] + 0.5 rev[b][n-1-i][n-1-j] (the expression of strand_merge_kernel: the same bits), and with the two strands' reference maps
 // gap[b] = mean_ij |(fwd - ref_fwd)[i][j] - (rev - ref_rev)[n-1-i][n-1-j]| - how far the strands disagree about the item's effect.  One workgroup per map, one

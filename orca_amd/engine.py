@@ -1147,6 +1147,38 @@ def screen_dot_enrichment(ctx, maps, pixels_host, p, w, d_min=None):
     return out
 
 
+def screen_paired_dot_follow(ctx, alt_e, ref_ij, ref_enrich, bin_map_host, w, d_min=None):
+    """The reference dots of B pairs followed through each pair's bin map into the alt map (orca_screen_paired_dot_follow; include/orca_hip.h has the
+    rule).  ``alt_e`` [B, n, n] float32 (any batch stride, rows contiguous): `screen_dot_calls`' ``e_map`` of the alt maps; ``ref_ij`` [B, R, 2] int32 and
+    ``ref_enrich`` [B, R] float32: its ``ij`` and ``enrich`` of the reference maps, device tensors as it returned them (a slot that is no dot, 0 <= ri < rj
+    <= n - 1, is empty); ``bin_map_host`` [B, n] int32 numpy.  A dict of device tensors: ``candidates`` [B, R] int32 (the eligible alt pixels that stand for
+    the dot), ``at`` [B, R, 2] int32 (the one with the largest e, the earlier of equals; (-1, -1) without a candidate), ``enrich`` [B, R] float32 (e there)
+    and ``delta`` [B, R] float32 (e there minus the reference dot's e), NaN without a candidate."""
+    alt_e = _f32_cuda(alt_e, "alt_e")
+    if alt_e.dim() != 3 or alt_e.shape[0] < 1 or alt_e.shape[1] != alt_e.shape[2] or alt_e.stride(2) != 1 or alt_e.stride(1) != alt_e.shape[1]:
+        raise ValueError("alt_e: [B,n,n] with B >= 1 and contiguous maps")
+    B, n = alt_e.shape[0], alt_e.shape[1]
+    e_bs = alt_e.stride(0) if B > 1 else max(alt_e.stride(0), n * n)               # B = 1: torch may report any stride for the one map
+    ref_ij, ref_enrich = _on_device(ref_ij, "ref_ij", torch.int32), _on_device(ref_enrich, "ref_enrich", torch.float32)
+    if ref_ij.dim() != 3 or ref_ij.shape[0] != B or ref_ij.shape[2] != 2 or ref_enrich.shape != ref_ij.shape[:2] or ref_ij.device != alt_e.device \
+            or ref_enrich.device != alt_e.device:
+        raise ValueError(f"ref_ij: [{B},R,2] int32 and ref_enrich: [{B},R] float32 on the maps' device")
+    R, dev = ref_ij.shape[1], alt_e.device
+    m = _host_table(bin_map_host, np.int32, n, "bin map")
+    if m.shape[0] != B:
+        raise ValueError(f"bin map: [{B},{n}] int32, one row per pair")
+    md = torch.from_numpy(m).to(dev)
+    w = int(w)
+    d_min = 2 * w + 1 if d_min is None else int(d_min)
+    enrich, delta = _f32_outputs(dev, (B, R), (B, R))
+    candidates = torch.empty((B, R), dtype=torch.int32, device=dev)
+    at = torch.empty((B, R, 2), dtype=torch.int32, device=dev)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_paired_dot_follow(ctx.handle, _dev_p(alt_e), e_bs, B, n, w, d_min, _dev_p(ref_ij), _dev_p(ref_enrich), R, _dev_p(md), _np_p(m),
+                                                    _dev_p(candidates), _dev_p(at), _dev_p(enrich), _dev_p(delta)), "orca_screen_paired_dot_follow")
+    return {"candidates": candidates, "at": at, "enrich": enrich, "delta": delta}
+
+
 # both strands (orca_screen_merge_strands)
 def screen_merge_strands(ctx, fwd, rev, ref_fwd=None, ref_rev=None, out=None):
     """The '+' strand's maps ``fwd`` [B, n, n] and the '-' strand's ``rev`` [B, n, n] (any batch stride, rows contiguous) merged as genomepredict merges

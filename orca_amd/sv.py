@@ -349,6 +349,130 @@ def paired_strata_host(alt, ref, bin_map, d_range=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Loops per level.  The dot calls are the 1 Mb screen's (orca_screen_dot_calls on the reference maps and on the alt maps; `screen.LoopParams`); what
+# is new is the way from a reference dot into the alt map.  Under a duplication two alt bins stand for one reference bin, so a reference dot has up
+# to four alt pixels: it is followed to EVERY one that is eligible and the strongest is reported - "does this loop survive anywhere in the allele" -
+# with their number beside it (orca_screen_paired_dot_follow; include/orca_hip.h and DESIGN 3d have the rule).
+# ---------------------------------------------------------------------------------------------------------------------------------
+LOOP_SCORE_FIELDS = ("ref_loops", "loops", "ref_loop_enrichment", "loop_enrichment", "ref_loop_count", "loop_count", "loop_candidates", "loop_followed_at",
+                     "loop_followed_enrichment", "loop_delta", "loop_is_gained", "ref_loop_is_lost", "loops_gained", "loops_lost")
+
+
+def check_loops_arg(loops):
+    """The ``loops`` argument of `sv_screen` / `sv_scores`, checked: None when unset (None or False), else the validated `screen.LoopParams`
+    (`screen.check_loops` on the levels' 250 bins; True = the defaults).  One parameter set serves all six levels."""
+    from . import screen
+    if loops is None or loops is False:
+        return None
+    return screen.check_loops(loops, LEVEL_BINS)
+
+
+def _is_dot_slot(ij, n):
+    """bool [...]: the slots of a dot list [..., 2] that hold a dot, 0 <= i < j <= n - 1 (the -1 padding and anything else is an empty slot)."""
+    return (ij[..., 0] >= 0) & (ij[..., 0] < ij[..., 1]) & (ij[..., 1] <= n - 1)
+
+
+def _follow_beats(v, at, w, other):
+    """The total order of the follow: is candidate (e = v at pixel ``at``) better than (w at ``other``)?  A non-NaN e beats a NaN e, a larger e a
+    smaller one (fp32), and of two equals the earlier pixel in row-major order."""
+    vn, wn = bool(np.isnan(v)), bool(np.isnan(w))
+    if vn != wn:
+        return wn
+    if not vn and v != w:
+        return bool(v > w)
+    return at < other
+
+
+def paired_dot_follow_host(alt_e, ref_ij, ref_enrich, bin_map, params):
+    """Numpy restatement of orca_screen_paired_dot_follow, brute force over A x C: ``alt_e`` [B, n, n] float32 (the alt maps' enrichment map,
+    `screen.dot_calls_host`'s or the device's ``e_map``), ``ref_ij`` [B, R, 2] and ``ref_enrich`` [B, R] (the reference maps' dot lists), pair b
+    through ``bin_map`` [B, n] (or one [n] for all); ``params``: a `screen.LoopParams` (w and d_min are used).  For reference dot (ri, rj), 0 <= ri <
+    rj <= n - 1 (any other slot is empty): A = the alt bins a with map a = ri, C = those with map c = rj, the candidates are the pixels (min(a, c),
+    max(a, c)) over A x C with w <= i, j <= n - 1 - w and j - i >= d_min.  A dict of ``candidates`` [B, R] int32 (their number), ``at`` [B, R, 2]
+    int32 (the best: a non-NaN e beats a NaN e, a larger e a smaller one, the earlier pixel of two equals), ``enrich`` [B, R] float32 (alt_e there)
+    and ``delta`` [B, R] float32 = enrich - ref_enrich (fp32); (-1, -1), NaN, NaN without a candidate."""
+    from . import screen
+    q = screen._loop_params(params)
+    e = np.asarray(alt_e, dtype=np.float32)
+    if e.ndim != 3 or e.shape[1] != e.shape[2]:
+        raise ValueError("alt_e: [B, n, n]")
+    B, n = e.shape[0], e.shape[1]
+    ij, re = np.asarray(ref_ij, dtype=np.int64), np.asarray(ref_enrich, dtype=np.float32)
+    if ij.ndim != 3 or ij.shape[0] != B or ij.shape[2] != 2 or re.shape != ij.shape[:2]:
+        raise ValueError(f"ref_ij: [{B}, R, 2], ref_enrich: [{B}, R]")
+    bm = np.asarray(bin_map, dtype=np.int64)
+    bm = np.broadcast_to(bm, (B, n)) if bm.ndim == 1 else bm
+    if bm.shape != (B, n) or bm.min(initial=0) < -1 or bm.max(initial=0) >= n:
+        raise ValueError(f"bin map: [{B}, {n}] (or [{n}]) with values -1 .. {n - 1}")
+    R = ij.shape[1]
+    out = {"candidates": np.zeros((B, R), dtype=np.int32), "at": np.full((B, R, 2), -1, dtype=np.int32),
+           "enrich": np.full((B, R), np.nan, dtype=np.float32), "delta": np.full((B, R), np.nan, dtype=np.float32)}
+    dot = _is_dot_slot(ij, n)
+    for b, k in zip(*np.nonzero(dot)):
+        ri, rj = int(ij[b, k, 0]), int(ij[b, k, 1])
+        best, cnt = None, 0
+        for a in np.flatnonzero(bm[b] == ri):
+            for c in np.flatnonzero(bm[b] == rj):
+                i, j = int(min(a, c)), int(max(a, c))
+                if not (i >= q.w and j <= n - 1 - q.w and j - i >= q.d_min):
+                    continue
+                cnt += 1
+                if best is None or _follow_beats(e[b, i, j], i * n + j, e[b, best[0], best[1]], best[0] * n + best[1]):
+                    best = (i, j)
+        out["candidates"][b, k] = cnt
+        if best is not None:
+            out["at"][b, k] = best
+            out["enrich"][b, k] = e[b, best[0], best[1]]
+            with np.errstate(invalid="ignore"):
+                out["delta"][b, k] = e[b, best[0], best[1]] - re[b, k]
+    return out
+
+
+def paired_match_loops_host(alt_ij, ref_ij, bin_map_row, tol):
+    """Match the listed dots of an alt map, ``alt_ij`` [K, 2], to its reference map's, ``ref_ij`` [R, 2], through the pair's bin map ``bin_map_row``
+    [n]: (is_gained [K] bool, is_lost [R] bool).  An alt dot (a, c) stands for the reference pixel (min(map a, map c), max(map a, map c)) - the mirror
+    rule: inside an inversion the bin map descends - or for nothing if either bin is unmapped; it matches a listed reference dot within Chebyshev
+    distance ``tol``.  gained = a listed alt dot that matches none, lost = a listed reference dot that none matches; both False in the empty slots
+    (-1 padding, or anything but 0 <= i < j <= n - 1)."""
+    alt, ref = np.asarray(alt_ij, dtype=np.int64).reshape(-1, 2), np.asarray(ref_ij, dtype=np.int64).reshape(-1, 2)
+    bm = np.asarray(bin_map_row, dtype=np.int64)
+    n = bm.shape[0]
+    listed, ref_listed = _is_dot_slot(alt, n), _is_dot_slot(ref, n)
+    m = bm[np.where(listed[:, None], alt, 0)]
+    ok = listed & (m >= 0).all(axis=1)
+    px = np.stack([m.min(axis=1), m.max(axis=1)], axis=1)
+    near = (np.abs(px[:, None, :] - ref[None, :, :]).max(axis=2) <= int(tol)) & ok[:, None] & ref_listed[None, :]       # [K, R]
+    return listed & ~near.any(axis=1), ref_listed & ~near.any(axis=0)
+
+
+def _loop_fields(rc, ac, fl, bin_map, tol):
+    """The loop fields of B pairs, [B, ...] numpy arrays, from the dot calls of the reference maps ``rc`` and of the alt maps ``ac`` (``count``,
+    ``ij``, ``enrich``), the follow ``fl`` and the matching on the host."""
+    B, K = ac["ij"].shape[0], ac["ij"].shape[1]
+    gained, lost = np.zeros((B, K), dtype=bool), np.zeros((B, K), dtype=bool)
+    for b in range(B):
+        gained[b], lost[b] = paired_match_loops_host(ac["ij"][b], rc["ij"][b], bin_map[b], tol)
+    return {"ref_loops": rc["ij"], "loops": ac["ij"], "ref_loop_enrichment": rc["enrich"], "loop_enrichment": ac["enrich"],
+            "ref_loop_count": rc["count"], "loop_count": ac["count"], "loop_candidates": fl["candidates"], "loop_followed_at": fl["at"],
+            "loop_followed_enrichment": fl["enrich"], "loop_delta": fl["delta"], "loop_is_gained": gained, "ref_loop_is_lost": lost,
+            "loops_gained": gained.sum(axis=1).astype(np.int32), "loops_lost": lost.sum(axis=1).astype(np.int32)}
+
+
+def paired_loop_scores_host(alt, ref, bin_map, params):
+    """Numpy restatement of the loop fields of ``sv_screen(..., scores=True, loops=)`` for B pairs: alt [B, n, n] against ref [B, n, n], pair b through
+    ``bin_map`` [B, n] (or one [n] for all), ``params`` a `screen.LoopParams` (or True).  `screen.dot_calls_host` on both, `paired_dot_follow_host`
+    from the reference's list into the alt maps' enrichment map, `paired_match_loops_host` per pair: a dict of `LOOP_SCORE_FIELDS`, each [B, ...]
+    (K = max_calls): ``ref_loops``, ``loops`` int32 [B, K, 2]; ``ref_loop_enrichment``, ``loop_enrichment`` float32 [B, K]; ``ref_loop_count``,
+    ``loop_count`` int32 [B] (all dots); ``loop_candidates`` int32 [B, K]; ``loop_followed_at`` int32 [B, K, 2]; ``loop_followed_enrichment``,
+    ``loop_delta`` float32 [B, K]; ``loop_is_gained``, ``ref_loop_is_lost`` bool [B, K]; ``loops_gained``, ``loops_lost`` int32 [B]."""
+    from . import screen
+    a, r, bm, B, n = _pairs_host(alt, ref, bin_map, np.float32)
+    q = screen.check_loops(params, n)
+    rc, ac = screen.dot_calls_host(r, q), screen.dot_calls_host(a, q)
+    return _loop_fields(rc, ac, paired_dot_follow_host(ac["e_map"], rc["ij"], rc["enrich"], bm, q), bm, q.tol)
+
+
 def check_tracks(insulation=None, viewpoints=None, strata=None):
     """The three readout arguments of `sv_screen` / `sv_scores`, checked: None when all are unset, else {"insulation": int32 widths or None,
     "viewpoints": [positions] or None, "strata": (d_lo, d_hi) or None}.  ``insulation`` as `screen.check_insulation` takes it, ``strata`` as
@@ -378,10 +502,12 @@ def _strata_counts(bm):
     return np.correlate(ok, ok, "full")[ok.size - 1:].astype(np.int32)
 
 
-def _scores_entry(sv, chrlen, ref_out, alt_out, tracks=None):
-    """The model-independent part of an entry's ``scores`` (``tracks``: `check_tracks`' dict or None)."""
+def _scores_entry(sv, chrlen, ref_out, alt_out, tracks=None, loops=None):
+    """The model-independent part of an entry's ``scores`` (``tracks``: `check_tracks`' dict or None; ``loops``: `check_loops_arg`'s)."""
     bm = level_bin_maps(sv, chrlen, ref_out, alt_out)
     entry = {"bin_map": bm, "count": (bm >= 0).sum(axis=1).astype(np.int32), "junction_bins": junction_bins(sv, chrlen, alt_out), "models": []}
+    if loops is not None:
+        entry["loop_params"] = loops
     if tracks is None:
         return entry
     if tracks["insulation"] is not None:
@@ -418,7 +544,28 @@ def _model_scores(ctx, ref_maps, alt_maps, bin_map, entry=None):
         st = engine.screen_paired_strata_scores(ctx, alt, ref, bmc, entry["strata_range"])
         for k in STRATA_FIELDS:
             out["strata_corr" if k == "corr" else k] = st[k].cpu().numpy().reshape((lv, C, n) if k.startswith("dist_") else (lv, C))
+    if "loop_params" in entry:
+        for k, v in _model_loops(ctx, alt, ref, bmc, entry["loop_params"]).items():
+            out[k] = v.reshape((lv, C) + v.shape[1:])
     return out
+
+
+def _model_loops(ctx, alt, ref, bin_map, q):
+    """The loop fields (`LOOP_SCORE_FIELDS`, numpy [B, ...]) of B pairs of maps on the device, alt [B, n, n] against ref [B, n, n] (contiguous) through
+    ``bin_map`` [B, n], on the current stream: orca_screen_dot_calls over the reference and the alt maps - ONE call when the alt maps lie right behind
+    the reference maps in one allocation, as the screen's do, else two; a map's calls do not depend on the batch it is in - then
+    orca_screen_paired_dot_follow from the reference's device lists into the alt maps' enrichment map, the small copies back and the matching in numpy."""
+    B, n = alt.shape[0], alt.shape[1]
+    args = (q.p, q.w, q.r, q.threshold, q.max_calls, q.d_min)
+    if (ref.is_contiguous() and alt.is_contiguous() and ref.untyped_storage().data_ptr() == alt.untyped_storage().data_ptr()
+            and alt.storage_offset() == ref.storage_offset() + ref.numel()):
+        got = engine.screen_dot_calls(ctx, ref.as_strided((2 * B, n, n), (n * n, n, 1)), *args)
+        rc, ac = {k: v[:B] for k, v in got.items()}, {k: v[B:] for k, v in got.items()}
+    else:
+        rc, ac = engine.screen_dot_calls(ctx, ref, *args), engine.screen_dot_calls(ctx, alt, *args)
+    fl = engine.screen_paired_dot_follow(ctx, ac["e_map"], rc["ij"], rc["enrich"], bin_map, q.w, q.d_min)
+    host = [{k: d[k].cpu().numpy() for k in d if k != "e_map"} for d in (rc, ac, fl)]
+    return _loop_fields(*host, bin_map, q.tol)
 
 
 def _dict_maps(out, m, device):
@@ -427,16 +574,16 @@ def _dict_maps(out, m, device):
     return torch.from_numpy(np.ascontiguousarray(maps)).to(device)
 
 
-def sv_scores(sv, ref_out, alt_out, chrlen, device=None, insulation=None, viewpoints=None, strata=None):
+def sv_scores(sv, ref_out, alt_out, chrlen, device=None, insulation=None, viewpoints=None, strata=None, loops=None):
     """The ``scores`` of `sv_screen(..., scores=True)` from ANY pair of `genomepredict` output dicts of a variant's reference and alternative
     allele (the `process_*` drivers', `sv_screen(..., incremental=False)`'s): the maps are uploaded to ``device`` (default: the current MI355X)
-    and scored by the same kernel through `level_bin_maps` - the same dict.  ``insulation``, ``viewpoints``, ``strata``: the readouts of
+    and scored by the same kernel through `level_bin_maps` - the same dict.  ``insulation``, ``viewpoints``, ``strata``, ``loops``: the readouts of
     `sv_screen`, the same keys."""
-    tracks = check_tracks(insulation, viewpoints, strata)
+    tracks, lp = check_tracks(insulation, viewpoints, strata), check_loops_arg(loops)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if ref_out["predictions"] is None or alt_out["predictions"] is None:
         raise ValueError("sv_scores: the output dicts hold no maps (keep_maps=False)")
-    entry = _scores_entry(sv, chrlen, ref_out, alt_out, tracks)
+    entry = _scores_entry(sv, chrlen, ref_out, alt_out, tracks, lp)
     ctx = engine.get_context(dev)
     for m in range(len(alt_out["predictions"])):
         entry["models"].append(_model_scores(ctx, _dict_maps(ref_out, m, dev), _dict_maps(alt_out, m, dev), entry["bin_map"], entry))
@@ -664,8 +811,15 @@ class GenomeEncodings:
 
     def _s3_make(self, ce, region, need):
         dev = ce.codes.device
-        if dev.type != "cuda" or need + 40e9 >= _hbm_available(dev):
+        if dev.type != "cuda":
             return None
+        if need + 40e9 >= _hbm_available(dev):
+            # a store that was dropped (`sv_drivers.clear_encoding_cache`, a deleted genome) is cyclic garbage - its ChromEncodings reach it back through
+            # their `codes` callables - so its caches hold their HBM until Python's cycle collector happens to run: run it before giving this cache up
+            import gc
+            gc.collect()
+            if need + 40e9 >= _hbm_available(dev):
+                return None
         s3 = Stage4Cache(self.net0, ce.codes, region)
         return s3 if s3.build_all() else None
 
@@ -1137,7 +1291,7 @@ def _window_outputs(model, merged, starts, params, mchr, keep_maps=True):
 
 
 def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, incremental=True, min_uses=3, stats=None, on_result=None,
-              streams=None, group=2, stage3="auto", scores=False, keep_maps=True, insulation=None, viewpoints=None, strata=None):
+              streams=None, group=2, stage3="auto", scores=False, keep_maps=True, insulation=None, viewpoints=None, strata=None, loops=None):
     """Predict reference and alternative allele (6 maps each, per model) for this rank's share of ``svs``
     (independent windows: replicas, no collective).  genome_codes: [chrlen] uint8 tensor on the MI355X.
     Returns {sv_index: {"sv": SV, "ref": output_dict, "alt": output_dict}} with genomepredict's output dicts.
@@ -1186,15 +1340,27 @@ def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, i
         model ``dist_delta``, ``dist_abs``, ``dist_rms`` float32 [6, C, 250], ``dist_corr`` float64 [6, C, 250], ``mse`` float32 [6, C],
         ``strata_corr``, ``scc`` float64 [6, C] (the strata kernel's pooled Pearson and HiCRep's stratum-adjusted correlation over the range;
         ``corr`` keeps its meaning).  Inside an inversion the reference pixel is read mirrored into the upper triangle.
+    ``loops=True`` or a `screen.LoopParams` (needs ``scores=True``; `screen.check_loops` on 250 bins, one parameter set for all six levels; the
+      default threshold is NOT calibrated on the published checkpoints): dot (loop) calls per level and target on the variant's own reference map
+      and on its alt map (orca_screen_dot_calls), every listed reference dot followed through the level's bin map to EVERY eligible alt pixel that
+      stands for it, the strongest reported (orca_screen_paired_dot_follow; `paired_loop_scores_host` restates all of it in numpy).  Adds
+      ``loop_params`` (the validated parameters) and per model, with K = max_calls: ``ref_loops``, ``loops`` int32 [6, C, K, 2] (the first K dots,
+      row-major, -1 behind them), ``ref_loop_enrichment``, ``loop_enrichment`` float32 [6, C, K], ``ref_loop_count``, ``loop_count`` int32 [6, C] (ALL
+      dots), ``loop_candidates`` int32 [6, C, K] (the eligible alt pixels that stand for reference dot k: 0 = an anchor deleted, outside the alt
+      window or too near the diagonal or the edge, 1 ordinarily, 2 to 4 under a tandem duplication), ``loop_followed_at`` int32 [6, C, K, 2] (the
+      one with the largest enrichment, (-1, -1) without one), ``loop_followed_enrichment``, ``loop_delta`` float32 [6, C, K] (its e, and its e
+      minus the reference dot's; NaN without one), ``loop_is_gained``, ``ref_loop_is_lost`` bool [6, C, K] (a listed alt dot whose reference pixel
+      (min(map a, map c), max(map a, map c)) has no listed reference dot within ``tol`` - one with an unmapped bin is gained; a listed reference
+      dot that no listed alt dot matches) and their sums ``loops_gained``, ``loops_lost`` int32 [6, C].  Unset, nothing is launched.
     ``keep_maps=False`` (needs ``scores=True``): the maps are not copied to the host - the output dicts keep ``start_coords``, ``end_coords``,
     ``chr`` and ``normmats`` and have "predictions": None.  A screen then returns a few KB per variant instead of 3 MB."""
     import time
     from . import dist, orca_predict
     if not keep_maps and not scores:
         raise ValueError("sv_screen: keep_maps=False returns nothing without scores=True")
-    tracks = check_tracks(insulation, viewpoints, strata)
-    if tracks is not None and not scores:
-        raise ValueError("sv_screen: insulation, viewpoints and strata are part of the scores (scores=True)")
+    tracks, lp = check_tracks(insulation, viewpoints, strata), check_loops_arg(loops)
+    if (tracks is not None or lp is not None) and not scores:
+        raise ValueError("sv_screen: insulation, viewpoints, strata and loops are part of the scores (scores=True)")
     res = {}
     mine = list(dist.shard_indices(len(svs), rank, world))
     if not incremental:
@@ -1205,7 +1371,7 @@ def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, i
             alt = orca_predict.genomepredict(assemble_codes(genome_codes, ap)[None], mchr, am, aw, models=models)
             entry = {"sv": sv, "ref": ref, "alt": alt}
             if scores:
-                entry["scores"] = sv_scores(sv, ref, alt, chrlen, genome_codes.device, insulation, viewpoints, strata)
+                entry["scores"] = sv_scores(sv, ref, alt, chrlen, genome_codes.device, insulation, viewpoints, strata, loops)
                 if not keep_maps:
                     ref["predictions"] = alt["predictions"] = None
             if on_result is not None:
@@ -1322,7 +1488,7 @@ def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, i
                     if mi == 0:
                         entries[i] = {"sv": svs[i], "ref": r, "alt": a}
                         if scores:
-                            entries[i]["scores"] = _scores_entry(svs[i], chrlen, r, a, tracks)
+                            entries[i]["scores"] = _scores_entry(svs[i], chrlen, r, a, tracks, lp)
                     else:
                         for o, n in ((entries[i]["ref"], r), (entries[i]["alt"], a)):
                             if keep_maps:

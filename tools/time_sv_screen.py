@@ -3,12 +3,16 @@
 alternated in one run, best of three each; writes profiles/sv_screen_scores.json
 --tracks: what the readouts per level cost - the same variants with (a) scores=True, (b) scores=True, insulation=(5, 10, 25), viewpoints=[one position],
 strata=True, alternated in one run, best of three each; the added ms per variant is reported against the scores=True repetition beside it, with the
-spread of the baseline's three repetitions; writes profiles/sv_screen_tracks.json"""
+spread of the baseline's three repetitions; writes profiles/sv_screen_tracks.json
+--loops: what the loop calls per level cost - the same variants with (a) scores=True, (b) scores=True, loops=True (on the synthetic weights the default
+threshold may call nothing) and (c) scores=True, loops=LoopParams(threshold=-1e30): every list full, alternated in one run, best of three each; the added
+ms per variant against the scores=True repetition beside it, with the spread of the baseline's three repetitions; writes profiles/sv_screen_loops.json"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SCORES = "--scores" in sys.argv
 TRACKS = "--tracks" in sys.argv
-sys.argv = [a for a in sys.argv if a not in ("--scores", "--tracks")]
+LOOPS = "--loops" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--scores", "--tracks", "--loops")]
 import torch
 from orca_amd import orca_models, sv
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 32
@@ -73,6 +77,46 @@ if TRACKS:
            "tracks_added_ms_per_sv_best_of_three": round(best["tracks"] - best["scores"], 3),
            "tracks_within_scores_spread": bool(best["tracks"] <= best["scores"] + spread)}
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sv_screen_tracks.json")
+    json.dump(out, open(path, "w"), indent=1)
+    print(json.dumps({k: v for k, v in out.items() if k != "runs"}))
+    sys.exit(0)
+if LOOPS:
+    import json
+    from orca_amd import screen
+    modes = {"scores": {"scores": True}, "loops": {"scores": True, "loops": True},
+             "loops_filled": {"scores": True, "loops": screen.LoopParams(threshold=-1e30)}}
+    sv.sv_screen([h1], genome, svs[:2], 40_000_000, incremental=inc, min_uses=1, streams=streams, **modes["loops_filled"])     # the new kernel's first launch
+    torch.cuda.synchronize()
+    runs = {k: [] for k in modes}
+    dots = {k: 0 for k in modes}
+
+    def tally(k):
+        def on_result(i, e):
+            if "loop_params" in e["scores"]:
+                dots[k] += int(sum(m["ref_loop_count"].sum() + m["loop_count"].sum() for m in e["scores"]["models"]))
+        return on_result
+    for rep in range(3):
+        for k, kw in modes.items():
+            st = {}
+            dots[k] = 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sv.sv_screen([h1], genome, svs[2:], 40_000_000, incremental=inc, stats=st, streams=streams, on_result=tally(k), **kw)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            build = (st.get("stage3_cache") or {}).get("build_s", 0.0)      # the stage cache is rebuilt by every call: its time is not the screen's
+            runs[k].append({"total_s": round(dt, 4), "stage_cache_build_s": build, "ms_per_sv": round((dt - build) / n * 1e3, 3)})
+            print(k, runs[k][-1], "dots", dots[k])
+    best = {k: min(r["ms_per_sv"] for r in v) for k, v in runs.items()}
+    spread = max(r["ms_per_sv"] for r in runs["scores"]) - best["scores"]
+    out = {"tool": "tools/time_sv_screen.py --loops", "n_svs": n, "incremental": inc, "streams": streams, "align": align,
+           "modes": {"scores": "scores=True", "loops": "scores=True, loops=True", "loops_filled": "scores=True, loops=LoopParams(threshold=-1e30)"},
+           "dots_called_per_run": dots, "runs": runs, "best_ms_per_sv": best, "scores_spread_ms_per_sv": round(spread, 3)}
+    for k in ("loops", "loops_filled"):       # each against the baseline repetition beside it
+        out[k + "_added_ms_per_sv_per_repetition"] = [round(t["ms_per_sv"] - s["ms_per_sv"], 3) for s, t in zip(runs["scores"], runs[k])]
+        out[k + "_added_ms_per_sv_best_of_three"] = round(best[k] - best["scores"], 3)
+        out[k + "_within_scores_spread"] = bool(best[k] <= best["scores"] + spread)
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sv_screen_loops.json")
     json.dump(out, open(path, "w"), indent=1)
     print(json.dumps({k: v for k, v in out.items() if k != "runs"}))
     sys.exit(0)
