@@ -527,6 +527,44 @@ int orca_screen_paired_dot_follow(orca_ctx* ctx, const float* alt_e, int64_t e_b
                                   const float* ref_enrich, int R, const int32_t* bin_map, const int32_t* bin_map_host, int32_t* candidates, int32_t* at,
                                   float* enrich, float* delta);
 
+/* Compartments per level of the SV screen (sv.sv_screen(..., scores=True, compartments=)): the K leading eigenpairs of B maps, one map per workgroup.
+ *   maps [B][n][n] float32 at maps + b * map_bs (map_bs >= n * n), 1 <= n <= 256, 1 <= K <= 3, 0 <= d_lo <= n - 1, center 0 / 1, tol > 0, max_iter >= 1,
+ *   phase [B][n] float32 on the device or NULL.
+ *   Outputs: E [B][K][n] float32, eigenvalue [B][K] float64, residual [B][K] float64, iterations [B][K] int32, n_valid [B] int32.
+ * - Symmetrised input.  S[i][j] = M[min(i,j)][max(i,j)].  Only the upper triangle of a map is ever read, which is the rule of the strata and loop kernels.
+ * - Kept pixels.  Pixel (i, j) is kept when |i - j| >= d_lo and both bins are valid.  Bin i is invalid when S[i][j] is NaN for some j with |i - j| >= d_lo.
+ *   n_valid counts the valid bins.  If n_valid <= K, every output of that map is NaN (iterations is 0).
+ * - The matrix A.  A[i][j] = S[i][j] - mu on kept pixels and 0 elsewhere.  mu is the fp64 mean of the kept pixels, summed in a fixed order.  mu is 0 when
+ *   center is 0.
+ * - Eigenpairs.  (lambda_k, v_k), k < K, are the eigenpairs of A in descending |lambda| with |v_k|_2 = 1.  They are computed in fp64, in a fixed order,
+ *   without atomics.  Each is computed to relative residual |A v - lambda v|_2 / |lambda| <= tol, or until max_iter iterations.  residual reports the
+ *   value reached.  A pair counts as converged when residual <= tol; it is never set to NaN merely for not converging.
+ * - Scaling.  E_k = v_k * sqrt(|lambda_k|) (the cooltools convention).  E_k[i] is NaN on invalid bins.
+ * - Sign.  With a phase track, the sign makes the fp64 Pearson correlation of E_k with the phase non-negative.  The correlation runs over valid bins
+ *   whose phase is finite.  The fallback applies without a phase track, with fewer than 2 such bins, or with a zero or NaN correlation.  The component of
+ *   largest |E_k| is made positive, lowest index on a tie.
+ * - Batch independence.  A map's result does not depend on the batch it is in.  It is the same bits whether it is computed alone or among others.
+ * The algorithm is deflated power iteration: for vector k, v starts at the valid bins i as (h >> 8) / 2^24 - 0.5 with the 32-bit hash h = (i + 1) *
+ * 2654435761 + (k + 1) * 40503, h ^= h >> 15, h *= 2246822519, h ^= h >> 13; per iteration v is orthogonalised against v_0 .. v_{k-1} in turn
+ * (Gram-Schmidt) and normalised, w = A v is orthogonalised likewise, lambda = v . w (the Rayleigh quotient), residual = |w - lambda v|_2 / |lambda|, and
+ * v <- w unless the residual is <= tol or this was iteration max_iter (iterations reports the number done; lambda and the residual belong to the v that
+ * is returned).  For k >= 1 the residual is that of w AFTER its orthogonalisation, i.e. of A restricted to the complement of v_0 .. v_{k-1}: the
+ * residual of A itself is larger by at most sum_{j<k} residual_j |lambda_j| / |lambda_k|, the earlier vectors' own error.  residual is 0 where w - lambda v is exactly 0 - also with lambda = 0, the case of a map with no kept pixel apart from its mean - and
+ * +inf where lambda = 0 otherwise.  Two eigenvalues of (nearly) equal |lambda| - a tied spectrum - do not converge: the pair is returned as it stands
+ * after max_iter iterations with residual > tol.  The sign's correlation is taken as the sign of the centred cross sum C (two passes: the means, then
+ * X, Y, C) when X > 0, Y > 0 and C is neither 0 nor NaN; "largest |E_k|" compares the fp32 values that are returned.  A is the packed upper triangle of
+ * S in LDS (orca_amd/csrc/screen.h has the layout and the order of the sums).  Anything else - a NULL pointer other than phase, a bound above - is
+ * ORCA_EINVAL before any launch. */
+int orca_screen_eigenvectors(orca_ctx* ctx, const float* maps, int64_t map_bs, int B, int n, int K, int d_lo, int center, double tol, int max_iter,
+                             const float* phase, float* E, double* eigenvalue, double* residual, int32_t* iterations, int32_t* n_valid);
+
+/* GC content per bin of W windows of one code array - the phase track of the compartments.  codes [L] uint8 on the device, the project's codes: 0..3 = A,
+ * C, G, T, 4 = N (anything above 3 counts as N); HOST arrays offsets [W] and binsizes [W] (int64); n = the bins per window (1..65535); out [W][n] float32.
+ *   out[w][i] = float((double)#{C, G} / (double)#{A, C, G, T}) over the bases [off_w + i * bs_w, off_w + (i + 1) * bs_w); NaN when the bin holds no
+ *   A/C/G/T.  The counts are integers, so the result is exact and independent of order.
+ * A window that leaves [0, L) - off_w < 0, bs_w < 1 or off_w + n * bs_w > L - is refused with ORCA_EINVAL before any launch. */
+int orca_screen_gc_tracks(orca_ctx* ctx, const uint8_t* codes, int64_t L, const int64_t* offsets, const int64_t* binsizes, int W, int n, float* out);
+
 /* Number of 4 kb bins Encoder emits for an L-bp input (floor through the
  * 4,4,5,5,5,2 pooling chain). */
 int64_t orca_encoder_num_bins(int64_t L);

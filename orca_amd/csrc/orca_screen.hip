@@ -443,6 +443,41 @@ extern "C" int orca_screen_paired_dot_follow(orca_ctx* ctx, const float* alt_e, 
                 ref_enrich, R, bin_map, candidates, at, enrich, delta);
 }
 
+// ---- compartments: the leading eigenpairs of B maps, and the GC track that phases them -----------------------------------------------------------------------
+extern "C" int orca_screen_eigenvectors(orca_ctx* ctx, const float* maps, int64_t map_bs, int B, int n, int K, int d_lo, int center, double tol, int max_iter,
+                                        const float* phase, float* E, double* eigenvalue, double* residual, int32_t* iterations, int32_t* n_valid) {
+  if (!ctx || !maps || !E || !eigenvalue || !residual || !iterations || !n_valid) return fail(ORCA_EINVAL, "orca_screen_eigenvectors: NULL argument");
+  if (B < 1 || n < 1 || n > SCREEN_ALIGNED_MAX_BINS || map_bs < (int64_t)n * n)
+    return fail(ORCA_EINVAL, "orca_screen_eigenvectors: %d maps (>= 1) of %d bins (1..%d), batch stride %ld (>= n * n)", B, n, SCREEN_ALIGNED_MAX_BINS, (long)map_bs);
+  if (K < 1 || K > SCREEN_EIG_MAX_K) return fail(ORCA_EINVAL, "orca_screen_eigenvectors: K = %d eigenpairs per map (1..%d)", K, SCREEN_EIG_MAX_K);
+  if (d_lo < 0 || d_lo > n - 1) return fail(ORCA_EINVAL, "orca_screen_eigenvectors: d_lo = %d (0..n - 1 = %d)", d_lo, n - 1);
+  if (center != 0 && center != 1) return fail(ORCA_EINVAL, "orca_screen_eigenvectors: center = %d (0 or 1)", center);
+  if (!(tol > 0.0)) return fail(ORCA_EINVAL, "orca_screen_eigenvectors: tol = %g (> 0)", tol);
+  if (max_iter < 1) return fail(ORCA_EINVAL, "orca_screen_eigenvectors: max_iter = %d (>= 1)", max_iter);
+  return launch(ctx, "screen_eigenvectors_kernel", screen_eigenvectors_kernel, dim3((unsigned)B), SCREEN_EIG_THREADS, maps, (long)map_bs, n, K, d_lo, center, tol,
+                max_iter, phase, E, eigenvalue, residual, iterations, n_valid);
+}
+
+// the windows' offsets and bin sizes are host arrays: checked here, handed to the kernel by value, SCREEN_GC_WINDOWS windows per launch
+extern "C" int orca_screen_gc_tracks(orca_ctx* ctx, const uint8_t* codes, int64_t L, const int64_t* offsets, const int64_t* binsizes, int W, int n, float* out) {
+  if (!ctx || !codes || !offsets || !binsizes || !out) return fail(ORCA_EINVAL, "orca_screen_gc_tracks: NULL argument");
+  if (L < 1 || W < 1 || n < 1 || n > 65535) return fail(ORCA_EINVAL, "orca_screen_gc_tracks: %d windows (>= 1) of %d bins (1..65535) of %ld codes (>= 1)", W, n, (long)L);
+  for (int w = 0; w < W; ++w)
+    if (offsets[w] < 0 || offsets[w] >= L || binsizes[w] < 1 || binsizes[w] > (L - offsets[w]) / n)
+      return fail(ORCA_EINVAL, "orca_screen_gc_tracks: window %d = %d bins of %ld bases from base %ld leaves the %ld codes", w, n, (long)binsizes[w], (long)offsets[w], (long)L);
+  for (int w0 = 0; w0 < W; w0 += SCREEN_GC_WINDOWS) {
+    const int cnt = W - w0 < SCREEN_GC_WINDOWS ? W - w0 : SCREEN_GC_WINDOWS;
+    screen_gc_windows win = {};
+    for (int w = 0; w < cnt; ++w) {
+      win.off[w] = offsets[w0 + w];
+      win.bs[w] = binsizes[w0 + w];
+    }
+    ORCA_TRY(launch(ctx, "screen_gc_tracks_kernel", screen_gc_tracks_kernel, dim3((unsigned)n, (unsigned)cnt), 256, codes, (long)L, win, cnt, n,
+                    out + (size_t)w0 * n));
+  }
+  return ORCA_OK;
+}
+
 // ---- both strands --------------------------------------------------------------------------------------------------------------------------------------------
 extern "C" int orca_screen_merge_strands(orca_ctx* ctx, const float* fwd, int64_t fwd_bs, const float* rev, int64_t rev_bs, const float* ref_fwd, const float* ref_rev,
                                          int B, int n, float* out, int64_t out_bs, float* gap) {

@@ -1017,6 +1017,303 @@ static __global__ void __launch_bounds__(64 * SCREEN_FOLLOW_DOTS) screen_paired_
   delta[out] = best < 0 ? qnan : best_e - ref_enrich[out];
 }
 
+// ---- compartments per level of the SV screen (sv.sv_screen(..., scores=True, compartments=)): the K leading eigenpairs of a map ----------------------------
+// include/orca_hip.h (orca_screen_eigenvectors) has the definition: the symmetrised upper triangle S, the valid bins, the kept pixels, A = S - mu on them,
+// the eigenpairs of A in descending |lambda|, E_k = v_k sqrt(|lambda_k|), the sign by a phase track or by the largest component.
+// One workgroup of 16 waves per map.  A IS KEPT AS THE PACKED UPPER TRIANGLE OF S IN LDS, fp32 as it came (131 584 bytes at n = 256, 125 500 at n = 250; the
+// CU has 160 KiB): S[i][j], i <= j, at i n - i (i - 1) / 2 + (j - i), and A[i][j] = (double)S - mu is formed on the fly where the pixel is kept.  Every
+// iteration reads all of A once; from LDS a row and a column cost the same, so nothing is symmetrised or copied and no workspace is needed.
+// Deflated power iteration in fp64, per vector k: v <- start_k (screen_eig_start, on the valid bins), then per iteration: v -= u (u . v) for the earlier
+// vectors u in turn, v /= |v|, w = A v, w -= u (u . w) in turn, lambda = v . w, r = |w - lambda v| / |lambda|; stop when r <= tol or after max_iter
+// iterations, else v <- w.  (lambda, r) belong to the v that is kept.  r = 0 where w - lambda v is exactly 0 (also with lambda = 0: A = 0 has no kept pixel
+// apart from its mean), +inf where lambda = 0 otherwise.
+// The order of every sum is fixed by (n, K, d_lo, the valid bins) alone: in w = A v four threads share a row - thread q takes the columns q, q + 4, ..
+// ascending - and their sums meet as (q0 + q1) + (q2 + q3) by xor shuffles; a dot product is formed by EVERY wave from the same LDS vectors - lane l takes
+// the bins l, l + 64, .., then xor shuffles - so all waves hold the same bits and the loop's exit is uniform.  mu: the rows' sums (the same four-thread
+// order) added serially for i ascending.  No atomics, nothing scattered: a map's bits depend neither on B nor on its place in the batch nor on the stride.
+#define SCREEN_EIG_MAX_K 3
+#define SCREEN_EIG_THREADS 1024
+#define SCREEN_EIG_TRI (SCREEN_ALIGNED_MAX_BINS * (SCREEN_ALIGNED_MAX_BINS + 1) / 2)
+
+// the start vector of eigenvector k at bin i: a fixed integer hash of (i, k) mapped to [-0.5, 0.5) - no bin is special, no two vectors start alike
+static __device__ __forceinline__ double screen_eig_start(int i, int k) {
+  unsigned h = (unsigned)(i + 1) * 2654435761u + (unsigned)(k + 1) * 40503u;
+  h ^= h >> 15;
+  h *= 2246822519u;
+  h ^= h >> 13;
+  return (double)(h >> 8) * (1.0 / 16777216.0) - 0.5;
+}
+
+// S[i][j] from the packed upper triangle
+static __device__ __forceinline__ float screen_eig_s(const float* s_tri, int i, int j, int n) {
+  const int lo = i < j ? i : j, hi = i < j ? j : i;
+  return s_tri[lo * n - lo * (lo - 1) / 2 + (hi - lo)];
+}
+
+// a . b over the SCREEN_ALIGNED_MAX_BINS entries of two LDS vectors (0 outside the valid bins), by one wave: the same bits in every lane of every wave
+static __device__ __forceinline__ double screen_eig_dot(const double* a, const double* b, int lane) {
+  double s = 0.0;
+  for (int j = lane; j < SCREEN_ALIGNED_MAX_BINS; j += 64) s = fma(a[j], b[j], s);
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  return s;
+}
+
+// x -= u (u . x) on LDS vectors, by the whole workgroup
+static __device__ __forceinline__ void screen_eig_deflate(double* x, const double* u, int lane) {
+  const double d = screen_eig_dot(u, x, lane);
+  __syncthreads();                                                 // every wave has read x
+  if (threadIdx.x < SCREEN_ALIGNED_MAX_BINS) x[threadIdx.x] = fma(-d, u[threadIdx.x], x[threadIdx.x]);
+  __syncthreads();
+}
+
+static __global__ void __launch_bounds__(SCREEN_EIG_THREADS) screen_eigenvectors_kernel(const float* __restrict__ maps, long map_bs, int n, int K, int d_lo,
+                                                                                        int center, double tol, int max_iter,
+                                                                                        const float* __restrict__ phase, float* __restrict__ E,
+                                                                                        double* __restrict__ eigenvalue, double* __restrict__ residual,
+                                                                                        int* __restrict__ iterations, int* __restrict__ n_valid) {
+  __shared__ float s_tri[SCREEN_EIG_TRI];
+  __shared__ double s_v[SCREEN_ALIGNED_MAX_BINS], s_w[SCREEN_ALIGNED_MAX_BINS], s_row[SCREEN_ALIGNED_MAX_BINS];
+  __shared__ double s_u[SCREEN_EIG_MAX_K][SCREEN_ALIGNED_MAX_BINS];
+  __shared__ int s_ok[SCREEN_ALIGNED_MAX_BINS], s_cnt[SCREEN_ALIGNED_MAX_BINS];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, row = tid >> 2, q = tid & 3;
+  n = n > SCREEN_ALIGNED_MAX_BINS ? SCREEN_ALIGNED_MAX_BINS : n;
+  K = K > SCREEN_EIG_MAX_K ? SCREEN_EIG_MAX_K : K;
+  d_lo = d_lo < 0 ? 0 : d_lo;
+  const float* m = maps + (long)b * map_bs;
+  const float qnan = __int_as_float(0x7fc00000);
+  const double dnan = (double)qnan;
+  for (int i = wave; i < n; i += SCREEN_EIG_THREADS / 64)
+    for (int j = i + lane; j < n; j += 64) s_tri[i * n - i * (i - 1) / 2 + (j - i)] = m[(long)i * n + j];
+  __syncthreads();
+  // the valid bins: no NaN in the row of S at |i - j| >= d_lo
+  int bad = 0;
+  if (row < n)
+    for (int j = q; j < n; j += 4) {
+      const float s = screen_eig_s(s_tri, row, j, n);
+      bad |= (abs(row - j) >= d_lo && s != s) ? 1 : 0;
+    }
+  bad |= __shfl_xor(bad, 1, 64);
+  bad |= __shfl_xor(bad, 2, 64);
+  if (q == 0) s_ok[row] = (row < n && !bad) ? 1 : 0;
+  __syncthreads();
+  int nv = 0;
+  for (int j = lane; j < SCREEN_ALIGNED_MAX_BINS; j += 64) nv += s_ok[j];
+  for (int o = 32; o > 0; o >>= 1) nv += __shfl_xor(nv, o, 64);
+  if (tid == 0) n_valid[b] = nv;
+  if (nv <= K) {                                                   // (uniform)
+    for (int t = tid; t < K * n; t += SCREEN_EIG_THREADS) E[(long)b * K * n + t] = qnan;
+    if (tid < K) {
+      eigenvalue[(long)b * K + tid] = dnan;
+      residual[(long)b * K + tid] = dnan;
+      iterations[(long)b * K + tid] = 0;
+    }
+    return;
+  }
+  const bool mine = row < n && s_ok[row] != 0;
+  // mu: the mean of the kept pixels
+  double rs = 0.0;
+  int rc = 0;
+  if (mine)
+    for (int j = q; j < n; j += 4)
+      if (s_ok[j] && abs(row - j) >= d_lo) {
+        rs += (double)screen_eig_s(s_tri, row, j, n);
+        ++rc;
+      }
+  rs += __shfl_xor(rs, 1, 64);
+  rc += __shfl_xor(rc, 1, 64);
+  rs += __shfl_xor(rs, 2, 64);
+  rc += __shfl_xor(rc, 2, 64);
+  if (q == 0) {
+    s_row[row] = rs;
+    s_cnt[row] = rc;
+  }
+  __syncthreads();
+  double mu = 0.0;
+  if (center) {
+    double tot = 0.0;
+    long cnt = 0;
+    for (int i = 0; i < n; ++i) {
+      tot += s_row[i];
+      cnt += s_cnt[i];
+    }
+    mu = cnt > 0 ? tot / (double)cnt : 0.0;
+  }
+  for (int k = 0; k < K; ++k) {
+    if (tid < SCREEN_ALIGNED_MAX_BINS) s_v[tid] = (tid < n && s_ok[tid]) ? screen_eig_start(tid, k) : 0.0;
+    __syncthreads();
+    double lam = 0.0, rel = 0.0;
+    int it = 1;
+    for (;; ++it) {
+      for (int p = 0; p < k; ++p) screen_eig_deflate(s_v, s_u[p], lane);
+      const double vv = screen_eig_dot(s_v, s_v, lane);
+      const double inv = vv > 0.0 ? 1.0 / sqrt(vv) : 0.0;
+      __syncthreads();
+      if (tid < SCREEN_ALIGNED_MAX_BINS) s_v[tid] *= inv;
+      __syncthreads();
+      double acc = 0.0;
+      if (mine)
+        for (int j = q; j < n; j += 4) {
+          const double a = (s_ok[j] && abs(row - j) >= d_lo) ? (double)screen_eig_s(s_tri, row, j, n) - mu : 0.0;
+          acc = fma(a, s_v[j], acc);
+        }
+      acc += __shfl_xor(acc, 1, 64);
+      acc += __shfl_xor(acc, 2, 64);
+      if (q == 0) s_w[row] = acc;
+      __syncthreads();
+      for (int p = 0; p < k; ++p) screen_eig_deflate(s_w, s_u[p], lane);
+      lam = screen_eig_dot(s_v, s_w, lane);
+      double r2 = 0.0;
+      for (int j = lane; j < SCREEN_ALIGNED_MAX_BINS; j += 64) {
+        const double t = fma(-lam, s_v[j], s_w[j]);
+        r2 = fma(t, t, r2);
+      }
+      for (int o = 32; o > 0; o >>= 1) r2 += __shfl_xor(r2, o, 64);
+      const double rn = sqrt(r2), al = fabs(lam);
+      rel = rn == 0.0 ? 0.0 : (al > 0.0 ? rn / al : (double)__int_as_float(0x7f800000));
+      if (rel <= tol || it >= max_iter) break;                     // (uniform: every wave holds the same bits)
+      __syncthreads();                                             // every wave has read v
+      if (tid < SCREEN_ALIGNED_MAX_BINS) s_v[tid] = s_w[tid];
+      __syncthreads();
+    }
+    // the sign: the Pearson correlation with the phase track over the valid bins whose phase is finite, two passes (the means, then the centred sums)
+    const double sc = sqrt(fabs(lam));
+    double sgn = 0.0;
+    if (phase != nullptr) {
+      const float* ph = phase + (long)b * n;
+      double sp = 0.0, sv = 0.0;
+      int c = 0;
+      for (int j = lane; j < n; j += 64) {
+        const float p = ph[j];
+        if (s_ok[j] && p - p == 0.f) {
+          sp += (double)p;
+          sv += s_v[j];
+          ++c;
+        }
+      }
+      for (int o = 32; o > 0; o >>= 1) {
+        sp += __shfl_xor(sp, o, 64);
+        sv += __shfl_xor(sv, o, 64);
+        c += __shfl_xor(c, o, 64);
+      }
+      if (c >= 2) {
+        const double mp = sp / (double)c, mv = sv / (double)c;
+        double X = 0.0, Y = 0.0, C = 0.0;
+        for (int j = lane; j < n; j += 64) {
+          const float p = ph[j];
+          if (s_ok[j] && p - p == 0.f) {
+            const double ex = s_v[j] - mv, ey = (double)p - mp;
+            X = fma(ex, ex, X);
+            Y = fma(ey, ey, Y);
+            C = fma(ex, ey, C);
+          }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+          X += __shfl_xor(X, o, 64);
+          Y += __shfl_xor(Y, o, 64);
+          C += __shfl_xor(C, o, 64);
+        }
+        if (X > 0.0 && Y > 0.0 && C != 0.0 && C == C) sgn = C < 0.0 ? -1.0 : 1.0;
+      }
+    }
+    if (sgn == 0.0) {                                              // the fallback: the component of largest |E_k| (as fp32) positive, the lowest index of equals
+      float best = -1.f, bv = 0.f;
+      int bi = SCREEN_ALIGNED_MAX_BINS;
+      for (int j = lane; j < n; j += 64) {
+        const float e = (float)(s_v[j] * sc);
+        if (s_ok[j] && fabsf(e) > best) {
+          best = fabsf(e);
+          bv = e;
+          bi = j;
+        }
+      }
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64), ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ob > best || (ob == best && oi < bi)) {
+          best = ob;
+          bv = ov;
+          bi = oi;
+        }
+      }
+      sgn = bv < 0.f ? -1.0 : 1.0;
+    }
+    if (tid < n) E[((long)b * K + k) * n + tid] = s_ok[tid] ? (float)(sgn * s_v[tid] * sc) : qnan;
+    if (tid == 0) {
+      eigenvalue[(long)b * K + k] = lam;
+      residual[(long)b * K + k] = rel;
+      iterations[(long)b * K + k] = it;
+    }
+    if (tid < SCREEN_ALIGNED_MAX_BINS) s_u[k][tid] = s_v[tid];
+    __syncthreads();
+  }
+}
+
+// ---- GC content per bin (orca_screen_gc_tracks): the phase track of the compartments, from the codes the screen already holds ----------------------------
+// out[w][i] = #{C, G} / #{A, C, G, T} over the bases [off_w + i bs_w, off_w + (i + 1) bs_w) of codes [L] (0..3 = A, C, G, T; anything else counts as N),
+// NaN where the bin holds no A/C/G/T.  One workgroup per (bin, window); up to SCREEN_GC_WINDOWS windows per launch, their offsets and bin sizes by value.
+// The bases between the first and the last 16-byte boundary of the bin are read 16 at a time.  Integer counts (any order gives the same), one fp64 division,
+// rounded to fp32 once.  The host checks that every window lies in [0, L); the kernel clips all the same.
+#define SCREEN_GC_WINDOWS 16
+struct screen_gc_windows {
+  long long off[SCREEN_GC_WINDOWS], bs[SCREEN_GC_WINDOWS];
+};
+
+static __device__ __forceinline__ void screen_gc_count(unsigned c, unsigned& cg, unsigned& all) {
+  all += c < 4u ? 1u : 0u;
+  cg += (c == 1u || c == 2u) ? 1u : 0u;
+}
+
+static __global__ void __launch_bounds__(256) screen_gc_tracks_kernel(const unsigned char* __restrict__ codes, long L, screen_gc_windows win, int W, int n,
+                                                                      float* __restrict__ out) {
+  __shared__ unsigned long long s_cg[4], s_all[4];
+  const int i = blockIdx.x, w = blockIdx.y, tid = threadIdx.x;
+  if (w >= W || w >= SCREEN_GC_WINDOWS || i >= n) return;          // (uniform)
+  long long off = 0, bs = 0;
+  for (int t = 0; t < SCREEN_GC_WINDOWS; ++t)                      // (a select chain: the table stays in registers)
+    if (t == w) {
+      off = win.off[t];
+      bs = win.bs[t];
+    }
+  long lo = (long)(off + (long long)i * bs), hi = (long)(off + (long long)(i + 1) * bs);
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > L ? L : hi;
+  unsigned long long cg = 0, all = 0;
+  if (lo < hi) {
+    long a0 = lo + (long)((16 - (reinterpret_cast<unsigned long long>(codes + lo) & 15u)) & 15u);
+    a0 = a0 > hi ? hi : a0;
+    const long a1 = a0 + ((hi - a0) & ~15L);
+    unsigned c1 = 0, c2 = 0;
+    for (long p = lo + tid; p < a0; p += 256) screen_gc_count(codes[p], c1, c2);
+    for (long p = a1 + tid; p < hi; p += 256) screen_gc_count(codes[p], c1, c2);
+    cg += c1;
+    all += c2;
+    for (long p = a0 + 16L * tid; p < a1; p += 16L * 256) {
+      const uint4 v = *reinterpret_cast<const uint4*>(codes + p);
+      const unsigned word[4] = {v.x, v.y, v.z, v.w};
+      c1 = c2 = 0;
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int s = 0; s < 32; s += 8) screen_gc_count((word[t] >> s) & 255u, c1, c2);
+      cg += c1;
+      all += c2;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    cg += __shfl_xor(cg, o, 64);
+    all += __shfl_xor(all, o, 64);
+  }
+  if ((tid & 63) == 0) {
+    s_cg[tid >> 6] = cg;
+    s_all[tid >> 6] = all;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  cg = s_cg[0] + s_cg[1] + s_cg[2] + s_cg[3];
+  all = s_all[0] + s_all[1] + s_all[2] + s_all[3];
+  out[(long)w * n + i] = all > 0 ? (float)((double)cg / (double)all) : __int_as_float(0x7fc00000);
+}
+
 // ---- both strands (screen.screen_1m(..., strands="both")): the '-' strand's map is merged into the '+' strand's as genomepredict merges them ------------
 // out[b][i][j] = 0.5 fwd[b][i][j] + 0.5 rev[b][n-1-i][n-1-j] (the expression of strand_merge_kernel: the same bits), and with the two strands' reference maps
 // gap[b] = mean_ij |(fwd - ref_fwd)[i][j] - (rev - ref_rev)[n-1-i][n-1-j]| - how far the strands disagree about the item's effect.  One workgroup per map, one

@@ -1179,6 +1179,54 @@ def screen_paired_dot_follow(ctx, alt_e, ref_ij, ref_enrich, bin_map_host, w, d_
     return {"candidates": candidates, "at": at, "enrich": enrich, "delta": delta}
 
 
+# compartments (orca_screen_eigenvectors, orca_screen_gc_tracks): the leading eigenpairs of maps and the GC track that phases them
+def screen_eigenvectors(ctx, maps, n_eigs=1, d_lo=2, center=True, tol=1e-8, max_iter=1000, phase=None):
+    """The ``n_eigs`` (1..3) leading eigenpairs of maps [B, n, n] (any batch stride, rows contiguous; n <= 256), one map per workgroup
+    (orca_screen_eigenvectors; include/orca_hip.h has the definition: the symmetrised upper triangle, the valid bins, A = S - mean on the kept pixels
+    |i - j| >= ``d_lo``, E_k = v_k sqrt(|lambda_k|), descending |lambda|).  ``phase``: [B, n] float32 on the device (or None) - the sign makes E_k's
+    correlation with it non-negative; without it the component of largest |E_k| is positive.  A dict of device tensors: ``E`` [B, K, n] float32 (NaN on
+    invalid bins), ``eigenvalue``, ``residual`` [B, K] float64 (the relative residual reached: converged means <= ``tol``), ``iterations`` [B, K] int32
+    and ``n_valid`` [B] int32; a map with n_valid <= K is all NaN."""
+    maps = _f32_cuda(maps, "maps")
+    if maps.dim() != 3 or maps.shape[1] != maps.shape[2] or maps.stride(2) != 1 or maps.stride(1) != maps.shape[1]:
+        raise ValueError("maps: [B,n,n] with contiguous maps")
+    B, n = maps.shape[0], maps.shape[1]
+    if B < 1:
+        raise ValueError("maps: at least one map")
+    bs = maps.stride(0) if B > 1 else max(maps.stride(0), n * n)                   # B = 1: torch may report any stride for the one map
+    K, dev = int(n_eigs), maps.device
+    if phase is not None:
+        phase = _on_device(phase, "phase", torch.float32)
+        if tuple(phase.shape) != (B, n) or phase.device != dev:
+            raise ValueError(f"phase: [{B},{n}] float32 on the maps' device")
+    E, = _f32_outputs(dev, (B, max(K, 0), n))
+    eigenvalue, residual = (torch.empty((B, max(K, 0)), dtype=torch.float64, device=dev) for _ in range(2))
+    iterations = torch.empty((B, max(K, 0)), dtype=torch.int32, device=dev)
+    n_valid = torch.empty(B, dtype=torch.int32, device=dev)
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_eigenvectors(ctx.handle, _dev_p(maps), bs, B, n, K, int(d_lo), int(bool(center)), float(tol), int(max_iter),
+                                               None if phase is None else _dev_p(phase), _dev_p(E), _dev_p(eigenvalue), _dev_p(residual), _dev_p(iterations),
+                                               _dev_p(n_valid)), "orca_screen_eigenvectors")
+    return {"E": E, "eigenvalue": eigenvalue, "residual": residual, "iterations": iterations, "n_valid": n_valid}
+
+
+def gc_tracks(ctx, codes, offsets, binsizes, n):
+    """GC content per bin of W windows of ``codes`` [L] uint8 on the device (0..3 = A, C, G, T, 4 = N): window w has ``n`` bins of ``binsizes[w]`` bases
+    from base ``offsets[w]`` (host sequences of W ints).  [W, n] float32 on the device: #{C, G} / #{A, C, G, T} per bin, NaN where the bin holds no
+    A/C/G/T (orca_screen_gc_tracks).  A window that leaves [0, L) is an OrcaHipError."""
+    codes = _on_device(codes, "codes", torch.uint8)
+    if codes.dim() != 1:
+        raise ValueError("codes: [L] uint8")
+    off, bs = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1), np.ascontiguousarray(binsizes, dtype=np.int64).reshape(-1)
+    if off.size < 1 or bs.size != off.size:
+        raise ValueError("offsets, binsizes: one int64 each per window, at least one window")
+    W, n = off.size, int(n)
+    out, = _f32_outputs(codes.device, (W, max(n, 0)))
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_gc_tracks(ctx.handle, _dev_p(codes), codes.numel(), _np_p(off), _np_p(bs), W, n, _dev_p(out)), "orca_screen_gc_tracks")
+    return out
+
+
 # both strands (orca_screen_merge_strands)
 def screen_merge_strands(ctx, fwd, rev, ref_fwd=None, ref_rev=None, out=None):
     """The '+' strand's maps ``fwd`` [B, n, n] and the '-' strand's ``rev`` [B, n, n] (any batch stride, rows contiguous) merged as genomepredict merges

@@ -473,6 +473,221 @@ def paired_loop_scores_host(alt, ref, bin_map, params):
     return _loop_fields(rc, ac, paired_dot_follow_host(ac["e_map"], rc["ij"], rc["enrich"], bm, q), bm, q.tol)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Compartments per level.  The compartment signal of a map is its leading eigenvector (orca_screen_eigenvectors; include/orca_hip.h and DESIGN 3d
+# have the definition): the K leading eigenpairs of every level's reference and alt map, oriented by the GC content of the window's own bins
+# (orca_screen_gc_tracks on the assembled codes: A compartment = GC-rich = positive), compared through the level's bin map on the host.  Only
+# the coarse levels (128 kb, 64 kb bins) have a compartment meaning; the fine levels get the same numbers without one.
+# ---------------------------------------------------------------------------------------------------------------------------------
+CompartmentParams = namedtuple("CompartmentParams", "n_eigs d_lo center tol max_iter", defaults=(1, 2, True, 1e-8, 1000))
+COMPARTMENT_MAX_EIGS = 3
+COMPARTMENT_SCORE_FIELDS = ("ref_compartment", "compartment", "compartment_delta", "ref_compartment_eigenvalue", "compartment_eigenvalue",
+                            "ref_compartment_residual", "compartment_residual", "ref_compartment_converged", "compartment_converged",
+                            "ref_compartment_iterations", "compartment_iterations", "compartment_corr", "compartment_flips")
+
+
+def check_compartments_arg(compartments, n=LEVEL_BINS):
+    """The ``compartments`` argument of `sv_screen` / `sv_scores`, checked for maps of ``n`` bins: None when unset (None or False), else the validated
+    `CompartmentParams` (True = the defaults).  A ValueError for anything else and for values outside their ranges: 1 <= n_eigs <= 3, 0 <= d_lo
+    <= n - 1, center a bool, tol > 0 (finite), max_iter >= 1.  One parameter set serves all six levels."""
+    if compartments is None or compartments is False:
+        return None
+    q = CompartmentParams() if compartments is True else compartments
+    if not isinstance(q, CompartmentParams):
+        raise ValueError("compartments: True (the defaults) or an sv.CompartmentParams")
+    vals = {}
+    for k in ("n_eigs", "d_lo", "max_iter"):
+        v = getattr(q, k)
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"compartments: {k} = {v!r} must be an int")
+        vals[k] = int(v)
+    if not 1 <= vals["n_eigs"] <= COMPARTMENT_MAX_EIGS:
+        raise ValueError(f"compartments: n_eigs = {vals['n_eigs']}: 1 .. {COMPARTMENT_MAX_EIGS}")
+    if not 0 <= vals["d_lo"] <= n - 1:
+        raise ValueError(f"compartments: d_lo = {vals['d_lo']}: 0 .. {n - 1} on maps of {n} bins")
+    if vals["max_iter"] < 1:
+        raise ValueError(f"compartments: max_iter = {vals['max_iter']} must be at least 1")
+    if not isinstance(q.center, (bool, np.bool_)):
+        raise ValueError(f"compartments: center = {q.center!r} must be a bool")
+    try:
+        tol = float(q.tol)
+    except (TypeError, ValueError):
+        raise ValueError("compartments: tol must be a number") from None
+    if isinstance(q.tol, (bool, np.bool_)) or not (tol > 0.0 and np.isfinite(tol)):
+        raise ValueError(f"compartments: tol = {q.tol!r} must be a finite number > 0")
+    return CompartmentParams(vals["n_eigs"], vals["d_lo"], bool(q.center), tol, vals["max_iter"])
+
+
+def compartment_matrix_host(m, d_lo=2, center=True):
+    """(A float64 [n, n], valid bool [n]) of one map ``m`` [n, n], as orca_screen_eigenvectors prepares it: S[i][j] = m[min(i,j)][max(i,j)] (the lower
+    triangle of ``m`` is never read); bin i is invalid when S[i][j] is NaN for some j with |i - j| >= d_lo; a pixel is kept when |i - j| >= d_lo
+    and both bins are valid; A = S - mu on the kept pixels (mu = their fp64 mean, 0 without ``center`` or without a kept pixel) and 0 elsewhere."""
+    m = np.asarray(m, dtype=np.float64)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError("a map: [n, n]")
+    n = m.shape[0]
+    S = np.triu(m)
+    S = S + np.triu(S, 1).T
+    i, j = np.indices((n, n))
+    band = np.abs(i - j) >= int(d_lo)
+    valid = ~(np.isnan(S) & band).any(axis=1)
+    keep = band & valid[:, None] & valid[None, :]
+    mu = S[keep].mean() if center and keep.any() else 0.0
+    return np.where(keep, S - mu, 0.0), valid
+
+
+def _compartment_sign(v, scale, valid, phase):
+    """The sign rule of orca_screen_eigenvectors for one unit vector ``v`` [n] (fp64) with E = v * scale: +1.0 or -1.0."""
+    if phase is not None:
+        p = np.asarray(phase, dtype=np.float32)
+        use = valid & np.isfinite(p)
+        if use.sum() >= 2:
+            ex, ey = v[use] - v[use].mean(), p[use].astype(np.float64) - p[use].astype(np.float64).mean()
+            X, Y, C = (ex * ex).sum(), (ey * ey).sum(), (ex * ey).sum()
+            if X > 0.0 and Y > 0.0 and C != 0.0 and C == C:
+                return -1.0 if C < 0.0 else 1.0
+    e = (v * scale).astype(np.float32)
+    return -1.0 if e[int(np.argmax(np.where(valid, np.abs(e), np.float32(-1.0))))] < 0.0 else 1.0      # argmax: the lowest index of equals
+
+
+def eigenvectors_host(maps, n_eigs=1, d_lo=2, center=True, phase=None):
+    """Numpy restatement of orca_screen_eigenvectors through `numpy.linalg.eigh` on the prepared A (`compartment_matrix_host`): ``maps`` [B, n, n],
+    ``phase`` [B, n] or None.  The ``n_eigs`` eigenpairs of largest |lambda| (descending |lambda|), E_k = v_k sqrt(|lambda_k|) with NaN on the invalid
+    bins, the sign by the same rule: with a phase, the Pearson correlation with it over the valid bins whose phase is finite is non-negative; without
+    one (or below 2 such bins, or with a zero or NaN correlation) the component of largest |E_k| (as fp32) is positive, the lowest index of equals.
+    A dict of ``E`` float32 [B, K, n], ``eigenvalue`` float64 [B, K], ``residual`` float64 [B, K] (|A v - lambda v| / |lambda| of eigh's pair) and
+    ``n_valid`` int32 [B]; a map with n_valid <= K is all NaN.  eigh is exact where the device iterates: the two agree to the device's ``residual``
+    (times |lambda| / gap for the vectors), not bit for bit."""
+    m = np.asarray(maps, dtype=np.float32)
+    if m.ndim != 3 or m.shape[1] != m.shape[2]:
+        raise ValueError("maps: [B, n, n]")
+    B, n, K = m.shape[0], m.shape[1], int(n_eigs)
+    if not 1 <= K <= COMPARTMENT_MAX_EIGS or not 0 <= int(d_lo) <= n - 1:
+        raise ValueError(f"n_eigs: 1 .. {COMPARTMENT_MAX_EIGS}, d_lo: 0 .. n - 1")
+    ph = None if phase is None else np.asarray(phase, dtype=np.float32)
+    if ph is not None and ph.shape != (B, n):
+        raise ValueError(f"phase: [{B}, {n}]")
+    out = {"E": np.full((B, K, n), np.nan, dtype=np.float32), "eigenvalue": np.full((B, K), np.nan), "residual": np.full((B, K), np.nan),
+           "n_valid": np.zeros(B, dtype=np.int32)}
+    for b in range(B):
+        A, valid = compartment_matrix_host(m[b], d_lo, center)
+        out["n_valid"][b] = valid.sum()
+        if valid.sum() <= K:
+            continue
+        lam, U = np.linalg.eigh(A)
+        order = np.argsort(-np.abs(lam), kind="stable")[:K]
+        for k, o in enumerate(order):
+            v = np.where(valid, U[:, o], 0.0)
+            v = v / np.linalg.norm(v)
+            scale = np.sqrt(abs(lam[o]))
+            rn = np.linalg.norm(A @ v - lam[o] * v)
+            out["eigenvalue"][b, k] = lam[o]
+            out["residual"][b, k] = 0.0 if rn == 0.0 else (rn / abs(lam[o]) if lam[o] != 0.0 else np.inf)
+            sgn = _compartment_sign(v, scale, valid, None if ph is None else ph[b])
+            out["E"][b, k] = np.where(valid, (sgn * v * scale).astype(np.float32), np.float32(np.nan))
+    return out
+
+
+def gc_tracks_host(codes, offsets, binsizes, n):
+    """Numpy restatement of orca_screen_gc_tracks: float32 [W, n], out[w][i] = #{C, G} / #{A, C, G, T} (one fp64 division, rounded once) over the
+    bases [off_w + i bs_w, off_w + (i + 1) bs_w) of ``codes`` [L] uint8 (0..3 = A, C, G, T; anything above is N), NaN where the bin holds no
+    A/C/G/T.  A ValueError for a window that leaves [0, L)."""
+    c = np.asarray(codes, dtype=np.uint8).reshape(-1)
+    off, bs, n = np.asarray(offsets, dtype=np.int64).reshape(-1), np.asarray(binsizes, dtype=np.int64).reshape(-1), int(n)
+    if off.size < 1 or bs.size != off.size or n < 1:
+        raise ValueError("offsets, binsizes: one each per window, at least one window; n >= 1")
+    L = c.size
+    ct = np.int32 if L < 2 ** 31 else np.int64
+    acgt, cg = np.zeros(L + 1, dtype=ct), np.zeros(L + 1, dtype=ct)
+    np.cumsum(c < 4, dtype=ct, out=acgt[1:])
+    np.cumsum((c == 1) | (c == 2), dtype=ct, out=cg[1:])
+    out = np.full((off.size, n), np.nan, dtype=np.float32)
+    for w in range(off.size):
+        if off[w] < 0 or bs[w] < 1 or off[w] + n * bs[w] > L:
+            raise ValueError(f"window {w}: {n} bins of {bs[w]} bases from base {off[w]} leave the {L} codes")
+        edges = off[w] + np.arange(n + 1, dtype=np.int64) * bs[w]
+        a, g = np.diff(acgt[edges]), np.diff(cg[edges])
+        ok = a > 0
+        out[w, ok] = (g[ok].astype(np.float64) / a[ok].astype(np.float64)).astype(np.float32)
+    return out
+
+
+def paired_compartment_scores_host(alt_E, ref_E, bin_map):
+    """The compartment vectors of B alt maps against their reference maps' through the bin maps, in numpy - what `sv_screen` runs on the host:
+    ``alt_E``, ``ref_E`` [B, K, n] (or [K, n]), ``bin_map`` [B, n] (or one [n] for all).  The PAIRS of (b, k) are the alt bins i with map i >= 0
+    whose two values alt_E[i] and ref_E[map i] are both finite.  A dict of ``delta`` float32 [B, K, n] = alt_E[i] - ref_E[map i] by alt bin (one
+    fp32 subtraction; NaN where bin i is unmapped or either value is NaN), ``corr`` float64 [B, K] = the Pearson correlation over the pairs (fp64,
+    the means first, then the centred sums; NaN below 2 pairs or where either side is constant) and ``flips`` int32 [B, K] = the pairs whose two
+    values have opposite sign (a bin that changed compartment, where the vectors are oriented alike)."""
+    a, r = np.asarray(alt_E, dtype=np.float32), np.asarray(ref_E, dtype=np.float32)
+    if a.ndim == 2:
+        a, r = a[None], r[None] if r.ndim == 2 else r
+    if a.ndim != 3 or r.shape != a.shape:
+        raise ValueError("alt_E, ref_E: [B, K, n]")
+    B, K, n = a.shape
+    bm = np.asarray(bin_map, dtype=np.int64)
+    bm = np.broadcast_to(bm, (B, n)) if bm.ndim == 1 else bm
+    if bm.shape != (B, n) or bm.min(initial=0) < -1 or bm.max(initial=0) >= n:
+        raise ValueError(f"bin map: [{B}, {n}] (or [{n}]) with values -1 .. {n - 1}")
+    out = {"delta": np.full((B, K, n), np.nan, dtype=np.float32), "corr": np.full((B, K), np.nan), "flips": np.zeros((B, K), dtype=np.int32)}
+    for b in range(B):
+        M = np.flatnonzero(bm[b] >= 0)
+        for k in range(K):
+            x, y = a[b, k, M], r[b, k, bm[b, M]]
+            with np.errstate(invalid="ignore"):
+                out["delta"][b, k, M] = x - y
+            ok = np.isfinite(x) & np.isfinite(y)
+            x, y = x[ok].astype(np.float64), y[ok].astype(np.float64)
+            out["flips"][b, k] = int((x * y < 0.0).sum())
+            if x.size >= 2:
+                ex, ey = x - x.mean(), y - y.mean()
+                X, Y = (ex * ex).sum(), (ey * ey).sum()
+                if X > 0.0 and Y > 0.0:
+                    out["corr"][b, k] = (ex * ey).sum() / np.sqrt(X * Y)
+    return out
+
+
+def _window_gc(ctx, codes, start_coords, wpos):
+    """float32 [6, 250] numpy: the GC content of the bins of every level of one assembled 32 Mb window ``codes`` [32 000 000] uint8 on the device
+    (ONE orca_screen_gc_tracks call): level k starts at base start_coords[k] - (wpos - 16 000 000) of the window and has bins of 128000 >> k bases."""
+    off = [int(start_coords[k]) - (int(wpos) - WINDOW // 2) for k in range(LEVELS)]
+    return engine.gc_tracks(ctx, codes, off, [128000 >> k for k in range(LEVELS)], LEVEL_BINS).cpu().numpy()
+
+
+def _model_compartments(ctx, alt, ref, bin_map, q, ref_phase=None, alt_phase=None):
+    """The compartment fields (`COMPARTMENT_SCORE_FIELDS`, numpy [B, ...]) of B pairs of maps on the device, alt [B, n, n] against ref [B, n, n]
+    (contiguous) through ``bin_map`` [B, n], on the current stream: orca_screen_eigenvectors over the reference and the alt maps - ONE launch when the
+    alt maps lie right behind the reference maps in one allocation, as the screen's do, else two; a map's result does not depend on the batch it is
+    in - phased by ``ref_phase`` / ``alt_phase`` [B, n] (numpy).  Without them the reference takes the kernel's fallback orientation and every alt
+    vector is flipped so that its dot product with the reference's through the bin map is not negative.  The small arrays come back and
+    `paired_compartment_scores_host` compares them."""
+    B, n = alt.shape[0], alt.shape[1]
+    phased = ref_phase is not None and alt_phase is not None
+    args = (q.n_eigs, q.d_lo, q.center, q.tol, q.max_iter)
+    ph = torch.from_numpy(np.ascontiguousarray(np.concatenate([ref_phase, alt_phase]), dtype=np.float32)).to(alt.device) if phased else None
+    if (ref.is_contiguous() and alt.is_contiguous() and ref.untyped_storage().data_ptr() == alt.untyped_storage().data_ptr()
+            and alt.storage_offset() == ref.storage_offset() + ref.numel()):
+        got = engine.screen_eigenvectors(ctx, ref.as_strided((2 * B, n, n), (n * n, n, 1)), *args, phase=ph)
+        got = {k: v.cpu().numpy() for k, v in got.items()}
+        rc, ac = {k: v[:B] for k, v in got.items()}, {k: v[B:] for k, v in got.items()}
+    else:
+        rc = engine.screen_eigenvectors(ctx, ref, *args, phase=None if ph is None else ph[:B])
+        ac = engine.screen_eigenvectors(ctx, alt, *args, phase=None if ph is None else ph[B:])
+        rc, ac = ({k: v.cpu().numpy() for k, v in d.items()} for d in (rc, ac))
+    if not phased:
+        ac["E"] = ac["E"].copy()
+        for b in range(B):
+            M = np.flatnonzero(bin_map[b] >= 0)
+            prod = ac["E"][b][:, M].astype(np.float64) * rc["E"][b][:, bin_map[b, M]].astype(np.float64)
+            ac["E"][b][np.nansum(prod, axis=1) < 0.0] *= np.float32(-1.0)
+    sc = paired_compartment_scores_host(ac["E"], rc["E"], bin_map)
+    return {"ref_compartment": rc["E"], "compartment": ac["E"], "compartment_delta": sc["delta"],
+            "ref_compartment_eigenvalue": rc["eigenvalue"], "compartment_eigenvalue": ac["eigenvalue"],
+            "ref_compartment_residual": rc["residual"], "compartment_residual": ac["residual"],
+            "ref_compartment_converged": rc["residual"] <= q.tol, "compartment_converged": ac["residual"] <= q.tol,
+            "ref_compartment_iterations": rc["iterations"], "compartment_iterations": ac["iterations"], "compartment_corr": sc["corr"], "compartment_flips": sc["flips"]}
+
+
 def check_tracks(insulation=None, viewpoints=None, strata=None):
     """The three readout arguments of `sv_screen` / `sv_scores`, checked: None when all are unset, else {"insulation": int32 widths or None,
     "viewpoints": [positions] or None, "strata": (d_lo, d_hi) or None}.  ``insulation`` as `screen.check_insulation` takes it, ``strata`` as
@@ -502,12 +717,19 @@ def _strata_counts(bm):
     return np.correlate(ok, ok, "full")[ok.size - 1:].astype(np.int32)
 
 
-def _scores_entry(sv, chrlen, ref_out, alt_out, tracks=None, loops=None):
-    """The model-independent part of an entry's ``scores`` (``tracks``: `check_tracks`' dict or None; ``loops``: `check_loops_arg`'s)."""
+def _scores_entry(sv, chrlen, ref_out, alt_out, tracks=None, loops=None, compartments=None, phase=None):
+    """The model-independent part of an entry's ``scores`` (``tracks``: `check_tracks`' dict or None; ``loops``: `check_loops_arg`'s;
+    ``compartments``: `check_compartments_arg`'s, with ``phase`` = (ref_gc, gc), each [6, 250], or None)."""
     bm = level_bin_maps(sv, chrlen, ref_out, alt_out)
     entry = {"bin_map": bm, "count": (bm >= 0).sum(axis=1).astype(np.int32), "junction_bins": junction_bins(sv, chrlen, alt_out), "models": []}
     if loops is not None:
         entry["loop_params"] = loops
+    if compartments is not None:
+        entry["compartment_params"] = compartments
+        if phase is not None:
+            entry["ref_gc"], entry["gc"] = (np.ascontiguousarray(p, dtype=np.float32) for p in phase)
+            if entry["ref_gc"].shape != (LEVELS, LEVEL_BINS) or entry["gc"].shape != (LEVELS, LEVEL_BINS):
+                raise ValueError(f"phase: (ref_phase, alt_phase), each [{LEVELS}, {LEVEL_BINS}]")
     if tracks is None:
         return entry
     if tracks["insulation"] is not None:
@@ -547,6 +769,10 @@ def _model_scores(ctx, ref_maps, alt_maps, bin_map, entry=None):
     if "loop_params" in entry:
         for k, v in _model_loops(ctx, alt, ref, bmc, entry["loop_params"]).items():
             out[k] = v.reshape((lv, C) + v.shape[1:])
+    if "compartment_params" in entry:
+        rp, ap = (np.repeat(entry[k], C, axis=0) if k in entry else None for k in ("ref_gc", "gc"))
+        for k, v in _model_compartments(ctx, alt, ref, bmc, entry["compartment_params"], rp, ap).items():
+            out[k] = v.reshape((lv, C) + v.shape[1:])
     return out
 
 
@@ -574,16 +800,25 @@ def _dict_maps(out, m, device):
     return torch.from_numpy(np.ascontiguousarray(maps)).to(device)
 
 
-def sv_scores(sv, ref_out, alt_out, chrlen, device=None, insulation=None, viewpoints=None, strata=None, loops=None):
+def sv_scores(sv, ref_out, alt_out, chrlen, device=None, insulation=None, viewpoints=None, strata=None, loops=None, compartments=None, phase=None):
     """The ``scores`` of `sv_screen(..., scores=True)` from ANY pair of `genomepredict` output dicts of a variant's reference and alternative
     allele (the `process_*` drivers', `sv_screen(..., incremental=False)`'s): the maps are uploaded to ``device`` (default: the current MI355X)
-    and scored by the same kernel through `level_bin_maps` - the same dict.  ``insulation``, ``viewpoints``, ``strata``, ``loops``: the readouts of
-    `sv_screen`, the same keys."""
-    tracks, lp = check_tracks(insulation, viewpoints, strata), check_loops_arg(loops)
+    and scored by the same kernel through `level_bin_maps` - the same dict.  ``insulation``, ``viewpoints``, ``strata``, ``loops``,
+    ``compartments``: the readouts of `sv_screen`, the same keys.
+    ``phase`` (with ``compartments``): (ref_phase, alt_phase), each [6, 250] - a GC or gene-density track per level and bin of the reference and of
+    the alt window, which orients the compartment vectors (positive correlation) and is returned as ``ref_gc`` / ``gc``.  WITHOUT ``phase`` the output
+    dicts say nothing about the sequence, and the orientation is ARBITRARY: every reference vector has its largest component positive, and every alt
+    vector is flipped so that its dot product with the reference vector through the bin map is not negative - ``compartment_delta``, ``_corr`` and
+    ``_flips`` are meaningful, the sign of a vector is not (A and B are not told apart), and there are no ``ref_gc`` / ``gc`` keys."""
+    tracks, lp, cp = check_tracks(insulation, viewpoints, strata), check_loops_arg(loops), check_compartments_arg(compartments)
+    if phase is not None and cp is None:
+        raise ValueError("sv_scores: phase orients the compartments (compartments=)")
+    if phase is not None and (not isinstance(phase, (tuple, list)) or len(phase) != 2):
+        raise ValueError("sv_scores: phase = (ref_phase, alt_phase), each [6, 250]")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if ref_out["predictions"] is None or alt_out["predictions"] is None:
         raise ValueError("sv_scores: the output dicts hold no maps (keep_maps=False)")
-    entry = _scores_entry(sv, chrlen, ref_out, alt_out, tracks, lp)
+    entry = _scores_entry(sv, chrlen, ref_out, alt_out, tracks, lp, cp, phase)
     ctx = engine.get_context(dev)
     for m in range(len(alt_out["predictions"])):
         entry["models"].append(_model_scores(ctx, _dict_maps(ref_out, m, dev), _dict_maps(alt_out, m, dev), entry["bin_map"], entry))
@@ -1291,7 +1526,8 @@ def _window_outputs(model, merged, starts, params, mchr, keep_maps=True):
 
 
 def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, incremental=True, min_uses=3, stats=None, on_result=None,
-              streams=None, group=2, stage3="auto", scores=False, keep_maps=True, insulation=None, viewpoints=None, strata=None, loops=None):
+              streams=None, group=2, stage3="auto", scores=False, keep_maps=True, insulation=None, viewpoints=None, strata=None, loops=None,
+              compartments=None):
     """Predict reference and alternative allele (6 maps each, per model) for this rank's share of ``svs``
     (independent windows: replicas, no collective).  genome_codes: [chrlen] uint8 tensor on the MI355X.
     Returns {sv_index: {"sv": SV, "ref": output_dict, "alt": output_dict}} with genomepredict's output dicts.
@@ -1352,26 +1588,46 @@ def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, i
       minus the reference dot's; NaN without one), ``loop_is_gained``, ``ref_loop_is_lost`` bool [6, C, K] (a listed alt dot whose reference pixel
       (min(map a, map c), max(map a, map c)) has no listed reference dot within ``tol`` - one with an unmapped bin is gained; a listed reference
       dot that no listed alt dot matches) and their sums ``loops_gained``, ``loops_lost`` int32 [6, C].  Unset, nothing is launched.
+    ``compartments=True`` or a `CompartmentParams` (needs ``scores=True``; `check_compartments_arg`, one parameter set for all six levels): the
+      compartment signal per level and target - the K = n_eigs leading eigenvectors of the variant's own reference map and of its alt map
+      (orca_screen_eigenvectors: one launch per (variant, model) over the 12 C maps; include/orca_hip.h has the definition, `eigenvectors_host`
+      restates it through numpy's eigh), scaled by sqrt(|eigenvalue|) and oriented by the GC content of the window's own bins (orca_screen_gc_tracks
+      on the assembled codes, one call per window: A compartment = GC-rich = positive) - compared through the level's bin map on the host
+      (`paired_compartment_scores_host`).  Adds ``compartment_params``, ``ref_gc``, ``gc`` float32 [6, 250] and per model ``ref_compartment``,
+      ``compartment`` float32 [6, C, K, 250] (by reference bin, by alt bin; NaN on a bin with a NaN pixel), ``compartment_delta`` float32 [6, C, K,
+      250] (E_alt[i] - E_ref[map i]; NaN where bin i is unmapped or either value is NaN), ``ref_compartment_eigenvalue``,
+      ``compartment_eigenvalue``, ``ref_compartment_residual``, ``compartment_residual`` float64 [6, C, K], ``ref_compartment_converged``,
+      ``compartment_converged`` bool [6, C, K] (residual <= tol), ``ref_compartment_iterations``, ``compartment_iterations`` int32 [6, C, K],
+      ``compartment_corr`` float64 [6, C, K] (Pearson of E_alt[i] against E_ref[map i] over the pairs where both are finite; NaN below 2 pairs) and
+      ``compartment_flips`` int32 [6, C, K] (the pairs whose two values have opposite sign).  CAVEATS: only the coarse levels (128 kb and 64 kb bins)
+      have a compartment meaning - the fine levels (4-16 kb bins) get the same numbers without one; and where the spectrum reorders between
+      reference and alt (E1 <-> E2) ``compartment_delta`` is meaningless - ``compartment_corr`` near 0 shows it.  A vector that did not converge is
+      returned as it stands (``*_converged`` False), never NaN for that.  Unset, nothing is launched.
     ``keep_maps=False`` (needs ``scores=True``): the maps are not copied to the host - the output dicts keep ``start_coords``, ``end_coords``,
     ``chr`` and ``normmats`` and have "predictions": None.  A screen then returns a few KB per variant instead of 3 MB."""
     import time
     from . import dist, orca_predict
     if not keep_maps and not scores:
         raise ValueError("sv_screen: keep_maps=False returns nothing without scores=True")
-    tracks, lp = check_tracks(insulation, viewpoints, strata), check_loops_arg(loops)
-    if (tracks is not None or lp is not None) and not scores:
-        raise ValueError("sv_screen: insulation, viewpoints, strata and loops are part of the scores (scores=True)")
+    tracks, lp, cp = check_tracks(insulation, viewpoints, strata), check_loops_arg(loops), check_compartments_arg(compartments)
+    if (tracks is not None or lp is not None or cp is not None) and not scores:
+        raise ValueError("sv_screen: insulation, viewpoints, strata, loops and compartments are part of the scores (scores=True)")
     res = {}
     mine = list(dist.shard_indices(len(svs), rank, world))
     if not incremental:
         for i in mine:
             sv = svs[i]
             rp, rw, rm, ap, aw, am = sv_windows(sv, chrlen)
-            ref = orca_predict.genomepredict(assemble_codes(genome_codes, rp)[None], mchr, rm, rw, models=models)
-            alt = orca_predict.genomepredict(assemble_codes(genome_codes, ap)[None], mchr, am, aw, models=models)
+            rcodes, acodes = assemble_codes(genome_codes, rp), assemble_codes(genome_codes, ap)
+            ref = orca_predict.genomepredict(rcodes[None], mchr, rm, rw, models=models)
+            alt = orca_predict.genomepredict(acodes[None], mchr, am, aw, models=models)
             entry = {"sv": sv, "ref": ref, "alt": alt}
             if scores:
-                entry["scores"] = sv_scores(sv, ref, alt, chrlen, genome_codes.device, insulation, viewpoints, strata, loops)
+                phase = None
+                if cp is not None:                  # the GC of the two windows assembled above
+                    gctx = engine.get_context(genome_codes.device)
+                    phase = (_window_gc(gctx, rcodes, ref["start_coords"], rw), _window_gc(gctx, acodes, alt["start_coords"], aw))
+                entry["scores"] = sv_scores(sv, ref, alt, chrlen, genome_codes.device, insulation, viewpoints, strata, loops, compartments, phase)
                 if not keep_maps:
                     ref["predictions"] = alt["predictions"] = None
             if on_result is not None:
@@ -1488,7 +1744,10 @@ def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, i
                     if mi == 0:
                         entries[i] = {"sv": svs[i], "ref": r, "alt": a}
                         if scores:
-                            entries[i]["scores"] = _scores_entry(svs[i], chrlen, r, a, tracks, lp)
+                            # (the GC of this variant's two assembled windows, once per group's window: every model shares it)
+                            phase = None if cp is None else tuple(_window_gc(ctx, pl["codes"][2 * v + t], o["start_coords"], pl["params"][2 * v + t][1])
+                                                                  for t, o in enumerate((r, a)))
+                            entries[i]["scores"] = _scores_entry(svs[i], chrlen, r, a, tracks, lp, cp, phase)
                     else:
                         for o, n in ((entries[i]["ref"], r), (entries[i]["alt"], a)):
                             if keep_maps:

@@ -6,13 +6,18 @@ strata=True, alternated in one run, best of three each; the added ms per variant
 spread of the baseline's three repetitions; writes profiles/sv_screen_tracks.json
 --loops: what the loop calls per level cost - the same variants with (a) scores=True, (b) scores=True, loops=True (on the synthetic weights the default
 threshold may call nothing) and (c) scores=True, loops=LoopParams(threshold=-1e30): every list full, alternated in one run, best of three each; the added
-ms per variant against the scores=True repetition beside it, with the spread of the baseline's three repetitions; writes profiles/sv_screen_loops.json"""
+ms per variant against the scores=True repetition beside it, with the spread of the baseline's three repetitions; writes profiles/sv_screen_loops.json
+--compartments: what the compartment eigenvectors per level cost - the same variants with (a) scores=True, (b) scores=True, compartments=True and (c)
+scores=True, compartments=CompartmentParams(n_eigs=3), alternated in one run, best of three each; the added ms per variant against the scores=True
+repetition beside it, with the spread of the baseline's three repetitions, and - the weights are synthetic - the share of (allele, level, channel, vector)
+pairs that converged with the median and the largest number of iterations; writes profiles/sv_screen_compartments.json"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SCORES = "--scores" in sys.argv
 TRACKS = "--tracks" in sys.argv
 LOOPS = "--loops" in sys.argv
-sys.argv = [a for a in sys.argv if a not in ("--scores", "--tracks", "--loops")]
+COMPARTMENTS = "--compartments" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--scores", "--tracks", "--loops", "--compartments")]
 import torch
 from orca_amd import orca_models, sv
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 32
@@ -117,6 +122,52 @@ if LOOPS:
         out[k + "_added_ms_per_sv_best_of_three"] = round(best[k] - best["scores"], 3)
         out[k + "_within_scores_spread"] = bool(best[k] <= best["scores"] + spread)
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sv_screen_loops.json")
+    json.dump(out, open(path, "w"), indent=1)
+    print(json.dumps({k: v for k, v in out.items() if k != "runs"}))
+    sys.exit(0)
+if COMPARTMENTS:
+    import json
+    import numpy as np
+    modes = {"scores": {"scores": True}, "compartments": {"scores": True, "compartments": True},
+             "compartments_3": {"scores": True, "compartments": sv.CompartmentParams(n_eigs=3)}}
+    sv.sv_screen([h1], genome, svs[:2], 40_000_000, incremental=inc, min_uses=1, streams=streams, **modes["compartments_3"])     # the new kernels' first launches
+    torch.cuda.synchronize()
+    runs = {k: [] for k in modes}
+    seen = {k: {"converged": [], "iterations": []} for k in modes}
+
+    def tally(k):
+        def on_result(i, e):
+            if "compartment_params" in e["scores"]:
+                for m in e["scores"]["models"]:
+                    for side in ("ref_", ""):
+                        seen[k]["converged"].append(m[side + "compartment_converged"].reshape(-1))
+                        seen[k]["iterations"].append(m[side + "compartment_iterations"].reshape(-1))
+        return on_result
+    for rep in range(3):
+        for k, kw in modes.items():
+            st = {}
+            seen[k] = {"converged": [], "iterations": []}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sv.sv_screen([h1], genome, svs[2:], 40_000_000, incremental=inc, stats=st, streams=streams, on_result=tally(k), **kw)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            build = (st.get("stage3_cache") or {}).get("build_s", 0.0)      # the stage cache is rebuilt by every call: its time is not the screen's
+            runs[k].append({"total_s": round(dt, 4), "stage_cache_build_s": build, "ms_per_sv": round((dt - build) / n * 1e3, 3)})
+            print(k, runs[k][-1])
+    best = {k: min(r["ms_per_sv"] for r in v) for k, v in runs.items()}
+    spread = max(r["ms_per_sv"] for r in runs["scores"]) - best["scores"]
+    out = {"tool": "tools/time_sv_screen.py --compartments", "n_svs": n, "incremental": inc, "streams": streams, "align": align, "weights": "synthetic",
+           "modes": {"scores": "scores=True", "compartments": "scores=True, compartments=True", "compartments_3": "scores=True, compartments=CompartmentParams(n_eigs=3)"},
+           "runs": runs, "best_ms_per_sv": best, "scores_spread_ms_per_sv": round(spread, 3)}
+    for k in ("compartments", "compartments_3"):       # each against the baseline repetition beside it
+        out[k + "_added_ms_per_sv_per_repetition"] = [round(t["ms_per_sv"] - s["ms_per_sv"], 3) for s, t in zip(runs["scores"], runs[k])]
+        out[k + "_added_ms_per_sv_best_of_three"] = round(best[k] - best["scores"], 3)
+        out[k + "_within_scores_spread"] = bool(best[k] <= best["scores"] + spread)
+        conv, its = np.concatenate(seen[k]["converged"]), np.concatenate(seen[k]["iterations"])
+        out[k + "_convergence"] = {"pairs": int(conv.size), "converged_share": round(float(conv.mean()), 4), "iterations_median": float(np.median(its)),
+                                   "iterations_max": int(its.max())}
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sv_screen_compartments.json")
     json.dump(out, open(path, "w"), indent=1)
     print(json.dumps({k: v for k, v in out.items() if k != "runs"}))
     sys.exit(0)
