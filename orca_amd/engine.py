@@ -675,6 +675,21 @@ def _f32_outputs(device, *shapes):
     return tuple(torch.empty(s, dtype=torch.float32, device=device) for s in shapes)
 
 
+def _map_batch(t, name):
+    """The map-batch rule of the readouts: ``t`` is [B, n, n] float32 on the device with contiguous maps (any batch stride) and at least one map.
+    (t, B, n, batch stride) - for B = 1 a stride of at least n * n: torch may report any stride for the one map."""
+    t = _f32_cuda(t, name)
+    if t.dim() != 3 or t.shape[0] < 1 or t.shape[1] != t.shape[2] or t.stride(2) != 1 or t.stride(1) != t.shape[1]:
+        raise ValueError(f"{name}: [B,n,n] with B >= 1 and contiguous maps, got {tuple(t.shape)}")
+    B, n = t.shape[0], t.shape[1]
+    return t, B, n, t.stride(0) if B > 1 else max(t.stride(0), n * n)
+
+
+def _host_list(a, name):
+    """A short list of ints (widths, viewpoints) as a contiguous int32 [k] numpy table."""
+    return _host_table(np.asarray(a).reshape(-1, 1), np.int32, 1, name)[:, 0]
+
+
 def screen_scores(ctx, alt, ref):
     """alt [B, n, n] (any batch stride, rows contiguous) against ref [n, n]: (profile [B, n], mean [B], max [B]) of |alt - ref|."""
     alt, ref, n = _maps_args(alt, ref)
@@ -832,7 +847,7 @@ def screen_epistasis_scores(ctx, alt, bank, ref, member_off_host, members_host, 
     B, U = alt.shape[0], bank.shape[0]
     if o.ndim != 1 or o.size != B + 1 or m.ndim != 1 or B < 1:
         raise ValueError(f"member table: offsets [{B + 1}] int64 (one set per alt map, at least one), members [P] int32")
-    bs, bank_bs = (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), n * n) for t in (alt, bank))      # one map: torch may report any stride for it
+    bs, bank_bs = _map_batch(alt, "alt")[3], _map_batch(bank, "bank")[3]
     od, md = torch.from_numpy(o).to(alt.device), torch.from_numpy(m).to(alt.device)
     head = (ctx.handle, _dev_p(alt), bs, _dev_p(bank), bank_bs, U, _p(ref), B, n, _dev_p(od), _np_p(o), _dev_p(md), _np_p(m), m.size)
     profile, mean, amax, add = _f32_outputs(alt.device, (B, n), (B,), (B,), (B,))
@@ -901,11 +916,8 @@ def _track_args(alt, ref, table_host, name, bin_map_host, bin_map):
         (alt, ref, _), m, md = _maps_args(alt, ref), None, None
     else:
         alt, ref, m, md = _aligned_args(alt, ref, bin_map_host, bin_map)
-    if alt.shape[0] < 1:
-        raise ValueError("alt: at least one map")
-    t = _host_table(np.asarray(table_host).reshape(-1, 1), np.int32, 1, name)[:, 0]
-    n = ref.shape[0]
-    bs = alt.stride(0) if alt.shape[0] > 1 else max(alt.stride(0), n * n)          # B = 1: torch may report any stride for the one map
+    alt, _, _, bs = _map_batch(alt, "alt")
+    t = _host_list(table_host, name)
     return alt, ref, bs, t, torch.from_numpy(t).to(alt.device), m, md
 
 
@@ -953,6 +965,20 @@ def screen_viewpoints(ctx, alt, ref, views_host, bin_map_host=None, bin_map=None
 
 
 # distance strata (orca_screen_strata_scores): similarity scores per genomic distance and per map; the bin map is optional
+def _strata_args(d_range, B, n, dev, counts=True):
+    """What the two strata entry points share: (d_lo, d_hi, the dict of the eight outputs) - ``d_range`` = (d_lo, d_hi), every stratum of the ``n`` by
+    default; ``dist_count`` is None without ``counts``."""
+    try:
+        d_lo, d_hi = (0, n) if d_range is None else (int(v) for v in d_range)
+    except (TypeError, ValueError):
+        raise ValueError("d_range: (d_lo, d_hi)") from None
+    out = dict(zip(("dist_delta", "dist_abs", "dist_rms", "mse"), _f32_outputs(dev, (B, n), (B, n), (B, n), (B,))))
+    out["dist_corr"] = torch.empty((B, n), dtype=torch.float64, device=dev)
+    out["corr"], out["scc"] = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(2))
+    out["dist_count"] = torch.empty((B, n), dtype=torch.int32, device=dev) if counts else None
+    return d_lo, d_hi, out
+
+
 def screen_strata_scores(ctx, alt, ref, bin_map=None, d_range=None, bin_map_dev=None):
     """Distance-stratified similarity of alt [B, n, n] (any batch stride, rows contiguous) to ref [n, n] (orca_screen_strata_scores; include/orca_hip.h
     has the definitions): a dict of ``dist_delta``, ``dist_abs``, ``dist_rms`` [B, n] float32 (the mean of alt - ref, of its absolute value and its root
@@ -964,23 +990,12 @@ def screen_strata_scores(ctx, alt, ref, bin_map=None, d_range=None, bin_map_dev=
     if bin_map is None:
         if bin_map_dev is not None:
             raise ValueError("bin_map_dev: the device copy of bin_map, which is None")
-        (alt, ref, n), m, md = _maps_args(alt, ref), None, None
+        (alt, ref, _), m, md = _maps_args(alt, ref), None, None
     else:
         alt, ref, m, md = _aligned_args(alt, ref, bin_map, bin_map_dev)
-        n = ref.shape[0]
-    B = alt.shape[0]
-    if B < 1:
-        raise ValueError("alt: at least one map")
-    try:
-        d_lo, d_hi = (0, n) if d_range is None else (int(v) for v in d_range)
-    except (TypeError, ValueError):
-        raise ValueError("d_range: (d_lo, d_hi)") from None
-    bs = alt.stride(0) if B > 1 else max(alt.stride(0), n * n)                     # B = 1: torch may report any stride for the one map
-    dev, null = alt.device, ctypes.c_void_p(0)
-    out = dict(zip(("dist_delta", "dist_abs", "dist_rms", "mse"), _f32_outputs(dev, (B, n), (B, n), (B, n), (B,))))
-    out["dist_corr"] = torch.empty((B, n), dtype=torch.float64, device=dev)
-    out["corr"], out["scc"] = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(2))
-    out["dist_count"] = None if m is None else torch.empty((B, n), dtype=torch.int32, device=dev)
+    alt, B, n, bs = _map_batch(alt, "alt")
+    d_lo, d_hi, out = _strata_args(d_range, B, n, alt.device, counts=m is not None)
+    null = ctypes.c_void_p(0)
     ctx.sync_stream()
     check(_lib.load().orca_screen_strata_scores(ctx.handle, _dev_p(alt), bs, _p(ref), B, n, null if m is None else _dev_p(md), null if m is None else _np_p(m),
                                                 d_lo, d_hi, _dev_p(out["dist_delta"]), _dev_p(out["dist_abs"]), _dev_p(out["dist_rms"]), _dev_p(out["dist_corr"]),
@@ -993,24 +1008,30 @@ def screen_strata_scores(ctx, alt, ref, bin_map=None, d_range=None, bin_map_dev=
 PAIRED_SCORE_FIELDS = ("profile", "abs_mean", "abs_max", "delta_mean", "rms", "corr", "count")
 
 
+def _pair_bin_map(bin_map_host, B, n, device):
+    """The bin maps of B pairs: (``bin_map_host`` as [B, n] int32 on the host, its device copy)."""
+    m = _host_table(bin_map_host, np.int32, n, "bin map")
+    if m.shape[0] != B:
+        raise ValueError(f"bin map: [{B},{n}] int32, one row per pair")
+    return m, torch.from_numpy(m).to(device)
+
+
+def _pair_args(alt, ref, bin_map_host):
+    """What the paired entry points share: (alt, alt batch stride, ref, ref batch stride, bin map [B, n] int32 on the host, its device copy)."""
+    alt, ref = _f32_cuda(alt, "alt"), _f32_cuda(ref, "ref")
+    if ref.shape != alt.shape or ref.device != alt.device:
+        raise ValueError(f"alt, ref: [B,n,n] with B >= 1 on one device, got {tuple(alt.shape)} and {tuple(ref.shape)}")
+    (alt, B, n, alt_bs), (ref, _, _, ref_bs) = _map_batch(alt, "alt"), _map_batch(ref, "ref")
+    return (alt, alt_bs, ref, ref_bs) + _pair_bin_map(bin_map_host, B, n, alt.device)
+
+
 def screen_paired_aligned_scores(ctx, alt, ref, bin_map_host):
     """B pairs of maps, alt [B, n, n] against ref [B, n, n] (both any batch stride, rows contiguous), pair b through row b of ``bin_map_host`` [B, n]
     int32 numpy: the reference bin alt bin i stands for, or -1 (orca_screen_paired_aligned_scores; include/orca_hip.h has the definitions).  A dict of
     device tensors: ``profile`` [B, n], ``abs_mean``, ``abs_max``, ``delta_mean``, ``rms`` [B] float32, ``corr`` [B] float64 and ``count`` [B] int32,
     the mapped bins; every float is NaN for a pair with none."""
-    alt, ref = _f32_cuda(alt, "alt"), _f32_cuda(ref, "ref")
-    if alt.dim() != 3 or alt.shape[0] < 1 or alt.shape[1] != alt.shape[2] or ref.shape != alt.shape or ref.device != alt.device:
-        raise ValueError(f"alt, ref: [B,n,n] with B >= 1 on one device, got {tuple(alt.shape)} and {tuple(ref.shape)}")
-    B, n = alt.shape[0], alt.shape[1]
-    for t, name in ((alt, "alt"), (ref, "ref")):
-        if t.stride(2) != 1 or t.stride(1) != n:
-            raise ValueError(f"{name}: [{B},{n},{n}] with contiguous maps")
-    m = _host_table(bin_map_host, np.int32, n, "bin map")
-    if m.shape[0] != B:
-        raise ValueError(f"bin map: [{B},{n}] int32, one row per pair")
-    alt_bs, ref_bs = (t.stride(0) if B > 1 else max(t.stride(0), n * n) for t in (alt, ref))       # B = 1: torch may report any stride for the one map
-    dev = alt.device
-    md = torch.from_numpy(m).to(dev)
+    alt, alt_bs, ref, ref_bs, m, md = _pair_args(alt, ref, bin_map_host)
+    (B, n), dev = m.shape, alt.device
     out = dict(zip(PAIRED_SCORE_FIELDS[:5], _f32_outputs(dev, (B, n), (B,), (B,), (B,), (B,))))
     out["corr"] = torch.empty(B, dtype=torch.float64, device=dev)
     out["count"] = torch.empty(B, dtype=torch.int32, device=dev)
@@ -1022,22 +1043,6 @@ def screen_paired_aligned_scores(ctx, alt, ref, bin_map_host):
 
 # paired tracks and strata (orca_screen_paired_insulation / _viewpoints / _strata_scores): the 1 Mb screen's readouts, every alt map against a reference
 # map of its own through its bin map
-def _pair_args(alt, ref, bin_map_host):
-    """What the paired entry points share: (alt, alt batch stride, ref, ref batch stride, bin map [B, n] int32 on the host, its device copy)."""
-    alt, ref = _f32_cuda(alt, "alt"), _f32_cuda(ref, "ref")
-    if alt.dim() != 3 or alt.shape[0] < 1 or alt.shape[1] != alt.shape[2] or ref.shape != alt.shape or ref.device != alt.device:
-        raise ValueError(f"alt, ref: [B,n,n] with B >= 1 on one device, got {tuple(alt.shape)} and {tuple(ref.shape)}")
-    B, n = alt.shape[0], alt.shape[1]
-    for t, name in ((alt, "alt"), (ref, "ref")):
-        if t.stride(2) != 1 or t.stride(1) != n:
-            raise ValueError(f"{name}: [{B},{n},{n}] with contiguous maps")
-    m = _host_table(bin_map_host, np.int32, n, "bin map")
-    if m.shape[0] != B:
-        raise ValueError(f"bin map: [{B},{n}] int32, one row per pair")
-    alt_bs, ref_bs = (t.stride(0) if B > 1 else max(t.stride(0), n * n) for t in (alt, ref))       # B = 1: torch may report any stride for the one map
-    return alt, alt_bs, ref, ref_bs, m, torch.from_numpy(m).to(alt.device)
-
-
 def screen_paired_insulation(ctx, alt, ref, widths_host, bin_map_host):
     """Insulation tracks of B pairs of maps, alt [B, n, n] against ref [B, n, n] (both any batch stride, rows contiguous) at the W widths ``widths_host``
     (1 to 8 ints, each 1 .. 128 bins) through ``bin_map_host`` [B, n] int32 numpy (orca_screen_paired_insulation): (track, ref_track, aligned), each
@@ -1045,7 +1050,7 @@ def screen_paired_insulation(ctx, alt, ref, widths_host, bin_map_host):
     NaN where alt bin i stands for no reference bin or either diamond does not fit."""
     alt, alt_bs, ref, ref_bs, m, md = _pair_args(alt, ref, bin_map_host)
     B, n = m.shape
-    w = _host_table(np.asarray(widths_host).reshape(-1, 1), np.int32, 1, "widths")[:, 0]
+    w = _host_list(widths_host, "widths")
     W = w.shape[0]
     wd = torch.from_numpy(w).to(alt.device)
     track, ref_track, aligned = _f32_outputs(alt.device, (B, W, n), (B, W, n), (B, W, n))
@@ -1066,7 +1071,7 @@ def screen_paired_viewpoints(ctx, alt, ref, views_host, bin_map_host):
     if v.ndim == 1:
         v = np.broadcast_to(v, (B, v.shape[0]))
     if v.ndim != 2 or v.shape[0] != B:
-        raise ValueError(f"viewpoints: [{B},V] int32, one row per pair (or one [V] list for all)")
+        raise ValueError(f"viewpoints: [{B},V] int32 (or one [V] list for all {B} pairs)")
     v = np.ascontiguousarray(v, dtype=np.int32)
     V = v.shape[1]
     vd = torch.from_numpy(v).to(alt.device)
@@ -1089,15 +1094,7 @@ def screen_paired_strata_scores(ctx, alt, ref, bin_map_host, d_range=None):
     lower side of the diagonal of neither map is read, whichever way the bin map runs."""
     alt, alt_bs, ref, ref_bs, m, md = _pair_args(alt, ref, bin_map_host)
     B, n = m.shape
-    try:
-        d_lo, d_hi = (0, n) if d_range is None else (int(v) for v in d_range)
-    except (TypeError, ValueError):
-        raise ValueError("d_range: (d_lo, d_hi)") from None
-    dev = alt.device
-    out = dict(zip(("dist_delta", "dist_abs", "dist_rms", "mse"), _f32_outputs(dev, (B, n), (B, n), (B, n), (B,))))
-    out["dist_corr"] = torch.empty((B, n), dtype=torch.float64, device=dev)
-    out["corr"], out["scc"] = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(2))
-    out["dist_count"] = torch.empty((B, n), dtype=torch.int32, device=dev)
+    d_lo, d_hi, out = _strata_args(d_range, B, n, alt.device)
     ctx.sync_stream()
     check(_lib.load().orca_screen_paired_strata_scores(ctx.handle, _dev_p(alt), alt_bs, _dev_p(ref), ref_bs, B, n, _dev_p(md), _np_p(m), d_lo, d_hi,
                                                        *(_dev_p(out[k]) for k in PAIRED_STRATA_FIELDS)), "orca_screen_paired_strata_scores")
@@ -1106,14 +1103,7 @@ def screen_paired_strata_scores(ctx, alt, ref, bin_map_host, d_range=None):
 
 # loops (orca_screen_dot_calls, orca_screen_dot_enrichment): dot calls per map and the enrichment at listed pixels
 def _dot_args(maps, p, w, d_min):
-    maps = _f32_cuda(maps, "maps")
-    if maps.dim() != 3 or maps.shape[1] != maps.shape[2] or maps.stride(2) != 1 or maps.stride(1) != maps.shape[1]:
-        raise ValueError("maps: [B,n,n] with contiguous maps")
-    B, n = maps.shape[0], maps.shape[1]
-    if B < 1:
-        raise ValueError("maps: at least one map")
-    bs = maps.stride(0) if B > 1 else max(maps.stride(0), n * n)                   # B = 1: torch may report any stride for the one map
-    return maps, B, n, bs, int(p), int(w), 2 * int(w) + 1 if d_min is None else int(d_min)
+    return _map_batch(maps, "maps") + (int(p), int(w), 2 * int(w) + 1 if d_min is None else int(d_min))
 
 
 def screen_dot_calls(ctx, maps, p, w, r, threshold, max_calls, d_min=None):
@@ -1154,20 +1144,13 @@ def screen_paired_dot_follow(ctx, alt_e, ref_ij, ref_enrich, bin_map_host, w, d_
     <= n - 1, is empty); ``bin_map_host`` [B, n] int32 numpy.  A dict of device tensors: ``candidates`` [B, R] int32 (the eligible alt pixels that stand for
     the dot), ``at`` [B, R, 2] int32 (the one with the largest e, the earlier of equals; (-1, -1) without a candidate), ``enrich`` [B, R] float32 (e there)
     and ``delta`` [B, R] float32 (e there minus the reference dot's e), NaN without a candidate."""
-    alt_e = _f32_cuda(alt_e, "alt_e")
-    if alt_e.dim() != 3 or alt_e.shape[0] < 1 or alt_e.shape[1] != alt_e.shape[2] or alt_e.stride(2) != 1 or alt_e.stride(1) != alt_e.shape[1]:
-        raise ValueError("alt_e: [B,n,n] with B >= 1 and contiguous maps")
-    B, n = alt_e.shape[0], alt_e.shape[1]
-    e_bs = alt_e.stride(0) if B > 1 else max(alt_e.stride(0), n * n)               # B = 1: torch may report any stride for the one map
+    alt_e, B, n, e_bs = _map_batch(alt_e, "alt_e")
     ref_ij, ref_enrich = _on_device(ref_ij, "ref_ij", torch.int32), _on_device(ref_enrich, "ref_enrich", torch.float32)
     if ref_ij.dim() != 3 or ref_ij.shape[0] != B or ref_ij.shape[2] != 2 or ref_enrich.shape != ref_ij.shape[:2] or ref_ij.device != alt_e.device \
             or ref_enrich.device != alt_e.device:
         raise ValueError(f"ref_ij: [{B},R,2] int32 and ref_enrich: [{B},R] float32 on the maps' device")
     R, dev = ref_ij.shape[1], alt_e.device
-    m = _host_table(bin_map_host, np.int32, n, "bin map")
-    if m.shape[0] != B:
-        raise ValueError(f"bin map: [{B},{n}] int32, one row per pair")
-    md = torch.from_numpy(m).to(dev)
+    m, md = _pair_bin_map(bin_map_host, B, n, dev)
     w = int(w)
     d_min = 2 * w + 1 if d_min is None else int(d_min)
     enrich, delta = _f32_outputs(dev, (B, R), (B, R))
@@ -1187,13 +1170,7 @@ def screen_eigenvectors(ctx, maps, n_eigs=1, d_lo=2, center=True, tol=1e-8, max_
     correlation with it non-negative; without it the component of largest |E_k| is positive.  A dict of device tensors: ``E`` [B, K, n] float32 (NaN on
     invalid bins), ``eigenvalue``, ``residual`` [B, K] float64 (the relative residual reached: converged means <= ``tol``), ``iterations`` [B, K] int32
     and ``n_valid`` [B] int32; a map with n_valid <= K is all NaN."""
-    maps = _f32_cuda(maps, "maps")
-    if maps.dim() != 3 or maps.shape[1] != maps.shape[2] or maps.stride(2) != 1 or maps.stride(1) != maps.shape[1]:
-        raise ValueError("maps: [B,n,n] with contiguous maps")
-    B, n = maps.shape[0], maps.shape[1]
-    if B < 1:
-        raise ValueError("maps: at least one map")
-    bs = maps.stride(0) if B > 1 else max(maps.stride(0), n * n)                   # B = 1: torch may report any stride for the one map
+    maps, B, n, bs = _map_batch(maps, "maps")
     K, dev = int(n_eigs), maps.device
     if phase is not None:
         phase = _on_device(phase, "phase", torch.float32)
@@ -1254,7 +1231,7 @@ def screen_merge_strands(ctx, fwd, rev, ref_fwd=None, ref_rev=None, out=None):
                 raise ValueError(f"{name}: [{n},{n}] beside fwd")
         refs.append(t)
     gap = None if refs[0] is None else torch.empty(B, dtype=torch.float32, device=fwd.device)
-    bs = [max(t.stride(0), n * n) for t in (fwd, rev, out)]          # B = 1: torch may report any stride for the one map
+    bs = [_map_batch(t, name)[3] for t, name in ((fwd, "fwd"), (rev, "rev"), (out, "out"))]
     null = ctypes.c_void_p(0)
     ctx.sync_stream()
     check(_lib.load().orca_screen_merge_strands(ctx.handle, _p(fwd), bs[0], _p(rev), bs[1], null if refs[0] is None else _p(refs[0]),

@@ -31,111 +31,95 @@ genome = torch.randint(0, 4, (40_000_000,), device=dev, generator=g, dtype=torch
 svs = sv.synth_svs(n + 2, 40_000_000, align=align)
 sv.sv_screen([h1], genome, svs[:2], 40_000_000, incremental=inc, min_uses=1, streams=streams)
 torch.cuda.synchronize()
-if SCORES:
-    import json
-    modes = {"plain": {}, "scores": {"scores": True}, "scores_no_maps": {"scores": True, "keep_maps": False}}
+
+
+def timed_runs(modes, warm=None, on_result=None, note=None):
+    """The loop of all four comparisons: {mode: [a record per repetition]} of three repetitions with the ``modes`` ({name: sv_screen keywords})
+    alternated, a synchronise on both sides of the clock and the stage-cache build time subtracted.  ``warm``: the mode that is called once before
+    the clock (a new kernel's first launch); ``on_result(name)``: called before every run, returns that run's on_result; ``note(name)``: more to print."""
+    if warm is not None:
+        sv.sv_screen([h1], genome, svs[:2], 40_000_000, incremental=inc, min_uses=1, streams=streams, **modes[warm])
+        torch.cuda.synchronize()
     runs = {k: [] for k in modes}
     for rep in range(3):
         for k, kw in modes.items():
             st = {}
+            cb = on_result(k) if on_result else (lambda i, e: None)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            sv.sv_screen([h1], genome, svs[2:], 40_000_000, incremental=inc, stats=st, streams=streams, on_result=lambda i, e: None, **kw)
+            sv.sv_screen([h1], genome, svs[2:], 40_000_000, incremental=inc, stats=st, streams=streams, on_result=cb, **kw)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             build = (st.get("stage3_cache") or {}).get("build_s", 0.0)      # the stage cache is rebuilt by every call: its time is not the screen's
             runs[k].append({"total_s": round(dt, 4), "stage_cache_build_s": build, "ms_per_sv": round((dt - build) / n * 1e3, 3)})
-            print(k, runs[k][-1])
+            print(k, runs[k][-1], *(note(k) if note else ()))
+    return runs
+
+
+def summary(flag, runs, base, **more):
+    """The head of a mode's JSON: the run's settings, ``more``, the runs, the best of three per mode and the spread of the baseline ``base``'s three."""
     best = {k: min(r["ms_per_sv"] for r in v) for k, v in runs.items()}
-    spread = max(r["ms_per_sv"] for r in runs["plain"]) - best["plain"]
-    out = {"tool": "tools/time_sv_screen.py --scores", "n_svs": n, "incremental": inc, "streams": streams, "align": align, "runs": runs,
-           "best_ms_per_sv": best, "plain_spread_ms_per_sv": round(spread, 3),
-           "scores_cost_ms_per_sv": round(best["scores"] - best["plain"], 3), "scores_within_plain_spread": bool(best["scores"] <= best["plain"] + spread),
-           "no_maps_saving_ms_per_sv": round(best["plain"] - best["scores_no_maps"], 3)}
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sv_screen_scores.json")
+    spread = max(r["ms_per_sv"] for r in runs[base]) - best[base]
+    return {"tool": "tools/time_sv_screen.py " + flag, "n_svs": n, "incremental": inc, "streams": streams, "align": align, **more, "runs": runs,
+            "best_ms_per_sv": best, base + "_spread_ms_per_sv": round(spread, 3)}, best, spread
+
+
+def added(out, runs, best, spread, k, base="scores"):
+    """What mode ``k`` adds to the baseline: per repetition against the baseline repetition beside it, and best of three against best of three."""
+    out[k + "_added_ms_per_sv_per_repetition"] = [round(t["ms_per_sv"] - s["ms_per_sv"], 3) for s, t in zip(runs[base], runs[k])]
+    out[k + "_added_ms_per_sv_best_of_three"] = round(best[k] - best[base], 3)
+    out[k + "_within_" + base + "_spread"] = bool(best[k] <= best[base] + spread)
+
+
+def finish(name, out):
+    import json
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sv_screen_" + name + ".json")
     json.dump(out, open(path, "w"), indent=1)
     print(json.dumps({k: v for k, v in out.items() if k != "runs"}))
     sys.exit(0)
+
+
+if SCORES:
+    runs = timed_runs({"plain": {}, "scores": {"scores": True}, "scores_no_maps": {"scores": True, "keep_maps": False}})
+    out, best, spread = summary("--scores", runs, "plain")
+    out.update({"scores_cost_ms_per_sv": round(best["scores"] - best["plain"], 3), "scores_within_plain_spread": bool(best["scores"] <= best["plain"] + spread),
+                "no_maps_saving_ms_per_sv": round(best["plain"] - best["scores_no_maps"], 3)})
+    finish("scores", out)
 if TRACKS:
-    import json
     modes = {"scores": {"scores": True},
              "tracks": {"scores": True, "insulation": (5, 10, 25), "viewpoints": [20_000_000], "strata": True}}
-    sv.sv_screen([h1], genome, svs[:2], 40_000_000, incremental=inc, min_uses=1, streams=streams, **modes["tracks"])     # the new kernels' first launch
-    torch.cuda.synchronize()
-    runs = {k: [] for k in modes}
-    for rep in range(3):
-        for k, kw in modes.items():
-            st = {}
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            sv.sv_screen([h1], genome, svs[2:], 40_000_000, incremental=inc, stats=st, streams=streams, on_result=lambda i, e: None, **kw)
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            build = (st.get("stage3_cache") or {}).get("build_s", 0.0)      # the stage cache is rebuilt by every call: its time is not the screen's
-            runs[k].append({"total_s": round(dt, 4), "stage_cache_build_s": build, "ms_per_sv": round((dt - build) / n * 1e3, 3)})
-            print(k, runs[k][-1])
-    best = {k: min(r["ms_per_sv"] for r in v) for k, v in runs.items()}
-    beside = [round(t["ms_per_sv"] - s["ms_per_sv"], 3) for s, t in zip(runs["scores"], runs["tracks"])]      # each against the baseline repetition beside it
-    spread = max(r["ms_per_sv"] for r in runs["scores"]) - best["scores"]
-    out = {"tool": "tools/time_sv_screen.py --tracks", "n_svs": n, "incremental": inc, "streams": streams, "align": align, "modes": {k: {a: list(b) if isinstance(b, tuple) else b for a, b in kw.items()} for k, kw in modes.items()},
-           "runs": runs, "best_ms_per_sv": best, "scores_spread_ms_per_sv": round(spread, 3), "tracks_added_ms_per_sv_per_repetition": beside,
-           "tracks_added_ms_per_sv_best_of_three": round(best["tracks"] - best["scores"], 3),
-           "tracks_within_scores_spread": bool(best["tracks"] <= best["scores"] + spread)}
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sv_screen_tracks.json")
-    json.dump(out, open(path, "w"), indent=1)
-    print(json.dumps({k: v for k, v in out.items() if k != "runs"}))
-    sys.exit(0)
+    runs = timed_runs(modes, warm="tracks")
+    out, best, spread = summary("--tracks", runs, "scores", modes={k: {a: list(b) if isinstance(b, tuple) else b for a, b in kw.items()} for k, kw in modes.items()})
+    added(out, runs, best, spread, "tracks")
+    finish("tracks", out)
 if LOOPS:
-    import json
     from orca_amd import screen
     modes = {"scores": {"scores": True}, "loops": {"scores": True, "loops": True},
              "loops_filled": {"scores": True, "loops": screen.LoopParams(threshold=-1e30)}}
-    sv.sv_screen([h1], genome, svs[:2], 40_000_000, incremental=inc, min_uses=1, streams=streams, **modes["loops_filled"])     # the new kernel's first launch
-    torch.cuda.synchronize()
-    runs = {k: [] for k in modes}
     dots = {k: 0 for k in modes}
 
     def tally(k):
+        dots[k] = 0
+
         def on_result(i, e):
             if "loop_params" in e["scores"]:
                 dots[k] += int(sum(m["ref_loop_count"].sum() + m["loop_count"].sum() for m in e["scores"]["models"]))
         return on_result
-    for rep in range(3):
-        for k, kw in modes.items():
-            st = {}
-            dots[k] = 0
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            sv.sv_screen([h1], genome, svs[2:], 40_000_000, incremental=inc, stats=st, streams=streams, on_result=tally(k), **kw)
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            build = (st.get("stage3_cache") or {}).get("build_s", 0.0)      # the stage cache is rebuilt by every call: its time is not the screen's
-            runs[k].append({"total_s": round(dt, 4), "stage_cache_build_s": build, "ms_per_sv": round((dt - build) / n * 1e3, 3)})
-            print(k, runs[k][-1], "dots", dots[k])
-    best = {k: min(r["ms_per_sv"] for r in v) for k, v in runs.items()}
-    spread = max(r["ms_per_sv"] for r in runs["scores"]) - best["scores"]
-    out = {"tool": "tools/time_sv_screen.py --loops", "n_svs": n, "incremental": inc, "streams": streams, "align": align,
-           "modes": {"scores": "scores=True", "loops": "scores=True, loops=True", "loops_filled": "scores=True, loops=LoopParams(threshold=-1e30)"},
-           "dots_called_per_run": dots, "runs": runs, "best_ms_per_sv": best, "scores_spread_ms_per_sv": round(spread, 3)}
-    for k in ("loops", "loops_filled"):       # each against the baseline repetition beside it
-        out[k + "_added_ms_per_sv_per_repetition"] = [round(t["ms_per_sv"] - s["ms_per_sv"], 3) for s, t in zip(runs["scores"], runs[k])]
-        out[k + "_added_ms_per_sv_best_of_three"] = round(best[k] - best["scores"], 3)
-        out[k + "_within_scores_spread"] = bool(best[k] <= best["scores"] + spread)
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sv_screen_loops.json")
-    json.dump(out, open(path, "w"), indent=1)
-    print(json.dumps({k: v for k, v in out.items() if k != "runs"}))
-    sys.exit(0)
+    runs = timed_runs(modes, warm="loops_filled", on_result=tally, note=lambda k: ("dots", dots[k]))
+    out, best, spread = summary("--loops", runs, "scores", dots_called_per_run=dots,
+                                modes={"scores": "scores=True", "loops": "scores=True, loops=True", "loops_filled": "scores=True, loops=LoopParams(threshold=-1e30)"})
+    for k in ("loops", "loops_filled"):
+        added(out, runs, best, spread, k)
+    finish("loops", out)
 if COMPARTMENTS:
-    import json
     import numpy as np
     modes = {"scores": {"scores": True}, "compartments": {"scores": True, "compartments": True},
              "compartments_3": {"scores": True, "compartments": sv.CompartmentParams(n_eigs=3)}}
-    sv.sv_screen([h1], genome, svs[:2], 40_000_000, incremental=inc, min_uses=1, streams=streams, **modes["compartments_3"])     # the new kernels' first launches
-    torch.cuda.synchronize()
-    runs = {k: [] for k in modes}
-    seen = {k: {"converged": [], "iterations": []} for k in modes}
+    seen = {}
 
     def tally(k):
+        seen[k] = {"converged": [], "iterations": []}
+
         def on_result(i, e):
             if "compartment_params" in e["scores"]:
                 for m in e["scores"]["models"]:
@@ -143,34 +127,15 @@ if COMPARTMENTS:
                         seen[k]["converged"].append(m[side + "compartment_converged"].reshape(-1))
                         seen[k]["iterations"].append(m[side + "compartment_iterations"].reshape(-1))
         return on_result
-    for rep in range(3):
-        for k, kw in modes.items():
-            st = {}
-            seen[k] = {"converged": [], "iterations": []}
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            sv.sv_screen([h1], genome, svs[2:], 40_000_000, incremental=inc, stats=st, streams=streams, on_result=tally(k), **kw)
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            build = (st.get("stage3_cache") or {}).get("build_s", 0.0)      # the stage cache is rebuilt by every call: its time is not the screen's
-            runs[k].append({"total_s": round(dt, 4), "stage_cache_build_s": build, "ms_per_sv": round((dt - build) / n * 1e3, 3)})
-            print(k, runs[k][-1])
-    best = {k: min(r["ms_per_sv"] for r in v) for k, v in runs.items()}
-    spread = max(r["ms_per_sv"] for r in runs["scores"]) - best["scores"]
-    out = {"tool": "tools/time_sv_screen.py --compartments", "n_svs": n, "incremental": inc, "streams": streams, "align": align, "weights": "synthetic",
-           "modes": {"scores": "scores=True", "compartments": "scores=True, compartments=True", "compartments_3": "scores=True, compartments=CompartmentParams(n_eigs=3)"},
-           "runs": runs, "best_ms_per_sv": best, "scores_spread_ms_per_sv": round(spread, 3)}
-    for k in ("compartments", "compartments_3"):       # each against the baseline repetition beside it
-        out[k + "_added_ms_per_sv_per_repetition"] = [round(t["ms_per_sv"] - s["ms_per_sv"], 3) for s, t in zip(runs["scores"], runs[k])]
-        out[k + "_added_ms_per_sv_best_of_three"] = round(best[k] - best["scores"], 3)
-        out[k + "_within_scores_spread"] = bool(best[k] <= best["scores"] + spread)
+    runs = timed_runs(modes, warm="compartments_3", on_result=tally)
+    out, best, spread = summary("--compartments", runs, "scores", weights="synthetic",
+                                modes={"scores": "scores=True", "compartments": "scores=True, compartments=True", "compartments_3": "scores=True, compartments=CompartmentParams(n_eigs=3)"})
+    for k in ("compartments", "compartments_3"):
+        added(out, runs, best, spread, k)
         conv, its = np.concatenate(seen[k]["converged"]), np.concatenate(seen[k]["iterations"])
         out[k + "_convergence"] = {"pairs": int(conv.size), "converged_share": round(float(conv.mean()), 4), "iterations_median": float(np.median(its)),
                                    "iterations_max": int(its.max())}
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sv_screen_compartments.json")
-    json.dump(out, open(path, "w"), indent=1)
-    print(json.dumps({k: v for k, v in out.items() if k != "runs"}))
-    sys.exit(0)
+    finish("compartments", out)
 t0 = time.perf_counter()
 st = {}
 sv.sv_screen([h1], genome, svs[2:], 40_000_000, incremental=inc, stats=st, streams=streams)
