@@ -565,6 +565,26 @@ int orca_screen_eigenvectors(orca_ctx* ctx, const float* maps, int64_t map_bs, i
  * A window that leaves [0, L) - off_w < 0, bs_w < 1 or off_w + n * bs_w > L - is refused with ORCA_EINVAL before any launch. */
 int orca_screen_gc_tracks(orca_ctx* ctx, const uint8_t* codes, int64_t L, const int64_t* offsets, const int64_t* binsizes, int W, int n, float* out);
 
+/* Domain boundary calls from insulation tracks (screen.screen_1m(..., insulation=, boundaries=), sv.sv_screen(..., insulation=, boundaries=)).
+ *   tracks [B][W][n] float32 on the device, contiguous: tracks exactly as orca_screen_insulation / orca_screen_paired_insulation write them - lower = more
+ *   insulated, NaN where the diamond does not fit or holds a NaN.  B >= 1, 1 <= W <= 8, 3 <= n <= 256, min_strength >= 0 (not NaN), 0 <= K <= n.
+ *   Outputs: count [B][W] int32, bins [B][W][K] int32, strength [B][W][K] float32, strength_track [B][W][n] float32 or NULL.
+ * - Minimum.  Bin i of a track t is a minimum when 1 <= i <= n - 2, t[i - 1], t[i] and t[i + 1] are all not NaN, t[i] < t[i - 1] and t[i] <= t[i + 1]:
+ *   the first bin of a plateau.
+ * - Strength.  The topographic prominence of the dip (scipy's peak_prominences on -t over the NaN-free run that holds i).  Walk left from i - 1 while the
+ *   bin exists, is not NaN and is >= t[i]; L = the largest value met on that walk, or t[i] if none.  R = the same, walking right.
+ *   strength = min(L, R) - t[i], ONE fp32 subtraction.  Only comparisons and that subtraction occur: a host restatement agrees bit for bit.  A NaN ends a
+ *   run: nothing is bridged across it, so a dip beside a NaN bin is measured against its own side of the gap only.  The unit is the track's: mean log
+ *   observed / expected.
+ * - Call.  A minimum is a boundary when strength > 0 and strength >= min_strength.  A shelf such as 3 2 2 1 has strength 0 and is never a boundary.
+ * - Lists.  The boundaries of a track in ascending bin order: bins / strength hold the first K, count ALL of them; unused slots hold -1 / NaN.
+ *   strength_track[i] = the strength at every minimum with strength > 0 (whatever min_strength), NaN elsewhere.
+ * - Batch independence.  A track's outputs are the same bits whatever B, W and its place among them; no atomics.
+ * One workgroup of 256 threads per track on a grid of (B, W).  Anything else - a NULL pointer other than strength_track, a bound above - is ORCA_EINVAL
+ * before any launch, and no output is written. */
+int orca_screen_boundary_calls(orca_ctx* ctx, const float* tracks, int B, int W, int n, float min_strength, int K, int32_t* count, int32_t* bins,
+                               float* strength, float* strength_track);
+
 /* Number of 4 kb bins Encoder emits for an L-bp input (floor through the
  * 4,4,5,5,5,2 pooling chain). */
 int64_t orca_encoder_num_bins(int64_t L);

@@ -478,6 +478,18 @@ extern "C" int orca_screen_gc_tracks(orca_ctx* ctx, const uint8_t* codes, int64_
   return ORCA_OK;
 }
 
+// ---- boundaries: domain boundary calls from B x W insulation tracks that are on the device already ------------------------------------------------------------
+extern "C" int orca_screen_boundary_calls(orca_ctx* ctx, const float* tracks, int B, int W, int n, float min_strength, int K, int32_t* count, int32_t* bins,
+                                          float* strength, float* strength_track) {
+  if (!ctx || !tracks || !count || !bins || !strength) return fail(ORCA_EINVAL, "orca_screen_boundary_calls: NULL argument");
+  if (B < 1 || W < 1 || W > SCREEN_INSULATION_MAX_WIDTHS || n < 3 || n > SCREEN_ALIGNED_MAX_BINS)
+    return fail(ORCA_EINVAL, "orca_screen_boundary_calls: %d x %d tracks (B >= 1, W 1..%d) of %d bins (3..%d)", B, W, SCREEN_INSULATION_MAX_WIDTHS, n, SCREEN_ALIGNED_MAX_BINS);
+  if (K < 0 || K > n) return fail(ORCA_EINVAL, "orca_screen_boundary_calls: K = %d listed boundaries per track (0..n = %d)", K, n);
+  if (!(min_strength >= 0.f)) return fail(ORCA_EINVAL, "orca_screen_boundary_calls: min_strength = %g (>= 0, not NaN)", (double)min_strength);
+  return launch(ctx, "screen_boundary_calls_kernel", screen_boundary_calls_kernel, dim3((unsigned)B, (unsigned)W), 256, tracks, n, min_strength, K, count, bins, strength,
+                strength_track);
+}
+
 // ---- both strands --------------------------------------------------------------------------------------------------------------------------------------------
 extern "C" int orca_screen_merge_strands(orca_ctx* ctx, const float* fwd, int64_t fwd_bs, const float* rev, int64_t rev_bs, const float* ref_fwd, const float* ref_rev,
                                          int B, int n, float* out, int64_t out_bs, float* gap) {

@@ -937,6 +937,70 @@ static __global__ void __launch_bounds__(256) screen_dot_calls_kernel(const floa
   }
 }
 
+// ---- boundaries: domain boundary calls from insulation tracks (screen_1m(..., insulation=, boundaries=), sv.sv_screen(..., insulation=, boundaries=)) ----
+// include/orca_hip.h (orca_screen_boundary_calls) has the definitions.  One workgroup of 256 threads per track, grid (B, W); the track goes to LDS once
+// and thread i owns bin i.  Bin i is a minimum when 1 <= i <= n - 2, t[i - 1], t[i], t[i + 1] are not NaN, t[i] < t[i - 1] and t[i] <= t[i + 1] (the first
+// bin of a plateau).  Its strength is the prominence of the dip: the thread walks left from i - 1 while the bin exists, is not NaN and is >= t[i], L = the
+// largest value met (t[i] if none), R the same to the right, strength = min(L, R) - t[i] - comparisons and ONE fp32 subtraction, so the host restatement
+// agrees bit for bit.  A NaN ends a walk: nothing is bridged across it.  The walks diverge by design, at most n LDS reads each way.  A minimum is a
+// boundary when strength > 0 and strength >= min_strength.  The list is ascending in the bin: a ballot per wave, the four waves' counts through LDS and a
+// prefix, as in screen_dot_calls_kernel - no atomics, and a track's outputs depend on the track alone.  count = all boundaries; the first K are written,
+// the rest of the K slots get -1 / NaN.  strength_track (may be NULL): the strength at every minimum with strength > 0, NaN elsewhere.
+static __global__ void __launch_bounds__(256) screen_boundary_calls_kernel(const float* __restrict__ tracks, int n, float min_strength, int K,
+                                                                           int* __restrict__ count, int* __restrict__ bins, float* __restrict__ strength,
+                                                                           float* __restrict__ strength_track) {
+  __shared__ float s_t[SCREEN_ALIGNED_MAX_BINS];
+  __shared__ int s_wave[4];
+  const int i = threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long tr = (long)blockIdx.x * gridDim.y + blockIdx.y;
+  const float nan = __int_as_float(0x7fc00000);
+  n = n > SCREEN_ALIGNED_MAX_BINS ? SCREEN_ALIGNED_MAX_BINS : (n < 0 ? 0 : n);
+  K = K < 0 ? 0 : K;
+  s_t[i] = i < n ? tracks[tr * n + i] : nan;
+  __syncthreads();
+  float s = nan;
+  if (i >= 1 && i <= n - 2) {
+    const float v = s_t[i], a = s_t[i - 1], b = s_t[i + 1];
+    if (v == v && a == a && b == b && v < a && v <= b) {
+      float L = v, R = v;
+      for (int j = i - 1; j >= 0; --j) {
+        const float f = s_t[j];
+        if (!(f >= v)) break;                            // lower, or NaN
+        L = f > L ? f : L;
+      }
+      for (int j = i + 1; j < n; ++j) {
+        const float f = s_t[j];
+        if (!(f >= v)) break;
+        R = f > R ? f : R;
+      }
+      s = (L < R ? L : R) - v;
+    }
+  }
+  const bool dip = s > 0.f;                              // false for NaN: no minimum here, or a shelf
+  if (strength_track && i < n) strength_track[tr * n + i] = dip ? s : nan;
+  const bool call = dip && s >= min_strength;
+  const unsigned long long mask = __ballot(call);
+  if (lane == 0) s_wave[wave] = __popcll(mask);
+  __syncthreads();
+  int at = __popcll(mask & ((1ull << lane) - 1ull)), total = 0;
+  for (int k = 0; k < 4; ++k) {
+    const int c = s_wave[k];
+    if (k < wave) at += c;
+    total += c;
+  }
+  int* my_bins = bins + tr * K;
+  float* my_st = strength + tr * K;
+  if (call && at < K) {
+    my_bins[at] = i;
+    my_st[at] = s;
+  }
+  if (i == 0) count[tr] = total;
+  for (int k = (total < K ? total : K) + i; k < K; k += 256) {
+    my_bins[k] = -1;
+    my_st[k] = nan;
+  }
+}
+
 // ---- loops per level of the SV screen (sv.sv_screen(..., scores=True, loops=)): a reference dot followed through the pair's bin map ---------------------
 // include/orca_hip.h (orca_screen_paired_dot_follow) has the rule.  Reference dot k = (ri, rj) of pair b, A = the alt bins a with map a = ri, C = those
 // with map c = rj: the candidates are the pixels (min(a, c), max(a, c)) over A x C that are eligible in the alt map - the min/max mirrors a pixel of a

@@ -1162,6 +1162,29 @@ def screen_paired_dot_follow(ctx, alt_e, ref_ij, ref_enrich, bin_map_host, w, d_
     return {"candidates": candidates, "at": at, "enrich": enrich, "delta": delta}
 
 
+# boundaries (orca_screen_boundary_calls): domain boundary calls from insulation tracks that are on the device already
+def screen_boundary_calls(ctx, tracks, min_strength, max_calls, strength_track=True):
+    """Domain boundary calls on insulation tracks [B, W, n] float32 on the device (`screen_insulation`'s or `screen_paired_insulation`'s, contiguous;
+    orca_screen_boundary_calls, include/orca_hip.h has the definitions): a dict of ``count`` [B, W] int32 (all boundaries of the track), ``bins`` [B, W, K]
+    int32 and ``strength`` [B, W, K] float32 (the first K = ``max_calls`` boundaries in ascending bin order, -1 / NaN behind them) and, unless
+    ``strength_track`` is False (then None), ``strength_track`` [B, W, n] float32: the strength at every minimum with strength > 0, NaN elsewhere.
+    B >= 1, 1 <= W <= 8, 3 <= n <= 256, ``min_strength`` >= 0, 0 <= K <= n."""
+    tracks = _on_device(_f32_cuda(tracks, "tracks"), "tracks", torch.float32)
+    if tracks.dim() != 3:
+        raise ValueError(f"tracks: [B,W,n] float32, got {tuple(tracks.shape)}")
+    (B, W, n), K, dev = tracks.shape, int(max_calls), tracks.device
+    count = torch.empty((B, W), dtype=torch.int32, device=dev)
+    bins = torch.empty((B, W, max(K, 0)), dtype=torch.int32, device=dev)
+    strength, = _f32_outputs(dev, (B, W, max(K, 0)))
+    st = _f32_outputs(dev, (B, W, n))[0] if strength_track else None
+    spare = torch.empty(2, dtype=torch.int32, device=dev)    # K = 0: the lists are empty, and the entry point takes no NULL for them
+    ctx.sync_stream()
+    check(_lib.load().orca_screen_boundary_calls(ctx.handle, _dev_p(tracks), B, W, n, float(min_strength), K, _dev_p(count), _dev_p(bins if K else spare[:1]),
+                                                 _dev_p(strength if K else spare[1:]), ctypes.c_void_p(0) if st is None else _dev_p(st)),
+          "orca_screen_boundary_calls")
+    return {"count": count, "bins": bins, "strength": strength, "strength_track": st}
+
+
 # compartments (orca_screen_eigenvectors, orca_screen_gc_tracks): the leading eigenpairs of maps and the GC track that phases them
 def screen_eigenvectors(ctx, maps, n_eigs=1, d_lo=2, center=True, tol=1e-8, max_iter=1000, phase=None):
     """The ``n_eigs`` (1..3) leading eigenpairs of maps [B, n, n] (any batch stride, rows contiguous; n <= 256), one map per workgroup

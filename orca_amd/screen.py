@@ -59,6 +59,11 @@ log observed / expected, thresholded and reduced to local maxima on the device (
 change of the enrichment at every reference dot and which dots were gained or lost, bin with bin and, with ``aligned=True``, through `bin_map`
 (`loop_scores_host` restates it all).  "Which CTCF-site knock-out removes this loop" needs no ``keep_maps``.
 
+``screen_1m(..., insulation=widths, boundaries=True)`` (or a `BoundaryParams`) calls domain boundaries on the insulation tracks: the minima of a
+track whose strength - the prominence of the dip, in mean log observed / expected - reaches ``min_strength``, listed on the device
+(orca_screen_boundary_calls), then which reference boundaries an item keeps, weakens or loses and which it creates, bin with bin and, with
+``aligned=True``, through `bin_map` (`boundary_scores_host` restates it all).  "Which deletion fuses the two domains" is ``boundaries_lost``.
+
 Every score above compares an item with the unedited window.  `epistasis_1m` asks whether the effect of an `EditSet` is the sum of its members'
 effects: it screens the distinct members and the sets in one pass, keeps the members' maps in a device bank, and scores per set the residual
 r = (alt_set - ref) - sum_m (alt_m - ref), every pixel in fp64 (orca_screen_epistasis_scores, orca_screen_epistasis_region_scores;
@@ -1374,6 +1379,258 @@ def loop_scores_host(maps, ref_map, params, bin_map=None):
     return out
 
 
+# ---- boundaries: domain boundary calls from the insulation tracks (orca_screen_boundary_calls) --------------------------------------------------
+BOUNDARY_MIN_BINS, BOUNDARY_MAX_BINS = 3, 256
+BOUNDARY_MATCH_FIELDS = ("boundary_followed_at", "boundary_strength_delta", "boundary_delta", "boundary_is_gained", "ref_boundary_is_lost",
+                         "boundary_is_unmapped", "ref_boundary_is_unmapped", "boundaries_gained", "boundaries_lost")
+
+
+@dataclass(frozen=True)
+class BoundaryParams:
+    """The parameters of the boundary calls of ``screen_1m(..., insulation=, boundaries=)`` and ``sv_screen(..., insulation=, boundaries=)``;
+    include/orca_hip.h (orca_screen_boundary_calls) defines a minimum, its strength and a call.
+      min_strength  a boundary is a minimum of the insulation track whose strength - the prominence of the dip, in the track's unit, mean log
+                    observed / expected - is > 0 and >= min_strength (compared in fp32); >= 0.  The default, 0.1, is NOT calibrated on the
+                    published checkpoints - nobody on this project has them; choose it from ``ref_boundary_strength`` (run once with
+                    ``min_strength=0.0``) and known boundaries of the cell type
+      max_calls     K, the boundaries listed per track, in ascending bin order (``boundary_count`` still counts all); 1 <= K <= n
+      tol           an alt boundary matches a reference boundary when the reference bin it stands for is within tol bins of it; >= 0"""
+    min_strength: float = 0.1
+    max_calls: int = 32
+    tol: int = 1
+
+
+def check_boundaries(boundaries, n):
+    """``boundaries`` as a validated `BoundaryParams` for tracks of n bins (3 <= n <= 256): True stands for the defaults; ``min_strength`` comes back
+    as the fp32 the kernel compares with.  A ValueError for anything that is not True or a `BoundaryParams` and for values outside their ranges
+    (min_strength a number >= 0 and not NaN, 1 <= max_calls <= n, tol >= 0, both ints)."""
+    q = BoundaryParams() if boundaries is True else boundaries
+    if not isinstance(q, BoundaryParams):
+        raise ValueError("boundaries: True (the defaults) or a screen.BoundaryParams")
+    if not BOUNDARY_MIN_BINS <= int(n) <= BOUNDARY_MAX_BINS:
+        raise ValueError(f"boundaries: tracks of {n} bins ({BOUNDARY_MIN_BINS} .. {BOUNDARY_MAX_BINS})")
+    for k in ("max_calls", "tol"):
+        v = getattr(q, k)
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"boundaries: {k} = {v!r} must be an int")
+    if not 1 <= q.max_calls <= int(n):
+        raise ValueError(f"boundaries: max_calls = {q.max_calls}: 1 .. {int(n)} on tracks of {int(n)} bins")
+    if q.tol < 0:
+        raise ValueError(f"boundaries: tol = {q.tol} must not be negative")
+    try:
+        s = float(np.float32(q.min_strength))
+    except (TypeError, ValueError):
+        raise ValueError("boundaries: min_strength must be a number") from None
+    if isinstance(q.min_strength, (bool, np.bool_)) or not s >= 0.0:
+        raise ValueError(f"boundaries: min_strength = {q.min_strength!r} must be a number >= 0, not NaN")
+    return BoundaryParams(s, int(q.max_calls), int(q.tol))
+
+
+def boundary_strength_host(track):
+    """The strength track of one insulation track [n] (host restatement of orca_screen_boundary_calls' ``strength_track``): float32 [n], the strength
+    at every minimum with strength > 0, NaN elsewhere.  Bin i is a minimum when 1 <= i <= n - 2, t[i - 1], t[i], t[i + 1] are not NaN, t[i] <
+    t[i - 1] and t[i] <= t[i + 1]; walking left from i - 1 while the bin exists, is not NaN and is >= t[i], L = the largest value met (t[i] if none),
+    R the same to the right; strength = min(L, R) - t[i], one fp32 subtraction.  A NaN ends a walk: nothing is bridged across it."""
+    t = np.asarray(track, dtype=np.float32)
+    if t.ndim != 1:
+        raise ValueError("track: [n]")
+    n = t.shape[0]
+    out = np.full(n, np.nan, dtype=np.float32)
+    ok = ~np.isnan(t)
+    for i in range(1, n - 1):
+        v = t[i]
+        if not (ok[i - 1] and ok[i] and ok[i + 1] and v < t[i - 1] and v <= t[i + 1]):
+            continue
+        side = []
+        for step in (-1, 1):
+            best, j = v, i + step
+            while 0 <= j < n and t[j] >= v:              # False for a NaN
+                if t[j] > best:
+                    best = t[j]
+                j += step
+            side.append(best)
+        s = np.float32(min(side[0], side[1])) - v
+        if s > 0:
+            out[i] = s
+    return out
+
+
+def boundary_calls_host(tracks, params):
+    """The boundary calls of insulation tracks [..., n] (host restatement of orca_screen_boundary_calls; ``params``: a `BoundaryParams` or True): a
+    dict of ``count`` [...] int32 (all boundaries of the track), ``bins`` [..., K] int32 and ``strength`` [..., K] float32 (the first K = max_calls
+    boundaries in ascending bin order, -1 / NaN behind them) and ``strength_track`` [..., n] float32 (`boundary_strength_host`).  A boundary is a
+    minimum with strength > 0 and strength >= min_strength, compared in fp32."""
+    t = np.asarray(tracks, dtype=np.float32)
+    if t.ndim < 1:
+        raise ValueError("tracks: [..., n]")
+    lead, n = t.shape[:-1], t.shape[-1]
+    q = check_boundaries(params, n)
+    K, T = q.max_calls, np.float32(q.min_strength)
+    flat = t.reshape(-1, n)
+    P = flat.shape[0]
+    count, bins = np.zeros(P, dtype=np.int32), np.full((P, K), -1, dtype=np.int32)
+    strength, st = np.full((P, K), np.nan, dtype=np.float32), np.full((P, n), np.nan, dtype=np.float32)
+    for p in range(P):
+        st[p] = boundary_strength_host(flat[p])
+        with np.errstate(invalid="ignore"):
+            at = np.flatnonzero(st[p] >= T)              # the track holds strengths > 0 only; NaN compares False
+        count[p] = at.size
+        bins[p, : min(at.size, K)] = at[:K]
+        strength[p, : min(at.size, K)] = st[p, at[:K]]
+    return {"count": count.reshape(lead), "bins": bins.reshape(lead + (K,)), "strength": strength.reshape(lead + (K,)),
+            "strength_track": st.reshape(lead + (n,))}
+
+
+def match_boundaries_host(alt_bins, alt_strength, ref_bins, ref_strength, alt_track, ref_track, tol, bin_map_row=None):
+    """Match the listed boundaries of ONE alt track to its reference track's, plainly (the loops below state the rule; `_match_boundaries` is the
+    batched form the screens run).  ``alt_bins`` [K] / ``ref_bins`` [R] int32 (-1 = an empty slot) with their strengths, ``alt_track`` /
+    ``ref_track`` [n] the insulation tracks the lists were called on, ``bin_map_row`` [n] the reference bin every alt bin stands for, -1 for none
+    (None = the identity).  With map = the bin map:
+      - an alt boundary at alt bin a stands for reference bin map[a]; it is MAPPED when map[a] >= 0 and ref_track[map[a]] is not NaN;
+      - a reference boundary r is MAPPED when some alt bin a has map[a] >= 0, |map[a] - r| <= tol and alt_track[a] not NaN - something of the alt
+        allele stands where it was, and the alt track can be read there;
+      - r MATCHES a listed alt boundary a when map[a] >= 0 and |map[a] - r| <= tol (symmetric: a descending map needs no special case); its PARTNER
+        is the matching alt boundary of largest strength, the lower alt bin of equals;
+      - lost = a mapped reference boundary without a partner; gained = a mapped alt boundary that matches no listed reference boundary; an
+        unmapped one is neither - a boundary that left the window, or sits in inserted sequence, is not a false call.
+    A dict of ``followed_at`` [R] int32 (the partner's alt bin, -1 without), ``strength_delta`` [R] float32 (the partner's strength - the reference
+    strength, one fp32 subtraction; -the reference strength when lost; NaN when unmapped or the slot is empty), ``is_lost``, ``ref_is_unmapped``
+    [R] bool, ``is_gained``, ``is_unmapped`` [K] bool."""
+    ab, rb = np.asarray(alt_bins, dtype=np.int64).reshape(-1), np.asarray(ref_bins, dtype=np.int64).reshape(-1)
+    a_s, r_s = np.asarray(alt_strength, dtype=np.float32).reshape(-1), np.asarray(ref_strength, dtype=np.float32).reshape(-1)
+    ta, tr = np.asarray(alt_track, dtype=np.float32), np.asarray(ref_track, dtype=np.float32)
+    n, tol = ta.shape[0], int(tol)
+    bm = np.arange(n, dtype=np.int64) if bin_map_row is None else np.asarray(bin_map_row, dtype=np.int64)
+    K, R = ab.shape[0], rb.shape[0]
+    out = {"followed_at": np.full(R, -1, dtype=np.int32), "strength_delta": np.full(R, np.nan, dtype=np.float32), "is_lost": np.zeros(R, dtype=bool),
+           "ref_is_unmapped": np.zeros(R, dtype=bool), "is_gained": np.zeros(K, dtype=bool), "is_unmapped": np.zeros(K, dtype=bool)}
+    matched = np.zeros(K, dtype=bool)
+    for k in range(R):
+        r = int(rb[k])
+        if r < 0:
+            continue
+        best = -1
+        for j in range(K):
+            a = int(ab[j])
+            if a >= 0 and bm[a] >= 0 and abs(int(bm[a]) - r) <= tol:
+                matched[j] = True
+                if best < 0 or a_s[j] > a_s[best] or (a_s[j] == a_s[best] and a < int(ab[best])):
+                    best = j
+        mapped = any(bm[a] >= 0 and abs(int(bm[a]) - r) <= tol and not np.isnan(ta[a]) for a in range(n))
+        if best >= 0:
+            out["followed_at"][k], out["strength_delta"][k] = ab[best], a_s[best] - r_s[k]
+        elif mapped:
+            out["is_lost"][k], out["strength_delta"][k] = True, -r_s[k]
+        else:
+            out["ref_is_unmapped"][k] = True
+    for j in range(K):
+        a = int(ab[j])
+        if a < 0:
+            continue
+        mapped = bm[a] >= 0 and not np.isnan(tr[bm[a]])
+        out["is_unmapped"][j] = not mapped
+        out["is_gained"][j] = mapped and not matched[j]
+    return out
+
+
+def _match_boundaries(alt_bins, alt_strength, ref_bins, ref_strength, alt_track, ref_track, tol, bin_map=None):
+    """`match_boundaries_host` of P pairs at once: ``alt_bins`` / ``alt_strength`` [P, K], ``ref_bins`` / ``ref_strength`` [P, R], ``alt_track`` /
+    ``ref_track`` [P, n], ``bin_map`` [P, n] or None (the identity) -> its dict with a leading P, plus ``first_at`` [P, R] int32: the lowest alt bin
+    that stands for the reference boundary's own bin, -1 for none."""
+    ab, rb = np.asarray(alt_bins, dtype=np.int32), np.asarray(ref_bins, dtype=np.int32)
+    a_s, r_s = np.asarray(alt_strength, dtype=np.float32), np.asarray(ref_strength, dtype=np.float32)
+    ta, tr = np.asarray(alt_track, dtype=np.float32), np.asarray(ref_track, dtype=np.float32)
+    (P, K), R, n, tol = ab.shape, rb.shape[1], ta.shape[1], int(tol)
+    rows = np.arange(P)[:, None]
+    a_listed, r_listed = ab >= 0, rb >= 0
+    r_safe = np.where(r_listed, rb, 0)
+    has = np.zeros((P, n + 2 * tol), dtype=bool)                                                  # per reference bin (offset tol): a readable alt bin stands for it
+    if bin_map is None:                                                                           # the identity: every bin stands for itself
+        m, first_at = np.where(a_listed, ab, -1), np.where(r_listed, rb, -1)
+        has[:, tol: tol + n] = ~np.isnan(ta)
+    else:
+        bm = np.asarray(bin_map, dtype=np.int32)
+        m = np.where(a_listed, bm[rows, np.where(a_listed, ab, 0)], -1)                           # the reference bin every listed alt boundary stands for
+        pr, pa = np.nonzero((bm >= 0) & ~np.isnan(ta))                                            # readable: stands for a reference bin and has a track value
+        has[pr, bm[pr, pa] + tol] = True
+        first = np.full((P, n), -1, dtype=np.int32)
+        pr, pa = np.nonzero(bm >= 0)
+        first[pr[::-1], bm[pr[::-1], pa[::-1]]] = pa[::-1]                                        # written in descending order: the lowest alt bin stays
+        first_at = np.where(r_listed, first[rows, r_safe], -1)
+    a_mapped = a_listed & (m >= 0) & ~np.isnan(tr[rows, np.where(m >= 0, m, 0)])
+    near = np.zeros((P, n), dtype=bool)
+    for d in range(2 * tol + 1):
+        near |= has[:, d: d + n]
+    r_mapped = r_listed & near[rows, r_safe]
+    with np.errstate(invalid="ignore"):                                                           # what holds without a single match
+        out = {"followed_at": np.full((P, R), -1, dtype=np.int32), "strength_delta": np.where(r_mapped, -r_s, np.float32(np.nan)).astype(np.float32),
+               "is_gained": a_mapped.copy(), "first_at": first_at.astype(np.int32)}
+    has_partner = np.zeros((P, R), dtype=bool)
+    Ku, Ru = (int(np.flatnonzero(x.any(axis=0)).max(initial=-1)) + 1 for x in (a_listed, r_listed))      # the slots that some pair uses: the lists are mostly short
+    step = max(1, (1 << 21) // max(1, Ku * Ru))                                                   # pairs per pass: [step, Ru, Ku] temporaries of a few MB
+    for p0 in range(0, P if Ku and Ru else 0, step):
+        s = slice(p0, p0 + step)
+        mk, rk, sk = m[s, None, :Ku], rb[s, :Ru, None], a_s[s, :Ku]
+        match = (r_listed[s, :Ru, None] & (mk >= 0)) & (np.abs(mk - rk) <= tol)                   # [p, Ru, Ku]
+        with np.errstate(invalid="ignore"):
+            best = np.where(match, sk[:, None, :], -np.inf).argmax(axis=2)                        # the first of equals: the lists ascend, so the lower alt bin
+        hp = match.any(axis=2)
+        pk = np.arange(match.shape[0])[:, None]
+        has_partner[s, :Ru] = hp
+        out["followed_at"][s, :Ru] = np.where(hp, ab[s][pk, best], -1)
+        with np.errstate(invalid="ignore"):
+            out["strength_delta"][s, :Ru] = np.where(hp, sk[pk, best] - r_s[s, :Ru], out["strength_delta"][s, :Ru])
+        out["is_gained"][s, :Ku] = a_mapped[s, :Ku] & ~match.any(axis=1)
+    out["is_lost"], out["ref_is_unmapped"] = r_mapped & ~has_partner, r_listed & ~r_mapped
+    out["is_unmapped"] = a_listed & ~a_mapped
+    return out
+
+
+def _boundary_fields(alt, ref, alt_track, ref_track, tol, bin_map=None, delta=None):
+    """The matched boundary fields (`BOUNDARY_MATCH_FIELDS`) of P pairs of tracks, a dict of [P, ...] numpy arrays, from the calls of the alt tracks
+    ``alt`` and of the reference tracks ``ref`` (``bins``, ``strength`` [P, K]), the tracks themselves [P, n], and ``bin_map`` [P, n] (None = the
+    identity).  ``delta`` [P, n] float32 or None: the signed insulation difference by ALT bin; ``boundary_delta`` gathers it at the lowest alt bin
+    that stands for each reference boundary's own bin (NaN where there is none, or the slot is empty) and is left out without it; that bin is
+    ``first_at`` [P, R] int32 of the dict (-1 for none), for a caller that gathers on the device - not a field."""
+    got = _match_boundaries(alt["bins"], alt["strength"], ref["bins"], ref["strength"], alt_track, ref_track, tol, bin_map)
+    out = {"boundary_followed_at": got["followed_at"], "boundary_strength_delta": got["strength_delta"], "boundary_is_gained": got["is_gained"],
+           "ref_boundary_is_lost": got["is_lost"], "boundary_is_unmapped": got["is_unmapped"], "ref_boundary_is_unmapped": got["ref_is_unmapped"],
+           "boundaries_gained": got["is_gained"].sum(axis=1).astype(np.int32), "boundaries_lost": got["is_lost"].sum(axis=1).astype(np.int32),
+           "first_at": got["first_at"]}
+    if delta is not None:
+        at = got["first_at"]
+        d = np.asarray(delta, dtype=np.float32)
+        out["boundary_delta"] = np.where(at >= 0, d[np.arange(d.shape[0])[:, None], np.where(at >= 0, at, 0)], np.float32(np.nan))
+    return out
+
+
+def boundary_scores_host(tracks, ref_tracks, params, bin_map=None, delta=None, aligned_delta=None):
+    """Every boundary field of `ScreenResult` from the insulation tracks of the alt maps ``tracks`` [E, W, n] and of the reference ``ref_tracks``
+    [W, n] (host restatement of ``screen_1m(..., insulation=, boundaries=)`` on `ScreenResult.insulation` and ``ref_insulation``): a dict of
+    ``ref_boundaries``, ``ref_boundary_strength`` [W, K], ``ref_boundary_count`` [W], ``boundaries``, ``boundary_strength`` [E, W, K],
+    ``boundary_count`` [E, W] (`boundary_calls_host`) and the matched fields `BOUNDARY_MATCH_FIELDS` bin with bin (`match_boundaries_host` under the
+    identity); with ``bin_map`` ([E, n], or one [n] for all) also their ``aligned_`` forms through it.  ``boundary_delta`` /
+    ``aligned_boundary_delta`` need ``delta`` / ``aligned_delta`` [E, W, n] (`ScreenResult.delta_insulation` / ``aligned_insulation``: fp64
+    differences rounded once, which the fp32 tracks cannot give back) and are left out without them."""
+    t, r = np.asarray(tracks, dtype=np.float32), np.asarray(ref_tracks, dtype=np.float32)
+    if t.ndim != 3 or r.shape != t.shape[1:]:
+        raise ValueError("tracks: [E, W, n], ref_tracks: [W, n]")
+    E, W, n = t.shape
+    q = check_boundaries(params, n)
+    rc, ac = boundary_calls_host(r, q), boundary_calls_host(t, q)
+    out = {"ref_boundaries": rc["bins"], "ref_boundary_strength": rc["strength"], "ref_boundary_count": rc["count"], "boundaries": ac["bins"],
+           "boundary_strength": ac["strength"], "boundary_count": ac["count"]}
+    flat = lambda a: np.ascontiguousarray(a).reshape((E * W,) + a.shape[2:])
+    alt = {k: flat(ac[k]) for k in ("bins", "strength")}
+    ref = {k: flat(np.broadcast_to(rc[k], (E,) + rc[k].shape)) for k in ("bins", "strength")}
+    rt = flat(np.broadcast_to(r, (E, W, n)))
+    bms = None if bin_map is None else np.repeat(_bin_maps(bin_map, E, n), W, axis=0)
+    for pre, bm, dl in (("", None, delta), ("aligned_", bms, aligned_delta)) if bms is not None else (("", None, delta),):
+        got = _boundary_fields(alt, ref, flat(t), rt, q.tol, bm, None if dl is None else flat(np.asarray(dl, dtype=np.float32)))
+        out.update((pre + k, v.reshape((E, W) + v.shape[1:])) for k, v in got.items() if k != "first_at")
+    return out
+
+
 def merge_strands_host(plus, minus, ref_plus=None, ref_minus=None):
     """The merged maps of ``strands="both"`` (fp64 host restatement of orca_screen_merge_strands): ``plus``, ``minus`` [E, n, n] (or [n, n]) the two
     strands' maps, ``minus`` in the '-' strand's own orientation.  (merged, gap) with merged = 0.5 plus + 0.5 flip(minus), flip reversing both bin
@@ -1548,9 +1805,30 @@ class ScreenResult:
     reference dot (i, j) is followed to alt pixel (lowest a with map a = i, highest b with map b = j) - NaN when either bin does not exist or
     the pixel is ineligible - and an alt dot (a, b) stands for (map a, map b), gained if either bin is unmapped; where the bin map is the
     identity they hold the plain fields' bits.
+    With ``insulation=`` and ``boundaries=`` (None otherwise) - domain boundary calls on the insulation tracks above, per width (`BoundaryParams`;
+    include/orca_hip.h, orca_screen_boundary_calls, defines a minimum, its strength - the prominence of the dip, in mean log observed / expected -
+    and a call).  K = max_calls; a list slot beyond a track's boundaries holds -1 / NaN / False:
+      boundary_params          BoundaryParams  the validated parameters
+      ref_boundaries           [W, K] int32    the boundaries of ``ref_insulation``, ascending;  ref_boundary_strength [W, K] their strengths;
+                                               ref_boundary_count [W] int32 all of them (above K the list is truncated)
+      boundaries               [E, W, K] int32 the boundaries of ``insulation``;  boundary_strength [E, W, K];  boundary_count [E, W] int32
+      boundary_followed_at     [E, W, K] int32 per REFERENCE boundary k: the alt bin of its partner - the matching alt boundary (within tol bins) of
+                                               largest strength, the lower bin of equals - or -1
+      boundary_strength_delta  [E, W, K]       the partner's strength - the reference strength: "this boundary weakened by x"; -the reference
+                                               strength when lost; NaN when unmapped
+      boundary_delta           [E, W, K]       ``delta_insulation`` at the reference boundary's own bin (positive = less insulated there)
+      ref_boundary_is_lost     [E, W, K] bool  a mapped reference boundary without a partner;  boundaries_lost [E, W] int32 their number
+      boundary_is_gained       [E, W, K] bool  per ALT boundary: mapped, and no listed reference boundary within tol;  boundaries_gained [E, W] int32
+      boundary_is_unmapped, ref_boundary_is_unmapped [E, W, K] bool  neither lost nor gained: an alt boundary whose bin stands for no reference bin
+                                               or for one where ``ref_insulation`` is NaN; a reference boundary with no alt bin within tol whose
+                                               ``insulation`` can be read
+    and with ``aligned=True`` the ``aligned_`` forms of the nine matched fields (`BOUNDARY_MATCH_FIELDS`) through ``bin_map``: an alt boundary at
+    alt bin a stands for reference bin map a, so a boundary that a deletion merely shifted is kept, one inside the deleted span is unmapped (not
+    lost), and ``aligned_boundary_delta`` is ``aligned_insulation`` at the lowest alt bin that stands for the reference boundary's bin (NaN without
+    one); where the bin map is the identity they hold the plain fields' bits.  The default ``min_strength`` is NOT calibrated.
     `scores_host` computes the three map scores from maps on the host, `region_scores_host` the two region scores, `aligned_scores_host` and
     `aligned_region_scores_host` the aligned ones, `insulation_scores_host` and `viewpoint_scores_host` the tracks, `strata_scores_host` the
-    distance-stratified scores, `loop_scores_host` the loop fields."""
+    distance-stratified scores, `loop_scores_host` the loop fields, `boundary_scores_host` the boundary fields."""
     ref_map: torch.Tensor
     ref_1d: Optional[torch.Tensor]
     delta_profile: torch.Tensor
@@ -1612,6 +1890,31 @@ class ScreenResult:
     aligned_loops_lost: Optional[torch.Tensor] = None
     aligned_loop_is_gained: Optional[torch.Tensor] = None
     aligned_ref_loop_is_lost: Optional[torch.Tensor] = None
+    boundary_params: Optional[BoundaryParams] = None
+    ref_boundaries: Optional[torch.Tensor] = None
+    ref_boundary_strength: Optional[torch.Tensor] = None
+    ref_boundary_count: Optional[torch.Tensor] = None
+    boundaries: Optional[torch.Tensor] = None
+    boundary_strength: Optional[torch.Tensor] = None
+    boundary_count: Optional[torch.Tensor] = None
+    boundary_followed_at: Optional[torch.Tensor] = None
+    boundary_strength_delta: Optional[torch.Tensor] = None
+    boundary_delta: Optional[torch.Tensor] = None
+    boundary_is_gained: Optional[torch.Tensor] = None
+    ref_boundary_is_lost: Optional[torch.Tensor] = None
+    boundary_is_unmapped: Optional[torch.Tensor] = None
+    ref_boundary_is_unmapped: Optional[torch.Tensor] = None
+    boundaries_gained: Optional[torch.Tensor] = None
+    boundaries_lost: Optional[torch.Tensor] = None
+    aligned_boundary_followed_at: Optional[torch.Tensor] = None
+    aligned_boundary_strength_delta: Optional[torch.Tensor] = None
+    aligned_boundary_delta: Optional[torch.Tensor] = None
+    aligned_boundary_is_gained: Optional[torch.Tensor] = None
+    aligned_ref_boundary_is_lost: Optional[torch.Tensor] = None
+    aligned_boundary_is_unmapped: Optional[torch.Tensor] = None
+    aligned_ref_boundary_is_unmapped: Optional[torch.Tensor] = None
+    aligned_boundaries_gained: Optional[torch.Tensor] = None
+    aligned_boundaries_lost: Optional[torch.Tensor] = None
 
 
 # ---- the screen -----------------------------------------------------------------------------------------------------------------------------
@@ -1779,7 +2082,7 @@ class _Screen:
 
 
 def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regions=None, flank=None, aligned=False, flank_bp=None, strands="+",
-              insulation=None, viewpoints=None, strata=None, loops=None):
+              insulation=None, viewpoints=None, strata=None, loops=None, boundaries=None):
     """Score ``edits`` (a list of `Edit` and `EditSet`, one row of every result tensor each) of one window with the 1 Mb model: a `ScreenResult`.
 
     ``model``: an ``H1esc_1M`` / ``Hff_1M`` container or a bare ``orca_modules.Net``.  ``window``: the window's base codes, a [L] uint8 tensor on
@@ -1846,18 +2149,32 @@ def screen_1m(model, window, edits, batch=64, keep_maps=False, stats=None, regio
     published checkpoints.  Taken from the batch's final maps whichever route made them, with ``strands="both"`` from the merged maps; the
     reference's dots are called once from the final ``ref_map``; the lists are matched on the host after the last batch.  With None (or False)
     nothing more is launched and every other field is what it was.  ``stats`` gains ``loops`` (K, 0 when absent) and ``loop_truncated_items``
-    (items with more than K dots)."""
-    return _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, aligned, flank_bp, strands, insulation, viewpoints, strata=strata, loops=loops)
+    (items with more than K dots).
+
+    ``boundaries`` (with ``insulation``; without it a ValueError): True (the defaults) or a `BoundaryParams` (`check_boundaries`), for domain
+    boundary calls on the insulation tracks the screen already computes (orca_screen_boundary_calls: one launch over the reference's tracks, one per
+    batch over its items' tracks, every width at once): `ScreenResult.ref_boundaries`, ``ref_boundary_strength``, ``ref_boundary_count``,
+    ``boundaries``, ``boundary_strength``, ``boundary_count``, and which reference boundaries an item keeps, weakens or loses and which it creates -
+    ``boundary_followed_at``, ``boundary_strength_delta``, ``boundary_delta``, ``ref_boundary_is_lost`` / ``boundaries_lost``, ``boundary_is_gained`` /
+    ``boundaries_gained`` and the two ``*_is_unmapped`` masks; with ``aligned=True`` also their ``aligned_`` forms through `bin_map`.  A boundary's
+    strength is the prominence of the dip in mean log observed / expected; the default ``min_strength`` is NOT calibrated on the published
+    checkpoints - choose it from ``ref_boundary_strength``.  With ``strands="both"`` the tracks are the merged maps'.  The lists are matched on the
+    host after the last batch.  With None (or False) nothing more is launched and every other field is what it was.  ``stats`` gains ``boundaries``
+    (K, 0 when absent)."""
+    return _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, aligned, flank_bp, strands, insulation, viewpoints, strata=strata, loops=loops,
+                       boundaries=boundaries)
 
 
 def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, aligned, flank_bp, strands, insulation, viewpoints, hook=None, strata=None,
-                loops=None):
+                loops=None, boundaries=None):
     """The body of `screen_1m` (its arguments, its result).  ``hook``: called as ``hook(res, i0, i1, maps)`` at the end of every batch, on every
     route, with the `ScreenResult` under construction (``res.ref_map`` is final) and the FINAL maps [i1 - i0, n, n] of items [i0, i1) - after the
     strand merge and after any range fallback; the buffer is the batch's own, so the hook reads it before it returns.  Without a hook nothing
     is launched that `screen_1m` did not launch."""
     if strands not in ("+", "both"):
         raise ValueError(f"strands must be '+' or 'both', got {strands!r}")
+    if boundaries is not None and boundaries is not False and insulation is None:
+        raise ValueError("boundaries: called on the insulation tracks (insulation=widths)")
     both = strands == "both"
     net = _net_of(model)
     if flank_bp is not None:
@@ -1880,12 +2197,14 @@ def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, a
     views = None if viewpoints is None else check_viewpoints(viewpoints, win.numel() // 4000)
     drange = None if strata is None or strata is False else check_strata(strata, win.numel() // 4000)
     lp = None if loops is None or loops is False else check_loops(loops, win.numel() // 4000)
+    bp = None if boundaries is None or boundaries is False else check_boundaries(boundaries, win.numel() // 4000)
     st = {"route": None, "two_part_batches": 0, "whole_window_batches": 0, "range_fallback_batches": 0, "range_fallback_reference": False,
           "front_runs": 0, "front_bases": 0, "edits": len(edits), "set_items": sum(isinstance(e, EditSet) for e in edits), "segments": 0,
           "indel_items": sum(changes_length(e) for e in edits), "take_rows": 0, "cache_phases": 0, "aligned_items": 0,
           "strands": strands, "reverse_two_part_items": 0, "reverse_whole_items": 0,
           "insulation_widths": 0 if widths is None else len(widths), "viewpoints": 0 if views is None else len(views),
-          "strata": 0 if drange is None else drange[1] - drange[0], "loops": 0 if lp is None else lp.max_calls, "loop_truncated_items": 0}
+          "strata": 0 if drange is None else drange[1] - drange[0], "loops": 0 if lp is None else lp.max_calls, "loop_truncated_items": 0,
+          "boundaries": 0 if bp is None else bp.max_calls}
     fl = _flank_codes(window, flank, win, flank_bp) if (flank is not None or st["indel_items"]) else None
     sc = _Screen(net, win, st, fl if st["indel_items"] else None)
     E, n, dev = len(edits), sc.n, sc.dev
@@ -1963,6 +2282,13 @@ def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, a
             res.delta_insulation = torch.zeros((E, len(widths), n), dtype=torch.float32, device=dev)
             if aligned:
                 res.aligned_insulation = torch.zeros((E, len(widths), n), dtype=torch.float32, device=dev)
+            if bp is not None:                           # the reference's boundaries once, from its own tracks
+                got = engine.screen_boundary_calls(sc.ctx, res.ref_insulation[None], bp.min_strength, bp.max_calls, strength_track=False)
+                res.boundary_params = bp
+                res.ref_boundaries, res.ref_boundary_strength, res.ref_boundary_count = got["bins"][0], got["strength"][0], got["count"][0]
+                res.boundaries = torch.full((E, len(widths), bp.max_calls), -1, dtype=torch.int32, device=dev)
+                res.boundary_strength = torch.full((E, len(widths), bp.max_calls), float("nan"), dtype=torch.float32, device=dev)
+                res.boundary_count = torch.zeros((E, len(widths)), dtype=torch.int32, device=dev)
         if views is not None:
             res.viewpoint_bins = sc._upload(views, torch.int32)
             res.delta_viewpoint = torch.zeros((E, len(views), n), dtype=torch.float32, device=dev)
@@ -2041,6 +2367,9 @@ def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, a
                 res.insulation[i0:i1], res.delta_insulation[i0:i1] = tr, dl
                 if aligned:
                     res.aligned_insulation[i0:i1] = al
+                if bp is not None:
+                    got = engine.screen_boundary_calls(sc.ctx, tr, bp.min_strength, bp.max_calls, strength_track=False)
+                    res.boundaries[i0:i1], res.boundary_strength[i0:i1], res.boundary_count[i0:i1] = got["bins"], got["strength"], got["count"]
             if views is not None:
                 dl, al = engine.screen_viewpoints(sc.ctx, maps, ref_map, views, bmaps[i0:i1] if aligned else None, res.bin_map[i0:i1] if aligned else None)
                 res.delta_viewpoint[i0:i1] = dl
@@ -2081,9 +2410,41 @@ def _run_screen(model, window, edits, batch, keep_maps, stats, regions, flank, a
                 setattr(res, pre + "ref_loop_is_lost", sc._upload(lost, torch.bool))
                 setattr(res, pre + "loops_gained", sc._upload(gained.sum(axis=1), torch.int32))
                 setattr(res, pre + "loops_lost", sc._upload(lost.sum(axis=1), torch.int32))
+        if bp is not None:                               # the lists and the tracks' NaN pattern on the host, the matching in numpy
+            _screen_boundaries(res, sc, bp, bmaps if aligned else None)
     if stats is not None:
         stats.update(st)
     return res
+
+
+def _screen_boundaries(res, sc, bp, bmaps):
+    """The matched boundary fields of a finished `ScreenResult` (`BOUNDARY_MATCH_FIELDS`, and their ``aligned_`` forms with the items' bin maps
+    ``bmaps`` [E, n]): `_boundary_fields` on the lists and tracks copied to the host once; ``boundary_delta`` is gathered on the device."""
+    E, W, n = res.insulation.shape
+    K = bp.max_calls
+    host = lambda t: t.cpu().numpy().reshape((E * W,) + tuple(t.shape[2:]))
+    alt = {"bins": host(res.boundaries), "strength": host(res.boundary_strength)}
+    ref = {k: np.ascontiguousarray(np.broadcast_to(v.cpu().numpy(), (E, W, K))).reshape(E * W, K)
+           for k, v in (("bins", res.ref_boundaries), ("strength", res.ref_boundary_strength))}
+    ta, tr = host(res.insulation), np.ascontiguousarray(np.broadcast_to(res.ref_insulation.cpu().numpy(), (E, W, n))).reshape(E * W, n)
+    nan = torch.full((), float("nan"), dtype=torch.float32, device=sc.dev)
+    got = None
+    for pre in ("", "aligned_") if bmaps is not None else ("",):
+        if not pre:
+            got = _boundary_fields(alt, ref, ta, tr, bp.tol)
+        else:                                            # an identity bin map changes nothing: only the other items are matched again
+            moved = np.flatnonzero(np.repeat((bmaps != np.arange(n, dtype=np.int32)[None]).any(axis=1), W))
+            got = {k: v.copy() for k, v in got.items()}
+            if moved.size:
+                sub = lambda d: {k: v[moved] for k, v in d.items()}
+                for k, v in _boundary_fields(sub(alt), sub(ref), ta[moved], tr[moved], bp.tol, np.repeat(bmaps, W, axis=0)[moved]).items():
+                    got[k][moved] = v
+        for k, v in got.items():
+            if k != "first_at":
+                setattr(res, pre + k, sc._upload(v.reshape((E, W) + v.shape[1:]), {"b": torch.bool, "i": torch.int32, "f": torch.float32}[v.dtype.kind]))
+        at_dev = sc._upload(got["first_at"].reshape(E, W, K), torch.int64)
+        src = res.aligned_insulation if pre else res.delta_insulation
+        setattr(res, pre + "boundary_delta", torch.where(at_dev >= 0, torch.gather(src, 2, at_dev.clamp(min=0)), nan))
 
 
 def epistasis_1m(model, window, sets, batch=64, regions=None, strands="+", keep_maps=False, stats=None, bank_bytes=4 << 30):

@@ -17,7 +17,8 @@ import torch
 from . import engine
 # what compares a pair of finished maps through a bin map lives in sv_readouts.py; its public names stay reachable as sv.NAME
 from .sv_readouts import (LEVELS, LEVEL_BINS, SCORE_FIELDS, LOOP_SCORE_FIELDS, COMPARTMENT_SCORE_FIELDS, COMPARTMENT_MAX_EIGS, CompartmentParams,
-                          check_tracks, check_loops_arg, check_compartments_arg, check_readouts, entry_readouts, _model_scores,
+                          BOUNDARY_SCORE_FIELDS, check_tracks, check_loops_arg, check_compartments_arg, check_boundaries_arg, check_readouts, entry_readouts,
+                          _model_scores, paired_boundary_scores_host,
                           paired_aligned_scores_host, paired_insulation_host, paired_viewpoints_host, paired_strata_host, paired_dot_follow_host,
                           paired_match_loops_host, paired_loop_scores_host, compartment_matrix_host, eigenvectors_host, gc_tracks_host,
                           paired_compartment_scores_host)
@@ -216,17 +217,18 @@ def _dict_maps(out, m, device):
     return torch.from_numpy(np.ascontiguousarray(maps)).to(device)
 
 
-def sv_scores(sv, ref_out, alt_out, chrlen, device=None, insulation=None, viewpoints=None, strata=None, loops=None, compartments=None, phase=None):
+def sv_scores(sv, ref_out, alt_out, chrlen, device=None, insulation=None, viewpoints=None, strata=None, loops=None, compartments=None, phase=None,
+              boundaries=None):
     """The ``scores`` of `sv_screen(..., scores=True)` from ANY pair of `genomepredict` output dicts of a variant's reference and alternative
     allele (the `process_*` drivers', `sv_screen(..., incremental=False)`'s): the maps are uploaded to ``device`` (default: the current MI355X)
     and scored by the same kernel through `level_bin_maps` - the same dict.  ``insulation``, ``viewpoints``, ``strata``, ``loops``,
-    ``compartments``: the readouts of `sv_screen`, the same keys (sv_readouts.py describes them).
+    ``compartments``, ``boundaries``: the readouts of `sv_screen`, the same keys (sv_readouts.py describes them).
     ``phase`` (with ``compartments``): (ref_phase, alt_phase), each [6, 250] - a GC or gene-density track per level and bin of the reference and of
     the alt window, which orients the compartment vectors (positive correlation) and is returned as ``ref_gc`` / ``gc``.  WITHOUT ``phase`` the output
     dicts say nothing about the sequence, and the orientation is ARBITRARY: every reference vector has its largest component positive, and every alt
     vector is flipped so that its dot product with the reference vector through the bin map is not negative - ``compartment_delta``, ``_corr`` and
     ``_flips`` are meaningful, the sign of a vector is not (A and B are not told apart), and there are no ``ref_gc`` / ``gc`` keys."""
-    readouts = check_readouts(insulation, viewpoints, strata, loops, compartments)
+    readouts = check_readouts(insulation, viewpoints, strata, loops, compartments, boundaries)
     if phase is not None and (readouts is None or readouts.compartments is None):
         raise ValueError("sv_scores: phase orients the compartments (compartments=)")
     if phase is not None and (not isinstance(phase, (tuple, list)) or len(phase) != 2):
@@ -943,7 +945,7 @@ def _window_outputs(model, merged, starts, params, mchr, keep_maps=True):
 
 def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, incremental=True, min_uses=3, stats=None, on_result=None,
               streams=None, group=2, stage3="auto", scores=False, keep_maps=True, insulation=None, viewpoints=None, strata=None, loops=None,
-              compartments=None):
+              compartments=None, boundaries=None):
     """Predict reference and alternative allele (6 maps each, per model) for this rank's share of ``svs``
     (independent windows: replicas, no collective).  genome_codes: [chrlen] uint8 tensor on the MI355X.
     Returns {sv_index: {"sv": SV, "ref": output_dict, "alt": output_dict}} with genomepredict's output dicts.
@@ -973,7 +975,7 @@ def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, i
     ``bin_map``, ``count``, ``junction_bins`` and per model ``abs_mean``, ``abs_max``, ``delta_mean``, ``rms``, ``corr``, ``profile``.  The docstring of
     sv_readouts.py describes these and every field that the readouts below add.  With ``incremental=False`` the scores come from the returned
     host maps (`sv_scores`).
-    The five readouts each need ``scores=True`` (else ValueError), read the same final maps through the same bin maps, and launch nothing when unset:
+    The six readouts each need ``scores=True`` (else ValueError), read the same final maps through the same bin maps, and launch nothing when unset:
     ``insulation``: diamond widths in bins, e.g. (5, 10, 25), the same at every level (`screen.check_insulation` on 250 bins).
     ``viewpoints``: 1 to 64 base positions on the ORIGINAL chromosome (`viewpoint_bins`).
     ``strata``: True or (d_lo, d_hi) (`screen.check_strata` on 250 bins).
@@ -981,16 +983,19 @@ def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, i
       NOT calibrated on the published checkpoints).
     ``compartments``: True or a `CompartmentParams` (`check_compartments_arg`, one parameter set for all six levels); the vectors are oriented by
       the GC content of the windows' own bins.  Only the coarse levels (128 kb and 64 kb bins) have a compartment meaning.
+    ``boundaries`` (with ``insulation``, else ValueError): True or a `screen.BoundaryParams` (`check_boundaries_arg`, one parameter set for all six
+      levels and every width) - domain boundary calls on every level's reference and alt insulation track, matched through the level's bin map:
+      which boundaries the allele keeps, weakens, loses or creates.  The default ``min_strength`` is NOT calibrated on the published checkpoints.
     ``keep_maps=False`` (needs ``scores=True``): the maps are not copied to the host - the output dicts keep ``start_coords``, ``end_coords``,
     ``chr`` and ``normmats`` and have "predictions": None.  A screen then returns a few KB per variant instead of 3 MB."""
     import time
     from . import dist, orca_predict
     if not keep_maps and not scores:
         raise ValueError("sv_screen: keep_maps=False returns nothing without scores=True")
-    readouts = check_readouts(insulation, viewpoints, strata, loops, compartments)
+    readouts = check_readouts(insulation, viewpoints, strata, loops, compartments, boundaries)
     phased = readouts is not None and readouts.compartments is not None       # the compartment vectors are oriented by the windows' GC
     if readouts is not None and not scores:
-        raise ValueError("sv_screen: insulation, viewpoints, strata, loops and compartments are part of the scores (scores=True)")
+        raise ValueError("sv_screen: insulation, viewpoints, strata, loops, compartments and boundaries are part of the scores (scores=True)")
     res = {}
     mine = list(dist.shard_indices(len(svs), rank, world))
     if not incremental:
@@ -1007,7 +1012,7 @@ def sv_screen(models, genome_codes, svs, chrlen, mchr="chrS", rank=0, world=1, i
                     gctx = engine.get_context(genome_codes.device)
                     phase = (_window_gc(gctx, rcodes, ref["start_coords"], rw), _window_gc(gctx, acodes, alt["start_coords"], aw))
                 entry["scores"] = sv_scores(sv, ref, alt, chrlen, genome_codes.device, insulation=insulation, viewpoints=viewpoints, strata=strata,
-                                            loops=loops, compartments=compartments, phase=phase)
+                                            loops=loops, compartments=compartments, phase=phase, boundaries=boundaries)
                 if not keep_maps:
                     ref["predictions"] = alt["predictions"] = None
             if on_result is not None:

@@ -40,6 +40,23 @@ bits above.
   ``loop_is_gained``, ``ref_loop_is_lost`` bool [6, C, K] (a listed alt dot whose reference pixel (min(map a, map c), max(map a, map c)) has no listed
   reference dot within ``tol`` - one with an unmapped bin is gained; a listed reference dot that no listed alt dot matches) and their sums
   ``loops_gained``, ``loops_lost`` int32 [6, C].  Unset, nothing is launched.
+``boundaries=True`` or a `screen.BoundaryParams` (with ``insulation=``, else a ValueError; `check_boundaries_arg`, one parameter set for all six levels
+  and every width; the default ``min_strength`` is NOT calibrated on the published checkpoints - choose it from ``ref_boundary_strength``): domain
+  boundary calls per level, target and width on the variant's own reference track and on its alt track (orca_screen_boundary_calls on the tracks the
+  insulation readout holds on the device - two launches, the maps are not needed again; include/orca_hip.h defines a minimum, its strength - the
+  prominence of the dip, in mean log observed / expected, nothing bridged across a NaN - and a call), matched through the level's bin map on the host
+  (`paired_boundary_scores_host` restates all of it in numpy).  Adds ``boundary_params`` and per model, with K = max_calls: ``ref_boundaries``,
+  ``boundaries`` int32 [6, C, W, K] (ascending bins, -1 behind them), ``ref_boundary_strength``, ``boundary_strength`` float32 [6, C, W, K],
+  ``ref_boundary_count``, ``boundary_count`` int32 [6, C, W] (ALL boundaries); per REFERENCE boundary ``boundary_followed_at`` int32 (the alt bin of
+  its partner: the listed alt boundary a with |map a - r| <= tol of largest strength, the lower bin of equals; -1 without), ``boundary_strength_delta``
+  float32 (the partner's strength - the reference's; -the reference's when lost; NaN when unmapped), ``boundary_delta`` float32 (``insulation_delta``
+  at the lowest alt bin that stands for the boundary's own bin; NaN without one), ``ref_boundary_is_lost`` (some alt bin with a track value stands
+  within tol of it, but no listed alt boundary does) and ``ref_boundary_is_unmapped`` (no such alt bin: deleted, or outside the alt window - not
+  lost); per ALT boundary ``boundary_is_gained`` (its bin stands for a reference bin where the reference track is not NaN, and no listed reference
+  boundary is within tol) and ``boundary_is_unmapped`` (its bin stands for no such reference bin - inserted sequence or refill: not gained) - all
+  [6, C, W, K] - and the sums ``boundaries_gained``, ``boundaries_lost`` int32 [6, C, W].  Under a tandem duplication both copies of a boundary match
+  the reference boundary and the stronger is its partner; inside an inversion the bin map descends and |map a - r| needs no special case.  Unset,
+  nothing is launched.
 ``compartments=True`` or a `CompartmentParams` (`check_compartments_arg`, one parameter set for all six levels): the compartment signal per level and
   target - the K = n_eigs leading eigenvectors of the variant's own reference map and of its alt map (orca_screen_eigenvectors: one launch per
   (variant, model) over the 12 C maps; include/orca_hip.h has the definition, `eigenvectors_host` restates it through numpy's eigh), scaled by
@@ -518,6 +535,63 @@ def paired_compartment_scores_host(alt_E, ref_E, bin_map):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Boundaries per level.  Domain boundary calls on the insulation tracks of every level's reference and alt map (orca_screen_boundary_calls on
+# the tracks the insulation readout already holds on the device; `screen.BoundaryParams`; include/orca_hip.h and DESIGN 3d / 3e have the
+# definitions), matched through the level's bin map on the host: which reference boundaries the allele keeps, weakens or loses, which it creates.
+# ---------------------------------------------------------------------------------------------------------------------------------
+BOUNDARY_SCORE_FIELDS = ("ref_boundaries", "boundaries", "ref_boundary_strength", "boundary_strength", "ref_boundary_count", "boundary_count",
+                         "boundary_followed_at", "boundary_strength_delta", "boundary_delta", "boundary_is_gained", "ref_boundary_is_lost",
+                         "boundary_is_unmapped", "ref_boundary_is_unmapped", "boundaries_gained", "boundaries_lost")
+
+
+def check_boundaries_arg(boundaries, insulation=None):
+    """The ``boundaries`` argument of `sv_screen` / `sv_scores`, checked: None when unset (None or False), else the validated
+    `screen.BoundaryParams` (`screen.check_boundaries` on the levels' 250 bins; True = the defaults).  ``insulation``: the checked widths - the
+    boundaries are called on the insulation tracks, so without them it is a ValueError.  One parameter set serves all six levels and every width."""
+    from . import screen
+    if boundaries is None or boundaries is False:
+        return None
+    if insulation is None:
+        raise ValueError("boundaries: called on the insulation tracks (insulation=widths)")
+    return screen.check_boundaries(boundaries, LEVEL_BINS)
+
+
+def _paired_boundary_fields(rc, ac, track, ref_track, delta, bin_map, tol):
+    """The boundary fields (`BOUNDARY_SCORE_FIELDS`, numpy [B, W, ...]) of B pairs from the calls of the reference tracks ``rc`` and of the alt
+    tracks ``ac`` (``count`` [B, W], ``bins``, ``strength`` [B, W, K]), the tracks [B, W, n], ``insulation_delta`` ``delta`` [B, W, n] and
+    ``bin_map`` [B, n] (one row per pair, every width): the matching on the host (`screen._boundary_fields`)."""
+    from . import screen
+    B, W, n = track.shape
+    flat = lambda a: np.ascontiguousarray(a).reshape((B * W,) + a.shape[2:])
+    got = screen._boundary_fields({k: flat(ac[k]) for k in ("bins", "strength")}, {k: flat(rc[k]) for k in ("bins", "strength")}, flat(track), flat(ref_track),
+                                  tol, np.repeat(np.asarray(bin_map), W, axis=0), flat(delta))
+    out = {"ref_boundaries": rc["bins"], "boundaries": ac["bins"], "ref_boundary_strength": rc["strength"], "boundary_strength": ac["strength"],
+           "ref_boundary_count": rc["count"], "boundary_count": ac["count"]}
+    out.update((k, v.reshape((B, W) + v.shape[1:])) for k, v in got.items() if k != "first_at")
+    return out
+
+
+def paired_boundary_scores_host(track, ref_track, insulation_delta, bin_map, params):
+    """Numpy restatement of the boundary fields of ``sv_screen(..., scores=True, insulation=, boundaries=)`` for B pairs of tracks: ``track``,
+    ``ref_track``, ``insulation_delta`` [B, W, n] (an entry's ``insulation``, ``ref_insulation``, ``insulation_delta`` with [6, C] flattened to B),
+    pair b through ``bin_map`` [B, n] (or one [n] for all), ``params`` a `screen.BoundaryParams` (or True).  `screen.boundary_calls_host` on both
+    tracks, `screen.match_boundaries_host`'s rule per (pair, width): a dict of `BOUNDARY_SCORE_FIELDS`, with K = max_calls: ``ref_boundaries``,
+    ``boundaries`` int32 [B, W, K] (ascending, -1 behind them); ``ref_boundary_strength``, ``boundary_strength`` float32 [B, W, K];
+    ``ref_boundary_count``, ``boundary_count`` int32 [B, W] (all); per reference boundary ``boundary_followed_at`` int32 (the partner's alt bin or
+    -1), ``boundary_strength_delta`` float32 (partner - reference; -reference when lost; NaN when unmapped), ``boundary_delta`` float32
+    (``insulation_delta`` at the lowest alt bin that stands for the boundary's own bin, NaN without one), ``ref_boundary_is_lost``,
+    ``ref_boundary_is_unmapped`` bool; per alt boundary ``boundary_is_gained``, ``boundary_is_unmapped`` bool - all [B, W, K]; ``boundaries_gained``,
+    ``boundaries_lost`` int32 [B, W]."""
+    from . import screen
+    t, r, d = (np.asarray(x, dtype=np.float32) for x in (track, ref_track, insulation_delta))
+    if t.ndim != 3 or r.shape != t.shape or d.shape != t.shape:
+        raise ValueError("track, ref_track, insulation_delta: [B, W, n]")
+    B, n = t.shape[0], t.shape[2]
+    q = screen.check_boundaries(params, n)
+    return _paired_boundary_fields(screen.boundary_calls_host(r, q), screen.boundary_calls_host(t, q), t, r, d, _ref_bins_host(bin_map, B, n), q.tol)
+
+
 # The arguments, checked once, and what they add to an entry before any model is scored.
 def check_tracks(insulation=None, viewpoints=None, strata=None):
     """The three readout arguments of `sv_screen` / `sv_scores`, checked: None when all are unset, else {"insulation": int32 widths or None,
@@ -542,14 +616,15 @@ def check_tracks(insulation=None, viewpoints=None, strata=None):
     return spec
 
 
-Readouts = namedtuple("Readouts", "insulation viewpoints strata loops compartments")
+Readouts = namedtuple("Readouts", "insulation viewpoints strata loops compartments boundaries", defaults=(None,))
 
 
-def check_readouts(insulation=None, viewpoints=None, strata=None, loops=None, compartments=None):
-    """The five readout arguments of `sv_screen` / `sv_scores`, checked (`check_tracks`, `check_loops_arg`, `check_compartments_arg`, in that order): None
-    when all are unset, else a `Readouts` of the five checked values, each None where unset."""
+def check_readouts(insulation=None, viewpoints=None, strata=None, loops=None, compartments=None, boundaries=None):
+    """The six readout arguments of `sv_screen` / `sv_scores`, checked (`check_tracks`, `check_loops_arg`, `check_compartments_arg`,
+    `check_boundaries_arg`, in that order): None when all are unset, else a `Readouts` of the six checked values, each None where unset."""
     tracks = check_tracks(insulation, viewpoints, strata) or {}
-    rd = Readouts(tracks.get("insulation"), tracks.get("viewpoints"), tracks.get("strata"), check_loops_arg(loops), check_compartments_arg(compartments))
+    rd = Readouts(tracks.get("insulation"), tracks.get("viewpoints"), tracks.get("strata"), check_loops_arg(loops), check_compartments_arg(compartments),
+                  check_boundaries_arg(boundaries, tracks.get("insulation")))
     return None if all(v is None for v in rd) else rd
 
 
@@ -576,6 +651,8 @@ def entry_readouts(entry, rd, view_bins=None, phase=None):
                 raise ValueError(f"phase: (ref_phase, alt_phase), each [{LEVELS}, {LEVEL_BINS}]")
     if rd.insulation is not None:
         entry["insulation_widths"] = rd.insulation.copy()
+    if rd.boundaries is not None:
+        entry["boundary_params"] = rd.boundaries
     if rd.viewpoints is not None:
         vb = entry["viewpoint_bins"] = view_bins
         entry["viewpoint_count"] = np.where(vb >= 0, (bm[:, None, :] == vb[:, :, None]).sum(axis=2), 0).astype(np.int32)
@@ -663,6 +740,11 @@ def _model_scores(ctx, ref_maps, alt_maps, bin_map, entry=None):
     if "insulation_widths" in entry:
         tracks = engine.screen_paired_insulation(ctx, alt, ref, entry["insulation_widths"], bmc)
         out.update((k, t.cpu().numpy()) for k, t in zip(("insulation", "ref_insulation", "insulation_delta"), tracks))
+        if "boundary_params" in entry:                   # two launches over the tracks that are on the device; the maps are not needed again
+            q = entry["boundary_params"]
+            ac, rc = (_to_host({k: v for k, v in engine.screen_boundary_calls(ctx, t, q.min_strength, q.max_calls, strength_track=False).items() if v is not None})
+                      for t in tracks[:2])
+            out.update(_paired_boundary_fields(rc, ac, out["insulation"], out["ref_insulation"], out["insulation_delta"], bmc, q.tol))
     if "viewpoint_bins" in entry:
         aligned, _ = engine.screen_paired_viewpoints(ctx, alt, ref, np.repeat(entry["viewpoint_bins"], C, axis=0), bmc)
         out["viewpoint_delta"] = aligned.cpu().numpy()

@@ -1,0 +1,47 @@
+"""Build-time property of the kernel behind the boundary calls (orca_amd/csrc/screen.h: screen_boundary_calls_kernel), checked by cross-compiling
+for gfx950 (no GPU needed): it uses no scratch memory.  The track lives in LDS and every thread keeps its two running maxima in registers, in plain
+C++; a spill would mean they went to memory."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KERNELS = ("screen_boundary_calls_kernel",)
+UNIT = """#include <hip/hip_runtime.h>
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "screen.h"
+const void* screen_kernels[] = {%s};
+"""
+
+
+def test_boundary_calls_kernel_does_not_spill(tmp_path):
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    src = os.path.join(ROOT, "orca_amd", "csrc")
+    unit = tmp_path / "screen_boundary_unit.hip"
+    unit.write_text(UNIT % ", ".join("(const void*)" + k for k in KERNELS))
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + src, "-I" + os.path.join(ROOT, "include"), "-Wno-unused-function", "-c",
+                        str(unit), "-o", str(tmp_path / "screen_boundary_unit.o"), "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    name, scratch, lds = None, {}, {}
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            continue
+        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
+        if m and name:
+            scratch[name] = int(m.group(1))
+        m = re.search(r"LDS Size \[bytes/block\]: (\d+)", line)
+        if m and name:
+            lds[name] = int(m.group(1))
+    for k in KERNELS:
+        hit = [n for n in scratch if k in n]
+        assert len(hit) == 1, (k, sorted(scratch))          # the remark format changed, or the kernel was not emitted?
+        assert scratch[hit[0]] == 0, (hit[0], scratch[hit[0]])
+        assert lds.get(hit[0]) == 256 * 4 + 4 * 4, (hit[0], lds)      # the track and the four waves' counts, nothing else

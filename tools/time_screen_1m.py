@@ -39,6 +39,11 @@ Loops, into profiles/screen_1m_loops.json:
   --loops        the 3 250-edit workload at B = 64 through screen_1m with loops=True, with the lists filled (threshold 0.0) and without, and both again with aligned=True, alternated in
                  the same run, best of three: what the dot-call kernels and the host matching add, set beside what aligned=True adds
 
+Boundaries, into profiles/screen_1m_boundaries.json:
+  --boundaries   the 3 250-edit workload at B = 64 through screen_1m with insulation=(5, 10, 25), with the same plus boundaries=True and plus
+                 boundaries=BoundaryParams(min_strength=0.0) (every list as full as it gets), alternated in the same run, best of three: what
+                 orca_screen_boundary_calls and the host matching add to the insulation tracks, beside the spread of that baseline's repetitions
+
 Non-additivity, into profiles/screen_1m_epistasis.json:
   --epistasis NA NB  the NA x NB pairs of 4 kb mask tiles (NA from base 100 000, NB from base 600 000) at B = 64 through screen.epistasis_1m, and
                  through today's route - screen_1m on the singles and on the pairs with keep_maps=True, then the residual in torch, in fp32 -
@@ -274,6 +279,39 @@ def time_loops(a, model, win, edits, dev):
     return rep
 
 
+def time_boundaries(a, model, win, edits, dev):
+    """The --boundaries workload: screen_1m on the same edits with insulation=(5, 10, 25) alone, with boundaries=True on top and with
+    boundaries=BoundaryParams(min_strength=0.0), which lists every minimum with a positive strength, alternated, at B = 64, best of max(--reps, 3).
+    The added time is against the insulation-only repetition beside it and against the best of three, with the spread of the baseline's repetitions;
+    ``ref_boundary_count_*`` and the largest ``boundary_count`` of the first batch say how many boundaries there were (the weights are synthetic and
+    the default min_strength is not calibrated)."""
+    B, reps = 64, max(a.reps, 3)
+    ins = {"insulation": (5, 10, 25)}
+    rep = {"device": torch.cuda.get_device_name(dev), "edits": len(edits), "batch": B, "reps": reps, "insulation": list(ins["insulation"]), "weights": "synthetic"}
+    runs = {"insulation": ins, "boundaries": dict(ins, boundaries=True), "boundaries_filled": dict(ins, boundaries=S.BoundaryParams(min_strength=0.0))}
+    st = {}
+    for k, kw in runs.items():                                                                   # warm-up
+        res = S.screen_1m(model, win, edits[:B], batch=B, stats=st, **kw)
+        if k != "insulation":
+            rep[f"ref_boundary_count_{k}"], rep[f"max_boundary_count_first_batch_{k}"] = res.ref_boundary_count.tolist(), int(res.boundary_count.max())
+    rep["route"] = st["route"]
+    t = {k: [] for k in runs}
+    for _ in range(reps):
+        for k, kw in runs.items():
+            t[k].append(timed(lambda: S.screen_1m(model, win, edits, batch=B, **kw))[0])
+    for k in runs:
+        rep[f"{k}_s"] = [round(x, 3) for x in t[k]]
+        rep[f"{k}_edits_per_s"] = round(len(edits) / min(t[k]), 1)
+    base = min(t["insulation"])
+    rep["insulation_spread_ms"] = round((max(t["insulation"]) - base) * 1e3, 1)
+    for k in ("boundaries", "boundaries_filled"):
+        rep[f"{k}_added_ms_per_repetition"] = [round((y - x) * 1e3, 1) for x, y in zip(t["insulation"], t[k])]
+        rep[f"{k}_added_ms_best_of_three"] = round((min(t[k]) - base) * 1e3, 1)
+        rep[f"{k}_over_insulation"] = round(min(t[k]) / base, 4)
+        rep[f"{k}_within_insulation_spread"] = bool(min(t[k]) <= max(t["insulation"]))
+    return rep
+
+
 def naive_both(model, win, edits, batch, keep_maps=False):
     """`naive` on both strands: every batch's edited windows through Net's Encoder and Decoder_1m forwards and reverse-complemented, merged."""
     sc = S._Screen(model.net, win, {})
@@ -378,6 +416,8 @@ def main():
     ap.add_argument("--tracks", action="store_true", help="time the 3 250-edit workload at B = 64 with insulation and viewpoint tracks against without")
     ap.add_argument("--strata", action="store_true", help="time the 3 250-edit workload at B = 64 with strata=True against without, plain and with aligned=True")
     ap.add_argument("--loops", action="store_true", help="time the 3 250-edit workload at B = 64 with loops=True against without, plain and with aligned=True")
+    ap.add_argument("--boundaries", action="store_true", help="time the 3 250-edit workload at B = 64 with insulation=(5, 10, 25) and boundaries=True against "
+                    "the insulation tracks alone")
     ap.add_argument("--strands", default="+", choices=("+", "both"), help="both: time the 3 250-edit workload on both strands at B = 64")
     ap.add_argument("--epistasis", type=int, nargs=2, metavar=("NA", "NB"), help="time the NA x NB mask-tile pairs through epistasis_1m against two screen_1m "
                     "calls with keep_maps=True plus fp32 arithmetic in torch")
@@ -429,6 +469,18 @@ def main():
         rep.update(time_strata(a, model, win, edits, dev))
         print(json.dumps(rep))
         out = a.out if a.out != ap.get_default("out") else os.path.join(os.path.dirname(a.out), "screen_1m_strata.json")
+        if out:
+            os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+            with open(out, "w") as f:
+                json.dump(rep, f, indent=1)
+        return
+    if a.boundaries:
+        rep = {"workload": f"H1esc_1M synthetic, 1 Mb window, {len(edits)} edits (saturation SNVs of 1 kb + 250 4 kb mask tiles); screen_1m with "
+                           "insulation=(5, 10, 25) against the same plus boundaries=True and plus boundaries=BoundaryParams(min_strength=0.0) (full lists), "
+                           "alternated (every call includes its reference)", "commit": a.commit}
+        rep.update(time_boundaries(a, model, win, edits, dev))
+        print(json.dumps(rep))
+        out = a.out if a.out != ap.get_default("out") else os.path.join(os.path.dirname(a.out), "screen_1m_boundaries.json")
         if out:
             os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
             with open(out, "w") as f:

@@ -10,14 +10,19 @@ ms per variant against the scores=True repetition beside it, with the spread of 
 --compartments: what the compartment eigenvectors per level cost - the same variants with (a) scores=True, (b) scores=True, compartments=True and (c)
 scores=True, compartments=CompartmentParams(n_eigs=3), alternated in one run, best of three each; the added ms per variant against the scores=True
 repetition beside it, with the spread of the baseline's three repetitions, and - the weights are synthetic - the share of (allele, level, channel, vector)
-pairs that converged with the median and the largest number of iterations; writes profiles/sv_screen_compartments.json"""
+pairs that converged with the median and the largest number of iterations; writes profiles/sv_screen_compartments.json
+--boundaries: what the boundary calls per level cost - the same variants with (a) scores=True, insulation=(5, 10, 25), (b) the same plus boundaries=True
+and (c) the same plus boundaries=BoundaryParams(min_strength=0.0): every list as full as it gets, alternated in one run, best of three each; the added
+ms per variant against the insulation-only repetition beside it, with the spread of that baseline's three repetitions, and the boundaries called per
+run; writes profiles/sv_screen_boundaries.json"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SCORES = "--scores" in sys.argv
 TRACKS = "--tracks" in sys.argv
 LOOPS = "--loops" in sys.argv
 COMPARTMENTS = "--compartments" in sys.argv
-sys.argv = [a for a in sys.argv if a not in ("--scores", "--tracks", "--loops", "--compartments")]
+BOUNDARIES = "--boundaries" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--scores", "--tracks", "--loops", "--compartments", "--boundaries")]
 import torch
 from orca_amd import orca_models, sv
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 32
@@ -136,6 +141,26 @@ if COMPARTMENTS:
         out[k + "_convergence"] = {"pairs": int(conv.size), "converged_share": round(float(conv.mean()), 4), "iterations_median": float(np.median(its)),
                                    "iterations_max": int(its.max())}
     finish("compartments", out)
+if BOUNDARIES:
+    from orca_amd import screen
+    ins = {"scores": True, "insulation": (5, 10, 25)}
+    modes = {"insulation": ins, "boundaries": dict(ins, boundaries=True), "boundaries_filled": dict(ins, boundaries=screen.BoundaryParams(min_strength=0.0))}
+    called = {k: 0 for k in modes}
+
+    def tally(k):
+        called[k] = 0
+
+        def on_result(i, e):
+            if "boundary_params" in e["scores"]:
+                called[k] += int(sum(m["ref_boundary_count"].sum() + m["boundary_count"].sum() for m in e["scores"]["models"]))
+        return on_result
+    runs = timed_runs(modes, warm="boundaries_filled", on_result=tally, note=lambda k: ("boundaries", called[k]))
+    out, best, spread = summary("--boundaries", runs, "insulation", weights="synthetic", boundaries_called_per_run=called,
+                                modes={"insulation": "scores=True, insulation=(5, 10, 25)", "boundaries": "scores=True, insulation=(5, 10, 25), boundaries=True",
+                                       "boundaries_filled": "scores=True, insulation=(5, 10, 25), boundaries=BoundaryParams(min_strength=0.0)"})
+    for k in ("boundaries", "boundaries_filled"):
+        added(out, runs, best, spread, k, base="insulation")
+    finish("boundaries", out)
 t0 = time.perf_counter()
 st = {}
 sv.sv_screen([h1], genome, svs[2:], 40_000_000, incremental=inc, stats=st, streams=streams)
