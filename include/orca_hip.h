@@ -92,6 +92,10 @@ int orca_ctx_set_stream(orca_ctx* ctx, void* hip_stream);
 int orca_ctx_workspace_bytes(orca_ctx* ctx, size_t* out);
 /* Free the workspace (it is re-grown on demand). */
 int orca_ctx_release_workspace(orca_ctx* ctx);
+/* Test entry: set every byte of the workspace arena and of the edge-fix scratch to `byte` (waits for the work in flight,
+ * synchronises afterwards; the range flag and the zero page are left alone).  *filled = arena bytes + scratch bytes; an
+ * empty arena is not an error.  A later call must compute what it would on any other contents (tests/test_gpu_arena.py). */
+int orca_ctx_fill_workspace(orca_ctx* ctx, int byte, size_t* filled);
 
 /* ---- per-kernel timing (bench.py roofline) ---------------------------------
  * When enabled, every conv1d launch over >= 65536 positions (the Encoder's

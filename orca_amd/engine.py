@@ -65,6 +65,12 @@ class Context:
     def release_workspace(self):
         check(_lib.load().orca_ctx_release_workspace(self.handle))
 
+    def fill_workspace(self, byte):
+        """Test hook: set every byte of the arena and of the edge-fix scratch to ``byte`` (syncs) -> bytes filled."""
+        n = ctypes.c_size_t()
+        check(_lib.load().orca_ctx_fill_workspace(self.handle, int(byte) & 0xFF, ctypes.byref(n)), "orca_ctx_fill_workspace")
+        return n.value
+
 
 def get_context(device):
     if isinstance(device, torch.device):

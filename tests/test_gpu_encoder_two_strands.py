@@ -10,6 +10,7 @@ import torch
 
 from orca_amd import engine
 from orca_amd import orca_predict as P
+from tests.arena import assert_arena_independent
 from tests.util import product_module
 
 pytestmark = pytest.mark.gpu
@@ -82,13 +83,23 @@ def test_joint_pass_is_bit_identical(enc, split, cuda, precision, L):
 @pytest.mark.parametrize("precision", ("f16x2", "bf16"))
 def test_gap_does_not_rely_on_a_fresh_workspace(enc, split, cuda, precision):
     """the 12 kb case twice in one process with a 1 Mb call in between: the second time its gap, guards and tails lie where the longer call
-    kept activations (the library's arena has no fill hook; the first call may have met a fresh allocation's zeros)"""
+    kept activations; then the same call on an arena filled with 0x00, 0xFF and 0x3C (tests/arena.py): the per-strand route's bits under every
+    fill, and no fill raises the range flag"""
     ref, _ = split(precision, LENGTHS[0])
     enc.precision = precision
     for L in (LENGTHS[0], LENGTHS[2], LENGTHS[0]):
         out, _ = _run(enc, _codes(L, L % 97, cuda), True)
         if L == LENGTHS[0]:
             assert np.array_equal(_bits(out), _bits(ref))
+    L = LENGTHS[0]
+    net, codes = enc._net(cuda), _codes(L, L % 97, cuda)
+    enc._apply_precision(net, precision)
+    assert net.encoder_two_strands()
+
+    def joint():      # the engine call itself: the module's range-guard retry would consume a flag that arena contents raised
+        return engine.encoder_forward_two_strands(net, codes, torch.full((2, 128, engine.encoder_num_bins(L)), float("nan"), dtype=torch.float32, device=cuda))
+    bits = assert_arena_independent(net.ctx, joint, what=("two strands", precision))
+    assert np.array_equal(bits, _bits(ref).reshape(-1))
 
 
 def test_guard_fires_on_the_reverse_strand_only(cuda):

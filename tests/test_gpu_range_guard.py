@@ -113,13 +113,13 @@ def test_p16p5_kernel_guard_in_every_pool_slot(cuda, n):
     stride 5; 8 waves = 2 position groups x 4 cout groups): `pool5_placements` - the spike in each of the five slots of windows in both position
     groups, on both sides of the tile boundary at 320 and in the last stored window; the octets move so that every wave and octet is hit.
     This kernel reads input units beyond the end of its planes for lanes whose results are never stored, and its guard sees those lanes too:
-    in the test entry the buffer behind the input planes is the output of the previous call, so an in-range call right behind a flagged one
-    (which left inf there) flags when the spike was in octet 0 (placements (0, 0) and (236, 2) at both n; the same call once more does not).  That is the conservative direction DESIGN.md describes - a retry, never a wrong value - so each pair runs its in-range call
-    twice: the first one rewrites the buffer and is reported only, the second one is the twin that is asserted."""
+    behind the last input plane the test entry keeps zero units of its own (as the Encoder's buffers do: tests/test_gpu_arena.py), so an in-range
+    call right behind a flagged one (which left inf in the output buffer next door) does not flag: each pair still runs its in-range call twice,
+    and neither may flag."""
     dev = _Dev1d(cuda, G.Conv1dSpike(128, 128, n, 9, True, True, 3))
     bad = _run_pairs(dev, G.pool5_placements(n), scrub=True)
-    print(f"\n  conv_p16p5.h, n = {n}: in-range calls that flagged right behind a flagged call (stale inf beside the input planes): {getattr(dev, 'stale', [])}")
     assert not bad, bad
+    assert not getattr(dev, "stale", []), dev.stale
 
 
 def test_p16_guard_sits_behind_residual_and_relu(cuda):
