@@ -589,6 +589,49 @@ int orca_screen_gc_tracks(orca_ctx* ctx, const uint8_t* codes, int64_t L, const 
 int orca_screen_boundary_calls(orca_ctx* ctx, const float* tracks, int B, int W, int n, float min_strength, int K, int32_t* count, int32_t* bins,
                                float* strength, float* strength_track);
 
+/* The chromosome scan (orca_amd/scan.py: scan_1m): a batch of overlapping window maps stitched into one banded map of a chromosome stretch, the band's
+ * insulation tracks, and boundary strengths on tracks of any length.  Notation: the stretch has N bins (1 .. 2^24); a window map has n <= 256 bins and
+ * window b starts at chromosome bin off[b]; the band has D distances, band[i][d] stands for pixel (i, i + d), 0 <= d < D.  Only the upper triangle
+ * (row <= column) of a window map is ever read.  Plain HIP, no atomics, no workspace arena, a fixed summation order: results do not depend on how the
+ * windows are batched.  Every launch goes to the context's stream.  A malformed call - a NULL pointer, a bound below - is ORCA_EINVAL before any launch, and
+ * no buffer is written.
+ *
+ * orca_scan_stitch_band accumulates one batch of window maps into the band.
+ *   maps [B][n][n] float32 on the device, batch stride map_bs >= n * n, rows contiguous; B >= 1, 1 <= n <= 256; n <= N.
+ *   off [B] int64 on the device, off_host its host copy (checked here): strictly ascending, 0 <= off[b] <= N - n.
+ *   trim >= 0 with n - 2 trim >= 1; 1 <= D <= n - 2 trim.
+ *   Accumulators on the device: sum [N][D] float64, count [N][D] int32, lo [N][D] and hi [N][D] float32.  The caller starts them at sum = 0, count = 0,
+ *   lo = +inf, hi = -inf.
+ *   Rule: window b covers band pixel (i, d) when r = i - off[b] satisfies r >= trim and r + d <= n - 1 - trim.  For every covered pixel, with b ascending,
+ *   v = maps[b][r][r + d]:  sum += (double) v;  count += 1;  lo = min(lo, v), hi = max(hi, v).  A NaN value makes sum, lo and hi of that pixel NaN, and they
+ *   stay NaN.
+ *   One thread per band pixel, d fastest; the launch covers rows off[0] .. off[B - 1] + n - 1 only.  Successive calls on one stream continue the same
+ *   accumulators, so splitting a window list (ascending over all calls) into batches at any point gives the same bits as one call.
+ *
+ * orca_scan_band_finish turns the accumulators into results.
+ *   band [N][D] float32 = (float)(sum / count), computed in fp64 and rounded once; NaN where count = 0, and where i + d >= N.
+ *   range [N][D] float32 (or NULL) = hi - lo, one fp32 subtraction: 0 where one window covers the pixel, NaN where none does (and where i + d >= N).  It says
+ *   how far the overlapping windows disagree about a pixel.  1 <= D <= 256.
+ *
+ * orca_scan_band_insulation computes insulation tracks from the band.
+ *   band [N][D] float32; widths [W] int32 on the device, widths_host its host copy: 1 <= W <= 8, distinct, 1 <= w and 2 w + 1 <= D.  track [W][N] float32.
+ *   track[k][i] = the fp64 mean, rounded once, of the w^2 pixels with rows r in [i - w, i) and columns c in (i, i + w], read as band[r][c - r].  NaN where
+ *   the diamond does not fit (i < w or i >= N - w), and NaN if any pixel of the diamond is NaN: every diamond is summed on its own.  This is
+ *   orca_screen_insulation's definition on the dense map the band stands for.  One wave per bin, lanes stride the diamond, then shuffles: the same bits on
+ *   every run.
+ *
+ * orca_scan_boundary_strength computes boundary strengths on tracks of any length.
+ *   tracks [W][N] float32 on the device, contiguous; 1 <= W <= 65535, N >= 1.  strength [W][N] float32.
+ *   strength = orca_screen_boundary_calls' strength_track, without its limit of 256 bins: bin i is a minimum when 1 <= i <= N - 2, t[i - 1], t[i] and t[i + 1]
+ *   are not NaN, t[i] < t[i - 1] and t[i] <= t[i + 1]; walk left from i - 1 while the bin exists, is not NaN and is >= t[i], L = the largest value met (t[i] if
+ *   none), R the same to the right; s = min(L, R) - t[i], ONE fp32 subtraction; strength[i] = s where s > 0, NaN elsewhere.  A NaN ends a walk.  One thread per
+ *   bin walks in global memory with its two running maxima in registers; the ordered lists are made on the host from this array. */
+int orca_scan_stitch_band(orca_ctx* ctx, const float* maps, int64_t map_bs, int B, int n, const int64_t* off, const int64_t* off_host, int trim, int64_t N, int D,
+                          double* sum, int32_t* count, float* lo, float* hi);
+int orca_scan_band_finish(orca_ctx* ctx, const double* sum, const int32_t* count, const float* lo, const float* hi, int64_t N, int D, float* band, float* range);
+int orca_scan_band_insulation(orca_ctx* ctx, const float* band, int64_t N, int D, const int32_t* widths, const int32_t* widths_host, int W, float* track);
+int orca_scan_boundary_strength(orca_ctx* ctx, const float* tracks, int W, int64_t N, float* strength);
+
 /* Number of 4 kb bins Encoder emits for an L-bp input (floor through the
  * 4,4,5,5,5,2 pooling chain). */
 int64_t orca_encoder_num_bins(int64_t L);

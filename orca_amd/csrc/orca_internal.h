@@ -3,7 +3,7 @@
 //   orca_encoder.hip       Conv1d launchers, the Encoder (orca_modules.py:929-980) and the U-net encoders (:1151-1169, :1388-1406)
 //   orca_decoder.hip       Conv2d launchers, Decoder / Decoder_1m (:461-488, :782-800), strand merge, background block means, the observed-data
 //                          smoother, the 2-bit genome expander
-//   orca_screen.hip        entry points of the 1 Mb mutagenesis screen (screen.h): table validation + one launch each
+//   orca_screen.hip        entry points of the 1 Mb mutagenesis screen (screen.h) and of the chromosome scan (scan.h): table validation + one launch each
 //   orca_comm.hip          the RCCL communicator of the sharded Encoder (dlopen'ed)
 //   orca_test_entries.hip  single-layer entry points for the kernel tests
 // Kernels live in the *.h files next to these; every non-template kernel there is `static`, so a header may be included by several units.

@@ -1,7 +1,9 @@
-// orca_screen.hip - entry points of the 1 Mb mutagenesis screen (orca_amd/screen.py; kernels in screen.h): table validation on the host, one launch each
+// orca_screen.hip - entry points of the 1 Mb mutagenesis screen (orca_amd/screen.py; kernels in screen.h) and of the chromosome scan (orca_amd/scan.py;
+// kernels in scan.h): table validation on the host, one launch each
 // Part of liborca_hip.so (include/orca_hip.h is the ABI; orca_internal.h what the units share).
 #include "orca_internal.h"
 
+#include "scan.h"
 #include "screen.h"
 
 static inline const f32x4* f4(const float* p) { return reinterpret_cast<const f32x4*>(p); }
@@ -507,4 +509,56 @@ extern "C" int orca_screen_merge_strands(orca_ctx* ctx, const float* fwd, int64_
   const int vec = n % 2 == 0 && fwd_bs % 2 == 0 && rev_bs % 2 == 0 && out_bs % 2 == 0 && al8(fwd) && al8(rev) && al8(out) && (!gap || (al8(ref_fwd) && al8(ref_rev)));
   return launch(ctx, "screen_merge_strands_kernel", screen_merge_strands_kernel, dim3((unsigned)B), 512, fwd, (long)fwd_bs, rev, (long)rev_bs, ref_fwd, ref_rev, n, out,
                 (long)out_bs, gap, vec);
+}
+
+// ---- the chromosome scan (orca_amd/scan.py; kernels in scan.h): window maps stitched into a band, the band's insulation, boundary strengths of any length ----
+#define SCAN_MAX_TOTAL_BINS (1L << 24)               // N: 67 Gb of 4 kb bins; keeps N * D and every grid far inside their types
+
+extern "C" int orca_scan_stitch_band(orca_ctx* ctx, const float* maps, int64_t map_bs, int B, int n, const int64_t* off, const int64_t* off_host, int trim, int64_t N,
+                                     int D, double* sum, int32_t* count, float* lo, float* hi) {
+  if (!ctx || !maps || !off || !off_host || !sum || !count || !lo || !hi) return fail(ORCA_EINVAL, "orca_scan_stitch_band: NULL argument");
+  if (B < 1 || n < 1 || n > SCAN_MAX_BINS || map_bs < (int64_t)n * n)
+    return fail(ORCA_EINVAL, "orca_scan_stitch_band: %d maps (>= 1) of %d bins (1..%d), batch stride %ld (>= n * n)", B, n, SCAN_MAX_BINS, (long)map_bs);
+  if (N < n || N > SCAN_MAX_TOTAL_BINS) return fail(ORCA_EINVAL, "orca_scan_stitch_band: a stretch of %ld bins (n = %d .. %ld)", (long)N, n, SCAN_MAX_TOTAL_BINS);
+  if (trim < 0 || n - 2 * (int64_t)trim < 1) return fail(ORCA_EINVAL, "orca_scan_stitch_band: trim = %d on maps of %d bins (trim >= 0, n - 2 trim >= 1)", trim, n);
+  if (D < 1 || D > n - 2 * trim) return fail(ORCA_EINVAL, "orca_scan_stitch_band: D = %d distances (1 .. n - 2 trim = %d)", D, n - 2 * trim);
+  for (int b = 0; b < B; ++b) {
+    if (off_host[b] < 0 || off_host[b] > N - n)
+      return fail(ORCA_EINVAL, "orca_scan_stitch_band: window %d starts at bin %ld, outside 0 .. N - n = %ld", b, (long)off_host[b], (long)(N - n));
+    if (b && off_host[b] <= off_host[b - 1])
+      return fail(ORCA_EINVAL, "orca_scan_stitch_band: windows %d and %d start at bins %ld and %ld (strictly ascending)", b - 1, b, (long)off_host[b - 1], (long)off_host[b]);
+  }
+  const long i0 = (long)off_host[0], rows = (long)off_host[B - 1] + n - i0;
+  return launch(ctx, "scan_stitch_band_kernel", scan_stitch_band_kernel, grid256(rows * D), 256, maps, (long)map_bs, B, n, i64(off), trim, (long)N, D, i0, rows, sum, count,
+                lo, hi);
+}
+
+extern "C" int orca_scan_band_finish(orca_ctx* ctx, const double* sum, const int32_t* count, const float* lo, const float* hi, int64_t N, int D, float* band,
+                                     float* range) {
+  if (!ctx || !sum || !count || !lo || !hi || !band) return fail(ORCA_EINVAL, "orca_scan_band_finish: NULL argument");
+  if (N < 1 || N > SCAN_MAX_TOTAL_BINS || D < 1 || D > SCAN_MAX_BINS)
+    return fail(ORCA_EINVAL, "orca_scan_band_finish: a band of %ld bins (1..%ld) x %d distances (1..%d)", (long)N, SCAN_MAX_TOTAL_BINS, D, SCAN_MAX_BINS);
+  return launch(ctx, "scan_band_finish_kernel", scan_band_finish_kernel, grid256((long)N * D), 256, sum, count, lo, hi, (long)N, D, band, range);
+}
+
+extern "C" int orca_scan_band_insulation(orca_ctx* ctx, const float* band, int64_t N, int D, const int32_t* widths, const int32_t* widths_host, int W, float* track) {
+  if (!ctx || !band || !widths || !widths_host || !track) return fail(ORCA_EINVAL, "orca_scan_band_insulation: NULL argument");
+  if (N < 1 || N > SCAN_MAX_TOTAL_BINS || D < 1 || D > SCAN_MAX_BINS)
+    return fail(ORCA_EINVAL, "orca_scan_band_insulation: a band of %ld bins (1..%ld) x %d distances (1..%d)", (long)N, SCAN_MAX_TOTAL_BINS, D, SCAN_MAX_BINS);
+  if (W < 1 || W > SCAN_MAX_WIDTHS) return fail(ORCA_EINVAL, "orca_scan_band_insulation: %d widths (1..%d)", W, SCAN_MAX_WIDTHS);
+  for (int k = 0; k < W; ++k) {
+    if (widths_host[k] < 1 || 2 * (int64_t)widths_host[k] + 1 > D)
+      return fail(ORCA_EINVAL, "orca_scan_band_insulation: width %d is %d bins; 1 <= w and 2 w + 1 <= D = %d (the diamond reaches distance 2 w)", k, widths_host[k], D);
+    for (int j = 0; j < k; ++j)
+      if (widths_host[j] == widths_host[k]) return fail(ORCA_EINVAL, "orca_scan_band_insulation: widths %d and %d are both %d bins (distinct)", j, k, widths_host[k]);
+  }
+  return launch(ctx, "scan_band_insulation_kernel", scan_band_insulation_kernel, dim3((unsigned)((N + SCAN_INSULATION_BINS - 1) / SCAN_INSULATION_BINS), (unsigned)W), 256,
+                band, (long)N, D, widths, W, track);
+}
+
+extern "C" int orca_scan_boundary_strength(orca_ctx* ctx, const float* tracks, int W, int64_t N, float* strength) {
+  if (!ctx || !tracks || !strength) return fail(ORCA_EINVAL, "orca_scan_boundary_strength: NULL argument");
+  if (W < 1 || W > 65535 || N < 1 || N > SCAN_MAX_TOTAL_BINS)
+    return fail(ORCA_EINVAL, "orca_scan_boundary_strength: %d tracks (1..65535) of %ld bins (1..%ld)", W, (long)N, SCAN_MAX_TOTAL_BINS);
+  return launch(ctx, "scan_boundary_strength_kernel", scan_boundary_strength_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)W), 256, tracks, (long)N, strength);
 }

@@ -1269,6 +1269,92 @@ def screen_merge_strands(ctx, fwd, rev, ref_fwd=None, ref_rev=None, out=None):
     return out, gap
 
 
+# the chromosome scan (orca_scan_*; scan.scan_1m): window maps stitched into a band [N, D] - band[i, d] stands for pixel (i, i + d) - the band's insulation
+# tracks, and boundary strengths on tracks of any length.  include/orca_hip.h has the definitions; no arena, every buffer is a torch tensor
+def scan_accumulators(device, N, D):
+    """Fresh accumulators of a band of ``N`` bins x ``D`` distances for `scan_stitch_band`: a dict of ``sum`` [N, D] float64 = 0, ``count`` [N, D]
+    int32 = 0, ``lo`` [N, D] float32 = +inf and ``hi`` [N, D] float32 = -inf on ``device``."""
+    N, D = int(N), int(D)
+    if N < 1 or D < 1:
+        raise ValueError(f"a band of {N} bins x {D} distances: at least one of each")
+    return {"sum": torch.zeros((N, D), dtype=torch.float64, device=device), "count": torch.zeros((N, D), dtype=torch.int32, device=device),
+            "lo": torch.full((N, D), float("inf"), dtype=torch.float32, device=device),
+            "hi": torch.full((N, D), float("-inf"), dtype=torch.float32, device=device)}
+
+
+def _scan_acc(acc, device=None):
+    """The four accumulators of a band as (sum, count, lo, hi, N, D), each a contiguous [N, D] tensor of its type on one device."""
+    try:
+        ts = [_on_device(acc[k], k, d) for k, d in (("sum", torch.float64), ("count", torch.int32), ("lo", torch.float32), ("hi", torch.float32))]
+    except (KeyError, TypeError, IndexError):
+        raise ValueError("acc: the dict of sum, count, lo and hi that scan_accumulators made") from None
+    if ts[0].dim() != 2 or any(t.shape != ts[0].shape or t.device != ts[0].device for t in ts) or (device is not None and ts[0].device != device):
+        raise ValueError("acc: sum, count, lo and hi are [N, D] on the maps' device")
+    return ts + [ts[0].shape[0], ts[0].shape[1]]
+
+
+def scan_stitch_band(ctx, maps, off_host, trim, acc, off=None):
+    """One batch of window maps [B, n, n] (any batch stride, rows contiguous; n <= 256) accumulated into the band ``acc`` (`scan_accumulators`;
+    orca_scan_stitch_band): ``off_host`` [B] int64 numpy, the chromosome bin every window starts at, strictly ascending, 0 <= off <= N - n (``off``: its
+    device copy, uploaded here when None); window b covers band pixel (i, d) when r = i - off[b] has ``trim`` <= r and r + d <= n - 1 - trim, and adds
+    maps[b, r, r + d] to ``sum`` in fp64, 1 to ``count`` and the value to the running ``lo`` / ``hi``; a NaN stays.  1 <= D <= n - 2 trim.  Calls
+    continue the same accumulators: a window list split into batches at any point gives the same bits as one call."""
+    maps, B, n, bs = _map_batch(maps, "maps")
+    s, c, lo, hi, N, D = _scan_acc(acc, maps.device)
+    o = np.ascontiguousarray(off_host, dtype=np.int64).reshape(-1)
+    if o.size != B:
+        raise ValueError(f"off_host: one int64 per map ({B}), got {o.size}")
+    od = torch.from_numpy(o).to(maps.device) if off is None else _on_device(off, "off", torch.int64)
+    if tuple(od.shape) != (B,) or od.device != maps.device:
+        raise ValueError("off: the device copy of off_host")
+    ctx.sync_stream()
+    check(_lib.load().orca_scan_stitch_band(ctx.handle, _dev_p(maps), bs, B, n, _dev_p(od), _np_p(o), int(trim), N, D, _dev_p(s), _dev_p(c), _dev_p(lo),
+                                            _dev_p(hi)), "orca_scan_stitch_band")
+
+
+def scan_band_finish(ctx, acc, spread=True):
+    """The accumulators ``acc`` of a band into (band [N, D], range [N, D] or None) float32 (orca_scan_band_finish): band = (float)(sum / count), the
+    fp64 quotient rounded once, NaN where no window covers the pixel and where i + d >= N; with ``spread`` range = hi - lo, how far the overlapping
+    windows disagree about the pixel (0 under one window, NaN under none)."""
+    s, c, lo, hi, N, D = _scan_acc(acc)
+    band, = _f32_outputs(s.device, (N, D))
+    rng = _f32_outputs(s.device, (N, D))[0] if spread else None
+    ctx.sync_stream()
+    check(_lib.load().orca_scan_band_finish(ctx.handle, _dev_p(s), _dev_p(c), _dev_p(lo), _dev_p(hi), N, D, _dev_p(band),
+                                            ctypes.c_void_p(0) if rng is None else _dev_p(rng)), "orca_scan_band_finish")
+    return band, rng
+
+
+def scan_band_insulation(ctx, band, widths_host):
+    """Insulation tracks [W, N] float32 of a band [N, D] (`scan_band_finish`'s) at the W widths ``widths_host`` (1 to 8 distinct ints, 1 <= w and
+    2 w + 1 <= D; orca_scan_band_insulation): track[k, i] = the fp64 mean of the w^2 pixels rows [i - w, i) x columns (i, i + w] of the dense map the band
+    stands for, read as band[r, c - r]; NaN where the diamond does not fit (i < w or i >= N - w) or holds a NaN - `screen_insulation`'s definition."""
+    band = _on_device(_f32_cuda(band, "band"), "band", torch.float32)
+    if band.dim() != 2 or band.shape[0] < 1 or band.shape[1] < 1:
+        raise ValueError(f"band: [N, D] float32, got {tuple(band.shape)}")
+    N, D = band.shape
+    w = _host_list(widths_host, "widths")
+    wd = torch.from_numpy(w).to(band.device)
+    track, = _f32_outputs(band.device, (w.shape[0], N))
+    ctx.sync_stream()
+    check(_lib.load().orca_scan_band_insulation(ctx.handle, _dev_p(band), N, D, _dev_p(wd), _np_p(w), w.shape[0], _dev_p(track)), "orca_scan_band_insulation")
+    return track
+
+
+def scan_boundary_strength(ctx, tracks):
+    """Boundary strengths [W, N] float32 of insulation tracks [W, N] float32 on the device, contiguous, of ANY length N >= 1
+    (orca_scan_boundary_strength): `screen_boundary_calls`' ``strength_track`` bit for bit - the prominence of the dip at every minimum where it is > 0,
+    NaN elsewhere; a NaN ends a walk - without its limit of 256 bins.  The ordered lists are made from it on the host."""
+    tracks = _on_device(_f32_cuda(tracks, "tracks"), "tracks", torch.float32)
+    if tracks.dim() != 2:
+        raise ValueError(f"tracks: [W, N] float32, got {tuple(tracks.shape)}")
+    W, N = tracks.shape
+    out, = _f32_outputs(tracks.device, (W, N))
+    ctx.sync_stream()
+    check(_lib.load().orca_scan_boundary_strength(ctx.handle, _dev_p(tracks), W, N, _dev_p(out)), "orca_scan_boundary_strength")
+    return out
+
+
 def encoder_forward_2bit(net, two, nmask, start, L, reverse=False, bin_lo=0, bin_hi=0, chunk_bp=0, out=None):
     """Encoder on bases [start, start + L) of a chromosome stored as 2 bits per base + N mask in HBM (genome.TwoBitGenome planes): no
     unpacked window is made (orca_encoder_forward_2bit).  Returns [1,128,bins]."""
