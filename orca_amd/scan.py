@@ -33,7 +33,8 @@ import torch
 
 from . import engine
 from ._lib import OrcaHipError
-from .screen import BIN_BP, BoundaryParams, _net_of, _widths
+from .map_readouts import BIN_BP, BoundaryParams, _widths
+from .screen import _net_of
 
 MAX_BINS = 256                      # bins of a window map (Net.forward's limit)
 

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import engine
+from .map_readouts import STRATA_FIELDS  # noqa: F401  (sv.STRATA_FIELDS is the one definition)
 # what compares a pair of finished maps through a bin map lives in sv_readouts.py; its public names stay reachable as sv.NAME
 from .sv_readouts import (LEVELS, LEVEL_BINS, SCORE_FIELDS, LOOP_SCORE_FIELDS, COMPARTMENT_SCORE_FIELDS, COMPARTMENT_MAX_EIGS, CompartmentParams,
                           BOUNDARY_SCORE_FIELDS, check_tracks, check_loops_arg, check_compartments_arg, check_boundaries_arg, check_readouts, entry_readouts,
@@ -22,14 +23,6 @@ from .sv_readouts import (LEVELS, LEVEL_BINS, SCORE_FIELDS, LOOP_SCORE_FIELDS, C
                           paired_aligned_scores_host, paired_insulation_host, paired_viewpoints_host, paired_strata_host, paired_dot_follow_host,
                           paired_match_loops_host, paired_loop_scores_host, compartment_matrix_host, eigenvectors_host, gc_tracks_host,
                           paired_compartment_scores_host)
-
-
-def __getattr__(name):
-    """``sv.STRATA_FIELDS`` is `screen.STRATA_FIELDS`, the one definition; `screen` builds on this module, so it is looked up when asked for."""
-    if name == "STRATA_FIELDS":
-        from .screen import STRATA_FIELDS
-        return STRATA_FIELDS
-    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 SV = namedtuple("SV", "kind start end")   # kind in {"del", "dup", "inv"}; half-open [start, end) on the chromosome

@@ -77,7 +77,8 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import engine        # (`screen` is loaded inside the functions that need it: it builds on the encoding half of the screen, which builds on this module)
+from . import engine, map_readouts
+from .map_readouts import STRATA_FIELDS, _boundary_fields, _loop_params, boundary_calls_host, check_boundaries, check_insulation, check_loops, check_strata, dot_calls_host, insulation_host
 
 LEVELS = 6
 LEVEL_BINS = 250
@@ -133,7 +134,7 @@ def paired_aligned_scores_host(alt, ref, bin_map):
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # Readouts per level: what changed, not only how much.  The 1 Mb screen's insulation tracks, viewpoint profiles (virtual 4C) and distance
-# strata (orca_amd/screen.py), in their paired forms: every (level, target) alt map against the variant's own reference map through the
+# strata (orca_amd/screen_readouts.py), in their paired forms: every (level, target) alt map against the variant's own reference map through the
 # level's bin map.  A genomic position is a different bin at every level, or none; inside an inversion the bin map descends, and the strata
 # read the reference pixel mirrored into the upper triangle (the min/max rule).
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -142,9 +143,8 @@ def paired_insulation_host(alt, ref, widths, bin_map):
     [n] for all), at ``widths`` (bins).  ins_w(m)[i] = the mean of m over rows [i - w, i) x columns (i, i + w], NaN unless w <= i < n - w
     (`screen.insulation_host`).  (track, ref_track, aligned), each fp64 [B, W, n]: track = ins(alt b)[i], ref_track = ins(ref b)[i] at the
     reference's own bin i, aligned = ins(alt b)[i] - ins(ref b)[map i] where map i >= 0 and both diamonds fit, else NaN."""
-    from . import screen
     a, r, bm, B, n = _pairs_host(alt, ref, bin_map, np.float64)
-    track, ref_track = screen.insulation_host(a, widths), screen.insulation_host(r, widths)
+    track, ref_track = insulation_host(a, widths), insulation_host(r, widths)
     aligned = np.full(track.shape, np.nan)
     for b in range(B):
         M = np.flatnonzero(bm[b] >= 0)
@@ -196,9 +196,8 @@ def paired_strata_host(alt, ref, bin_map, d_range=None):
     ascending, empty strata skipped, c = sum c_d: ``mse`` = sum sum dl^2 / c, ``scc`` = sum C_d / sum sqrt(X_d Y_d) (NaN when the denominator
     is 0), ``corr`` = the Pearson correlation from the pooled sums, mx = (sum c_d mx_d) / c, X = sum [X_d + c_d (mx_d - mx)^2], C = sum [C_d +
     c_d (mx_d - mx)(my_d - my)] (NaN when X or Y is 0 or c < 2); all three NaN when c = 0."""
-    from . import screen
     a, r, bm, B, n = _pairs_host(alt, ref, bin_map, np.float64)
-    lo, hi = screen.check_strata(True if d_range is None else d_range, n)
+    lo, hi = check_strata(True if d_range is None else d_range, n)
     out = {k: np.full((B, n), np.nan) for k in ("dist_delta", "dist_abs", "dist_rms", "dist_corr")}
     out.update({k: np.full(B, np.nan) for k in ("mse", "corr", "scc")})
     out["dist_count"] = np.zeros((B, n), dtype=np.int32)
@@ -256,10 +255,7 @@ LOOP_SCORE_FIELDS = ("ref_loops", "loops", "ref_loop_enrichment", "loop_enrichme
 def check_loops_arg(loops):
     """The ``loops`` argument of `sv_screen` / `sv_scores`, checked: None when unset (None or False), else the validated `screen.LoopParams`
     (`screen.check_loops` on the levels' 250 bins; True = the defaults).  One parameter set serves all six levels."""
-    from . import screen
-    if loops is None or loops is False:
-        return None
-    return screen.check_loops(loops, LEVEL_BINS)
+    return map_readouts.check_loops_arg(loops, LEVEL_BINS)
 
 
 def _is_dot_slot(ij, n):
@@ -286,8 +282,7 @@ def paired_dot_follow_host(alt_e, ref_ij, ref_enrich, bin_map, params):
     max(a, c)) over A x C with w <= i, j <= n - 1 - w and j - i >= d_min.  A dict of ``candidates`` [B, R] int32 (their number), ``at`` [B, R, 2]
     int32 (the best: a non-NaN e beats a NaN e, a larger e a smaller one, the earlier pixel of two equals), ``enrich`` [B, R] float32 (alt_e there)
     and ``delta`` [B, R] float32 = enrich - ref_enrich (fp32); (-1, -1), NaN, NaN without a candidate."""
-    from . import screen
-    q = screen._loop_params(params)
+    q = _loop_params(params)
     e = np.asarray(alt_e, dtype=np.float32)
     if e.ndim != 3 or e.shape[1] != e.shape[2]:
         raise ValueError("alt_e: [B, n, n]")
@@ -357,10 +352,9 @@ def paired_loop_scores_host(alt, ref, bin_map, params):
     (K = max_calls): ``ref_loops``, ``loops`` int32 [B, K, 2]; ``ref_loop_enrichment``, ``loop_enrichment`` float32 [B, K]; ``ref_loop_count``,
     ``loop_count`` int32 [B] (all dots); ``loop_candidates`` int32 [B, K]; ``loop_followed_at`` int32 [B, K, 2]; ``loop_followed_enrichment``,
     ``loop_delta`` float32 [B, K]; ``loop_is_gained``, ``ref_loop_is_lost`` bool [B, K]; ``loops_gained``, ``loops_lost`` int32 [B]."""
-    from . import screen
     a, r, bm, B, n = _pairs_host(alt, ref, bin_map, np.float32)
-    q = screen.check_loops(params, n)
-    rc, ac = screen.dot_calls_host(r, q), screen.dot_calls_host(a, q)
+    q = check_loops(params, n)
+    rc, ac = dot_calls_host(r, q), dot_calls_host(a, q)
     return _loop_fields(rc, ac, paired_dot_follow_host(ac["e_map"], rc["ij"], rc["enrich"], bm, q), bm, q.tol)
 
 
@@ -549,23 +543,17 @@ def check_boundaries_arg(boundaries, insulation=None):
     """The ``boundaries`` argument of `sv_screen` / `sv_scores`, checked: None when unset (None or False), else the validated
     `screen.BoundaryParams` (`screen.check_boundaries` on the levels' 250 bins; True = the defaults).  ``insulation``: the checked widths - the
     boundaries are called on the insulation tracks, so without them it is a ValueError.  One parameter set serves all six levels and every width."""
-    from . import screen
-    if boundaries is None or boundaries is False:
-        return None
-    if insulation is None:
-        raise ValueError("boundaries: called on the insulation tracks (insulation=widths)")
-    return screen.check_boundaries(boundaries, LEVEL_BINS)
+    return map_readouts.check_boundaries_arg(boundaries, LEVEL_BINS, insulation)
 
 
 def _paired_boundary_fields(rc, ac, track, ref_track, delta, bin_map, tol):
     """The boundary fields (`BOUNDARY_SCORE_FIELDS`, numpy [B, W, ...]) of B pairs from the calls of the reference tracks ``rc`` and of the alt
     tracks ``ac`` (``count`` [B, W], ``bins``, ``strength`` [B, W, K]), the tracks [B, W, n], ``insulation_delta`` ``delta`` [B, W, n] and
     ``bin_map`` [B, n] (one row per pair, every width): the matching on the host (`screen._boundary_fields`)."""
-    from . import screen
     B, W, n = track.shape
     flat = lambda a: np.ascontiguousarray(a).reshape((B * W,) + a.shape[2:])
-    got = screen._boundary_fields({k: flat(ac[k]) for k in ("bins", "strength")}, {k: flat(rc[k]) for k in ("bins", "strength")}, flat(track), flat(ref_track),
-                                  tol, np.repeat(np.asarray(bin_map), W, axis=0), flat(delta))
+    got = _boundary_fields({k: flat(ac[k]) for k in ("bins", "strength")}, {k: flat(rc[k]) for k in ("bins", "strength")}, flat(track), flat(ref_track),
+                           tol, np.repeat(np.asarray(bin_map), W, axis=0), flat(delta))
     out = {"ref_boundaries": rc["bins"], "boundaries": ac["bins"], "ref_boundary_strength": rc["strength"], "boundary_strength": ac["strength"],
            "ref_boundary_count": rc["count"], "boundary_count": ac["count"]}
     out.update((k, v.reshape((B, W) + v.shape[1:])) for k, v in got.items() if k != "first_at")
@@ -583,13 +571,12 @@ def paired_boundary_scores_host(track, ref_track, insulation_delta, bin_map, par
     (``insulation_delta`` at the lowest alt bin that stands for the boundary's own bin, NaN without one), ``ref_boundary_is_lost``,
     ``ref_boundary_is_unmapped`` bool; per alt boundary ``boundary_is_gained``, ``boundary_is_unmapped`` bool - all [B, W, K]; ``boundaries_gained``,
     ``boundaries_lost`` int32 [B, W]."""
-    from . import screen
     t, r, d = (np.asarray(x, dtype=np.float32) for x in (track, ref_track, insulation_delta))
     if t.ndim != 3 or r.shape != t.shape or d.shape != t.shape:
         raise ValueError("track, ref_track, insulation_delta: [B, W, n]")
     B, n = t.shape[0], t.shape[2]
-    q = screen.check_boundaries(params, n)
-    return _paired_boundary_fields(screen.boundary_calls_host(r, q), screen.boundary_calls_host(t, q), t, r, d, _ref_bins_host(bin_map, B, n), q.tol)
+    q = check_boundaries(params, n)
+    return _paired_boundary_fields(boundary_calls_host(r, q), boundary_calls_host(t, q), t, r, d, _ref_bins_host(bin_map, B, n), q.tol)
 
 
 # The arguments, checked once, and what they add to an entry before any model is scored.
@@ -597,12 +584,11 @@ def check_tracks(insulation=None, viewpoints=None, strata=None):
     """The three readout arguments of `sv_screen` / `sv_scores`, checked: None when all are unset, else {"insulation": int32 widths or None,
     "viewpoints": [positions] or None, "strata": (d_lo, d_hi) or None}.  ``insulation`` as `screen.check_insulation` takes it, ``strata`` as
     `screen.check_strata`, on the levels' 250 bins; ``viewpoints``: 1 to 64 base positions on the original chromosome."""
-    from . import screen
     if insulation is None and viewpoints is None and strata is None:
         return None
     spec = {"insulation": None, "viewpoints": None, "strata": None}
     if insulation is not None:
-        spec["insulation"] = screen.check_insulation(insulation, LEVEL_BINS)
+        spec["insulation"] = check_insulation(insulation, LEVEL_BINS)
     if viewpoints is not None:
         try:
             pos = [int(p) for p in viewpoints]
@@ -612,7 +598,7 @@ def check_tracks(insulation=None, viewpoints=None, strata=None):
             raise ValueError("viewpoints: 1 to 64 base positions >= 0")
         spec["viewpoints"] = pos
     if strata is not None:
-        spec["strata"] = screen.check_strata(strata, LEVEL_BINS)
+        spec["strata"] = check_strata(strata, LEVEL_BINS)
     return spec
 
 
@@ -731,7 +717,6 @@ def _model_scores(ctx, ref_maps, alt_maps, bin_map, entry=None):
     target channel here) - one launch of 6 C pairs on the current stream; a dict of numpy arrays [6, C] (``profile`` [6, C, n]).  ``entry``
     (an entry's ``scores`` after `entry_readouts`): one more launch per readout it names, over the same pairs; each gives arrays [6 C, ...], and all
     of them leave here as [6, C, ...]."""
-    from .screen import STRATA_FIELDS
     lv, C, n = alt_maps.shape[0], alt_maps.shape[1], alt_maps.shape[2]
     alt, ref, bmc = alt_maps.reshape(lv * C, n, n), ref_maps.reshape(lv * C, n, n), np.repeat(bin_map, C, axis=0)
     entry = {} if entry is None else entry
