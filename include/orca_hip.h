@@ -632,6 +632,37 @@ int orca_scan_band_finish(orca_ctx* ctx, const double* sum, const int32_t* count
 int orca_scan_band_insulation(orca_ctx* ctx, const float* band, int64_t N, int D, const int32_t* widths, const int32_t* widths_host, int W, float* track);
 int orca_scan_boundary_strength(orca_ctx* ctx, const float* tracks, int W, int64_t N, float* strength);
 
+/* Loops along the scan (scan.scan_1m(..., loops=)): dot calls on the band itself, for a whole chromosome.  The band is band[N][D] float32 as
+ * orca_scan_band_finish writes it: band[i][d] = pixel (i, i + d), NaN where uncovered or where i + d >= N; 1 <= N <= 2^24, 2 <= D <= 256.  Integers
+ * 0 <= p < w <= 16, 1 <= r <= 16, d_min >= 2 w + 1 and an fp32 threshold T (not NaN), as for orca_screen_dot_calls.
+ *   eligible      band pixel (i, d) with w <= i, i + d <= N - 1 - w and d_min <= d <= D - 1 - 2 w: every pixel of the (2 w + 1)^2 window then lies at a
+ *                 distance in [d - 2 w, d + 2 w], inside [1, D - 1], and in a row in [0, N).  The smallest band with an eligible pixel has
+ *                 D = d_min + 2 w + 1 and N = d_min + 2 w + 1
+ *   enrichment    e[i][d] = orca_screen_dot_calls' e on the dense map the band stands for, at (i, i + d): its five sets, each summed on its own in fp64
+ *                 (a ascending, then b ascending), one division per set, one rounding to fp32 - the same device function computes both, on the band as
+ *                 an image of row stride D - 1 (dense pixel (i + a, i + d + b) is band[(i + a) * D + d + b - a]).  NaN when any window pixel is NaN,
+ *                 NaN at every ineligible pixel
+ *   dot           (i, d) with e not NaN, e >= T, and for every (di, dj) with |di|, |dj| <= r, not both 0, whose neighbour e' = e_band[i + di][d + dj - di]
+ *                 exists (row in [0, N), distance in [0, D)) and is not NaN: e > e' where di < 0 or (di = 0 and dj < 0), e >= e' otherwise.  fp32
+ *                 comparisons; orca_screen_dot_calls' rule - row-major order of (i, j) is row-major order of (i, d).  A constant band with T = 0 has exactly
+ *                 one dot, (w, d_min)
+ *   list          ALL dots in ascending (i, d) order, as ij[L][2] = (i, i + d) int64 and enrich[L] float32.  Nothing is capped: a chromosome has as many
+ *                 loops as it has
+ * orca_scan_band_dot_enrichment writes e_band[N][D], every element of it (one workgroup per 32 band rows, which it keeps in LDS with their 2 w halo
+ * rows; a pixel's bits do not depend on the tiling).
+ * orca_scan_band_dot_offsets writes row_start[N + 1] int64 from e_band: row_start[i] = the number of dots in rows < i, row_start[N] = L.  Two launches:
+ * the rows' counts (one workgroup per row, ballots and popcounts) into row_start[0 .. N), then one workgroup turns them into the exclusive prefix in
+ * place.
+ * orca_scan_band_dot_list applies the same predicate again and writes dot k of row i, k counted within the row by ballot and popcount, to slot
+ * row_start[i] + k of ij[cap][2] and enrich[cap]; cap = the L the caller read from row_start[N] (cap = 0: no launch).  Only slots in [0, cap) are ever
+ * written, whatever row_start holds on the device.
+ * No atomics, no workspace arena; the order of every sum and of the list is fixed.  Anything else - a NULL pointer, N < 1, D outside 2 .. 256, a
+ * parameter outside its range, a NaN T, cap < 0 - is ORCA_EINVAL before any launch, and no buffer is written. */
+int orca_scan_band_dot_enrichment(orca_ctx* ctx, const float* band, int64_t N, int D, int p, int w, int d_min, float* e_band);
+int orca_scan_band_dot_offsets(orca_ctx* ctx, const float* e_band, int64_t N, int D, int r, float T, int64_t* row_start);
+int orca_scan_band_dot_list(orca_ctx* ctx, const float* e_band, int64_t N, int D, int r, float T, const int64_t* row_start, int64_t cap, int64_t* ij,
+                            float* enrich);
+
 /* Number of 4 kb bins Encoder emits for an L-bp input (floor through the
  * 4,4,5,5,5,2 pooling chain). */
 int64_t orca_encoder_num_bins(int64_t L);

@@ -1,10 +1,11 @@
 // orca_screen.hip - entry points of the 1 Mb mutagenesis screen (orca_amd/screen.py; kernels in screen.h) and of the chromosome scan (orca_amd/scan.py;
-// kernels in scan.h): table validation on the host, one launch each
+// kernels in scan.h and scan_loops.h): table validation on the host, one launch each
 // Part of liborca_hip.so (include/orca_hip.h is the ABI; orca_internal.h what the units share).
 #include "orca_internal.h"
 
 #include "scan.h"
 #include "screen.h"
+#include "scan_loops.h"
 
 static inline const f32x4* f4(const float* p) { return reinterpret_cast<const f32x4*>(p); }
 static inline const long long* i64(const int64_t* p) { return reinterpret_cast<const long long*>(p); }
@@ -561,4 +562,49 @@ extern "C" int orca_scan_boundary_strength(orca_ctx* ctx, const float* tracks, i
   if (W < 1 || W > 65535 || N < 1 || N > SCAN_MAX_TOTAL_BINS)
     return fail(ORCA_EINVAL, "orca_scan_boundary_strength: %d tracks (1..65535) of %ld bins (1..%ld)", W, (long)N, SCAN_MAX_TOTAL_BINS);
   return launch(ctx, "scan_boundary_strength_kernel", scan_boundary_strength_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)W), 256, tracks, (long)N, strength);
+}
+
+// ---- loops along the band (scan_1m(..., loops=); kernels in scan_loops.h): the enrichment band, the rows' offsets into the list, the list -----------------------
+static int check_band(const char* what, int64_t N, int D) {
+  if (N < 1 || N > SCAN_MAX_TOTAL_BINS || D < 2 || D > SCAN_LOOP_MAX_DEPTH)
+    return fail(ORCA_EINVAL, "%s: a band of %ld bins (1..%ld) x %d distances (2..%d)", what, (long)N, SCAN_MAX_TOTAL_BINS, D, SCAN_LOOP_MAX_DEPTH);
+  return ORCA_OK;
+}
+
+static int check_band_calls(const char* what, int64_t N, int D, int r, float T) {
+  ORCA_TRY(check_band(what, N, D));
+  if (r < 1 || r > SCREEN_DOT_MAX_R) return fail(ORCA_EINVAL, "%s: local-maximum radius r = %d (1..%d)", what, r, SCREEN_DOT_MAX_R);
+  if (T != T) return fail(ORCA_EINVAL, "%s: the threshold T is NaN", what);
+  return ORCA_OK;
+}
+
+static inline int row_threads(int D) { return (D + 63) / 64 * 64; }           // thread d of a row's workgroup stands at distance d: the waves D needs
+
+extern "C" int orca_scan_band_dot_enrichment(orca_ctx* ctx, const float* band, int64_t N, int D, int p, int w, int d_min, float* e_band) {
+  if (!ctx || !band || !e_band) return fail(ORCA_EINVAL, "orca_scan_band_dot_enrichment: NULL argument");
+  ORCA_TRY(check_band("orca_scan_band_dot_enrichment", N, D));
+  if (p < 0 || p >= w || w > SCREEN_DOT_MAX_W)
+    return fail(ORCA_EINVAL, "orca_scan_band_dot_enrichment: peak half-width p = %d, window half-width w = %d (0 <= p < w <= %d)", p, w, SCREEN_DOT_MAX_W);
+  if (d_min < 2 * w + 1) return fail(ORCA_EINVAL, "orca_scan_band_dot_enrichment: d_min = %d (>= 2 w + 1 = %d: the windows stay above the diagonal)", d_min, 2 * w + 1);
+  return launch(ctx, "scan_band_dot_enrich_kernel", scan_band_dot_enrich_kernel, dim3((unsigned)((N + SCAN_LOOP_ROWS - 1) / SCAN_LOOP_ROWS)), 256, band, (long)N, D, p, w,
+                d_min, e_band);
+}
+
+// two launches: the rows' dot counts into row_start[0 .. N), then their exclusive prefix in place and the total in row_start[N]
+extern "C" int orca_scan_band_dot_offsets(orca_ctx* ctx, const float* e_band, int64_t N, int D, int r, float T, int64_t* row_start) {
+  if (!ctx || !e_band || !row_start) return fail(ORCA_EINVAL, "orca_scan_band_dot_offsets: NULL argument");
+  ORCA_TRY(check_band_calls("orca_scan_band_dot_offsets", N, D, r, T));
+  long long* rows = reinterpret_cast<long long*>(row_start);
+  ORCA_TRY(launch(ctx, "scan_band_dot_count_kernel", scan_band_dot_count_kernel, dim3((unsigned)N), row_threads(D), e_band, (long)N, D, r, T, rows));
+  return launch(ctx, "scan_row_offsets_kernel", scan_row_offsets_kernel, dim3(1), 256, rows, (long)N);
+}
+
+extern "C" int orca_scan_band_dot_list(orca_ctx* ctx, const float* e_band, int64_t N, int D, int r, float T, const int64_t* row_start, int64_t cap, int64_t* ij,
+                                       float* enrich) {
+  if (!ctx || !e_band || !row_start || !ij || !enrich) return fail(ORCA_EINVAL, "orca_scan_band_dot_list: NULL argument");
+  ORCA_TRY(check_band_calls("orca_scan_band_dot_list", N, D, r, T));
+  if (cap < 0) return fail(ORCA_EINVAL, "orca_scan_band_dot_list: cap = %ld slots (>= 0)", (long)cap);
+  if (cap == 0) return ORCA_OK;                                              // an empty list: nothing to write
+  return launch(ctx, "scan_band_dot_list_kernel", scan_band_dot_list_kernel, dim3((unsigned)N), row_threads(D), e_band, (long)N, D, r, T, i64(row_start), (long)cap,
+                reinterpret_cast<long long*>(ij), enrich);
 }

@@ -1355,6 +1355,50 @@ def scan_boundary_strength(ctx, tracks):
     return out
 
 
+# loops along the band (orca_scan_band_dot_*; scan.scan_1m(..., loops=)): the enrichment band, then ALL its dots as one ordered list
+SCAN_LOOP_ROWS = 32             # band rows per workgroup of the enrichment kernel (orca_amd/csrc/scan_loops.h); no result depends on it
+
+
+def _band(t, name):
+    t = _on_device(_f32_cuda(t, name), name, torch.float32)
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{name}: [N, D] float32, got {tuple(t.shape)}")
+    return t, t.shape[0], t.shape[1]
+
+
+def scan_band_dot_enrichment(ctx, band, p, w, d_min=None):
+    """The enrichment band [N, D] float32 of a band [N, D] (`scan_band_finish`'s; 2 <= D <= 256; orca_scan_band_dot_enrichment): e[i, d] =
+    `screen_dot_calls`' enrichment of the dense map the band stands for at pixel (i, i + d), NaN where any pixel of the window is NaN and at every
+    ineligible pixel - eligible: w <= i, i + d <= N - 1 - w and ``d_min`` <= d <= D - 1 - 2 w.  0 <= p < w <= 16, ``d_min`` >= 2 w + 1 (its default)."""
+    band, N, D = _band(band, "band")
+    p, w = int(p), int(w)
+    d_min = 2 * w + 1 if d_min is None else int(d_min)
+    e_band, = _f32_outputs(band.device, (N, D))
+    ctx.sync_stream()
+    check(_lib.load().orca_scan_band_dot_enrichment(ctx.handle, _dev_p(band), N, D, p, w, d_min, _dev_p(e_band)), "orca_scan_band_dot_enrichment")
+    return e_band
+
+
+def scan_band_dot_calls(ctx, e_band, r, threshold):
+    """ALL dots of an enrichment band [N, D] (`scan_band_dot_enrichment`'s) in ascending (i, d) order, on the device: (ij [L, 2] int64, the pixel
+    (i, i + d); enrich [L] float32, its e).  (i, d) is a dot when e is not NaN, e >= ``threshold`` and e wins against every neighbour
+    e_band[i + di, d + dj - di], |di|, |dj| <= ``r``, that exists and is not NaN: e > e' where the neighbour comes first in (i, d) order, e >= e' where
+    it follows (include/orca_hip.h).  orca_scan_band_dot_offsets counts the dots per row and prefixes the counts, L comes to the host (one 8-byte
+    copy), and orca_scan_band_dot_list writes the lists; with L = 0 nothing more is launched."""
+    e_band, N, D = _band(e_band, "e_band")
+    dev = e_band.device
+    row_start = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    ctx.sync_stream()
+    check(_lib.load().orca_scan_band_dot_offsets(ctx.handle, _dev_p(e_band), N, D, int(r), float(threshold), _dev_p(row_start)), "orca_scan_band_dot_offsets")
+    L = int(row_start[N].item())
+    ij = torch.empty((L, 2), dtype=torch.int64, device=dev)
+    enrich, = _f32_outputs(dev, (L,))
+    if L:
+        check(_lib.load().orca_scan_band_dot_list(ctx.handle, _dev_p(e_band), N, D, int(r), float(threshold), _dev_p(row_start), L, _dev_p(ij), _dev_p(enrich)),
+              "orca_scan_band_dot_list")
+    return ij, enrich
+
+
 def encoder_forward_2bit(net, two, nmask, start, L, reverse=False, bin_lo=0, bin_hi=0, chunk_bp=0, out=None):
     """Encoder on bases [start, start + L) of a chromosome stored as 2 bits per base + N mask in HBM (genome.TwoBitGenome planes): no
     unpacked window is made (orca_encoder_forward_2bit).  Returns [1,128,bins]."""

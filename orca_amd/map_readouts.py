@@ -342,9 +342,55 @@ def check_loops(loops, n):
     return q
 
 
+def check_band_loops(loops, N, D):
+    """``loops`` as a validated `LoopParams` for a band of N bins x D distances (``scan.scan_1m(..., loops=)``): `check_loops`' ranges, and a
+    ValueError when no band pixel is eligible - pixel (i, d) needs w <= i, i + d <= N - 1 - w and d_min <= d <= D - 1 - 2 w, so D >= d_min + 2 w + 1
+    and N >= d_min + 2 w + 1.  ``max_calls`` and ``tol`` are checked and unused: nothing is capped or matched on a band."""
+    q = _loop_params(LoopParams() if loops is True else loops)
+    need = q.d_min + 2 * q.w + 1
+    if int(D) < need or int(N) < need:
+        raise ValueError(f"loops: a band of {int(N)} bins x {int(D)} distances has no eligible pixel at w = {q.w}, d_min = {q.d_min} "
+                         f"(N >= d_min + 2 w + 1 = {need} and D >= {need})")
+    return q
+
+
 def check_loops_arg(loops, n):
     """A screen's ``loops`` argument, checked for maps of n bins: None when unset (None or False), else `check_loops`' validated `LoopParams`."""
     return None if loops is None or loops is False else check_loops(loops, n)
+
+
+def _dot_enrichment_of(view, p, w):
+    """e (float32) of a block of pixels whose windows are all readable: ``view(a, b)`` is the fp64 array of the block's pixels shifted by the window
+    offset (a, b), |a|, |b| <= w.  The one numpy statement of the sets and of the order of the sums (a ascending, then b ascending), for a dense map
+    (`dot_enrichment_host`) and for a band (`scan.band_dot_enrichment_host`)."""
+    sums, cnt = dict.fromkeys("PDLHV", 0.0), dict.fromkeys("PDLHV", 0)
+    for a in range(-w, w + 1):
+        for b in range(-w, w + 1):
+            x = view(a, b)
+            sets = []
+            if abs(a) <= p and abs(b) <= p:
+                sets.append("P")
+            else:
+                if a != 0 and b != 0:
+                    sets.append("D")
+                if a >= 1 and b <= -1:
+                    sets.append("L")
+            if abs(a) <= 1 and abs(b) > p:
+                sets.append("H")
+            if abs(b) <= 1 and abs(a) > p:
+                sets.append("V")
+            for k in sets:
+                sums[k] = sums[k] + x
+                cnt[k] += 1
+    mean = {k: sums[k] / float(cnt[k]) for k in "PDLHV"}
+    nan = np.isnan(mean["P"])
+    for k in "DLHV":
+        nan = nan | np.isnan(mean[k])
+    with np.errstate(invalid="ignore"):
+        bg = mean["D"]
+        for k in "LHV":
+            bg = np.where(mean[k] > bg, mean[k], bg)
+        return np.where(nan, np.nan, mean["P"] - bg).astype(np.float32)
 
 
 def dot_enrichment_host(maps, params):
@@ -364,35 +410,7 @@ def dot_enrichment_host(maps, params):
     if c <= 0 or n < 2 * w + 1 + d_min:
         return out
     m64 = m.astype(np.float64)
-    sums = {k: np.zeros((E, c, c)) for k in "PDLHV"}
-    cnt = dict.fromkeys("PDLHV", 0)
-    for a in range(-w, w + 1):
-        for b in range(-w, w + 1):
-            x = m64[:, w + a: w + a + c, w + b: w + b + c]
-            sets = []
-            if abs(a) <= p and abs(b) <= p:
-                sets.append("P")
-            else:
-                if a != 0 and b != 0:
-                    sets.append("D")
-                if a >= 1 and b <= -1:
-                    sets.append("L")
-            if abs(a) <= 1 and abs(b) > p:
-                sets.append("H")
-            if abs(b) <= 1 and abs(a) > p:
-                sets.append("V")
-            for k in sets:
-                sums[k] = sums[k] + x
-                cnt[k] += 1
-    mean = {k: sums[k] / float(cnt[k]) for k in "PDLHV"}
-    nan = np.zeros((E, c, c), dtype=bool)
-    for k in "PDLHV":
-        nan |= np.isnan(mean[k])
-    with np.errstate(invalid="ignore"):
-        bg = mean["D"]
-        for k in "LHV":
-            bg = np.where(mean[k] > bg, mean[k], bg)
-        e = np.where(nan, np.nan, mean["P"] - bg).astype(np.float32)
+    e = _dot_enrichment_of(lambda a, b: m64[:, w + a: w + a + c, w + b: w + b + c], p, w)
     i = np.arange(w, n - w)
     e[:, ~(i[None, :] - i[:, None] >= d_min)] = np.nan
     out[:, w: n - w, w: n - w] = e

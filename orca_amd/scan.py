@@ -10,7 +10,9 @@ chromosome stretch,
 
 (orca_scan_stitch_band, orca_scan_band_finish), the insulation diamond runs on that band (orca_scan_band_insulation) and the boundary strengths
 on the chromosome-long tracks (orca_scan_boundary_strength); include/orca_hip.h has the definitions.  The ordered boundary lists are made on the
-host from the strength array, which is small.
+host from the strength array, which is small.  ``loops=`` calls the dots (`screen.LoopParams`, the screens' third readout) on the band itself: the
+enrichment of every band pixel (orca_scan_band_dot_enrichment) and ALL its local maxima as one ordered list made on the device
+(orca_scan_band_dot_offsets, orca_scan_band_dot_list).
 
 *Coverage.*  A window is trusted on its bins [trim, n - trim): window b, which starts at chromosome bin off[b], covers pixel (i, d) when
 r = i - off[b] has trim <= r and r + d <= n - 1 - trim.  `plan_windows` lays the windows out and `full_depth` says how many distances have no
@@ -21,10 +23,11 @@ privileged - summed in fp64 in ascending window order, so the bits do not depend
 minus the smallest of the values a pixel got: how far the overlapping windows disagree, the scan's confidence readout as ``strand_gap`` is the
 strands'.  A NaN from the model stays a NaN in mean and range.
 
-`stitch_band_host` and `band_insulation_host` restate the kernels in numpy; `screen.boundary_strength_host` is the restatement of the fourth.
+`stitch_band_host` and `band_insulation_host` restate the kernels in numpy; `screen.boundary_strength_host` is the restatement of the fourth, and
+`band_dot_enrichment_host` / `band_dot_calls_host` of the loop kernels.
 
-The defaults of ``trim_bins`` and of `screen.BoundaryParams.min_strength` are NOT calibrated on the published checkpoints - nobody on this project
-has them."""
+The defaults of ``trim_bins``, of `screen.BoundaryParams.min_strength` and of `screen.LoopParams.threshold` are NOT calibrated on the published
+checkpoints - nobody on this project has them."""
 from dataclasses import dataclass
 from typing import Optional
 
@@ -33,7 +36,7 @@ import torch
 
 from . import engine
 from ._lib import OrcaHipError
-from .map_readouts import BIN_BP, BoundaryParams, _widths
+from .map_readouts import BIN_BP, BoundaryParams, LoopParams, _dot_enrichment_of, _loop_params, _widths, check_band_loops
 from .screen import _net_of
 
 MAX_BINS = 256                      # bins of a window map (Net.forward's limit)
@@ -139,6 +142,57 @@ def band_insulation_host(band, widths):
     return out
 
 
+def band_dot_enrichment_host(band, params):
+    """Host restatement of orca_scan_band_dot_enrichment: the enrichment band [N, D] float32 of a band [N, D] under ``params`` (a
+    `screen.LoopParams`), NaN at the ineligible pixels.  Pixel (i, d) is eligible when w <= i, i + d <= N - 1 - w and d_min <= d <= D - 1 - 2 w; its
+    window pixel (a, b) - dense pixel (i + a, i + d + b) - is band[i + a, d + b - a], the flattened band at (i D + d) + a (D - 1) + b.  So the block of
+    pixels shifted by (a, b) is a slice of the band itself: no dense map is made, and a 10 000 x 131 band is a few hundred slices of it.  The sets, the
+    order of the fp64 sums (a ascending, then b ascending), the one division per set and the one rounding are `screen.dot_enrichment_host`'s - one
+    function computes both - so e is, bit for bit, its e of the dense map the band stands for."""
+    q = _loop_params(params)
+    f = np.asarray(band, dtype=np.float32)
+    if f.ndim != 2:
+        raise ValueError("band: [N, D]")
+    N, D = f.shape
+    p, w, d_min = q.p, q.w, q.d_min
+    out = np.full((N, D), np.nan, dtype=np.float32)
+    rows, cols = N - 2 * w, D - 2 * w - d_min              # the block: rows w .. N - 1 - w, distances d_min .. D - 1 - 2 w
+    if cols <= 0 or N < d_min + 2 * w + 1:
+        return out
+    f64 = f.astype(np.float64)
+    e = _dot_enrichment_of(lambda a, b: f64[w + a: w + a + rows, d_min + b - a: d_min + b - a + cols], p, w)
+    i, d = np.arange(w, N - w)[:, None], np.arange(d_min, D - 2 * w)[None, :]
+    e[i + d > N - 1 - w] = np.nan                          # the column i + d needs w bins behind it too (those windows met the band's NaN end anyway)
+    out[w: N - w, d_min: D - 2 * w] = e
+    return out
+
+
+def band_dot_calls_host(e_band, params):
+    """Host restatement of orca_scan_band_dot_offsets + orca_scan_band_dot_list: ALL dots of an enrichment band [N, D] (float32) in ascending (i, d)
+    order, as (ij int64 [L, 2] = (i, i + d), enrich float32 [L]).  (i, d) is a dot when e is not NaN, e >= threshold and, for every (di, dj) with
+    |di|, |dj| <= r, not both 0, whose neighbour e' = e_band[i + di, d + dj - di] exists and is not NaN: e > e' where di < 0 or (di = 0 and dj < 0),
+    e >= e' otherwise; all in fp32.  Only ``r`` and ``threshold`` of ``params`` are used: ``max_calls`` caps nothing here."""
+    q = _loop_params(params)
+    e = np.asarray(e_band, dtype=np.float32)
+    if e.ndim != 2:
+        raise ValueError("e_band: [N, D]")
+    N, D = e.shape
+    r, T = q.r, np.float32(q.threshold)
+    pad = np.full((N + 2 * r, D + 4 * r), np.nan, dtype=np.float32)
+    pad[r: r + N, 2 * r: 2 * r + D] = e
+    with np.errstate(invalid="ignore"):
+        dot = ~np.isnan(e) & (e >= T)
+        for di in range(-r, r + 1):
+            for dj in range(-r, r + 1):
+                if di == 0 and dj == 0:
+                    continue
+                f = pad[r + di: r + di + N, 2 * r + dj - di: 2 * r + dj - di + D]
+                wins = (e > f) if (di < 0 or (di == 0 and dj < 0)) else (e >= f)
+                dot &= np.isnan(f) | wins
+    at = np.argwhere(dot).astype(np.int64)                 # row-major: ascending (i, d)
+    return np.stack([at[:, 0], at[:, 0] + at[:, 1]], axis=1), e[at[:, 0], at[:, 1]].copy()
+
+
 # ---- the result -----------------------------------------------------------------------------------------------------------------------------------
 @dataclass
 class ScanResult:
@@ -156,7 +210,12 @@ class ScanResult:
       boundary_strength  [W, N] float32 on the device: the strength at every minimum with strength > 0, NaN elsewhere
       boundaries         per width a pair (bins int64 numpy, strength float32 numpy), ascending in the bin: the minima whose strength is >=
                          ``min_strength`` - ALL of them
-      boundary_params    the validated `screen.BoundaryParams` (``min_strength`` as the fp32 it was compared in)"""
+      boundary_params    the validated `screen.BoundaryParams` (``min_strength`` as the fp32 it was compared in)
+      loop_params        with ``loops=``: the validated `screen.LoopParams` (``d_min`` resolved, ``threshold`` as the fp32 it was compared in)
+      loop_enrichment    [N, D] float32 on the device: the enrichment e of band pixel (i, d), NaN where the pixel is ineligible or its window
+                         holds a NaN
+      loops              a pair (ij int64 numpy [L, 2], enrichment float32 numpy [L]): ALL dots (i, j = i + d) in ascending (i, d) order and
+                         their e; `loop_positions` gives the anchors in bases"""
     start: int
     binsize: int
     offsets: np.ndarray
@@ -170,6 +229,9 @@ class ScanResult:
     boundary_strength: Optional[torch.Tensor] = None
     boundaries: Optional[list] = None
     boundary_params: Optional[BoundaryParams] = None
+    loop_params: Optional[LoopParams] = None
+    loop_enrichment: Optional[torch.Tensor] = None
+    loops: Optional[tuple] = None
 
     def bin_of(self, pos):
         """The bin that holds base ``pos`` (in the coordinates of ``start``)."""
@@ -183,6 +245,12 @@ class ScanResult:
         if not 0 <= int(bin) <= self.n_bins:
             raise ValueError(f"bin {bin} is outside 0 .. {self.n_bins}")
         return self.start + int(bin) * self.binsize
+
+    def loop_positions(self):
+        """int64 numpy [L, 2]: the first base of the two anchor bins of every dot of ``loops`` (`pos_of`)."""
+        if self.loops is None:
+            raise ValueError("the scan called no loops (loops=)")
+        return self.start + self.loops[0].astype(np.int64) * self.binsize
 
     def dense(self, i0, i1):
         """The stretch of bins [i0, i1) as a symmetric [m, m] float32 numpy map, m = i1 - i0: pixel (a, b) = band[i0 + min(a, b), |a - b|], NaN
@@ -261,7 +329,7 @@ def _stretch_codes(codes, start, end, window_bp):
 
 
 def scan_1m(model, codes, start=0, end=None, window_bp=1_000_000, step_bp=400_000, trim_bins=10, depth=None, batch=32, strands="+", insulation=None,
-            boundaries=None, spread=False, stats=None):
+            boundaries=None, spread=False, stats=None, loops=None):
     """Predict bases [start, end) of a chromosome with the 1 Mb model, window by window, and stitch the maps into one band on the device: a
     `ScanResult`.
 
@@ -286,7 +354,15 @@ def scan_1m(model, codes, start=0, end=None, window_bp=1_000_000, step_bp=400_00
     ``boundary_strength`` (orca_scan_boundary_strength) and the lists ``boundaries``.  Only ``min_strength`` is used - its default is NOT calibrated
     either; choose it from ``boundary_strength`` - and ``max_calls`` does NOT cap the lists: a chromosome has as many boundaries as it has.
     ``spread=True`` adds ``band_range``.  ``stats``: a dict that receives ``windows``, ``decoded_windows`` (twice the windows on both strands),
-    ``batches``, ``bins``, ``depth`` and ``strands``."""
+    ``batches``, ``bins``, ``depth`` and ``strands``, and with ``loops=`` ``loops``, the number of dots.
+
+    ``loops``: True or a `screen.LoopParams` (`screen.check_band_loops`: a ValueError, before any device work, for a value outside its range and when
+    the band has no eligible pixel, D < d_min + 2 w + 1), for ``loop_enrichment`` (orca_scan_band_dot_enrichment) and the list ``loops``
+    (orca_scan_band_dot_offsets, orca_scan_band_dot_list): the screens' dot calls on the band, without their limit of 256 bins - a pixel at distance
+    d_min <= d <= D - 1 - 2 w is called with its whole window, wherever the windows' seams lie.  ``max_calls`` and ``tol`` are accepted and unused:
+    ``max_calls`` caps nothing here, a chromosome has as many loops as it has.  The default ``threshold`` is NOT calibrated on the published
+    checkpoints; choose it from ``loop_enrichment``.  The calls run on the stitched MEAN, so ``band_range`` (``spread=True``) at a dot says how far the
+    overlapping windows disagree there.  ``strands="both"`` needs nothing more: the band is already the merged one."""
     window_bp, step_bp, trim, batch = int(window_bp), int(step_bp), int(trim_bins), int(batch)
     if window_bp % BIN_BP or not 1 <= window_bp // BIN_BP <= MAX_BINS:
         raise ValueError(f"window_bp = {window_bp}: a multiple of {BIN_BP} with at most {MAX_BINS} bins (Net.forward's limit)")
@@ -310,6 +386,7 @@ def scan_1m(model, codes, start=0, end=None, window_bp=1_000_000, step_bp=400_00
         raise ValueError("boundaries: called on the insulation tracks (insulation=widths)")
     widths = None if insulation is None else _check_band_widths(insulation, D)
     bp = _check_min_strength(boundaries) if want_b else None
+    lp = None if loops is None or loops is False else check_band_loops(loops, n, D)      # the stretch has N >= n >= D bins: D decides
     codes, base, start, N = _stretch_codes(codes, start, end, window_bp)
     net = _net_of(model)
     both = strands == "both"
@@ -340,6 +417,12 @@ def scan_1m(model, codes, start=0, end=None, window_bp=1_000_000, step_bp=400_00
                 res.boundary_params = bp
                 res.boundary_strength = engine.scan_boundary_strength(ctx, res.insulation)
                 res.boundaries = boundary_lists_host(res.boundary_strength.cpu().numpy(), bp.min_strength)
+        if lp is not None:
+            res.loop_params = lp
+            res.loop_enrichment = engine.scan_band_dot_enrichment(ctx, band, lp.p, lp.w, lp.d_min)
+            ij, enrich = engine.scan_band_dot_calls(ctx, res.loop_enrichment, lp.r, lp.threshold)
+            res.loops = (ij.cpu().numpy(), enrich.cpu().numpy())
+            st["loops"] = int(ij.shape[0])
     if stats is not None:
         stats.update(st)
     return res

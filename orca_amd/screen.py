@@ -80,7 +80,7 @@ from ._lib import OrcaHipError
 from .map_readouts import (  # noqa: F401
     BIN_BP, _bin_maps, scores_host, check_regions, region_scores_host, aligned_scores_host, aligned_region_scores_host, check_insulation,
     check_viewpoints, _widths, insulation_host, insulation_scores_host, viewpoint_scores_host, STRATA_FIELDS, check_strata, strata_scores_host,
-    LOOP_MAX_W, LOOP_MAX_R, LOOP_MAX_CALLS, LOOP_FIELDS, LoopParams, _loop_params, check_loops, check_loops_arg, dot_enrichment_host, dot_calls_host,
+    LOOP_MAX_W, LOOP_MAX_R, LOOP_MAX_CALLS, LOOP_FIELDS, LoopParams, _loop_params, check_loops, check_band_loops, check_loops_arg, dot_enrichment_host, dot_calls_host,
     follow_loop, _follow_loops, match_loops_host, _match_loops, loop_scores_host, BOUNDARY_MIN_BINS, BOUNDARY_MAX_BINS, BOUNDARY_MATCH_FIELDS,
     BoundaryParams, check_boundaries, check_boundaries_arg, boundary_strength_host, boundary_calls_host, match_boundaries_host, _match_boundaries,
     _boundary_fields, boundary_scores_host, merge_strands_host, _member_table, epistasis_scores_host)

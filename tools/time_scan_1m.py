@@ -12,6 +12,14 @@ can resolve.
 
     python tools/time_scan_1m.py            # 40 Mb
     python tools/time_scan_1m.py 8          # 8 Mb
+
+``--loops``: what the loop (dot) calls of ``scan_1m(..., loops=)`` add to (b), the same way - (b) alternated with
+  (e) loops         (b) with loops=True: plus orca_scan_band_dot_enrichment, orca_scan_band_dot_offsets, orca_scan_band_dot_list and the lists' copy
+  (f) loops_every   (b) with loops=LoopParams(threshold=-1e30): every local maximum of the enrichment is called, the longest list the band can give
+into profiles/scan_1m_loops.json: the times, per repetition the difference to the band-only run beside it, and the spread of the band-only
+repetitions, which says how small a difference the run can resolve.
+
+    python tools/time_scan_1m.py --loops
 """
 import argparse
 import json
@@ -58,16 +66,49 @@ def timed(fn):
     return time.perf_counter() - t0, r
 
 
+def time_loops(a, model, codes):
+    """--loops: (b) alternated with (e) and (f)"""
+    every = S.LoopParams(threshold=-1e30)
+    runs = {"band": lambda: C.scan_1m(model, codes), "loops": lambda: C.scan_1m(model, codes, loops=True),
+            "loops_every": lambda: C.scan_1m(model, codes, loops=every)}
+    for fn in runs.values():                                                                     # warm-up
+        fn()
+    st, st_every = {}, {}
+    C.scan_1m(model, codes, loops=True, stats=st)
+    C.scan_1m(model, codes, loops=every, stats=st_every)
+    rep = {"workload": f"H1esc_1M synthetic, a synthetic chromosome of {a.mb:g} Mb, 1 Mb windows every 400 kb, trim 10, 32 windows per batch; scan_1m with "
+                       "the band only against the same with loops=True (LoopParams(): p 1, w 4, r 2, threshold 0.25) and with "
+                       "loops=LoopParams(threshold=-1e30), which calls every local maximum; alternated, best of three", "commit": a.commit,
+           "device": torch.cuda.get_device_name(torch.device("cuda:0")), "weights": "synthetic", "windows": st["windows"], "batches": st["batches"], "bins": st["bins"],
+           "depth": st["depth"], "reps": a.reps, "loops_listed": st["loops"], "loops_every_listed": st_every["loops"]}
+    t = {k: [] for k in runs}
+    for _ in range(a.reps):
+        for k, fn in runs.items():
+            t[k].append(timed(fn)[0])
+    for k in runs:
+        rep[f"{k}_s"] = [round(x, 4) for x in t[k]]
+    rep["band_spread_ms"] = round((max(t["band"]) - min(t["band"])) * 1e3, 3)
+    for k in ("loops", "loops_every"):
+        rep[f"{k}_minus_band_ms"] = [round((x - b) * 1e3, 3) for x, b in zip(t[k], t["band"])]       # per repetition, against the band-only run beside it
+        rep[f"{k}_over_band"] = round(min(t[k]) / min(t["band"]), 4)
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("mb", type=float, nargs="?", default=40.0, help="length of the synthetic chromosome in Mb")
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "scan_1m.json"))
+    ap.add_argument("--loops", action="store_true", help="time the loop calls against the band-only scan (profiles/scan_1m_loops.json)")
+    ap.add_argument("--out", default=None, help="the report; profiles/scan_1m.json, or profiles/scan_1m_loops.json with --loops")
     ap.add_argument("--commit", default="", help="recorded in the report")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "scan_1m_loops.json" if a.loops else "scan_1m.json")
     dev = torch.device("cuda:0")
     model = M.H1esc_1M(synthetic_seed=0).to(dev)
     codes = torch.from_numpy(chromosome(int(a.mb * 1_000_000))).to(dev)
+    if a.loops:
+        return report(time_loops(a, model, codes), a.out)
     runs = {"decode_only": lambda: decode_only(model, codes), "band": lambda: C.scan_1m(model, codes),
             "readouts": lambda: C.scan_1m(model, codes, **READOUTS), "both_strands": lambda: C.scan_1m(model, codes, strands="both", **READOUTS)}
     st = {}
@@ -90,10 +131,14 @@ def main():
     rep["decode_only_spread"] = round(max(t["decode_only"]) / base, 4)
     for k in ("band", "readouts", "both_strands"):
         rep[f"{k}_over_decode_only"] = round(min(t[k]) / base, 4)
+    report(rep, a.out)
+
+
+def report(rep, out):
     print(json.dumps(rep))
-    if a.out:
-        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
-        with open(a.out, "w") as f:
+    if out:
+        os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+        with open(out, "w") as f:
             json.dump(rep, f, indent=1)
 
 
